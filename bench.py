@@ -11,6 +11,14 @@ steps, d = 256, 4 layers.      frames/s = n_gpus * B * (burn_in + rollout) * ste
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --config C4        # Physion STEVE + 8-layer SlotFormer, B = 16, 6 + 40
     python bench.py --config C5        # PHYRE SAVi + SingleStepSlotRollouter, B = 64 (--batch 8: the per-GPU share on 8 GPUs), 1 + 80
+    python bench.py --full             # + the median of several windows, rooflines, untimed extras and the CPU baseline
+
+A plain run does only what the headline needs: build the pipeline, run --warmup batches, time ONE window of exactly --steps
+batches (`value`, `ms_per_step`) and print the line.  Everything else -- windows until the timed region holds >= 1 s with
+`value` = the median window, the per-unit step distribution, per-kernel event passes and roofline objects, one-batch latencies,
+the CPU baseline of the oracle -- runs with --full (--breakdown, --decode and --pcie imply it).  --dump-outputs DIR writes the
+slots the timed path computed for the last batch of the last window as DIR/slots.npy (float32 [B, burn_in + rollout, N, D]);
+the device generator of the kernel noise is reseeded before every window, so the same arguments give the same arrays.
 
 The timed schedule is the product one: `slotformer_amd.pipeline.EncodeRolloutPipeline` (the same object
 `harness.extract_and_rollout` uses, tested bit-identical to the serial path in tests/test_pipeline_gpu.py), fed from a
@@ -43,6 +51,8 @@ import torch  # noqa: E402
 PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense bf16 MFMA peak; bf16x3 issues 3 bf16 MFMA flops per algorithmic flop
 PEAK_HBM_GBPS = 8000.0        # HBM3E spec peak (6.3 TB/s achievable)
+NOISE_SEED = 2024             # device generator seed of the kernel noise of every timed window (+ rank)
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all (a larger batch is cut to its first videos)
 CLS_NAMES = ['conv_nhwc_implicit_gemm', 'conv_first', 'linear_gemm', 'slot_attn_iter', 'slot_update', 'attention', 'ffn_fused', 'seam', 'deconv_head', 'layer_tok']
 
 
@@ -432,6 +442,17 @@ def decode_leg(args, lib, savi, roll, ring, B, T, H, N, D, RES, dev, pipe, peak_
     return obj, roof
 
 
+def dump_outputs(path, slots):
+    """--dump-outputs: what EncodeRolloutPipeline.run returns for the last timed batch -- its slots [B, burn_in + rollout, N, D]
+    (encoded burn-in frames, then the predicted ones) -- as path/slots.npy in float32; above DUMP_LIMIT_BYTES only the first videos."""
+    os.makedirs(path, exist_ok=True)
+    a = slots.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        a = a[:max(1, DUMP_LIMIT_BYTES // a[0].nbytes)]
+    np.save(os.path.join(path, 'slots.npy'), np.ascontiguousarray(a))
+    log(f'wrote {os.path.join(path, "slots.npy")} {list(a.shape)} float32')
+
+
 def log(msg):
     if int(os.environ.get('RANK', 0)) == 0:
         print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
@@ -469,9 +490,20 @@ def main():
     ap.add_argument('--live-every', type=int, default=4, help='bracket every n-th conv / Slot-Attention launch with events in the untimed live pass')
     ap.add_argument('--live-mask', type=int, default=(1 << 0) | (1 << 3), help='kernel classes of that pass')
     ap.add_argument('--allow-stale-trace', action='store_true', help='use the committed rocprof summary although the kernel sources changed')
-    ap.add_argument('--windows', type=int, default=5, help='timed windows (at least) of --steps steps each on the warm pipeline; value = the median window')
-    ap.add_argument('--min-timed-s', type=float, default=1.0, help='keep adding windows until the timed region holds this many seconds (0: exactly --windows)')
+    ap.add_argument('--windows', type=int, default=None, help='timed windows (at least) of --steps steps each on the warm pipeline; value = the median window '
+                    '(default: 1, with --full 5)')
+    ap.add_argument('--min-timed-s', type=float, default=None, help='keep adding windows until the timed region holds this many seconds (0: exactly --windows; '
+                    'default: 0, with --full 1.0)')
+    ap.add_argument('--full', action='store_true', help='also the secondary measurements and checks: median of several windows, per-kernel / roofline objects, '
+                    'one-batch latencies, CPU baseline (implied by --breakdown, --decode, --pcie)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the slots of the last timed batch as DIR/slots.npy (float32)')
     args = ap.parse_args()
+    args.full = args.full or args.breakdown or args.decode or args.pcie
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if args.min_timed_s is None:
+        args.min_timed_s = 1.0 if args.full else 0.0
+    full = args.full
 
     if (args.gpus > 1 or args.self_launch) and 'WORLD_SIZE' not in os.environ:
         # (--self-launch: take the launcher path with --gpus 1 too -- how tests/test_dist_gpu.py runs it on the one GPU of the box)
@@ -565,7 +597,8 @@ def main():
         out_t = torch.empty((args.steps, ) + shape, device=dev)
         run(args.warmup, out_w)
         torch.cuda.synchronize()
-        assert torch.isfinite(out_w[:args.warmup]).all(), 'non-finite slots in the warmup batches'
+        if full:
+            assert torch.isfinite(out_w[:args.warmup]).all(), 'non-finite slots in the warmup batches'
         unit_sizes = None
         if overlap:   # the graphs of the timed run's unit plan exist before the clock starts (a remainder's units are captured on first use otherwise)
             unit_sizes = pipe.prepare(max(1, args.steps // E) if E > 1 else args.steps)
@@ -587,12 +620,13 @@ def main():
                 if more.item() == 0.0:
                     break
             w += 1
+            torch.cuda.manual_seed(NOISE_SEED + rank)   # every window draws the same kernel noise (--dump-outputs: same arguments, same arrays)
             barrier()
             t0 = time.perf_counter()
             run(args.steps, out_t)
             barrier()
             windows.append(time.perf_counter() - t0)
-            if overlap and len(pipe.completion_events) > 1:
+            if full and overlap and len(pipe.completion_events) > 1:
                 # device time between the completions of consecutive rollout units (units on the unmasked drain streams may
                 # overtake their predecessors: the completion times are sorted first)
                 ev0 = pipe.completion_events[0]
@@ -605,116 +639,120 @@ def main():
             windows_all = tw.tolist()
         elapsed = sorted(windows_all)[len(windows_all) // 2]
         log(f'timed windows done: {[round(x, 4) for x in windows_all]} s')
-        # conv + Slot-Attention launches LIVE: a second pass of the same schedule with library brackets (HIP events on the launch
-        # stream) around every LIVE_EVERY-th launch of the two classes
-        LIVE_EVERY = int(args.live_every)
-        lib.sf_profile_sample(LIVE_EVERY)
-        lib.sf_profile_enable(int(args.live_mask))
-        read_profile(lib)
-        run(max(args.warmup, 6), out_w)
-        torch.cuda.synchronize()
-        lib.sf_profile_enable(0)
-        lib.sf_profile_sample(1)
-        prof = read_profile(lib)
-        assert torch.isfinite(out_t).all(), 'non-finite slots in the timed batches'
-        # the three ring inputs give three different results (a stale slot buffer would repeat one)
-        if args.steps >= 3:
-            assert not torch.equal(out_t[0, :, :T_BURN], out_t[1, :, :T_BURN])
-
-        # ---- untimed extras: the two halves alone, per-kernel event timings ----
-        noise = engine.kernel_noise(savi, None, B, T_BURN, dev)
-        noise_p = engine.kernel_noise(savi, None, Bp, T_BURN, dev)
-
-        def encode():
-            post, _, _ = engine.savi_encode(savi, ring[0], noise=noise, side_stream=None)   # one stream: the kernels alone, for the rooflines
-            unit0.buf[:B, :T_BURN].copy_(post)
-
-        def encode_forked():   # the direct module path's default: two branches (engine.savi_encode side_stream='auto')
-            engine.savi_encode(savi, ring[0], noise=noise)
-
-        def rollout_eager():
-            engine.rollout(roll, unit0.buf, T_BURN, T_ROLL, ws_slot=unit0.key, opts=pipe.rollout_opts)
-
-        def rollout():          # one rollout UNIT: G batches
-            graph.replay() if graph is not None else rollout_eager()
-
-        def timed_on(stream, fn, n=3):
-            stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(stream):
-                fn()
-                stream.synchronize()
-                t = time.perf_counter()
-                for _ in range(n):
-                    fn()
-                stream.synchronize()
-            return (time.perf_counter() - t) / n
-
-        # one batch at a time (no pipelining, whole chip): the latency of ONE batch of B videos through encode + rollout
-        one_batch = []
-        for k in range(6):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            pipe.run([ringp[k % 3]], None, serial=True)
-            torch.cuda.synchronize()
-            one_batch.append(time.perf_counter() - t1)
-        one_batch_ms = 1e3 * sorted(one_batch[1:])[len(one_batch[1:]) // 2]   # (the first call captures the one-batch unit's graph)
-        torch.cuda.synchronize()
-        # the same through the MODULE calls a reference script makes per batch (savi forward, then the rollouter: extract_slots.py:19-38 ->
-        # rollout_clevrer_slots.py:20-65; engine.savi_encode in its default two-branch form + engine.rollout in the library's default forms), eager
-        one_buf = torch.zeros(Bp, T_BURN + T_ROLL, N_SLOTS, SLOT_D, device=dev)
-        direct = []
-        for k in range(6):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            post_k, _, _ = engine.savi_encode(savi, ringp[k % 3], noise=noise_p)
-            one_buf[:, :T_BURN].copy_(post_k)
-            engine.rollout(roll, one_buf, T_BURN, T_ROLL, ws_slot=('bench', 'one'))
-            torch.cuda.synchronize()
-            direct.append(time.perf_counter() - t1)
-        one_batch_direct_ms = 1e3 * sorted(direct[1:])[len(direct[1:]) // 2]
-        lib.sf_profile_enable((1 << 0) | (1 << 3))
-        t_enc = timed_on(torch.cuda.current_stream(), encode)
-        lib.sf_profile_enable(0)
-        prof_iso = read_profile(lib)  # same kernels with nothing else on the GPU
-        t_enc_fork = timed_on(torch.cuda.current_stream(), encode_forked)
-        t_roll = timed_on(torch.cuda.current_stream(), rollout)      # seconds per unit (G batches)
-        part_ms = None
-        if overlap and pipe.cu_split:
-            def lane_encode(li):
-                st, lo, hi = pipe.lanes[li]
-                return lambda: pipe._encode(ringp[0], noise_p, unit0.buf[:Bp], None, lo, hi, li, unit=(unit0, 0))
-
-            part_ms = {'encode_lane_ms_on_its_cus': [round(1e3 * timed_on(pipe.lanes[li][0], lane_encode(li)), 4) for li in range(len(pipe.lanes))],
-                       'encode_lane_videos': [hi - lo for _, lo, hi in pipe.lanes],
-                       'rollout_unit_ms_on_its_cus': 1e3 * timed_on(pipe.s_roll, rollout), 'batches_per_rollout_unit': G * E}
-            part_ms['encode_ms_on_its_cus'] = max(part_ms['encode_lane_ms_on_its_cus'])
-        # the rollout layer kernels, event-timed: (a) alone on the whole chip in one eager rollout unit, (b) LIVE in a pipelined
-        # pass with the product schedule (encode stream busy on its CUs) but eager launches -- inside the timed region they
-        # replay from a hipGraph, where HIP events cannot be inserted between the kernels
-        lib.sf_profile_enable((1 << 5) | (1 << 6) | (1 << 7) | (1 << 9))
-        read_profile(lib)
-        rollout_eager()
-        torch.cuda.synchronize()
-        prof_roll = read_profile(lib)
-        prof_roll_live = {}
-        if overlap:
-            saved = [(u, u.graph) for u in pipe.units]
-            for u in pipe.units:
-                u.graph = None
-            pipe.run([ringp[j % 3] for j in range(4 * G)], None)
-            torch.cuda.synchronize()
-            for u, g in saved:
-                u.graph = g
-            prof_roll_live = read_profile(lib)
-        lib.sf_profile_enable(0)
-        breakdown = None
-        if args.breakdown:
-            lib.sf_profile_enable(0x3ff)
-            encode()
-            rollout_eager()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out_t[-1])
+        if full:
+            # ---- --full: the secondary measurements and checks, all after the timed windows ----
+            # conv + Slot-Attention launches LIVE: a second pass of the same schedule with library brackets (HIP events on the launch
+            # stream) around every LIVE_EVERY-th launch of the two classes
+            LIVE_EVERY = int(args.live_every)
+            lib.sf_profile_sample(LIVE_EVERY)
+            lib.sf_profile_enable(int(args.live_mask))
+            read_profile(lib)
+            run(max(args.warmup, 6), out_w)
             torch.cuda.synchronize()
             lib.sf_profile_enable(0)
-            breakdown = read_profile(lib)
+            lib.sf_profile_sample(1)
+            prof = read_profile(lib)
+            assert torch.isfinite(out_t).all(), 'non-finite slots in the timed batches'
+            # the three ring inputs give three different results (a stale slot buffer would repeat one)
+            if args.steps >= 3:
+                assert not torch.equal(out_t[0, :, :T_BURN], out_t[1, :, :T_BURN])
+
+            # ---- untimed extras: the two halves alone, per-kernel event timings ----
+            noise = engine.kernel_noise(savi, None, B, T_BURN, dev)
+            noise_p = engine.kernel_noise(savi, None, Bp, T_BURN, dev)
+
+            def encode():
+                post, _, _ = engine.savi_encode(savi, ring[0], noise=noise, side_stream=None)   # one stream: the kernels alone, for the rooflines
+                unit0.buf[:B, :T_BURN].copy_(post)
+
+            def encode_forked():   # the direct module path's default: two branches (engine.savi_encode side_stream='auto')
+                engine.savi_encode(savi, ring[0], noise=noise)
+
+            def rollout_eager():
+                engine.rollout(roll, unit0.buf, T_BURN, T_ROLL, ws_slot=unit0.key, opts=pipe.rollout_opts)
+
+            def rollout():          # one rollout UNIT: G batches
+                graph.replay() if graph is not None else rollout_eager()
+
+            def timed_on(stream, fn, n=3):
+                stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(stream):
+                    fn()
+                    stream.synchronize()
+                    t = time.perf_counter()
+                    for _ in range(n):
+                        fn()
+                    stream.synchronize()
+                return (time.perf_counter() - t) / n
+
+            # one batch at a time (no pipelining, whole chip): the latency of ONE batch of B videos through encode + rollout
+            one_batch = []
+            for k in range(6):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                pipe.run([ringp[k % 3]], None, serial=True)
+                torch.cuda.synchronize()
+                one_batch.append(time.perf_counter() - t1)
+            one_batch_ms = 1e3 * sorted(one_batch[1:])[len(one_batch[1:]) // 2]   # (the first call captures the one-batch unit's graph)
+            torch.cuda.synchronize()
+            # the same through the MODULE calls a reference script makes per batch (savi forward, then the rollouter: extract_slots.py:19-38 ->
+            # rollout_clevrer_slots.py:20-65; engine.savi_encode in its default two-branch form + engine.rollout in the library's default forms), eager
+            one_buf = torch.zeros(Bp, T_BURN + T_ROLL, N_SLOTS, SLOT_D, device=dev)
+            direct = []
+            for k in range(6):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                post_k, _, _ = engine.savi_encode(savi, ringp[k % 3], noise=noise_p)
+                one_buf[:, :T_BURN].copy_(post_k)
+                engine.rollout(roll, one_buf, T_BURN, T_ROLL, ws_slot=('bench', 'one'))
+                torch.cuda.synchronize()
+                direct.append(time.perf_counter() - t1)
+            one_batch_direct_ms = 1e3 * sorted(direct[1:])[len(direct[1:]) // 2]
+            lib.sf_profile_enable((1 << 0) | (1 << 3))
+            t_enc = timed_on(torch.cuda.current_stream(), encode)
+            lib.sf_profile_enable(0)
+            prof_iso = read_profile(lib)  # same kernels with nothing else on the GPU
+            t_enc_fork = timed_on(torch.cuda.current_stream(), encode_forked)
+            t_roll = timed_on(torch.cuda.current_stream(), rollout)      # seconds per unit (G batches)
+            part_ms = None
+            if overlap and pipe.cu_split:
+                def lane_encode(li):
+                    st, lo, hi = pipe.lanes[li]
+                    return lambda: pipe._encode(ringp[0], noise_p, unit0.buf[:Bp], None, lo, hi, li, unit=(unit0, 0))
+
+                part_ms = {'encode_lane_ms_on_its_cus': [round(1e3 * timed_on(pipe.lanes[li][0], lane_encode(li)), 4) for li in range(len(pipe.lanes))],
+                           'encode_lane_videos': [hi - lo for _, lo, hi in pipe.lanes],
+                           'rollout_unit_ms_on_its_cus': 1e3 * timed_on(pipe.s_roll, rollout), 'batches_per_rollout_unit': G * E}
+                part_ms['encode_ms_on_its_cus'] = max(part_ms['encode_lane_ms_on_its_cus'])
+            # the rollout layer kernels, event-timed: (a) alone on the whole chip in one eager rollout unit, (b) LIVE in a pipelined
+            # pass with the product schedule (encode stream busy on its CUs) but eager launches -- inside the timed region they
+            # replay from a hipGraph, where HIP events cannot be inserted between the kernels
+            lib.sf_profile_enable((1 << 5) | (1 << 6) | (1 << 7) | (1 << 9))
+            read_profile(lib)
+            rollout_eager()
+            torch.cuda.synchronize()
+            prof_roll = read_profile(lib)
+            prof_roll_live = {}
+            if overlap:
+                saved = [(u, u.graph) for u in pipe.units]
+                for u in pipe.units:
+                    u.graph = None
+                pipe.run([ringp[j % 3] for j in range(4 * G)], None)
+                torch.cuda.synchronize()
+                for u, g in saved:
+                    u.graph = g
+                prof_roll_live = read_profile(lib)
+            lib.sf_profile_enable(0)
+            breakdown = None
+            if args.breakdown:
+                lib.sf_profile_enable(0x3ff)
+                encode()
+                rollout_eager()
+                torch.cuda.synchronize()
+                lib.sf_profile_enable(0)
+                breakdown = read_profile(lib)
 
     per_rank = None
     rccl_ranks, rccl_backend = None, None
@@ -791,6 +829,14 @@ def main():
                                  (f'encode stream on CU mask {cu_word if isinstance(cu_word, str) else hex(cu_word)} ({pipe.encode_cus} CUs, the same '
                                   'number in every XCD), rollout stream on the complement')) if (overlap and pipe.cu_split) else 'none',
             },
+            'whole_step_tflops': step_flops * args.steps * world / elapsed / 1e12,
+            'whole_step_flops': step_flops,
+            'whole_step_flops_without_folded_kv_projection': step_flops_fold,
+            'whole_step_tflops_without_folded_kv_projection': step_flops_fold * args.steps * world / elapsed / 1e12,
+            'flops_per_encoded_frame': enc_f, 'flops_per_video_rollout': roll_f,
+        }
+    if rank == 0 and full:
+        res.update({
             'one_batch_latency_ms': one_batch_ms,   # pipeline object, one batch per run() call (graph replays, one stream)
             'one_batch_latency_module_calls_ms': one_batch_direct_ms,   # savi forward + rollouter forward per batch, as the reference's scripts call them
             'one_batch_frames_per_s': Bp * (T_BURN + T_ROLL) / (one_batch_ms * 1e-3),
@@ -802,12 +848,7 @@ def main():
             'ms_per_step_distribution': step_dist,
             'encoded_frames_per_s': B * T_BURN / t_enc,
             'predicted_frames_per_s': G * Bp * T_ROLL / t_roll,
-            'whole_step_tflops': step_flops * args.steps * world / elapsed / 1e12,
-            'whole_step_flops': step_flops,
-            'whole_step_flops_without_folded_kv_projection': step_flops_fold,
-            'whole_step_tflops_without_folded_kv_projection': step_flops_fold * args.steps * world / elapsed / 1e12,
-            'flops_per_encoded_frame': enc_f, 'flops_per_video_rollout': roll_f,
-        }
+        })
         # ---- roofline objects, one per hot kernel; `roofline` = the one that dominates the committed rocprof summary of this
         #      command (profiles/r*_kernel_stats.csv), the others stay as secondary keys ----
         objs = {}
@@ -1016,6 +1057,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             log('cpu baseline ...')
             res['cpu_baseline'] = cpu_baseline(cfg, B, min(args.cpu_sample, B))
+    if rank == 0:
         # RCCL prints its version banner through C stdio (flushed at exit when stdout is a pipe): push it out first so
         # that the JSON line is the last thing on stdout
         try:

@@ -29,7 +29,7 @@ def test_bench_under_rccl_process_group(dev):
     env = dict(os.environ, RANK='0', WORLD_SIZE='1', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1',
                MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline', '--force-dist'], env=env, capture_output=True, text=True, timeout=600)
+                        '--no-cpu-baseline', '--force-dist', '--full'], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')][-1]
     d = json.loads(line)

@@ -1,23 +1,20 @@
-"""The reference's own `*_params.py` files load unchanged against this repository.
+"""The settings of the reference's own `*_params.py` files build models of this repository unchanged.
 
-Build-container only: the files are read from /root/reference (which does not travel to the GPU box) -- nothing of them is
-copied.  Every config file is imported through the top-level `nerv` alias package (`from nerv.training import BaseParams`),
-instantiated, and handed to the matching `build_model`; the hand-typed C1..C5 dictionaries the parity tests use
-(tests/golden_util.py) are compared attribute by attribute with the reference files, and every difference must be one of
-the documented overrides below.
+The settings of those files -- the attributes of their `SlotFormerParams()` and the names each file imports -- are a
+committed fixture (tests/golden/reference_params.json, written by `tools/gen_golden.py reference_params`); nothing of their
+program text is copied.  Every file's imports are resolved through the top-level `nerv` alias package (`from nerv.training
+import BaseParams`), its settings become a `BaseParams` subclass as in the file, and the result is handed to the matching
+`build_model`; the hand-typed C1..C5 dictionaries the parity tests use (tests/golden_util.py) are compared attribute by
+attribute with the reference files, and every difference must be one of the documented overrides below.
 """
 import importlib
-import importlib.util
+import json
 import os
-import sys
 
 import pytest
 import torch
 
 import golden_util as gu
-
-REF = '/root/reference/slotformer'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree not present (GPU box)')
 
 BASE = {
     'dvae_physion': 'base_slots/configs/dvae_physion_params.py',
@@ -34,13 +31,35 @@ VP = {   # config file, the base model whose checkpoint `dec_ckp_path` names
 }
 
 
+def _decode(v):
+    if isinstance(v, dict):
+        return tuple(_decode(x) for x in v['__tuple__']) if set(v) == {'__tuple__'} else {k: _decode(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return [_decode(x) for x in v]
+    return v
+
+
+def _reference_files():
+    with open(os.path.join(gu.GOLDEN_DIR, 'reference_params.json')) as f:
+        return json.load(f)['files']
+
+
 def load_params(rel):
-    path = os.path.join(REF, rel)
-    name = 'refcfg_' + os.path.basename(rel)[:-3].replace('-', '_')
-    spec = importlib.util.spec_from_file_location(name, path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)   # executes `from nerv.training import BaseParams`
-    return mod.SlotFormerParams()
+    entry = _reference_files()[rel]
+    names = {}
+    for imp in entry['imports']:   # the file's `from <module> import <name>` lines, resolved against this repository
+        module, name = imp.rsplit('.', 1)
+        names[name] = getattr(importlib.import_module(module), name)
+    attrs = {k: _decode(v) for k, v in entry['attrs'].items()}
+    return type('SlotFormerParams', (names['BaseParams'], ), attrs)()
+
+
+def test_reference_params_fixture_covers_every_file():
+    files = _reference_files()
+    assert sorted(files) == sorted(list(BASE.values()) + [rel for rel, _ in VP.values()])
+    for rel, entry in files.items():
+        assert entry['imports'] == ['nerv.training.BaseParams'], rel
+        assert load_params(rel).model == entry['attrs']['model']
 
 
 def test_nerv_alias_surface():

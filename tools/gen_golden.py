@@ -648,9 +648,57 @@ def case_phyre(name, scfg, rcfg, B, vid_len, seed):
     save(name, slot0=slot0, pred_slots=out['pred_slots'], **meta)
 
 
+REF_PARAMS = ['base_slots/configs/dvae_physion_params.py', 'base_slots/configs/savi_obj3d_params.py',
+              'base_slots/configs/savi_phyre_params-fold0.py', 'base_slots/configs/steve_physion_params.py',
+              'base_slots/configs/stosavi_clevrer_params.py', 'video_prediction/configs/slotformer_obj3d_params.py',
+              'video_prediction/configs/slotformer_clevrer_params.py', 'video_prediction/configs/slotformer_phyre_params-fold0.py',
+              'video_prediction/configs/slotformer_physion_params.py']
+
+
+def case_reference_params(name):
+    """The settings of the reference's *_params.py files (the attributes of SlotFormerParams(), tuples tagged) and the names
+    each file imports, as JSON: what tests/test_reference_configs.py builds models from (settings only, no program text)."""
+    import ast
+    import importlib.util
+    import json
+
+    def enc(v):
+        if isinstance(v, tuple):
+            return {'__tuple__': [enc(x) for x in v]}
+        if isinstance(v, list):
+            return [enc(x) for x in v]
+        if isinstance(v, dict):
+            assert all(isinstance(k, str) for k in v), v
+            return {k: enc(x) for k, x in v.items()}
+        assert v is None or isinstance(v, (bool, int, float, str)), (type(v), v)
+        return v
+
+    files = {}
+    for rel in REF_PARAMS:
+        path = os.path.join(REF, 'slotformer', rel)
+        with open(path) as f:
+            tree = ast.parse(f.read())
+        imports = [f'{n.module}.{a.name}' for n in tree.body if isinstance(n, ast.ImportFrom) for a in n.names]
+        spec = importlib.util.spec_from_file_location('refcfg_' + os.path.basename(rel)[:-3].replace('-', '_'), path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        p = mod.SlotFormerParams()
+        attrs = {k: enc(getattr(p, k)) for k in dir(p) if not k.startswith('_') and not callable(getattr(p, k))}
+        files[rel] = {'imports': imports, 'attrs': attrs}
+    path = os.path.join(gu.GOLDEN_DIR, name + '.json')
+    with open(path, 'w') as f:
+        json.dump({'source': 'attributes of SlotFormerParams() of the reference\'s config files (tools/gen_golden.py)', 'files': files},
+                  f, indent=1, sort_keys=True)
+        f.write('\n')
+    print(f'  wrote {name}.json  {os.path.getsize(path) / 1024:.0f} KB')
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
+    if len(sys.argv) > 1 and sys.argv[1] == 'reference_params':
+        case_reference_params('reference_params')
+        return
     if len(sys.argv) > 1 and sys.argv[1] == 'steve_tokens':   # regenerate only this fixture
         case_steve_tokens('steve_tokens', B=1, T=2, seed=601)
         return
@@ -711,6 +759,7 @@ def main():
     case_savi_train('savi_train', gu.TRAIN_SAVI, B=1, T=2, seed=901, noise_seed=9)
     case_savi_train('savi_train_c1', gu.C1_SAVI, B=1, T=3, seed=911, noise_seed=None, no_dropout=True)
     case_steve_train('steve_train', B=1, T=2, seed=921)
+    case_reference_params('reference_params')
 
 
 if __name__ == '__main__':

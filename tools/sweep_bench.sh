@@ -6,7 +6,7 @@ OUT=gpurun_out/sweep_$TAG.txt
 mkdir -p gpurun_out
 : > $OUT
 for cfg in "$@"; do
-  line=$(env $cfg timeout 300 python bench.py --steps ${STEPS:-20} --warmup 6 --no-cpu-baseline ${BENCH_ARGS:-} 2> gpurun_out/sweep_err.txt | tail -1)
+  line=$(env $cfg timeout 300 python bench.py --full --steps ${STEPS:-20} --warmup 6 --no-cpu-baseline ${BENCH_ARGS:-} 2> "${OUT%.txt}.err" | tail -1)
   python - "$cfg" "$line" >> $OUT <<'PY'
 import json, sys
 cfg, line = sys.argv[1], sys.argv[2]
