@@ -423,11 +423,15 @@ int sf_rollout_opts_f32(const sf_rollouter* m, float* slots, int B, int T_total,
  * row-tile / latency forms; with layer_tok on, to ~1e-6 per layer (a video's last bits depend on its position modulo the videos of a workgroup) */
 int sf_rollout_is_fused(const sf_rollouter* m);
 /* 1 when the layers before the last can run as token-stationary launches (sf_rollout_opts.layer_tok): fused-layer path, tok_packed on those layers,
- * every window of the rollout within the kernel's limits */
+ * every window of the rollout within the kernel's limits (whether layer_tok is on is not asked) */
 int sf_rollout_tok_ok(const sf_rollouter* m);
-/* 1 when sf_rollout_f32 would run seam launches for this model / batch with the calling thread's defaults */
+/* 1 when sf_rollout_f32 may run seam launches for this model / batch with the calling thread's defaults: the fused-layer path with
+ * packed in/out projections in split-bf16 mode, seams on, head-pair attention (attn_heads_per_wg 8, attn_qkv_rows and the
+ * token-stationary layers take other forms), a grid that fits the CUs, and a window of some step after the first that a seam launch
+ * accepts; 0 when none can run */
 int sf_rollout_uses_seam(const sf_rollouter* m, int B);
-/* ... with the options of the call in question (NULL: the thread's defaults): a caller on a CU-masked stream passes its cus_available */
+/* ... with the options of the call in question (NULL: the thread's defaults), precision included: a caller on a CU-masked stream passes
+ * its cus_available */
 int sf_rollout_uses_seam_opts(const sf_rollouter* m, int B, const sf_rollout_opts* opts);
 
 /* ---- differentiable building blocks for the slot-level layers --------------------------------

@@ -23,28 +23,30 @@
 
 namespace {
 
-// set by sf_rollout_bf16 for the duration of its call: every contraction on the generic GEMM core (which honours precision
-// mode 2 = single-pass bf16), none on the split-bf16-only fused kernels
-thread_local bool t_plain_gemms = false;
+inline size_t pad256(size_t nfloat) { return ((nfloat * sizeof(float)) + 255) & ~(size_t)255; }
 
+// Carves 256-byte aligned float buffers off a workspace; over a NULL base it only counts the bytes (`used`)
 struct Bump {
   char* p;
   size_t left;
   bool ok = true;
+  size_t used = 0;
   float* take(size_t nfloat) {
-    size_t bytes = ((nfloat * sizeof(float)) + 255) & ~(size_t)255;
+    const size_t bytes = pad256(nfloat);
     if (bytes > left) {
       ok = false;
       return nullptr;
     }
-    float* r = (float*)p;
-    p += bytes;
+    float* r = p ? (float*)(p + used) : nullptr;
+    used += bytes;
     left -= bytes;
     return r;
   }
 };
 
-inline size_t pad256(size_t nfloat) { return ((nfloat * sizeof(float)) + 255) & ~(size_t)255; }
+// the per-call single-pass modes (sf_rollout_opts.precision 2 / 3): every contraction on the generic GEMM core, which honours them, none
+// on the split-bf16-only fused kernels.  A process default of 2 (sf_set_precision, SF_PRECISION=bf16) keeps the fused kernels.
+inline bool plain_gemms(const SfThreadOpts& o) { return o.precision == 2 || o.precision == 3; }
 
 struct TfmWs {
   float *x2, *qkv, *att, *hid, *y;
@@ -77,7 +79,7 @@ int tfm_layer(const sf_tfm_layer& w, float* x, TfmWs& ws, int B, int L, int Lq, 
   if (norm_first) {
     // split-bf16 mode: LN1 + per-head q|k|v projection + attention in one launch (attn_fused.hip)
     int fused = 1;
-    if (sf_get_precision() >= 1 && !t_plain_gemms)
+    if (sf_get_precision() >= 1 && !plain_gemms(sf_thread_opts()))
       fused = sf_qkv_attn_ex(x, w.norm1_g, w.norm1_b, eps, w.in_proj_w, w.in_proj_b, ws.att, B, L, Lq, d, heads, st);
     if (fused < 0 || fused > 1) return fused;
     if (fused == 1) {
@@ -102,7 +104,7 @@ int tfm_layer(const sf_tfm_layer& w, float* x, TfmWs& ws, int B, int L, int Lq, 
   } else {
     if (Lq != L) return sf_set_err(-1, "row pruning requires norm_first", __FILE__, __LINE__);
     int fused = 1;
-    if (sf_get_precision() >= 1 && !t_plain_gemms)
+    if (sf_get_precision() >= 1 && !plain_gemms(sf_thread_opts()))
       fused = sf_qkv_attn_ex(x, nullptr, nullptr, eps, w.in_proj_w, w.in_proj_b, ws.att, B, L, L, d, heads, st);
     if (fused < 0 || fused > 1) return fused;
     if (fused == 1) {
@@ -134,6 +136,94 @@ int check_layers(const sf_tfm_layer* l, int n) {
   return 0;
 }
 
+// frames of the Transformer window of rollout step s (nf) and the first of them (f0)
+void step_window(const sf_rollouter* m, int s, int& nf, int& f0) {
+  nf = (m->single_step && s + 1 < m->window_len) ? s + 1 : m->window_len;
+  f0 = m->single_step ? s + 1 - nf : s;
+}
+
+// How sf_rollout_f32 runs a model, chosen once per call from its shape, which packed weight copies it has (their presence only: no
+// weight is read, so a plan is made without a GPU), the process defaults and the call's options
+struct RolloutPlan {
+  // GENERIC: GEMM-core layers (tfm_layer).  LONG_WINDOW (65..128 tokens): tfm_layer on LN1 + q|k|v + attention in one launch
+  // (attn_fused.hip), the out-projection GEMM and the fused FFN kernel.  FUSED_*: the two-launch layers of layer_fused.hip on
+  // x = in_proj(window) + PE (ROWS), or on the ring of cached in-projections with one launch per step boundary (RING)
+  enum Path { GENERIC, LONG_WINDOW, FUSED_ROWS, FUSED_RING } path = GENERIC;
+  int tok_layers = 0;   // leading layers run as token-stationary launches (layer_tok.hip, up to eight per launch): 0 or num_layers - 1
+  // fused paths, the attention block: head-pair partials (four, summed by the FFN) / one workgroup per video running all 8 heads /
+  // q|k|v on 128-row tiles + one core workgroup per video (attn_rows.hip); the last two write finished rows
+  enum Attn { HEAD_PAIRS, ALL_HEADS, ROW_TILES } attn = HEAD_PAIRS;
+  // ... the FFN block of the layers before the last: four chunk partials the next attention sums / one workgroup per 64-row tile
+  // (ffn_tile.hip) / that tile launch fused with LN1 + q|k|v of the next layer (whose attention is then its core launch alone)
+  enum Ffn { CHUNK_PARTS, TILE, TILE_QKV } ffn = CHUNK_PARTS;
+  // FUSED_RING: the last-layer FFN + boundary of step s and the layer-0 attention of step s + 1 in one grid, on the steps whose next
+  // window sf_seam_window_ok allows.  Every workgroup of it must be co-resident, one per CU: 160 fit the whole chip with room for
+  // neighbours, a CU-masked caller says how many CUs it has (sf_rollout_opts.cus_available)
+  bool seam = false;
+  bool fused() const { return path == FUSED_ROWS || path == FUSED_RING; }
+};
+
+RolloutPlan plan_rollout(const sf_rollouter* m, int B, const SfThreadOpts& o) {
+  RolloutPlan p;
+  if (!m || !m->layers) return p;
+  const int N = m->num_slots, W = m->window_len, Lmax = W * N, nl = m->num_layers, d = m->d_model;
+  bool packed = true, tok_packed = nl >= 2;
+  for (int l = 0; l < nl; ++l) {
+    const sf_tfm_layer& w = m->layers[l];
+    packed = packed && w.lin1_packed && w.lin2_packed && w.attn_in_packed && w.attn_out_packed;
+    if (l + 1 < nl) tok_packed = tok_packed && w.tok_packed;
+  }
+  const int precision = o.precision >= 0 ? o.precision : sf_get_precision();
+  const bool fusable = packed && !plain_gemms(o) && precision >= 1 && m->norm_first;
+  const bool tok_on = tok_packed && (o.layer_tok > 0 || (o.layer_tok == 0 && sf_get_layer_tok() != 0));
+  if (fusable && sf_layer_fused_ok(d, m->num_heads, m->ffn_dim, Lmax)) {
+    p.path = (m->in_proj_packed && m->out_proj_packed && sf_step_boundary_ok(d, m->slot_size)) ? RolloutPlan::FUSED_RING
+                                                                                               : RolloutPlan::FUSED_ROWS;
+    bool tok = tok_on;
+    for (int nf = m->single_step ? 1 : W; nf <= W && tok; ++nf) tok = sf_layer_tok_ok(nf * N);
+    p.tok_layers = tok ? nl - 1 : 0;
+    // the last layer behind token-stationary launches (finished rows, row-pruned) runs in the row-tile forms
+    p.attn = (o.attn_rows == 128 || tok) ? RolloutPlan::ROW_TILES : (o.attn_heads == 8 ? RolloutPlan::ALL_HEADS : RolloutPlan::HEAD_PAIRS);
+    if (p.attn != RolloutPlan::HEAD_PAIRS && o.ffn_tile >= 1)
+      p.ffn = (p.attn == RolloutPlan::ROW_TILES && o.ffn_tile == 2) ? RolloutPlan::TILE_QKV : RolloutPlan::TILE;
+    const int cus = o.cus > 0 && o.cus < 160 ? o.cus : 160;
+    p.seam = p.path == RolloutPlan::FUSED_RING && p.attn == RolloutPlan::HEAD_PAIRS &&
+             (o.seam >= 0 ? o.seam != 0 : sf_get_seam_fused() != 0) && sf_seam_blocks(B, N) <= cus;
+  } else if (fusable && sf_layer_fused_ok(d, m->num_heads, m->ffn_dim, 1) && Lmax > 64 && sf_ffn_tiles(B * Lmax) <= 1024) {
+    p.path = RolloutPlan::LONG_WINDOW;
+    if (tok_on && Lmax <= 96 && !m->single_step && sf_layer_tok_ok(Lmax)) p.tok_layers = nl - 1;   // one video per workgroup
+  }
+  return p;
+}
+
+// The rollout workspace: one fixed layout for every plan, M = B * window_len * num_slots rows
+struct RolloutWs {
+  float* x;        // [M][d]: in_proj(window) + PE
+  TfmWs tw;        // tfm_layer scratch
+  float* apb;      // attention output [8][M][d]: two sets of four head-pair partials (a seam or a parked q|k|v writes the second)
+  float* xpb;      // FFN hidden-chunk partials [4][M][d]
+  float *xa, *xb2; // layer outputs, alternating
+  int* counters;   // tile counters of the FFN launches (1024)
+  unsigned* seam_flags;   // per-tile epochs of the seam launches + an error word (1024)
+  float* ring;     // cached in-projections [B][window_len + 1][N][d]
+  float* planes;   // q / k / v^T fragment planes of the row-tile attention form (sf_attn_rows_plane_bytes)
+};
+
+bool rollout_ws_take(Bump& bp, RolloutWs& w, const sf_rollouter* m, int B) {
+  const size_t M = (size_t)B * m->window_len * m->num_slots, d = m->d_model;
+  w.x = bp.take(M * d);
+  tfm_ws_take(bp, w.tw, (int)M, (int)d, m->ffn_dim);
+  w.apb = bp.take(8 * M * d);
+  w.xpb = bp.take(4 * M * d);
+  w.xa = bp.take(M * d);
+  w.xb2 = bp.take(M * d);
+  w.counters = (int*)bp.take(1024);
+  w.seam_flags = (unsigned*)bp.take(1024);
+  w.ring = bp.take((size_t)B * (m->window_len + 1) * m->num_slots * d);
+  w.planes = bp.take(sf_attn_rows_plane_bytes(B) / 4);
+  return bp.ok;
+}
+
 }  // namespace
 
 extern "C" {
@@ -141,18 +231,11 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 size_t sf_rollout_workspace_bytes(const sf_rollouter* m, int B) {
   if (!m || B <= 0) return 0;
-  const int Lmax = m->window_len * m->num_slots;
-  const size_t M = (size_t)B * Lmax;
-  // + head partials [8][M][d], hidden-chunk partials [4][M][d], two layer-output buffers, the tile counters of the
-  // two-launch layer and the ring of cached in-projections [B][window_len + 1][N][d]
-  return pad256(M * m->d_model) + tfm_ws_bytes((int)M, m->d_model, m->ffn_dim) + pad256(8 * M * m->d_model) +
-         pad256(4 * M * m->d_model) + 2 * pad256(M * m->d_model) +
-         pad256((size_t)B * (m->window_len + 1) * m->num_slots * m->d_model) + 4096 + 4096 + 4096 +
-         pad256(sf_attn_rows_plane_bytes(B) / 4);   // q / k / v^T fragment planes of the row-tile attention form
+  Bump bp{nullptr, ~(size_t)0};
+  RolloutWs w;
+  rollout_ws_take(bp, w, m, B);
+  return bp.used;
 }
-
-extern "C" int sf_get_seam_fused(void);
-extern "C" int sf_get_layer_tok(void);
 
 // a[0..n) = b[0..n) = 0 (n a multiple of 4, both 16-byte aligned)
 // One wave kept busy for a given time (wall_clock64: the constant 100 MHz counter).  The pipeline launches two of them on two streams to
@@ -213,14 +296,6 @@ __global__ void zero_words_kernel(unsigned* a, unsigned* b) {
   if (p) p[threadIdx.x] = 0u;
 }
 
-// A seam launch hands rows over INSIDE a grid (consumers poll producers with a bounded wait): every workgroup of it must be resident at
-// once, one per CU.  160 fit the whole chip with room for neighbours; a caller whose stream carries a CU mask says how many CUs that is
-// (sf_rollout_opts.cus_available) and the seam is used only when the grid fits them -- otherwise the two launches it replaces.
-static int seam_capacity() {
-  const int cus = sf_thread_opts().cus;
-  return cus > 0 && cus < 160 ? cus : 160;
-}
-
 int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int pred_len, void* ws,
                    size_t ws_bytes, void* stream) {
   SF_REQUIRE(m && slots && ws, "null pointer");
@@ -234,307 +309,155 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
   SF_REQUIRE(T_total >= n_in + pred_len, "slots buffer shorter than burn-in + pred_len");
   SF_REQUIRE(ws_bytes >= sf_rollout_workspace_bytes(m, B), "workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int N = m->num_slots, C = m->slot_size, d = m->d_model, W = m->window_len;
-  const int Lmax = W * N;
+  const int N = m->num_slots, C = m->slot_size, d = m->d_model, W = m->window_len, nl = m->num_layers;
+  const float eps = 1e-5f;
   Bump bp{(char*)ws, ws_bytes};
-  float* x = bp.take((size_t)B * Lmax * d);
-  TfmWs tw;
-  if (!x || !tfm_ws_take(bp, tw, B * Lmax, d, m->ffn_dim))
-    return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
-  float* apb = bp.take((size_t)8 * B * Lmax * d);   // head-pair partials use the first 4
-  float* xpb = bp.take((size_t)4 * B * Lmax * d);
-  float* xa = bp.take((size_t)B * Lmax * d);
-  float* xb2 = bp.take((size_t)B * Lmax * d);
-  int* counters = (int*)bp.take(1024);
-  unsigned* seam_flags = (unsigned*)bp.take(1024);   // per-tile epochs of the seam launches + an error word
+  RolloutWs w;
+  if (!rollout_ws_take(bp, w, m, B)) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
+  const RolloutPlan p = plan_rollout(m, B, sf_thread_opts());
+  const bool ring_in = p.path == RolloutPlan::FUSED_RING;   // layer 0 reads the projection ring + PE, not x = in_proj(window) + PE
+  const bool long_ffn = p.path == RolloutPlan::LONG_WINDOW;
+  const int np = p.attn == RolloutPlan::HEAD_PAIRS ? 4 : 1;   // attention partials the FFN sums
   const int RF = W + 1;   // frames in the projection ring: the window being read + the frame being written
-  float* ring = bp.take((size_t)B * RF * N * d);
-  float* planes = bp.take(sf_attn_rows_plane_bytes(B) / 4);   // attn_rows.hip: q, k, v^T of every (video, head) as fragment planes
-  if (!apb || !xpb || !xa || !xb2 || !counters || !seam_flags || !ring || !planes)
-    return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
-  // two-launch layers (layer_fused.hip): split-bf16 mode, pre-LN, d=256 / 8 heads / ffn 1024, window <= 64 tokens
-  bool packed = true;
-  for (int l = 0; l < m->num_layers; ++l)
-    packed = packed && m->layers[l].lin1_packed && m->layers[l].lin2_packed && m->layers[l].attn_in_packed && m->layers[l].attn_out_packed;
-  const bool fused_layers = packed && !t_plain_gemms && sf_get_precision() >= 1 && m->norm_first &&
-                            sf_layer_fused_ok(d, m->num_heads, m->ffn_dim, Lmax);
-  // step boundary in one launch (out-proj of step s + in-proj of the new frame for step s+1) with cached in-projections
-  const bool ring_mode = fused_layers && m->in_proj_packed && m->out_proj_packed && sf_step_boundary_ok(d, C);
-  const bool boundary_fused = ring_mode;
-  // seam launches (layer_fused.hip): the last-layer FFN + boundary of step s and the layer-0 attention of step s+1 in one
-  // grid; needs every workgroup of it co-resident at one per CU -- 160 fit the 168-CU rollout partition
-  const int seam_opt = sf_thread_opts().seam;
-  // row-tile form of the attention block (per-call option attn_qkv_rows = 128, attn_rows.hip): q|k|v projection on 128-row tiles
-  // of the batch + one core / out-projection workgroup per video; finished rows like the all-heads form
-  bool tok_packed = fused_layers && m->num_layers >= 2;
-  for (int l = 0; l + 1 < m->num_layers; ++l) tok_packed = tok_packed && m->layers[l].tok_packed;
-  {
-    const int lt = sf_thread_opts().layer_tok;
-    tok_packed = tok_packed && (lt > 0 || (lt == 0 && sf_get_layer_tok() != 0));
-    for (int nf = m->single_step ? 1 : W; nf <= W && tok_packed; ++nf) tok_packed = sf_layer_tok_ok(nf * N);
-  }
-  const bool tok_layers = tok_packed;
-  const bool attn_rows = fused_layers && (sf_thread_opts().attn_rows == 128 || tok_layers);
-  const bool seam = boundary_fused && (seam_opt >= 0 ? seam_opt != 0 : sf_get_seam_fused() != 0) && sf_seam_blocks(B, N) <= seam_capacity() &&
-                    sf_thread_opts().attn_heads != 8 && !attn_rows;
-  // layers 0 .. n-2 leave their output as four FFN chunk partials that the next attention sums while loading (the last layer's
-  // FFN sums them itself: its last-arriving workgroup)
-  const bool parts_mode = ring_mode;
-  // throughput form of the attention block (per-call option attn_heads_per_wg = 8): one workgroup per video runs all 8 heads
-  // and writes finished rows; the FFN behind it reads one row instead of four head-pair partials (layer_fused.hip)
-  const bool all_heads = fused_layers && (sf_thread_opts().attn_heads == 8 || attn_rows);
-  // row-tile form of the FFN block behind finished attention rows (per-call option ffn_tile, ffn_tile.hip): finished rows out
-  const bool ffn_tile = all_heads && sf_thread_opts().ffn_tile >= 1;
-  // ... fused with LN1 + q|k|v of the NEXT layer on the same tiles (ffn_tile = 2, behind the row-tile attention form): the next attention
-  // block is then its core launch alone
-  const bool ffn_qkv = ffn_tile && attn_rows && sf_thread_opts().ffn_tile == 2;
-  const int np = all_heads ? 1 : 4;
-  // token-stationary whole-layer launches for the layers before the last (per-call option layer_tok, layer_tok.hip): finished rows in, finished rows
-  // out; the (row-pruned) last layer runs in the row-tile forms behind them
-  const bool layer_tok = tok_layers;
-  if (ring_mode) {
+  const long long bs = (long long)T_total * N * C;
+  if (ring_in) {
     // in-projection (without PE) of the burn-in frames -> ring slots 0 .. n_in-1
-    SF_TRY(sf_ring_init_ex(m->out_proj_packed, m->out_proj_b, m->in_proj_packed, m->in_proj_b, slots,
-                           (long long)T_total * N * C, n_in, ring, RF, N, B, st));
+    SF_TRY(sf_ring_init_ex(m->out_proj_packed, m->out_proj_b, m->in_proj_packed, m->in_proj_b, slots, bs, n_in, w.ring, RF, N, B, st));
   }
-  // windows of 65..128 tokens (the reference's Physion window: 15 frames x 6 slots): the attention kernels of layer_fused.hip
-  // hold two token blocks, so the layers run as LN1 + q|k|v + attention in one launch (attn_fused.hip, four token blocks), the
-  // out-projection GEMM, and the fused FFN kernel on its finished rows
-  const bool long_ffn = !fused_layers && packed && !t_plain_gemms && sf_get_precision() >= 1 && m->norm_first &&
-                        sf_layer_fused_ok(d, m->num_heads, m->ffn_dim, 1) && Lmax > 64 && sf_ffn_tiles(B * Lmax) <= 1024;
-  // ... and the layers before the last of such a window as token-stationary launches (per-call option layer_tok; layer_tok.hip: one video per workgroup)
-  bool long_tok_packed = long_ffn && m->num_layers >= 2 && Lmax <= 96 && !m->single_step && sf_layer_tok_ok(Lmax);
-  for (int l = 0; l + 1 < m->num_layers; ++l) long_tok_packed = long_tok_packed && m->layers[l].tok_packed;
-  const bool long_tok = long_tok_packed && (sf_thread_opts().layer_tok > 0 || (sf_thread_opts().layer_tok == 0 && sf_get_layer_tok() != 0));
-  if (fused_layers || long_ffn) {
-    SF_REQUIRE(sf_ffn_tiles(B * Lmax) <= 1024, "batch too large for the fused-layer tile counters");
+  if (p.fused() || long_ffn) {
+    SF_REQUIRE(sf_ffn_tiles(B * W * N) <= 1024, "batch too large for the fused-layer tile counters");
     // zeroed by a KERNEL, not hipMemsetAsync: the rollout is captured into hipGraphs, and the memset nodes of a graph were seen
     // to stop clearing these words after an OLDER graph exec had been destroyed (stale seam epochs -> consumers read ring rows
     // before they were written; found by tests/test_pipeline_gpu.py when a second pipeline followed a first in one process)
-    hipLaunchKernelGGL(zero_words_kernel, dim3(2), dim3(1024), 0, st, (unsigned*)counters, seam ? seam_flags : nullptr);
+    hipLaunchKernelGGL(zero_words_kernel, dim3(2), dim3(1024), 0, st, (unsigned*)w.counters, p.seam ? w.seam_flags : nullptr);
     SF_CHECK_LAUNCH();
-    if (attn_rows) {
+    if (p.attn == RolloutPlan::ROW_TILES) {
       // key positions >= L of the v^T planes meet probability 0 in the PV product: they must hold finite values
       const long long nfl = (long long)(sf_attn_rows_plane_bytes(B) / 4), half = nfl / 2;
-      hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)(((half + 3) / 4 + 255) / 256)), dim3(256), 0, st, planes, planes + half, half);
+      hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)(((half + 3) / 4 + 255) / 256)), dim3(256), 0, st, w.planes, w.planes + half, half);
       SF_CHECK_LAUNCH();
     }
   }
-  const long long bs = (long long)T_total * N * C;
-  auto window = [&](int s, int& nf, int& f0) {   // frames of the Transformer window of step s
-    if (!m->single_step) {
-      nf = W;
-      f0 = s;
-    } else {
-      const int have = s + 1;
-      nf = have < W ? have : W;
-      f0 = have - nf;
-    }
-  };
-  float* apb2 = apb + (size_t)4 * B * Lmax * d;   // second set of head-pair partials (the seam's attention writes there)
-  float* ap_l0 = apb;                              // where the layer-0 attention of the CURRENT step put its partials
-  bool attn0_done = false;                         // ... and whether it already ran (inside the previous seam launch)
+  float* apb2 = w.apb + (size_t)4 * B * W * N * d;   // second set of head-pair partials
+  float* ap0 = w.apb;        // where the layer-0 attention of the current step put its partials
+  bool attn0_done = false;   // ... and whether it already ran (inside the previous step's seam launch)
   for (int s = 0; s < pred_len; ++s) {
     int nf, f0;
-    window(s, nf, f0);
-    const int L = nf * N, M = B * L, pe_off = (W - nf) * N;
-    if (ring_mode) {
-      const float* cin = nullptr;
-      bool parts_in = false;   // the current layer's input is still the previous layer's four FFN chunk partials in xpb
-      float* parked = nullptr; // ffn_qkv: the buffer the previous layer's fused launch parked this layer's residual rows in (planes written)
-      for (int l = 0; l < m->num_layers; ++l) {
-        const bool lastl = (l == m->num_layers - 1);
-        const int Lq = lastl ? N : L;   // last layer: only the newest frame's rows are read (slotformer.py:121)
-        const long long pst = (long long)B * Lq * d;
-        float* xo = (cin == xa) ? xb2 : xa;
-        float* apl = (l == 0) ? ap_l0 : apb;
-        if (layer_tok && !lastl) {
-          // all layers before the last in ONE launch (up to eight; the rows stay in registers between them)
-          const int nlt = (m->num_layers - 1 - l) < 8 ? (m->num_layers - 1 - l) : 8;
-          SF_TRY(sf_layer_tok_ex(l == 0 ? 1 : 0, cin, ring, RF, N, f0, m->pe_tok + (long long)pe_off * d, m->layers + l, nlt, 1e-5f, xo, B, L, st));
-          cin = xo;
-          parts_in = false;
-          if (l == 0) ap_l0 = apb;
-          attn0_done = false;
-          l += nlt - 1;
-          continue;
-        }
-        if (parked) {
-          apl = parked;
-          SF_TRY(sf_attn_core_ex(m->layers[l], apl, planes, B, L, Lq, st));
-        } else if (attn_rows) {
-          if (l == 0)
-            SF_TRY(sf_attn_rows_ex(2, ring, (long long)RF * N * d, 0, m->pe_tok + (long long)pe_off * d, f0, RF, N, m->layers[l], 1e-5f, apl,
-                                   planes, B, L, Lq, st));
-          else if (parts_in)
-            SF_TRY(sf_attn_rows_ex(1, xpb, (long long)L * d, (long long)B * L * d, nullptr, 0, 1, 1, m->layers[l], 1e-5f, apl, planes, B, L,
-                                   Lq, st));
-          else
-            SF_TRY(sf_attn_rows_ex(0, cin, (long long)L * d, 0, nullptr, 0, 1, 1, m->layers[l], 1e-5f, apl, planes, B, L, Lq, st));
-        } else if (all_heads) {
-          if (l == 0)
-            SF_TRY(sf_attn_all_ring_ex(ring, RF, N, f0, m->pe_tok + (long long)pe_off * d, m->layers[l], 1e-5f, apl, B, L, Lq, st));
-          else if (parts_in)
-            SF_TRY(sf_attn_all_parts_ex(xpb, (long long)B * L * d, m->layers[l], 1e-5f, apl, B, L, Lq, st));
-          else
-            SF_TRY(sf_attn_all_ex(cin, m->layers[l], 1e-5f, apl, B, L, Lq, st));
-        } else if (l == 0) {
-          if (!attn0_done)
-            SF_TRY(sf_attn_oproj_ring_ex(ring, RF, N, f0, m->pe_tok + (long long)pe_off * d, m->layers[l], 1e-5f, apl, pst, B, L,
-                                         Lq, st));
-        } else if (parts_in) {
-          SF_TRY(sf_attn_oproj_parts_ex(xpb, (long long)B * L * d, m->layers[l], 1e-5f, apl, pst, B, L, Lq, st));
-        } else {
-          SF_TRY(sf_attn_oproj_ex(cin, m->layers[l], 1e-5f, apl, pst, B, L, Lq, st));
-        }
-        attn0_done = false;
-        if (lastl && boundary_fused) {
-          // last layer: FFN + step boundary in one launch.  pred = out_proj(last rows) -> frame n_in + s; its
-          // in-projection -> the ring   (slotformer.py:121-124, :115)
-          int nf1 = 0, f01 = 0;
-          if (s + 1 < pred_len) window(s + 1, nf1, f01);
-          if (seam && s + 1 < pred_len && sf_seam_window_ok(nf1 * N, N)) {
-            const int L1 = nf1 * N, Lq1 = (m->num_layers == 1) ? N : L1;
-            float* ap_next = (apl == apb) ? apb2 : apb;
-            SF_TRY(sf_seam_ex(apl, pst, m->layers[l], 1e-5f, xpb, pst, counters, m->ffn_dim, m->out_proj_packed, m->out_proj_b,
-                              m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s, ring, RF, N, B, m->layers[0], f01,
-                              m->pe_tok + (long long)((W - nf1) * N) * d, ap_next, (long long)B * Lq1 * d, L1, Lq1, seam_flags,
-                              (unsigned)(s + 1), st));
-            ap_l0 = ap_next;
-            attn0_done = true;
-          } else {
-            SF_TRY(sf_ffn_boundary_ex(apl, pst, m->layers[l], 1e-5f, xpb, pst, counters, m->ffn_dim, m->out_proj_packed,
-                                      m->out_proj_b, m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s, ring, RF, N, B, st, np));
-            ap_l0 = apb;
-          }
-          cin = nullptr;
-        } else if (ffn_qkv && !lastl) {
-          float* park = (apl == apb) ? apb2 : apb;
-          SF_TRY(sf_ffn_qkv_tile_ex(apl, m->layers[l], m->layers[l + 1], 1e-5f, park, planes, B, L, (l + 1 == m->num_layers - 1) ? N : L,
-                                    m->ffn_dim, st));
-          parked = park;
-          cin = nullptr;
-          parts_in = false;
-          if (l == 0) ap_l0 = apb;
-        } else if (ffn_tile && !lastl) {
-          SF_TRY(sf_ffn_tile_ex(apl, m->layers[l], 1e-5f, xo, B * Lq, m->ffn_dim, st));
-          cin = xo;
-          parts_in = false;
-          if (l == 0) ap_l0 = apb;
-        } else if (parts_mode && !lastl) {
-          // the chunk partials are the layer output: the next attention sums them
-          SF_TRY(sf_ffn_parts_ex(apl, pst, m->layers[l], 1e-5f, xpb, pst, B * Lq, m->ffn_dim, st, np));
-          parts_in = true;
-          cin = nullptr;
-          if (l == 0) ap_l0 = apb;
-        } else {
-          SF_TRY(sf_ffn_partial_ex(apl, pst, m->layers[l], 1e-5f, xpb, pst, xo, counters, B * Lq, m->ffn_dim, st, np));
-          cin = xo;
-          parts_in = false;
-          if (l == 0) ap_l0 = apb;
-        }
-      }
-      if (cin != nullptr)
-        SF_TRY(sf_step_boundary_ex(cin, m->out_proj_packed, m->out_proj_b, m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s,
-                                   ring, RF, N, B, st));
-      continue;
+    step_window(m, s, nf, f0);
+    const int L = nf * N, pe_off = (W - nf) * N;
+    const float* pe = m->pe_tok + (long long)pe_off * d;
+    float* cin = nullptr;   // the current layer's input rows (NULL: the ring, four chunk partials in xpb or rows parked with the planes)
+    if (!ring_in) {
+      // x = in_proj(window) + pe   (slotformer.py:115-117; single_step_slotformer.py:79-81)
+      SfRowMap pmap = sf_rows(d);
+      pmap.base = (long long)pe_off * d;
+      SF_TRY(sf_linear_ex(slots, sf_rows_batched(C, L, bs, (long long)f0 * N * C), m->in_proj_w, m->in_proj_b,
+                          nullptr, nullptr, 0.f, m->pe_tok, pmap, L, w.x, sf_rows(d), B * L, d, C, 0, st));
+      cin = w.x;
     }
-    // x = in_proj(window) + pe   (slotformer.py:115-117; single_step_slotformer.py:79-81)
-    SfRowMap pmap = sf_rows(d);
-    pmap.base = (long long)pe_off * d;
-    SF_TRY(sf_linear_ex(slots, sf_rows_batched(C, L, bs, (long long)f0 * N * C), m->in_proj_w, m->in_proj_b,
-                        nullptr, nullptr, 0.f, m->pe_tok, pmap, L, x, sf_rows(d), M, d, C, 0, st));
-    if (fused_layers) {
-      // every layer is two launches: attention + out-proj head partials, then the FFN (which also finishes the sums)
-      const float* cin = x;
-      bool parts_in = false;
-      float* parked = nullptr;   // (as in the ring path)
-      float* apn = apb;          // attention output / FFN input of the current layer
-      for (int l = 0; l < m->num_layers; ++l) {
-        const bool lastl = (l == m->num_layers - 1);
-        const int Lq = lastl ? N : L;
-        const long long pst = (long long)B * Lq * d;
-        float* xo = (cin == xa) ? xb2 : xa;
-        if (layer_tok && !lastl) {
-          const int nlt = (m->num_layers - 1 - l) < 8 ? (m->num_layers - 1 - l) : 8;
-          SF_TRY(sf_layer_tok_ex(0, cin, nullptr, 1, 1, 0, nullptr, m->layers + l, nlt, 1e-5f, xo, B, L, st));
-          cin = xo;
-          parts_in = false;
-          l += nlt - 1;
-          continue;
-        }
-        if (parked) {
-          apn = parked;
-          SF_TRY(sf_attn_core_ex(m->layers[l], apn, planes, B, L, Lq, st));
-        } else if (attn_rows) {
-          apn = apb;
-          if (parts_in)
-            SF_TRY(sf_attn_rows_ex(1, xpb, (long long)L * d, (long long)B * L * d, nullptr, 0, 1, 1, m->layers[l], 1e-5f, apb, planes, B, L,
-                                   Lq, st));
-          else
-            SF_TRY(sf_attn_rows_ex(0, cin, (long long)L * d, 0, nullptr, 0, 1, 1, m->layers[l], 1e-5f, apb, planes, B, L, Lq, st));
-        } else if (all_heads) {
-          if (parts_in)
-            SF_TRY(sf_attn_all_parts_ex(xpb, (long long)B * L * d, m->layers[l], 1e-5f, apb, B, L, Lq, st));
-          else
-            SF_TRY(sf_attn_all_ex(cin, m->layers[l], 1e-5f, apb, B, L, Lq, st));
-        } else if (parts_in) {
-          SF_TRY(sf_attn_oproj_parts_ex(xpb, (long long)B * L * d, m->layers[l], 1e-5f, apb, pst, B, L, Lq, st));
-        } else {
-          SF_TRY(sf_attn_oproj_ex(cin, m->layers[l], 1e-5f, apb, pst, B, L, Lq, st));
-        }
-        if (!lastl && ffn_qkv) {
-          float* park = (apn == apb) ? apb2 : apb;
-          SF_TRY(sf_ffn_qkv_tile_ex(apn, m->layers[l], m->layers[l + 1], 1e-5f, park, planes, B, L, (l + 1 == m->num_layers - 1) ? N : L,
-                                    m->ffn_dim, st));
-          parked = park;
-          cin = nullptr;
-          parts_in = false;
-        } else if (!lastl && ffn_tile) {
-          SF_TRY(sf_ffn_tile_ex(apn, m->layers[l], 1e-5f, xo, B * Lq, m->ffn_dim, st));
-          cin = xo;
-          parts_in = false;
-        } else if (!lastl) {
-          SF_TRY(sf_ffn_parts_ex(apn, pst, m->layers[l], 1e-5f, xpb, pst, B * Lq, m->ffn_dim, st, np));
-          parts_in = true;
-        } else {
-          SF_TRY(sf_ffn_partial_ex(apn, pst, m->layers[l], 1e-5f, xpb, pst, xo, counters, B * Lq, m->ffn_dim, st, np));
-          cin = xo;
-          parts_in = false;
-        }
+    // the leading layers as token-stationary launches of up to eight layers each (the rows stay in registers between them)
+    int l = 0;
+    while (l < p.tok_layers) {
+      const int nlt = (p.tok_layers - l) < 8 ? (p.tok_layers - l) : 8;
+      float* xo = (cin == w.xa) ? w.xb2 : w.xa;
+      if (ring_in)
+        SF_TRY(sf_layer_tok_ex(l == 0 ? 1 : 0, cin, w.ring, RF, N, f0, pe, m->layers + l, nlt, eps, xo, B, L, st));
+      else
+        SF_TRY(sf_layer_tok_ex(0, cin, nullptr, 1, 1, 0, nullptr, m->layers + l, nlt, eps, xo, B, L, st));
+      cin = xo;
+      l += nlt;
+    }
+    if (!p.fused()) {
+      int Lc = L;
+      for (; l < nl; ++l) {
+        const int Lq = (l == nl - 1 && m->norm_first) ? N : Lc;
+        SF_TRY(tfm_layer(m->layers[l], cin, w.tw, B, Lc, Lq, d, m->num_heads, m->ffn_dim, m->norm_first, st, &cin,
+                         long_ffn ? w.xpb : nullptr, long_ffn ? w.counters : nullptr));
+        Lc = Lq;
       }
-      SF_TRY(sf_linear_ex(cin, sf_rows(d), m->out_proj_w, m->out_proj_b, nullptr, nullptr, 0.f, nullptr, sf_rows(C), 0,
+      // pred = out_proj(x[:, -N:]) written straight into frame n_in + s   (slotformer.py:121-124)
+      const SfRowMap lastmap = (Lc == N) ? sf_rows(d) : sf_rows_batched(d, N, (long long)Lc * d, (long long)(Lc - N) * d);
+      SF_TRY(sf_linear_ex(cin, lastmap, m->out_proj_w, m->out_proj_b, nullptr, nullptr, 0.f, nullptr, sf_rows(C), 0,
                           slots, sf_rows_batched(C, N, bs, (long long)(n_in + s) * N * C), B * N, C, d, 0, st));
       continue;
     }
-    float* cur = x;
-    int Lc = L;
-    int l0 = 0;
-    if (long_tok) {
-      // windows of 65..96 tokens (the reference's Physion window, slotformer_physion_params.py: 15 frames x 6 slots): the layers before the last as
-      // token-stationary launches of one video per workgroup, up to eight layers per launch; the row-pruned last layer in the long-window forms below
-      while (l0 + 1 < m->num_layers) {
-        const int nlt = (m->num_layers - 1 - l0) < 8 ? (m->num_layers - 1 - l0) : 8;
-        float* xo = (cur == xa) ? xb2 : xa;
-        SF_TRY(sf_layer_tok_ex(0, cur, nullptr, 1, 1, 0, nullptr, m->layers + l0, nlt, 1e-5f, xo, B, L, st));
-        cur = xo;
-        l0 += nlt;
+    // every other layer is two launches: the attention block, then the FFN block (which also finishes the sums)
+    bool parts_in = false;     // the current layer's input is the previous layer's four FFN chunk partials in xpb
+    float* parked = nullptr;   // TILE_QKV: where the previous layer's launch parked this layer's residual rows (planes written)
+    for (; l < nl; ++l) {
+      const sf_tfm_layer& lw = m->layers[l];
+      const bool lastl = (l == nl - 1);
+      const int Lq = lastl ? N : L;   // last layer: only the newest frame's rows are read (slotformer.py:121)
+      const long long pst = (long long)B * Lq * d;
+      float* xo = (cin == w.xa) ? w.xb2 : w.xa;
+      float* ap = (l == 0) ? ap0 : w.apb;   // the attention block's output
+      if (parked) {
+        ap = parked;
+        SF_TRY(sf_attn_core_ex(lw, ap, w.planes, B, L, Lq, st));
+      } else if (p.attn == RolloutPlan::ROW_TILES) {
+        if (l == 0 && ring_in)
+          SF_TRY(sf_attn_rows_ex(2, w.ring, (long long)RF * N * d, 0, pe, f0, RF, N, lw, eps, ap, w.planes, B, L, Lq, st));
+        else if (parts_in)
+          SF_TRY(sf_attn_rows_ex(1, w.xpb, (long long)L * d, (long long)B * L * d, nullptr, 0, 1, 1, lw, eps, ap, w.planes, B, L, Lq, st));
+        else
+          SF_TRY(sf_attn_rows_ex(0, cin, (long long)L * d, 0, nullptr, 0, 1, 1, lw, eps, ap, w.planes, B, L, Lq, st));
+      } else if (p.attn == RolloutPlan::ALL_HEADS) {
+        if (l == 0 && ring_in)
+          SF_TRY(sf_attn_all_ring_ex(w.ring, RF, N, f0, pe, lw, eps, ap, B, L, Lq, st));
+        else if (parts_in)
+          SF_TRY(sf_attn_all_parts_ex(w.xpb, (long long)B * L * d, lw, eps, ap, B, L, Lq, st));
+        else
+          SF_TRY(sf_attn_all_ex(cin, lw, eps, ap, B, L, Lq, st));
+      } else if (l == 0 && ring_in) {
+        if (!attn0_done) SF_TRY(sf_attn_oproj_ring_ex(w.ring, RF, N, f0, pe, lw, eps, ap, pst, B, L, Lq, st));
+      } else if (parts_in) {
+        SF_TRY(sf_attn_oproj_parts_ex(w.xpb, (long long)B * L * d, lw, eps, ap, pst, B, L, Lq, st));
+      } else {
+        SF_TRY(sf_attn_oproj_ex(cin, lw, eps, ap, pst, B, L, Lq, st));
+      }
+      if (!lastl) {
+        if (p.ffn == RolloutPlan::TILE_QKV) {
+          float* park = (ap == w.apb) ? apb2 : w.apb;
+          SF_TRY(sf_ffn_qkv_tile_ex(ap, lw, m->layers[l + 1], eps, park, w.planes, B, L, (l + 1 == nl - 1) ? N : L, m->ffn_dim, st));
+          parked = park;
+          cin = nullptr;
+        } else if (p.ffn == RolloutPlan::TILE) {
+          SF_TRY(sf_ffn_tile_ex(ap, lw, eps, xo, B * Lq, m->ffn_dim, st));
+          cin = xo;
+        } else {
+          // the chunk partials are the layer output: the next attention sums them
+          SF_TRY(sf_ffn_parts_ex(ap, pst, lw, eps, w.xpb, pst, B * Lq, m->ffn_dim, st, np));
+          cin = nullptr;
+        }
+        parts_in = p.ffn == RolloutPlan::CHUNK_PARTS;
+      } else if (ring_in) {
+        // last layer: FFN + step boundary in one launch.  pred = out_proj(last rows) -> frame n_in + s; its
+        // in-projection -> the ring   (slotformer.py:121-124, :115)
+        int nf1 = 0, f01 = 0;
+        if (s + 1 < pred_len) step_window(m, s + 1, nf1, f01);
+        if (p.seam && s + 1 < pred_len && sf_seam_window_ok(nf1 * N, N)) {
+          // ... and the layer-0 attention of step s + 1 in the same grid
+          const int L1 = nf1 * N, Lq1 = (nl == 1) ? N : L1;
+          float* ap_next = (ap == w.apb) ? apb2 : w.apb;
+          SF_TRY(sf_seam_ex(ap, pst, lw, eps, w.xpb, pst, w.counters, m->ffn_dim, m->out_proj_packed, m->out_proj_b,
+                            m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s, w.ring, RF, N, B, m->layers[0], f01,
+                            m->pe_tok + (long long)((W - nf1) * N) * d, ap_next, (long long)B * Lq1 * d, L1, Lq1, w.seam_flags,
+                            (unsigned)(s + 1), st));
+          ap0 = ap_next;
+          attn0_done = true;
+        } else {
+          SF_TRY(sf_ffn_boundary_ex(ap, pst, lw, eps, w.xpb, pst, w.counters, m->ffn_dim, m->out_proj_packed, m->out_proj_b,
+                                    m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s, w.ring, RF, N, B, st, np));
+          ap0 = w.apb;
+          attn0_done = false;
+        }
+      } else {
+        // last layer: FFN into finished rows, then pred = out_proj(them) written straight into frame n_in + s
+        SF_TRY(sf_ffn_partial_ex(ap, pst, lw, eps, w.xpb, pst, xo, w.counters, B * Lq, m->ffn_dim, st, np));
+        SF_TRY(sf_linear_ex(xo, sf_rows(d), m->out_proj_w, m->out_proj_b, nullptr, nullptr, 0.f, nullptr, sf_rows(C), 0,
+                            slots, sf_rows_batched(C, N, bs, (long long)(n_in + s) * N * C), B * N, C, d, 0, st));
       }
     }
-    for (int l = l0; l < m->num_layers; ++l) {
-      const bool last = (l == m->num_layers - 1);
-      const int Lq = (last && m->norm_first) ? N : Lc;
-      float* outp = nullptr;
-      SF_TRY(tfm_layer(m->layers[l], cur, tw, B, Lc, Lq, d, m->num_heads, m->ffn_dim, m->norm_first, st, &outp,
-                       long_ffn ? xpb : nullptr, long_ffn ? counters : nullptr));
-      cur = outp;
-      Lc = Lq;
-    }
-    // pred = out_proj(x[:, -N:]) written straight into frame n_in + s   (slotformer.py:121-124)
-    const SfRowMap lastmap =
-        (Lc == N) ? sf_rows(d) : sf_rows_batched(d, N, (long long)Lc * d, (long long)(Lc - N) * d);
-    SF_TRY(sf_linear_ex(cur, lastmap, m->out_proj_w, m->out_proj_b, nullptr, nullptr, 0.f, nullptr, sf_rows(C), 0,
-                        slots, sf_rows_batched(C, N, bs, (long long)(n_in + s) * N * C), B * N, C, d, 0, st));
   }
   return 0;
 }
@@ -580,6 +503,21 @@ struct OptsScope {
   explicit OptsScope(const SfThreadOpts& o) : saved(sf_thread_opts()) { sf_thread_opts() = o; }
   ~OptsScope() { sf_thread_opts() = saved; }
 };
+
+// the thread options a rollout with per-call options `opts` runs under (NULL: the calling thread's own)
+SfThreadOpts rollout_thread_opts(const sf_rollout_opts* opts) {
+  SfThreadOpts o = sf_thread_opts();
+  if (!opts) return o;
+  if (opts->precision >= 0) o.precision = opts->precision;
+  if (opts->seam_fused >= 0) o.seam = opts->seam_fused ? 1 : 0;
+  if (opts->ffn_rows > 0) o.ffn_rows = opts->ffn_rows;
+  if (opts->attn_heads_per_wg > 0) o.attn_heads = opts->attn_heads_per_wg;
+  if (opts->attn_qkv_rows > 0) o.attn_rows = opts->attn_qkv_rows;
+  if (opts->ffn_tile > 0) o.ffn_tile = opts->ffn_tile;
+  if (opts->cus_available > 0) o.cus = opts->cus_available;
+  if (opts->layer_tok != 0) o.layer_tok = opts->layer_tok > 0 ? 1 : -1;
+  return o;
+}
 }  // namespace
 
 // sf_rollout_f32 with per-call options (include/slotformer_hip.h, sf_rollout_opts): arithmetic mode, seam launches, rows
@@ -596,69 +534,35 @@ int sf_rollout_opts_f32(const sf_rollouter* m, float* slots, int B, int T_total,
   SF_REQUIRE(opts->attn_qkv_rows == 0 || opts->attn_qkv_rows == 128, "sf_rollout_opts: attn_qkv_rows must be 0 (off) or 128");
   SF_REQUIRE(opts->ffn_tile >= 0 && opts->ffn_tile <= 2, "sf_rollout_opts: ffn_tile must be 0, 1 or 2");
   SF_REQUIRE(opts->cus_available >= 0 && opts->cus_available <= 256, "sf_rollout_opts: cus_available must be 0 (whole chip) .. 256");
-  SfThreadOpts o = sf_thread_opts();
-  if (opts->precision >= 0) o.precision = opts->precision;
-  if (opts->seam_fused >= 0) o.seam = opts->seam_fused ? 1 : 0;
-  if (opts->ffn_rows > 0) o.ffn_rows = opts->ffn_rows;
-  if (opts->attn_heads_per_wg > 0) o.attn_heads = opts->attn_heads_per_wg;
-  if (opts->attn_qkv_rows > 0) o.attn_rows = opts->attn_qkv_rows;
-  if (opts->ffn_tile > 0) o.ffn_tile = opts->ffn_tile;
-  if (opts->cus_available > 0) o.cus = opts->cus_available;
-  if (opts->layer_tok != 0) o.layer_tok = opts->layer_tok > 0 ? 1 : -1;
-  OptsScope scope(o);
-  const bool plain = (o.precision == 2 || o.precision == 3);
-  const bool old_plain = t_plain_gemms;
-  if (plain) t_plain_gemms = true;
-  const int rc = sf_rollout_f32(m, slots, B, T_total, pred_len, ws, ws_bytes, stream);
-  t_plain_gemms = old_plain;
-  return rc;
+  OptsScope scope(rollout_thread_opts(opts));
+  return sf_rollout_f32(m, slots, B, T_total, pred_len, ws, ws_bytes, stream);
 }
 
 // 1 when sf_rollout_f32 runs this model's layers as the two fused launches of layer_fused.hip (per-video / per-row kernels whose
 // results do not depend on how videos are grouped into batches); 0: the generic GEMM path, whose tile / split-K choice -- and
 // with it the summation order -- follows the batch size
-int sf_rollout_is_fused(const sf_rollouter* m) {
-  if (!m || !m->layers) return 0;
-  bool packed = true;
-  for (int l = 0; l < m->num_layers; ++l)
-    packed = packed && m->layers[l].lin1_packed && m->layers[l].lin2_packed && m->layers[l].attn_in_packed && m->layers[l].attn_out_packed;
-  return packed && sf_get_precision() >= 1 && m->norm_first && sf_layer_fused_ok(m->d_model, m->num_heads, m->ffn_dim, m->window_len * m->num_slots);
-}
+int sf_rollout_is_fused(const sf_rollouter* m) { return plan_rollout(m, 1, sf_thread_opts()).fused(); }
 
-// 1 when sf_rollout_f32 can run this model's layers before the last as token-stationary launches (sf_rollout_opts.layer_tok): the fused-layer path,
-// sf_pack_layer_tok_weights fragments on every layer but the last, every window of the rollout inside the kernel's key-block limit
+// 1 when sf_rollout_f32 can run this model's layers before the last as token-stationary launches (sf_rollout_opts.layer_tok): the
+// fused-layer path with layer_tok on takes them
 int sf_rollout_tok_ok(const sf_rollouter* m) {
-  if (!sf_rollout_is_fused(m) || m->num_layers < 2) return 0;
-  for (int l = 0; l + 1 < m->num_layers; ++l)
-    if (!m->layers[l].tok_packed) return 0;
-  for (int nf = m->single_step ? 1 : m->window_len; nf <= m->window_len; ++nf)
-    if (!sf_layer_tok_ok(nf * m->num_slots)) return 0;
-  return 1;
+  SfThreadOpts o = sf_thread_opts();
+  o.layer_tok = 1;
+  const RolloutPlan p = plan_rollout(m, 1, o);
+  return p.fused() && p.tok_layers > 0;
 }
 
-// 1 when sf_rollout_f32 would use seam launches for this model / batch with the calling thread's defaults (a caller that
-// wants to verify sf_seam_timeouts() after the call only needs to when this is non-zero)
+// 1 when sf_rollout_f32 with these options may launch seams for this model / batch (a caller that wants to verify
+// sf_seam_timeouts() after the call only needs to when this is non-zero)
 int sf_rollout_uses_seam_opts(const sf_rollouter* m, int B, const sf_rollout_opts* opts) {
-  if (!m || B <= 0 || !m->layers) return 0;
-  bool packed = m->in_proj_packed && m->out_proj_packed;
-  for (int l = 0; l < m->num_layers; ++l)
-    packed = packed && m->layers[l].lin1_packed && m->layers[l].lin2_packed && m->layers[l].attn_in_packed && m->layers[l].attn_out_packed;
-  // the call's own options where given (a CU-masked caller: cus_available bounds the grid a seam launch may have), else the thread's defaults
-  int seam_opt = sf_thread_opts().seam, cus = sf_thread_opts().cus, attn_heads = sf_thread_opts().attn_heads, attn_rows = sf_thread_opts().attn_rows;
-  int tok = sf_thread_opts().layer_tok;
-  if (opts) {
-    if (opts->seam_fused >= 0) seam_opt = opts->seam_fused ? 1 : 0;
-    if (opts->cus_available > 0) cus = opts->cus_available;
-    if (opts->attn_heads_per_wg > 0) attn_heads = opts->attn_heads_per_wg;
-    if (opts->attn_qkv_rows > 0) attn_rows = opts->attn_qkv_rows;
-    if (opts->layer_tok != 0) tok = opts->layer_tok > 0 ? 1 : -1;
+  if (B <= 0 || !plan_rollout(m, B, rollout_thread_opts(opts)).seam) return 0;
+  // the seam launch at the end of step s runs in the window of step s + 1
+  for (int s = 1; s <= m->window_len; ++s) {
+    int nf, f0;
+    step_window(m, s, nf, f0);
+    if (sf_seam_window_ok(nf * m->num_slots, m->num_slots)) return 1;
   }
-  const int cap = cus > 0 && cus < 160 ? cus : 160;
-  const bool tok_on = (tok > 0 || (tok == 0 && sf_get_layer_tok() != 0)) && sf_rollout_tok_ok(m);
-  return packed && sf_get_precision() >= 1 && m->norm_first &&
-         sf_layer_fused_ok(m->d_model, m->num_heads, m->ffn_dim, m->window_len * m->num_slots) &&
-         sf_step_boundary_ok(m->d_model, m->slot_size) && (seam_opt >= 0 ? seam_opt != 0 : sf_get_seam_fused() != 0) &&
-         sf_seam_blocks(B, m->num_slots) <= cap && attn_heads != 8 && attn_rows != 128 && !tok_on;
+  return 0;
 }
 int sf_rollout_uses_seam(const sf_rollouter* m, int B) { return sf_rollout_uses_seam_opts(m, B, nullptr); }
 
@@ -1166,7 +1070,7 @@ int sf_savi_encode_fork_f32(const sf_savi_encoder* m, const float* img, const fl
       } else {
         // Transformer predictor (+ LSTM wrapper) in one launch (pred_step.hip) when its packed weights are there
         int pstep = 1;
-        if (m->pred_type == 1 && m->pred_packed && sf_get_precision() >= 1 && !t_plain_gemms)
+        if (m->pred_type == 1 && m->pred_packed && sf_get_precision() >= 1)
           pstep = sf_pred_step_ex(prev, m->pred_layers, m->pred_num_layers, m->pred_num_heads, m->pred_ffn_dim, m->pred_norm_first,
                                   m->pred_packed, m->lstm_b_ih, m->lstm_b_hh, m->proj_b, m->pred_hidden, m->pred_rnn ? lstm_h : nullptr,
                                   m->pred_rnn ? lstm_c : nullptr, latents, B, N, D, 1e-5f, st);

@@ -43,11 +43,8 @@ int sf_attn_rows_ex(int mode, const float* xin, long long x_batch_stride, long l
                     hipStream_t st);
 int sf_attn_oproj_ring_ex(const float* ring, int ring_frames, int nslots, int f0, const float* pe, const sf_tfm_layer& w,
                           float eps, float* ap, long long ap_stride, int B, int L, int Lq, hipStream_t st);
-// out-proj of the finished rows y [B*nslots, 256] -> slots frame `frame`; in-proj of those rows -> projection ring
+// shapes of the step-boundary kernel: out-proj of a step's finished rows -> its slots frame, in-proj of those -> the projection ring
 bool sf_step_boundary_ok(int d, int slot_size);
-int sf_step_boundary_ex(const float* y, const void* wout_packed, const float* b_out, const void* win_packed,
-                        const float* b_in, float* slots, long long slots_bs, int frame, float* ring, int ring_frames,
-                        int nslots, int B, hipStream_t st);
 // ap: 8 head partials [M, 256] -> xout [M, 256] (finished layer output); xp: scratch for the 4 hidden-chunk partials
 // [4][M, 256]; counters: sf_ffn_tiles(M) ints, zero before the first launch (the kernel leaves them zero)
 int sf_ffn_partial_ex(const float* ap, long long ap_stride, const sf_tfm_layer& w, float eps, float* xp,

@@ -2185,15 +2185,6 @@ static int launch_boundary(const float* y, const SbArgs& sb, int M, int proj_onl
   return 0;
 }
 
-// frame index `frame` of the [B][T][N][128] slots buffer (slots_bs floats per video) and of the projection ring
-int sf_step_boundary_ex(const float* y, const void* wout_packed, const float* b_out, const void* win_packed,
-                        const float* b_in, float* slots, long long slots_bs, int frame, float* ring, int ring_frames,
-                        int nslots, int B, hipStream_t st) {
-  const SbArgs sb = make_sb(wout_packed, b_out, win_packed, b_in, slots, slots_bs, (long long)frame * nslots * SB_C, ring,
-                            (long long)ring_frames * nslots * LF_D, (long long)(frame % ring_frames) * nslots * LF_D, nslots);
-  return launch_boundary(y, sb, B * nslots, 0, st);
-}
-
 // in-projection of the first n_frames (<= ring_frames) frames of every video -> ring slots 0 .. n_frames-1
 int sf_ring_init_ex(const void* wout_packed, const float* b_out, const void* win_packed, const float* b_in, float* slots,
                     long long slots_bs, int n_frames, float* ring, int ring_frames, int nslots, int B, hipStream_t st) {
