@@ -631,7 +631,8 @@ int sf_savi_encode_pre_f32(const sf_savi_encoder* m, const float* img, const flo
 size_t sf_savi_encode_fork_workspace_bytes(const sf_savi_encoder* m, int B, int T);
 /* Workspace of the one-stream encode (side_stream NULL) that runs the 64 -> 64 convolutions of ALL T time steps as one launch per layer (three
  * buffers of B * T frames on top of sf_savi_encode_workspace_bytes): sf_savi_encode_fork_f32 takes that form when it is handed this much and the
- * encoder has fragment weights on every layer behind the first (B <= 32, T >= 2, split-bf16); the same bits as the step-by-step order. */
+ * encoder has fragment weights on every layer behind the first (B <= 32, T >= 2, split-bf16); the same bits as the step-by-step order.  Only while
+ * sf_set_slot_chain(1) is on and sf_savi_chain_ok holds does it also hold the feature planes of the video-stationary slot branch (below). */
 size_t sf_savi_encode_batched_workspace_bytes(const sf_savi_encoder* m, int B, int T);
 /* Where the slot prologue of time step t + 1 runs (process-wide; default 1).  1: with the packed predictor / kernel-distribution
  * copies of sf_savi_encoder (pm_w0_p, pm_w2_p, kd_w0_p) and the matrix-core slot update, at the tail of step t's last slot update -- one launch fewer per
@@ -639,7 +640,7 @@ size_t sf_savi_encode_batched_workspace_bytes(const sf_savi_encoder* m, int B, i
  * two agree to split-bf16 rounding (~1e-6 relative), not bit for bit; step 0 of a call always takes the stand-alone launch. */
 int sf_set_encode_fuse_next(int on);
 int sf_get_encode_fuse_next(void);
-/* The slot branch of a batched encode (all T steps' convolutions per launch, sf_savi_encode_batched_workspace_bytes) as ONE video-stationary launch
+/* The slot branch of a batched encode (all T steps' convolutions per launch, sf_savi_encode_batched_workspace_bytes queried while on) as ONE video-stationary launch
  * (csrc/slot_chain.hip; savi.py:76-100, 393-402): one workgroup per video walks the T steps x num_iterations Slot-Attention iterations, their slot
  * updates and the per-step prologues on feature rows kept as bf16 hi | lo -- 7 launches per encode instead of ~60.  OPT-IN: process default 0
  * (sf_set_slot_chain(1)).  Measured (profiles/r06_probes.txt): 0.80 ms per batch of 32 videos x 6 frames on 32 CUs against 0.58 ms for
@@ -666,7 +667,7 @@ int sf_get_pixel_tok(void);
  *     videos from planes [NB][T][B][64 * 64][512 B]: noise NULL or [NB * B][T][N][D], prev_slots NULL or [NB * B][N][D]; video v's slots of step t ->
  *     post + v * post_bs + t * N * D (post_bs in floats: a [NB * B][T + H][N][D] rollout buffer takes them in place); kernel_dist NULL or
  *     [NB * B][T][N][2 D]; attn NULL or [NB * B][T][N][64 * 64]; workspace sf_savi_slots_chain_workspace_bytes(m, NB * B).
- * The two in sequence are what sf_savi_encode_f32 runs when it is given sf_savi_encode_batched_workspace_bytes: the same bits. */
+ * The two in sequence give the bits of a batched sf_savi_encode_f32 under sf_set_slot_chain(1); the default (0) differs by split-bf16 rounding. */
 int sf_savi_chain_ok(const sf_savi_encoder* m, int B, int T);
 size_t sf_savi_planes_bytes(const sf_savi_encoder* m, int B, int T);
 size_t sf_savi_features_workspace_bytes(const sf_savi_encoder* m, int B, int T);

@@ -573,90 +573,155 @@ int sf_rollout_bf16(const sf_rollouter* m, float* slots, int B, int T_total, int
 }
 
 // ---------------------------------------------------------------------------------------------
-static int enc_chunk(int B) { return B < 32 ? B : 32; }
+}  // extern "C"
 
-// the slot branch of a batched encode as one video-stationary launch (slot_chain.hip): OPT-IN (sf_set_slot_chain(1)); the default keeps
-// the per-iteration launches (Slot-Attention iteration over the batch + slot update), which are faster for a batch alone on its CUs
-static int g_slot_chain = 0;
-int sf_get_slot_chain(void) { return g_slot_chain; }
-// the Slot-Attention iterations of the per-step encode on feature rows kept as bf16 hi | lo (sa_attn_planes_kernel, slot_chain.hip: split-bf16 16x16x32
-// MFMAs) instead of f32 rows and the exact-f32 tile kernel: process default below; sf_set_slot_attn_planes(0 / 1)
-static int g_sa_planes = 1;
-int sf_get_slot_attn_planes(void) { return g_sa_planes; }
-int sf_set_slot_attn_planes(int on) {
-  g_sa_planes = on ? 1 : 0;
-  return 0;
-}
-int sf_set_slot_chain(int on) {
-  g_slot_chain = on ? 1 : 0;
-  return 0;
-}
-
-// the slot prologue of step t + 1 at the tail of step t's last slot update (slot_update_mfma.hip, NEXT form): on by default where it applies;
-// sf_set_encode_fuse_next(0): the prologue as its own launch (sa_slot_prologue_kernel) on every step
-static int g_enc_fuse_next = -1;
-int sf_set_encode_fuse_next(int on) {
-  g_enc_fuse_next = on ? 1 : 0;
-  return 0;
-}
-int sf_get_encode_fuse_next(void) {
-  if (g_enc_fuse_next < 0) {
-    g_enc_fuse_next = 1;
-  }
-  return g_enc_fuse_next;
-}
-
-static size_t enc_ws_bytes(const sf_savi_encoder* m, int B, int kv_steps);
-size_t sf_savi_encode_workspace_bytes(const sf_savi_encoder* m, int B) { return enc_ws_bytes(m, B, 2); }   // (two: the interleaved order below)
+// StoSAVi.encode / STEVE.encode
+namespace {
+int enc_chunk(int B) { return B < 32 ? B : 32; }
 // the forked form keeps the Slot-Attention inputs of up to ENC_FORK_AHEAD time steps (the feature branch runs that far ahead of the slot branch)
-static constexpr int ENC_FORK_AHEAD = 4;
-static int enc_fork_steps(int T) { return T < 2 ? 2 : (T < ENC_FORK_AHEAD ? T : ENC_FORK_AHEAD); }
-size_t sf_savi_encode_fork_workspace_bytes(const sf_savi_encoder* m, int B, int T) { return T >= 1 ? enc_ws_bytes(m, B, enc_fork_steps(T)) : 0; }
-// One-stream encode with the convolutions of ALL T time steps as one launch per layer (the weights-stationary kernel of conv_ws.hip pays its 410 KB of
-// weights per workgroup once per launch: 81 instead of 99 us per time step and layer on a 128-CU partition): the activations of B * T frames in three
-// buffers on top of sf_savi_encode_workspace_bytes.  sf_savi_encode_fork_f32 (side_stream NULL) takes this form when it is handed that much workspace.
-static size_t enc_batched_extra(const sf_savi_encoder* m, int B, int T) {
+constexpr int ENC_FORK_AHEAD = 4;
+int enc_fork_steps(int T) { return T < 2 ? 2 : (T < ENC_FORK_AHEAD ? T : ENC_FORK_AHEAD); }
+constexpr int ENC_HW = 64 * 64;   // pixels of the encoder's feature maps (savi.py:226)
+
+// channels of the widest CNN layer output
+int enc_cmax(const sf_savi_encoder* m) {
   int cmax = 0;
   for (int i = 1; i <= m->enc_layers && i < 9; ++i) cmax = m->enc_channels[i] > cmax ? m->enc_channels[i] : cmax;
-  // + the Slot-Attention inputs of all B * T frames as bf16 hi | lo rows of 512 B (the video-stationary slot branch, slot_chain.hip)
-  return 3 * pad256((size_t)B * T * 64 * 64 * cmax) + pad256((size_t)B * T * 64 * 64 * 128);
+  return cmax;
 }
-static bool enc_batched_ok(const sf_savi_encoder* m, int B, int T) {
+// n CNN activation buffers of `frames` frames each
+void enc_cnn_take(Bump& bp, float** buf, int n, const sf_savi_encoder* m, size_t frames) {
+  for (int i = 0; i < n; ++i) buf[i] = bp.take(frames * ENC_HW * enc_cmax(m));
+}
+
+// the slot branch's four [rows][D] buffers: ping-pong slots, the predictor's latents, q (the video-stationary launch's row buffers too)
+struct SlotRows { float *a, *b, *lat, *q; };
+void slot_rows_take(Bump& bp, SlotRows& r, size_t rows, int D) {
+  for (float** f : {&r.a, &r.b, &r.lat, &r.q}) *f = bp.take(rows * D);
+}
+
+// How sf_savi_encode_fork_f32 runs a call, chosen once from the encoder's shape, which weights and packed copies it has (their presence only: no
+// weight is read, so a plan is made without a GPU), the process defaults and the size of the caller's workspace
+struct EncodePlan {
+  bool fork = false;   // two branches: the features on `stream`, the slot branch one step behind on `side_stream`
+  int KV = 2;          // resident Slot-Attention inputs: a ring of KV time steps
+  // the CNN features of step t: precomputed (t < n_pre), from the convolutions of all T steps as one launch per layer (batched), or per step
+  int n_pre = 0;
+  bool batched = false;
+  // Slot-Attention inputs, which also fix the iteration's form.  KV_*: k|v rows of 2 D, by three GEMMs or sf_pixel_mlp_kv_ex where that applies.
+  // FOLD_*: k / v folded into project_q and the GRU input matrix (include/slotformer_hip.h, sa_fold_*), keys == values = the normalised features
+  // as f32 rows (192: the 192-wide chain as one launch) or as bf16 hi | lo rows of 512 B (sa_attn_planes_kernel)
+  enum Feat { KV_GEMMS, KV_FUSED, FOLD_ROWS, FOLD_192, FOLD_PLANES } feat = KV_GEMMS;
+  // project_q and GRU input weights of that form
+  const float *q_w = nullptr, *q_w_t = nullptr, *gru_ih_t = nullptr;
+  const void *q_w_p = nullptr, *gru_ih_p = nullptr;
+  // slot update on the matrix cores from packed copies (slot size 128: slot_update_mfma.hip; 192: slot_update_wide.hip), else the VALU kernel.
+  // p_step 2: the update reads every second partial record (the one-pass iteration kernels leave the others zero -- eight, one round of requests)
+  enum Update { VALU, WIDE, MFMA } update = VALU;
+  int p_step = 1;
+  bool pred_step = false;     // the Transformer predictor (+ LSTM) tried as one launch (pred_step.hip)
+  bool prologue = false;      // the one-launch slot prologue (CLEVRER configuration: residual-MLP predictor, one-Linear kernel distribution)
+  bool fuse_next = false;     // ... of step t + 1 at the tail of step t's last slot update (slot_update_mfma.hip, NEXT form)
+  bool chain_model = false;   // the model runs the video-stationary slot branch (slot_chain.hip)
+  bool chain = false;         // ... and this call does: batched, sf_set_slot_chain(1), room for the feature planes
+  bool fold() const { return feat >= FOLD_ROWS; }
+};
+
+// The encode workspace of a plan (over a NULL base: its size)
+struct EncodeWs {
+  float* feat[2];         // CNN activations of up to 32 frames, ping-pong
+  float *h1, *h2;         // encoder_out_layer rows of the three-GEMM k|v
+  float* kv;              // the Slot-Attention inputs of KV time steps, B * 64 * 64 * 2 D floats each
+  SlotRows rows;
+  float *lnbuf, *px;      // predictor rows
+  float *kdist, *kdtmp;   // kernel distribution rows
+  float *pnum, *pden;     // partial records of an iteration
+  TfmWs tw;               // Transformer predictor
+  float* gates;           // LSTM gates
+  float* big[3];          // batched: CNN activations of all B * T frames
+  float* planes;          // chain: their Slot-Attention inputs as bf16 hi | lo rows of 512 B
+};
+
+bool enc_ws_take(Bump& bp, EncodeWs& w, const sf_savi_encoder* m, int B, int T, const EncodePlan& p) {
+  const int N = m->num_slots, D = m->slot_size, Ce = m->enc_out_channels, P = sf_sa_pick_partials(ENC_HW);
+  const size_t R = (size_t)B * N, Bc = enc_chunk(B), HW = ENC_HW;
+  enc_cnn_take(bp, w.feat, 2, m, Bc);
+  w.h1 = bp.take(Bc * HW * Ce);
+  w.h2 = bp.take(Bc * HW * Ce);
+  w.kv = bp.take((size_t)p.KV * B * HW * 2 * D);
+  slot_rows_take(bp, w.rows, R, D);
+  w.lnbuf = bp.take(R * D);
+  w.px = bp.take(R * D);
+  w.kdist = bp.take(R * 2 * D);
+  w.kdtmp = bp.take(R * 2 * D);
+  w.pnum = bp.take((size_t)B * P * N * D);
+  w.pden = bp.take((size_t)B * P * N);
+  tfm_ws_take(bp, w.tw, (int)R, D, m->pred_ffn_dim > 2 * D ? m->pred_ffn_dim : 2 * D);
+  w.gates = bp.take(R * 4 * (m->pred_hidden > 0 ? m->pred_hidden : 1));
+  if (p.batched) enc_cnn_take(bp, w.big, 3, m, (size_t)B * T);
+  if (p.chain) w.planes = bp.take((size_t)B * T * HW * 128);
+  return bp.ok;
+}
+
+size_t enc_ws_bytes(const sf_savi_encoder* m, int B, int T, const EncodePlan& p) {
+  Bump bp{nullptr, ~(size_t)0};
+  EncodeWs w;
+  enc_ws_take(bp, w, m, B, T, p);
+  return bp.used + 8192;
+}
+
+bool enc_batched_ok(const sf_savi_encoder* m, int B, int T, int precision) {
   // (at most 384 frames per call: 1.2 GB of activations + 0.8 GB of feature rows; longer clips keep the per-step order)
-  if (!m || T < 2 || B > enc_chunk(B) || (long long)B * T > 384 || m->enc_layers < 2 || sf_get_precision() != 1) return false;
+  if (T < 2 || B > enc_chunk(B) || (long long)B * T > 384 || m->enc_layers < 2 || precision != 1) return false;
   for (int i = 1; i < m->enc_layers; ++i)
     if (!m->conv_w_frag[i] || m->enc_channels[i] != 64 || m->enc_channels[i + 1] != 64) return false;
   return true;
 }
-size_t sf_savi_encode_batched_workspace_bytes(const sf_savi_encoder* m, int B, int T) {
-  if (!m || B <= 0 || T <= 0) return 0;
-  return enc_ws_bytes(m, B, 2) + (enc_batched_ok(m, B, T) ? enc_batched_extra(m, B, T) : 0);
-}
 
-static size_t enc_ws_bytes(const sf_savi_encoder* m, int B, int kv_steps) {
-  if (!m || B <= 0) return 0;
-  const size_t HW = 64 * 64;
-  int cmax = 0;
-  for (int i = 1; i <= m->enc_layers && i < 9; ++i) cmax = m->enc_channels[i] > cmax ? m->enc_channels[i] : cmax;
-  const int Bc = enc_chunk(B), N = m->num_slots, D = m->slot_size, Ce = m->enc_out_channels;
-  const int P = sf_sa_pick_partials((int)HW);
-  const int R = B * N;
-  const int hidp = m->pred_ffn_dim > 2 * D ? m->pred_ffn_dim : 2 * D;
-  size_t t = 0;
-  t += 2 * pad256((size_t)Bc * HW * cmax);
-  t += 2 * pad256((size_t)Bc * HW * Ce);
-  t += pad256((size_t)kv_steps * B * HW * 2 * D);
-  t += 6 * pad256((size_t)R * D) + 2 * pad256((size_t)R * 2 * D);
-  t += pad256((size_t)B * P * N * D) + pad256((size_t)B * P * N);
-  t += tfm_ws_bytes(R, D, hidp) + pad256((size_t)R * 4 * (m->pred_hidden > 0 ? m->pred_hidden : 1));
-  return t + 8192;
+EncodePlan plan_encode(const sf_savi_encoder* m, int B, int T, int n_pre, bool fork, size_t ws_bytes) {
+  EncodePlan p;
+  p.fork = fork;
+  p.KV = fork ? enc_fork_steps(T) : 2;
+  p.n_pre = n_pre;
+  if (!m || m->enc_layers < 1 || m->enc_layers > 8) return p;
+  const int precision = sf_get_precision();
+  const int HW = ENC_HW, N = m->num_slots, D = m->slot_size, Ce = m->enc_out_channels, Hm = m->slot_mlp_size, P = sf_sa_pick_partials(HW);
+  const int Cl = m->enc_channels[m->enc_layers];
+  const bool feat192 = Cl == 64 && Ce == 192 && m->enc_fc1_p && m->enc_fc2_p;
+  const bool fold = precision >= 1 && m->sa_fold_q_w && m->sa_fold_q_w_t && m->sa_fold_gru_ih_t && Ce == D && (sf_pixel_mlp_feat_ok(Cl, Ce) || feat192);
+  const bool planes = fold && !feat192 && sf_get_slot_attn_planes() && sf_slot_attn_planes_ok(HW, D, N) && Cl == 64 && P == HW / 256;
+  p.feat = fold ? (feat192 ? EncodePlan::FOLD_192 : planes ? EncodePlan::FOLD_PLANES : EncodePlan::FOLD_ROWS)
+                : (precision >= 1 ? EncodePlan::KV_FUSED : EncodePlan::KV_GEMMS);
+  p.q_w = fold ? m->sa_fold_q_w : m->sa_q_w;
+  p.q_w_t = fold ? m->sa_fold_q_w_t : m->sa_q_w_t;
+  p.gru_ih_t = fold ? m->sa_fold_gru_ih_t : m->gru_w_ih;
+  p.q_w_p = fold ? m->sa_fold_q_w_p : m->sa_q_w_p;
+  p.gru_ih_p = fold ? m->sa_fold_gru_ih_p : m->sa_gru_ih_p;
+  const bool su_packed = precision >= 1 && p.gru_ih_p && m->sa_gru_hh_p && m->sa_mlp_w1_p && m->sa_mlp_w2_p && p.q_w_p;
+  p.update = !su_packed ? EncodePlan::VALU : sf_slot_update_mfma_ok(D, Hm, P) ? EncodePlan::MFMA
+            : sf_slot_update_wide_ok(D, Hm, P) ? EncodePlan::WIDE : EncodePlan::VALU;
+  // (the folded iterations read keys == values)
+  if (fold && P == HW / 256 && (planes || sf_slot_attn_sparse_records(nullptr, nullptr, HW, D))) p.p_step = 2;
+  p.pred_step = m->pred_type == 1 && m->pred_packed && precision >= 1;
+  p.prologue = m->pred_type == 0 && !m->pred_rnn && m->kd_mode == 1 && m->pm_w0_t && m->pm_w2_t && m->kd_w0_t && p.q_w_t;
+  p.fuse_next = p.prologue && p.update == EncodePlan::MFMA && m->pm_w0_p && m->pm_w2_p && m->kd_w0_p && m->pm_ln_g && m->pm_ln_b && m->pm_b0 &&
+                m->pm_b2 && m->kd_b0 && sf_get_encode_fuse_next();
+  // (the CLEVRER shape of StoSAVi: savi.py:76-100, 393-402)
+  p.chain_model = precision == 1 && fold && p.feat != EncodePlan::FOLD_192 && p.update == EncodePlan::MFMA && p.fuse_next &&
+                  sf_slot_chain_ok(D, Hm, HW, N) && m->init_latents && m->enc_fc1_w && m->enc_fc2_w;
+  p.batched = !fork && n_pre == 0 && enc_batched_ok(m, B, T, precision);
+  p.chain = p.batched && p.chain_model && sf_get_slot_chain();
+  // without room for the feature planes: the per-iteration launches; without room for the batched activations: the per-step convolutions
+  if (p.chain && ws_bytes < enc_ws_bytes(m, B, T, p)) p.chain = false;
+  if (p.batched && ws_bytes < enc_ws_bytes(m, B, T, p)) p.batched = false;
+  return p;
 }
 
 // CNN stack (savi.py:231-244: convs + soft position embedding) for `nb` frames: frame i at src + i*frame_stride;
 // the last conv writes into `dst` (NHWC [nb,64,64,C_last]); featA/featB are ping-pong scratch.
 // layers [i0, i1) of the stack
-static int run_cnn_layers(const sf_savi_encoder* m, const float* src, long long frame_stride, int nb, float* dst, float* featA, float* featB,
-                          int i0, int i1, hipStream_t st) {
+int run_cnn_layers(const sf_savi_encoder* m, const float* src, long long frame_stride, int nb, float* dst, float* featA, float* featB,
+                   int i0, int i1, hipStream_t st) {
   const int res = m->resolution;
   for (int i = i0; i < i1; ++i) {
     const bool lastc = (i == m->enc_layers - 1);
@@ -682,16 +747,297 @@ static int run_cnn_layers(const sf_savi_encoder* m, const float* src, long long 
   }
   return 0;
 }
-static int run_cnn(const sf_savi_encoder* m, const float* src, long long frame_stride, int nb, float* dst, float* featA,
-                   float* featB, hipStream_t st) {
-  return run_cnn_layers(m, src, frame_stride, nb, dst, featA, featB, 0, m->enc_layers, st);
+
+// The CNN of all B x T frames, every layer as one launch (the first per time step where its grouped kernel does not apply: the frames of one step lie
+// T frames apart) -> big[2] [T][B][64 * 64][C_last]; big[0] / big[1] are ping-pong scratch
+int enc_cnn_all_steps(const sf_savi_encoder* m, const float* img, int B, int T, float* const* big, hipStream_t st) {
+  const int res = m->resolution, c1 = m->enc_channels[1];
+  const long long frame_elems = (long long)3 * res * res;
+  const int rc = sf_conv_first_grouped_ex(img, (long long)T * frame_elems, B, frame_elems, m->conv_w[0], m->conv_b[0], nullptr, big[0], B * T,
+                                          m->enc_channels[0], res, res, c1, m->enc_ks, res == 128 ? 2 : 1, 1, st);
+  if (rc < 0 || rc > 1) return rc;
+  for (int t = 0; t < T && rc == 1; ++t)
+    SF_TRY(sf_conv2d_nchw_in_f32(img + (long long)t * frame_elems, (long long)T * frame_elems, m->conv_w[0], m->conv_b[0], nullptr,
+                                 big[0] + (long long)t * B * ENC_HW * c1, B, m->enc_channels[0], res, res, c1, m->enc_ks, res == 128 ? 2 : 1, 1, st));
+  return run_cnn_layers(m, nullptr, 0, B * T, big[2], big[0], big[1], 1, m->enc_layers, st);
+}
+
+// ---- the encode in two halves (round 6): image features of a batch as bf16 hi | lo rows, and the slot branch of a GROUP of batches as one
+//      video-stationary launch (slot_chain.hip).  The batch pipeline runs the first on its encode lane and the second in front of the group's rollout, on
+//      the rollout stream: the slot branch is 32 workgroups of ~0.5 ms per batch that would leave the other 96 CUs of the lane idle. ----
+// CNN + encoder_out_layer + SlotAttention.norm_inputs of all B x T frames -> planes (big: enc_cnn_all_steps scratch)
+int enc_feature_planes(const sf_savi_encoder* m, const float* img, int B, int T, float* const* big, void* planes, hipStream_t st) {
+  SF_TRY(enc_cnn_all_steps(m, img, B, T, big, st));
+  return sf_pixel_mlp_feat_planes_ex(big[2], m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b, m->sa_norm_in_g, m->sa_norm_in_b,
+                                     planes, B * T * ENC_HW, 1e-5f, st);
+}
+// prologue of step 0 + the chain, for NB batches of B videos; the row buffers hold NB * B * N rows each
+int enc_slots_chain(const sf_savi_encoder* m, const void* planes, const float* noise, const float* prev, float* post, long long post_bs, float* kernel_dist,
+                    float* attn, int NB, int B, int T, const SlotRows& r, hipStream_t st) {
+  const int N = m->num_slots, D = m->slot_size;
+  const float ln_eps = 1e-5f;
+  const int pr = sf_slot_prologue_ex(prev, m->init_latents, m->pm_ln_g, m->pm_ln_b, m->pm_w0_t, m->pm_b0, m->pm_w2_t, m->pm_b2, m->pred_norm_first, m->kd_w0_t,
+                                     m->kd_b0, noise, (long long)T * N * D, kernel_dist, (long long)T * N * 2 * D, m->sa_q_ln_g, m->sa_q_ln_b, m->sa_fold_q_w_t,
+                                     r.a, r.q, NB * B, N, D, ln_eps, st);
+  if (pr != 0) return pr < 0 ? pr : sf_set_err(-1, "the one-launch slot prologue does not apply to this model", __FILE__, __LINE__);
+  SfChainWeights cw;
+  cw.gru_ih_p = m->sa_fold_gru_ih_p; cw.gru_hh_p = m->sa_gru_hh_p; cw.gru_b_ih = m->gru_b_ih; cw.gru_b_hh = m->gru_b_hh; cw.ln_g = m->mlp_ln_g; cw.ln_b = m->mlp_ln_b;
+  cw.w1_p = m->sa_mlp_w1_p; cw.b1 = m->mlp_b1; cw.w2_p = m->sa_mlp_w2_p; cw.b2 = m->mlp_b2; cw.q_ln_g = m->sa_q_ln_g; cw.q_ln_b = m->sa_q_ln_b; cw.q_w_p = m->sa_fold_q_w_p;
+  cw.pm_ln_g = m->pm_ln_g; cw.pm_ln_b = m->pm_ln_b; cw.pm_w0_p = m->pm_w0_p; cw.pm_b0 = m->pm_b0; cw.pm_w2_p = m->pm_w2_p; cw.pm_b2 = m->pm_b2;
+  cw.pm_norm_first = m->pred_norm_first; cw.kd_w_p = m->kd_w0_p; cw.kd_b = m->kd_b0;
+  return sf_slot_chain_ex(planes, NB, B, T, ENC_HW, N, m->num_iterations, 1.0f / sqrtf((float)D), m->sa_eps, ln_eps, r.a, r.b, r.lat, r.q, post, post_bs, attn,
+                          noise, kernel_dist, &cw, st);
+}
+
+// fork / join events of the forked encode, per host thread (created on first use, kept for the life of the thread: the library's
+// only host-side objects; no device memory)
+hipEvent_t enc_fork_event(int i) {
+  // keyed by the CURRENT device: an event belongs to the device it was created on, and one host thread may drive several GPUs (engine.py keeps its
+  // side streams per device); recording a device-0 event on a device-1 stream is hipErrorInvalidHandle
+  thread_local std::map<int, std::vector<hipEvent_t>> per_dev;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::vector<hipEvent_t>& ev = per_dev[dev];
+  while ((int)ev.size() <= i) {
+    hipEvent_t e = nullptr;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
+    ev.push_back(e);
+  }
+  return ev[i];
+}
+// fork event i of the forked encode: recorded on stream s / waited for on stream s
+int enc_fork_record(int i, hipStream_t s) {
+  const hipEvent_t e = enc_fork_event(i);
+  SF_REQUIRE(e != nullptr, "hipEventCreate failed");
+  return hipEventRecord(e, s) == hipSuccess ? 0 : sf_set_err((int)hipGetLastError(), "hipEventRecord", __FILE__, __LINE__);
+}
+int enc_fork_wait(int i, hipStream_t s) {
+  return hipStreamWaitEvent(s, enc_fork_event(i), 0) == hipSuccess ? 0 : sf_set_err((int)hipGetLastError(), "hipStreamWaitEvent", __FILE__, __LINE__);
+}
+
+// the arguments of one encode call that its steps read
+struct EncodeArgs {
+  const sf_savi_encoder* m;
+  const float *img, *feat_pre, *noise;
+  float *lstm_h, *lstm_c, *post, *kernel_dist, *attn;
+  int B, T;
+};
+
+// ---- the image features of step t: CNN (or its precomputed / batched output) -> encoder_out_layer (LN -> Linear -> ReLU -> Linear, savi.py:245-250)
+//      -> the Slot-Attention inputs (savi.py:66-70) at kv, per chunk of up to 32 frames ----
+int enc_step_features(const EncodeArgs& a, const EncodePlan& p, const EncodeWs& w, int t, float* kv, hipStream_t st) {
+  const sf_savi_encoder* m = a.m;
+  const int HW = ENC_HW, B = a.B, Bc = enc_chunk(B), Cl = m->enc_channels[m->enc_layers], Ce = m->enc_out_channels, D = m->slot_size;
+  const long long frame_elems = (long long)3 * m->resolution * m->resolution;
+  const float ln_eps = 1e-5f;
+  for (int b0 = 0; b0 < B; b0 += Bc) {
+    const int nb = (B - b0 < Bc) ? (B - b0) : Bc, Mp = nb * HW;
+    const float* cur;
+    if (t < p.n_pre) {
+      cur = a.feat_pre + ((long long)t * B + b0) * HW * Cl;
+    } else if (p.batched) {
+      cur = w.big[2] + ((long long)t * B + b0) * HW * Cl;
+    } else {
+      float* dstf = (m->enc_layers & 1) ? w.feat[0] : w.feat[1];   // the buffer the last conv does not read
+      SF_TRY(run_cnn_layers(m, a.img + ((long long)b0 * a.T + t) * frame_elems, (long long)a.T * frame_elems, nb, dstf, w.feat[0], w.feat[1], 0,
+                            m->enc_layers, st));
+      cur = dstf;
+    }
+    if (p.feat == EncodePlan::FOLD_192) {
+      SF_TRY(sf_pixel_mlp_feat192_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_p, m->enc_fc1_b, m->enc_fc2_p, m->enc_fc2_b,
+                                     m->sa_norm_in_g, m->sa_norm_in_b, kv + (long long)b0 * HW * Ce, Mp, ln_eps, st));
+    } else if (p.feat == EncodePlan::FOLD_PLANES) {
+      SF_TRY(sf_pixel_mlp_feat_planes_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b, m->sa_norm_in_g, m->sa_norm_in_b,
+                                         (char*)kv + (size_t)b0 * HW * 512, Mp, ln_eps, st));
+    } else if (p.feat == EncodePlan::FOLD_ROWS) {
+      SF_TRY(sf_pixel_mlp_feat_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b,
+                                  m->sa_norm_in_g, m->sa_norm_in_b, kv + (long long)b0 * HW * Ce, Mp, ln_eps, st));
+    } else {
+      float* kv_dst = kv + (long long)b0 * HW * 2 * D;
+      int rc = 1;
+      if (p.feat == EncodePlan::KV_FUSED)   // one kernel per 128-pixel tile (pixel_mlp.hip)
+        rc = sf_pixel_mlp_kv_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b, m->sa_norm_in_g, m->sa_norm_in_b,
+                                m->sa_kv_w, kv_dst, Mp, Cl, Ce, 2 * D, ln_eps, st);
+      if (rc < 0 || rc > 1) return rc;
+      if (rc == 1) {
+        SF_TRY(sf_linear_ex(cur, sf_rows(Cl), m->enc_fc1_w, m->enc_fc1_b, m->enc_ln_g, m->enc_ln_b, ln_eps, nullptr,
+                            sf_rows(Ce), 0, w.h1, sf_rows(Ce), Mp, Ce, Cl, 1, st));
+        SF_TRY(sf_linear_ex(w.h1, sf_rows(Ce), m->enc_fc2_w, m->enc_fc2_b, nullptr, nullptr, ln_eps, nullptr,
+                            sf_rows(Ce), 0, w.h2, sf_rows(Ce), Mp, Ce, Ce, 0, st));
+        SF_TRY(sf_linear_ex(w.h2, sf_rows(Ce), m->sa_kv_w, nullptr, m->sa_norm_in_g, m->sa_norm_in_b, ln_eps, nullptr,
+                            sf_rows(2 * D), 0, kv_dst, sf_rows(2 * D), Mp, 2 * D, Ce, 0, st));
+      }
+    }
+  }
+  return 0;
+}
+
+// ---- the prior of a step's slots: init_latents without previous slots, else predictor(prev) (savi.py:393-398) -> *lat ----
+int enc_predict(const EncodeArgs& a, const EncodePlan& p, const EncodeWs& w, const float* prev, hipStream_t st, const float** lat) {
+  const sf_savi_encoder* m = a.m;
+  const int N = m->num_slots, D = m->slot_size, R = a.B * N;
+  const float ln_eps = 1e-5f;
+  *lat = w.rows.lat;
+  if (prev == nullptr) return sf_copy_rows_ex(m->init_latents, sf_rows_batched(D, N, 0, 0), w.rows.lat, sf_rows(D), R, D, st);
+  int rc = 1;
+  if (p.pred_step)   // Transformer predictor (+ LSTM wrapper) in one launch (pred_step.hip)
+    rc = sf_pred_step_ex(prev, m->pred_layers, m->pred_num_layers, m->pred_num_heads, m->pred_ffn_dim, m->pred_norm_first, m->pred_packed, m->lstm_b_ih,
+                         m->lstm_b_hh, m->proj_b, m->pred_hidden, m->pred_rnn ? a.lstm_h : nullptr, m->pred_rnn ? a.lstm_c : nullptr, w.rows.lat, a.B, N, D,
+                         ln_eps, st);
+  if (rc != 1) return rc;
+  const float* pout;
+  if (m->pred_type == 0) {
+    // ResidualMLPPredictor (predictor.py:65-73)
+    SF_TRY(sf_layernorm_ex(prev, sf_rows(D), m->pm_ln_g, m->pm_ln_b, w.lnbuf, sf_rows(D), R, D, ln_eps, st));
+    SF_TRY(sf_linear_ex(w.lnbuf, sf_rows(D), m->pm_w0, m->pm_b0, nullptr, nullptr, ln_eps, nullptr, sf_rows(D), 0,
+                        w.tw.hid, sf_rows(2 * D), R, 2 * D, D, 1, st));
+    SF_TRY(sf_linear_ex(w.tw.hid, sf_rows(2 * D), m->pm_w2, m->pm_b2, nullptr, nullptr, ln_eps,
+                        m->pred_norm_first ? w.lnbuf : prev, sf_rows(D), 0, w.px, sf_rows(D), R, D, 2 * D, 0, st));
+    pout = w.px;
+  } else {
+    // TransformerPredictor over the N slots (predictor.py:20-44)
+    SF_TRY(sf_copy_rows_ex(prev, sf_rows(D), w.px, sf_rows(D), R, D, st));
+    float* cur = w.px;
+    TfmWs tw = w.tw;
+    for (int l = 0; l < m->pred_num_layers; ++l)
+      SF_TRY(tfm_layer(m->pred_layers[l], cur, tw, a.B, N, N, D, m->pred_num_heads, m->pred_ffn_dim, m->pred_norm_first, st, &cur));
+    pout = cur;
+  }
+  *lat = m->pred_rnn ? w.rows.lat : pout;
+  if (!m->pred_rnn) return 0;
+  // nn.LSTM, seq len 1, batch B*N (predictor.py:113-120)
+  const int Hh = m->pred_hidden;
+  SF_TRY(sf_linear_ex(pout, sf_rows(D), m->lstm_w_ih, m->lstm_b_ih, nullptr, nullptr, ln_eps, nullptr,
+                      sf_rows(4 * Hh), 0, w.gates, sf_rows(4 * Hh), R, 4 * Hh, D, 0, st));
+  SF_TRY(sf_linear_ex(a.lstm_h, sf_rows(Hh), m->lstm_w_hh, m->lstm_b_hh, nullptr, nullptr, ln_eps, w.gates,
+                      sf_rows(4 * Hh), 0, w.gates, sf_rows(4 * Hh), R, 4 * Hh, Hh, 0, st));
+  SF_TRY(sf_lstm_pointwise_ex(w.gates, a.lstm_c, a.lstm_h, a.lstm_c, R, Hh, st));
+  return sf_linear_ex(a.lstm_h, sf_rows(Hh), m->proj_w, m->proj_b, nullptr, nullptr, ln_eps, nullptr,
+                      sf_rows(D), 0, w.rows.lat, sf_rows(D), R, D, Hh, 0, st);
+}
+
+// ---- the slots of step t before its first iteration -> rows.a, their q -> rows.q: the one-launch slot prologue where it applies (*one_launch; predictor
+//      -> kernel_dist -> sampling -> q, slot_attn.hip), else the prior, the kernel distribution + sampling (savi.py:401-402) and q as an LN-fused GEMM ----
+int enc_slot_init(const EncodeArgs& a, const EncodePlan& p, const EncodeWs& w, const float* prev, int t, hipStream_t st, bool* one_launch) {
+  const sf_savi_encoder* m = a.m;
+  const int N = m->num_slots, D = m->slot_size, R = a.B * N, T = a.T;
+  const float ln_eps = 1e-5f;
+  int rc = 1;
+  if (p.prologue)
+    rc = sf_slot_prologue_ex(prev, m->init_latents, m->pm_ln_g, m->pm_ln_b, m->pm_w0_t, m->pm_b0, m->pm_w2_t, m->pm_b2, m->pred_norm_first, m->kd_w0_t,
+                             m->kd_b0, a.noise ? a.noise + (long long)t * N * D : nullptr, (long long)T * N * D,
+                             a.kernel_dist ? a.kernel_dist + (long long)t * N * 2 * D : nullptr, (long long)T * N * 2 * D, m->sa_q_ln_g, m->sa_q_ln_b,
+                             p.q_w_t, w.rows.a, w.rows.q, a.B, N, D, ln_eps, st);
+  *one_launch = rc == 0;
+  if (rc != 1) return rc;
+  const float* lat;
+  SF_TRY(enc_predict(a, p, w, prev, st, &lat));
+  if (m->kd_mode == 0) {
+    SF_TRY(sf_copy_rows_ex(lat, sf_rows(D), w.rows.a, sf_rows(D), R, D, st));
+  } else {
+    SF_TRY(sf_linear_ex(lat, sf_rows(D), m->kd_w0, m->kd_b0, nullptr, nullptr, ln_eps, nullptr, sf_rows(2 * D), 0,
+                        m->kd_mode == 1 ? w.kdist : w.kdtmp, sf_rows(2 * D), R, 2 * D, D, 0, st));
+    if (m->kd_mode == 2)   // Linear -> LayerNorm -> ReLU -> Linear
+      SF_TRY(sf_linear_ex(w.kdtmp, sf_rows(2 * D), m->kd_w3, m->kd_b3, m->kd_ln_g, m->kd_ln_b, ln_eps, nullptr,
+                          sf_rows(2 * D), 0, w.kdist, sf_rows(2 * D), R, 2 * D, 2 * D, 0, st, /*ln_relu=*/1));
+    const SfRowMap nmap = sf_rows_batched(D, N, (long long)T * N * D, (long long)t * N * D);
+    SF_TRY(sf_sample_dist_ex(w.kdist, a.noise, nmap, w.rows.a, R, D, st));
+    if (a.kernel_dist)
+      SF_TRY(sf_copy_rows_ex(w.kdist, sf_rows(2 * D), a.kernel_dist, sf_rows_batched(2 * D, N, (long long)T * N * 2 * D, (long long)t * N * 2 * D), R,
+                             2 * D, st));
+  }
+  // q of the first iteration; every later q comes out of the slot-update kernel
+  return sf_linear_ex(w.rows.a, sf_rows(D), p.q_w, nullptr, m->sa_q_ln_g, m->sa_q_ln_b, ln_eps, nullptr, sf_rows(D), 0, w.rows.q, sf_rows(D), R, D, D, 0, st);
+}
+
+// ---- the Slot-Attention iterations of step t (savi.py:76-100) on the inputs at kv, from rows.a and its q; the last slot update writes post[:, t]
+//      (next: and the slot prologue of step t + 1 into rows.a / rows.q, NEXT form).  *out: the buffer that holds step t's slots afterwards ----
+int enc_iterations(const EncodeArgs& a, const EncodePlan& p, const EncodeWs& w, const float* kv, int t, bool next, hipStream_t st, const float** out) {
+  const sf_savi_encoder* m = a.m;
+  const int HW = ENC_HW, N = m->num_slots, D = m->slot_size, Hm = m->slot_mlp_size, Ce = m->enc_out_channels, T = a.T, B = a.B, P = sf_sa_pick_partials(HW);
+  const float ln_eps = 1e-5f, scale = 1.0f / sqrtf((float)D);
+  const long long attn_bs = (long long)T * N * HW, post_bs = (long long)T * N * D;
+  float *s_in = w.rows.a, *s_out = w.rows.b;
+  for (int it = 0; it < m->num_iterations; ++it) {
+    const bool last_it = (it == m->num_iterations - 1), nx_on = next && last_it;
+    float* aout = (a.attn && last_it) ? a.attn + (long long)t * N * HW : nullptr;
+    float* post = last_it ? a.post + (long long)t * N * D : nullptr;
+    if (p.feat == EncodePlan::FOLD_PLANES)
+      SF_TRY(sf_slot_attn_planes_ex(kv, HW, w.rows.q, w.pnum, w.pden, aout, attn_bs, B, HW, N, scale, m->sa_eps, st));
+    else if (p.fold())   // keys = values = the normalised features (q is Wk^T q here, the GRU input matrix is W_ih Wv)
+      SF_TRY(sf_slot_attn_iter_ex(kv, kv, Ce, (long long)HW * Ce, w.rows.q, w.pnum, w.pden, aout, attn_bs, B, HW, N, D, scale, m->sa_eps, st));
+    else
+      SF_TRY(sf_slot_attn_iter_ex(kv, kv + D, 2 * D, (long long)HW * 2 * D, w.rows.q, w.pnum, w.pden, aout, attn_bs, B, HW, N, D, scale, m->sa_eps, st));
+    if (p.update == EncodePlan::MFMA) {
+      SfNextStep nx;   // (read in the NEXT form only)
+      nx.pm_ln_g = m->pm_ln_g; nx.pm_ln_b = m->pm_ln_b; nx.pm_w0_p = m->pm_w0_p; nx.pm_b0 = m->pm_b0; nx.pm_w2_p = m->pm_w2_p; nx.pm_b2 = m->pm_b2;
+      nx.norm_first = m->pred_norm_first; nx.kd_w_p = m->kd_w0_p; nx.kd_b = m->kd_b0;
+      nx.noise = a.noise ? a.noise + (long long)(t + 1) * N * D : nullptr; nx.noise_bs = (long long)T * N * D;
+      nx.kdist_out = a.kernel_dist ? a.kernel_dist + (long long)(t + 1) * N * 2 * D : nullptr; nx.kdist_bs = (long long)T * N * 2 * D;
+      nx.slots = w.rows.a;   // where the next step's iterations start
+      // (NEXT form: the finished rows of step t go to post[:, t]; their ping-pong copy is not read again, and must not alias the sampled slots)
+      SF_TRY(sf_slot_update_mfma_ex(w.pnum, w.pden, P, s_in, p.gru_ih_p, m->sa_gru_hh_p, m->gru_b_ih, m->gru_b_hh, m->mlp_ln_g, m->mlp_ln_b,
+                                    m->sa_mlp_w1_p, m->mlp_b1, m->sa_mlp_w2_p, m->mlp_b2, (nx_on && s_out == w.rows.a) ? w.rows.lat : s_out, post, post_bs,
+                                    m->sa_q_ln_g, m->sa_q_ln_b, p.q_w_p, (last_it && !nx_on) ? nullptr : w.rows.q, B, N, ln_eps, st, nx_on ? &nx : nullptr,
+                                    p.p_step));
+    } else if (p.update == EncodePlan::WIDE) {
+      SF_TRY(sf_slot_update_wide_ex(w.pnum, w.pden, P, s_in, p.gru_ih_p, m->sa_gru_hh_p, m->gru_b_ih, m->gru_b_hh, m->mlp_ln_g, m->mlp_ln_b,
+                                    m->sa_mlp_w1_p, m->mlp_b1, m->sa_mlp_w2_p, m->mlp_b2, s_out, post, post_bs, m->sa_q_ln_g, m->sa_q_ln_b,
+                                    p.q_w_p, last_it ? nullptr : w.rows.q, B, N, ln_eps, st));
+    } else {
+      SF_TRY(sf_slot_update_ex(w.pnum, w.pden, P, s_in, p.gru_ih_t, m->gru_w_hh, m->gru_b_ih, m->gru_b_hh, m->mlp_ln_g, m->mlp_ln_b, m->mlp_w1,
+                               m->mlp_b1, m->mlp_w2, m->mlp_b2, s_out, post, post_bs, m->sa_q_ln_g, m->sa_q_ln_b, p.q_w_t,
+                               (last_it || !p.q_w_t) ? nullptr : w.rows.q, B, N, D, Hm, ln_eps, st));
+      if (!last_it && !p.q_w_t)   // no transposed copy of project_q given: the LN-fused GEMM produces q
+        SF_TRY(sf_linear_ex(s_out, sf_rows(D), p.q_w, nullptr, m->sa_q_ln_g, m->sa_q_ln_b, ln_eps, nullptr, sf_rows(D), 0, w.rows.q,
+                            sf_rows(D), B * N, D, D, 0, st));
+    }
+    std::swap(s_in, s_out);
+  }
+  *out = s_in;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+// the slot branch of a batched encode as one video-stationary launch (slot_chain.hip): OPT-IN (sf_set_slot_chain(1)); the default keeps
+// the per-iteration launches (Slot-Attention iteration over the batch + slot update), which are faster for a batch alone on its CUs
+static int g_slot_chain = 0;
+int sf_get_slot_chain(void) { return g_slot_chain; }
+// the Slot-Attention iterations of the per-step encode on feature rows kept as bf16 hi | lo (sa_attn_planes_kernel, slot_chain.hip: split-bf16 16x16x32
+// MFMAs) instead of f32 rows and the exact-f32 tile kernel: process default below; sf_set_slot_attn_planes(0 / 1)
+static int g_sa_planes = 1;
+int sf_get_slot_attn_planes(void) { return g_sa_planes; }
+int sf_set_slot_attn_planes(int on) { g_sa_planes = on ? 1 : 0; return 0; }
+int sf_set_slot_chain(int on) { g_slot_chain = on ? 1 : 0; return 0; }
+
+// the slot prologue of step t + 1 at the tail of step t's last slot update (slot_update_mfma.hip, NEXT form): on by default where it applies;
+// sf_set_encode_fuse_next(0): the prologue as its own launch (sa_slot_prologue_kernel) on every step
+static int g_enc_fuse_next = 1;
+int sf_set_encode_fuse_next(int on) { g_enc_fuse_next = on ? 1 : 0; return 0; }
+int sf_get_encode_fuse_next(void) { return g_enc_fuse_next; }
+
+size_t sf_savi_encode_workspace_bytes(const sf_savi_encoder* m, int B) {
+  return (m && B > 0) ? enc_ws_bytes(m, B, 1, plan_encode(m, B, 1, 0, false, 0)) : 0;
+}
+size_t sf_savi_encode_fork_workspace_bytes(const sf_savi_encoder* m, int B, int T) {
+  return (m && B > 0 && T >= 1) ? enc_ws_bytes(m, B, T, plan_encode(m, B, T, 0, true, 0)) : 0;
+}
+// One-stream encode with the convolutions of ALL T time steps as one launch per layer (the weights-stationary kernel of conv_ws.hip pays its 410 KB of
+// weights per workgroup once per launch: 81 instead of 99 us per time step and layer on a 128-CU partition): the activations of B * T frames in three
+// buffers on top of sf_savi_encode_workspace_bytes, and under sf_set_slot_chain(1) the feature planes of the video-stationary slot branch.
+// sf_savi_encode_fork_f32 (side_stream NULL) takes this form when it is handed that much workspace.
+size_t sf_savi_encode_batched_workspace_bytes(const sf_savi_encoder* m, int B, int T) {
+  return (m && B > 0 && T > 0) ? enc_ws_bytes(m, B, T, plan_encode(m, B, T, 0, false, ~(size_t)0)) : 0;
 }
 
 size_t sf_savi_cnn_workspace_bytes(const sf_savi_encoder* m, int B) {
   if (!m || B <= 0) return 0;
-  int cmax = 0;
-  for (int i = 1; i <= m->enc_layers && i < 9; ++i) cmax = m->enc_channels[i] > cmax ? m->enc_channels[i] : cmax;
-  return 2 * pad256((size_t)enc_chunk(B) * 64 * 64 * cmax) + 4096;
+  Bump bp{nullptr, ~(size_t)0};
+  float* feat[2];
+  enc_cnn_take(bp, feat, 2, m, enc_chunk(B));
+  return bp.used + 4096;
 }
 
 // CNN features of time steps [t0, t1) of every video: feat [t1-t0][B][64*64][C_last].  Independent of the slots, so a
@@ -705,13 +1051,11 @@ int sf_savi_cnn_f32(const sf_savi_encoder* m, const float* img, int B, int T, in
   SF_REQUIRE(m->enc_layers >= 1 && m->enc_layers <= 8 && m->pos_table, "bad CNN config");
   SF_REQUIRE(ws_bytes >= sf_savi_cnn_workspace_bytes(m, B), "workspace too small");
   for (int i = 0; i < m->enc_layers; ++i) SF_REQUIRE(m->conv_w[i] != nullptr, "null conv weight");
-  int cmax = 0;
-  for (int i = 1; i <= m->enc_layers; ++i) cmax = m->enc_channels[i] > cmax ? m->enc_channels[i] : cmax;
-  const int Bc = enc_chunk(B), HW = 64 * 64, Cl = m->enc_channels[m->enc_layers];
+  const int Bc = enc_chunk(B), HW = ENC_HW, Cl = m->enc_channels[m->enc_layers];
   Bump bp{(char*)ws, ws_bytes};
-  float* featA = bp.take((size_t)Bc * HW * cmax);
-  float* featB = bp.take((size_t)Bc * HW * cmax);
-  if (!featA || !featB) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
+  float* fb[2];
+  enc_cnn_take(bp, fb, 2, m, Bc);
+  if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
   const long long frame_elems = (long long)3 * m->resolution * m->resolution;
   // these launches usually run on another stream / CU partition than the encode: keep them out of the per-class
   // HIP-event timer so that bench.py's live conv figure stays "launches of the encode stream"
@@ -720,52 +1064,24 @@ int sf_savi_cnn_f32(const sf_savi_encoder* m, const float* img, int B, int T, in
   for (int t = t0; t < t1 && rc == 0; ++t)
     for (int b0 = 0; b0 < B && rc == 0; b0 += Bc) {
       const int nb = (B - b0 < Bc) ? (B - b0) : Bc;
-      rc = run_cnn(m, img + ((long long)b0 * T + t) * frame_elems, (long long)T * frame_elems, nb,
-                   feat + ((long long)(t - t0) * B + b0) * HW * Cl, featA, featB, (hipStream_t)stream);
+      rc = run_cnn_layers(m, img + ((long long)b0 * T + t) * frame_elems, (long long)T * frame_elems, nb,
+                          feat + ((long long)(t - t0) * B + b0) * HW * Cl, fb[0], fb[1], 0, m->enc_layers, (hipStream_t)stream);
     }
   sf_prof_suppress(0);
   return rc;
 }
 
-// ---- the encode in two halves (round 6): image features of a batch as bf16 hi | lo rows, and the slot branch of a GROUP of batches as one
-//      video-stationary launch (slot_chain.hip).  The batch pipeline runs the first on its encode lane and the second in front of the group's rollout, on
-//      the rollout stream: the slot branch is 32 workgroups of ~0.5 ms per batch that would leave the other 96 CUs of the lane idle. ----
-// model-level conditions of the video-stationary slot branch (the CLEVRER shape of StoSAVi: savi.py:76-100, 393-402)
-static bool enc_chain_model_ok(const sf_savi_encoder* m) {
-  if (!m || sf_get_precision() != 1) return false;
-  const int HW = 64 * 64, D = m->slot_size, Ce = m->enc_out_channels, Hm = m->slot_mlp_size, N = m->num_slots;
-  const int Cl = m->enc_channels[m->enc_layers];
-  const bool fold = m->sa_fold_q_w && m->sa_fold_q_w_t && m->sa_fold_gru_ih_t && Ce == D && Cl == 64 && sf_pixel_mlp_feat_ok(Cl, Ce);
-  const bool su = m->sa_fold_gru_ih_p && m->sa_gru_hh_p && m->sa_mlp_w1_p && m->sa_mlp_w2_p && m->sa_fold_q_w_p && sf_slot_update_mfma_ok(D, Hm, sf_sa_pick_partials(HW));
-  const bool prologue = m->pred_type == 0 && !m->pred_rnn && m->kd_mode == 1 && m->pm_w0_t && m->pm_w2_t && m->kd_w0_t && m->pm_w0_p && m->pm_w2_p && m->kd_w0_p &&
-                        m->pm_ln_g && m->pm_ln_b && m->pm_b0 && m->pm_b2 && m->kd_b0 && m->init_latents;
-  return fold && su && prologue && sf_get_encode_fuse_next() && sf_slot_chain_ok(D, Hm, HW, N) && m->enc_fc1_w && m->enc_fc2_w;
+int sf_savi_chain_ok(const sf_savi_encoder* m, int B, int T) {
+  const EncodePlan p = plan_encode(m, B, T, 0, false, ~(size_t)0);   // (the conditions of a batched encode that runs the chain)
+  return (p.batched && p.chain_model) ? 1 : 0;
 }
-// prologue of step 0 + the chain, for NB batches of B videos; the four row buffers hold NB * B * N rows of D floats each
-static int enc_slots_chain(const sf_savi_encoder* m, const void* planes, const float* noise, const float* prev, float* post, long long post_bs, float* kernel_dist,
-                           float* attn, int NB, int B, int T, float* slotsA, float* slotsB, float* latents, float* q, hipStream_t st) {
-  const int N = m->num_slots, D = m->slot_size, HW = 64 * 64;
-  const float ln_eps = 1e-5f;
-  const int pr = sf_slot_prologue_ex(prev, m->init_latents, m->pm_ln_g, m->pm_ln_b, m->pm_w0_t, m->pm_b0, m->pm_w2_t, m->pm_b2, m->pred_norm_first, m->kd_w0_t,
-                                     m->kd_b0, noise, (long long)T * N * D, kernel_dist, (long long)T * N * 2 * D, m->sa_q_ln_g, m->sa_q_ln_b, m->sa_fold_q_w_t,
-                                     slotsA, q, NB * B, N, D, ln_eps, st);
-  if (pr != 0) return pr < 0 ? pr : sf_set_err(-1, "the one-launch slot prologue does not apply to this model", __FILE__, __LINE__);
-  SfChainWeights cw;
-  cw.gru_ih_p = m->sa_fold_gru_ih_p; cw.gru_hh_p = m->sa_gru_hh_p; cw.gru_b_ih = m->gru_b_ih; cw.gru_b_hh = m->gru_b_hh; cw.ln_g = m->mlp_ln_g; cw.ln_b = m->mlp_ln_b;
-  cw.w1_p = m->sa_mlp_w1_p; cw.b1 = m->mlp_b1; cw.w2_p = m->sa_mlp_w2_p; cw.b2 = m->mlp_b2; cw.q_ln_g = m->sa_q_ln_g; cw.q_ln_b = m->sa_q_ln_b; cw.q_w_p = m->sa_fold_q_w_p;
-  cw.pm_ln_g = m->pm_ln_g; cw.pm_ln_b = m->pm_ln_b; cw.pm_w0_p = m->pm_w0_p; cw.pm_b0 = m->pm_b0; cw.pm_w2_p = m->pm_w2_p; cw.pm_b2 = m->pm_b2;
-  cw.pm_norm_first = m->pred_norm_first; cw.kd_w_p = m->kd_w0_p; cw.kd_b = m->kd_b0;
-  return sf_slot_chain_ex(planes, NB, B, T, HW, N, m->num_iterations, 1.0f / sqrtf((float)D), m->sa_eps, ln_eps, slotsA, slotsB, latents, q, post, post_bs, attn,
-                          noise, kernel_dist, &cw, st);
-}
-
-int sf_savi_chain_ok(const sf_savi_encoder* m, int B, int T) { return (enc_chain_model_ok(m) && enc_batched_ok(m, B, T)) ? 1 : 0; }
-size_t sf_savi_planes_bytes(const sf_savi_encoder* m, int B, int T) { return (m && B > 0 && T > 0) ? (size_t)B * T * 64 * 64 * 512 : 0; }
+size_t sf_savi_planes_bytes(const sf_savi_encoder* m, int B, int T) { return (m && B > 0 && T > 0) ? (size_t)B * T * ENC_HW * 512 : 0; }
 size_t sf_savi_features_workspace_bytes(const sf_savi_encoder* m, int B, int T) {
   if (!m || B <= 0 || T <= 0) return 0;
-  int cmax = 0;
-  for (int i = 1; i <= m->enc_layers && i < 9; ++i) cmax = m->enc_channels[i] > cmax ? m->enc_channels[i] : cmax;
-  return 3 * pad256((size_t)B * T * 64 * 64 * cmax) + 4096;
+  Bump bp{nullptr, ~(size_t)0};
+  float* big[3];
+  enc_cnn_take(bp, big, 3, m, (size_t)B * T);
+  return bp.used + 4096;
 }
 // Image features of B videos x T frames as the Slot-Attention inputs of the video-stationary slot branch: CNN (savi.py:231-244), encoder_out_layer
 // (:245-250) and SlotAttention.norm_inputs (:66) -> planes [T][B][64 * 64] rows of 512 B (bf16 hi 128 | lo 128).  Independent of any slots.
@@ -773,28 +1089,18 @@ int sf_savi_features_planes_f32(const sf_savi_encoder* m, const float* img, int 
   SF_REQUIRE(m && img && planes && ws, "sf_savi_features_planes_f32: null pointer");
   SF_REQUIRE(B >= 1 && T >= 1 && sf_savi_chain_ok(m, B, T), "sf_savi_features_planes_f32: the video-stationary slot branch does not apply (sf_savi_chain_ok)");
   SF_REQUIRE(ws_bytes >= sf_savi_features_workspace_bytes(m, B, T), "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const int HW = 64 * 64, res = m->resolution;
-  int cmax = 0;
-  for (int i = 1; i <= m->enc_layers; ++i) cmax = m->enc_channels[i] > cmax ? m->enc_channels[i] : cmax;
   Bump bp{(char*)ws, ws_bytes};
   float* big[3];
-  for (int i = 0; i < 3; ++i) big[i] = bp.take((size_t)B * T * HW * cmax);
+  enc_cnn_take(bp, big, 3, m, (size_t)B * T);
   if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
-  const long long frame_elems0 = (long long)3 * res * res;
-  const int c1 = m->enc_channels[1];
-  int rc0 = sf_conv_first_grouped_ex(img, (long long)T * frame_elems0, B, frame_elems0, m->conv_w[0], m->conv_b[0], nullptr, big[0], B * T, m->enc_channels[0], res, res, c1,
-                                     m->enc_ks, res == 128 ? 2 : 1, 1, st);
-  if (rc0 < 0 || rc0 > 1) return rc0;
-  for (int t = 0; t < T && rc0 == 1; ++t)
-    SF_TRY(sf_conv2d_nchw_in_f32(img + (long long)t * frame_elems0, (long long)T * frame_elems0, m->conv_w[0], m->conv_b[0], nullptr,
-                                 big[0] + (long long)t * B * HW * c1, B, m->enc_channels[0], res, res, c1, m->enc_ks, res == 128 ? 2 : 1, 1, st));
-  SF_TRY(run_cnn_layers(m, nullptr, 0, B * T, big[2], big[0], big[1], 1, m->enc_layers, st));
-  return sf_pixel_mlp_feat_planes_ex(big[2], m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b, m->sa_norm_in_g, m->sa_norm_in_b, planes,
-                                     B * T * HW, 1e-5f, st);
+  return enc_feature_planes(m, img, B, T, big, planes, (hipStream_t)stream);
 }
 size_t sf_savi_slots_chain_workspace_bytes(const sf_savi_encoder* m, int videos) {
-  return (m && videos > 0) ? 4 * pad256((size_t)videos * m->num_slots * m->slot_size) + 4096 : 0;
+  if (!m || videos <= 0) return 0;
+  Bump bp{nullptr, ~(size_t)0};
+  SlotRows r;
+  slot_rows_take(bp, r, (size_t)videos * m->num_slots, m->slot_size);
+  return bp.used + 4096;
 }
 // The slot branch of NB batches of B videos over their T frames (StoSAVi.encode's per-step chain, savi.py:393-416, and the Slot-Attention iterations,
 // :76-100) from sf_savi_features_planes_f32 rows: planes [NB][T][B][64 * 64][256 bf16]; noise NULL or [NB * B][T][N][D]; prev_slots NULL or [NB * B][N][D];
@@ -802,17 +1108,15 @@ size_t sf_savi_slots_chain_workspace_bytes(const sf_savi_encoder* m, int videos)
 int sf_savi_slots_chain_f32(const sf_savi_encoder* m, const void* planes, const float* noise, const float* prev_slots, float* post, long long post_bs,
                             float* kernel_dist, float* attn, int NB, int B, int T, void* ws, size_t ws_bytes, void* stream) {
   SF_REQUIRE(m && planes && post && ws, "sf_savi_slots_chain_f32: null pointer");
-  SF_REQUIRE(NB >= 1 && B >= 1 && T >= 1 && enc_chain_model_ok(m), "sf_savi_slots_chain_f32: the video-stationary slot branch does not apply (sf_savi_chain_ok)");
+  SF_REQUIRE(NB >= 1 && B >= 1 && T >= 1 && plan_encode(m, B, T, 0, false, 0).chain_model,
+             "sf_savi_slots_chain_f32: the video-stationary slot branch does not apply (sf_savi_chain_ok)");
   SF_REQUIRE(noise == nullptr || m->kd_mode != 0, "noise given but the model has no kernel_dist layer");
   SF_REQUIRE(ws_bytes >= sf_savi_slots_chain_workspace_bytes(m, NB * B), "workspace too small");
-  const size_t R = (size_t)NB * B * m->num_slots;
   Bump bp{(char*)ws, ws_bytes};
-  float* sA = bp.take(R * m->slot_size);
-  float* sB = bp.take(R * m->slot_size);
-  float* lat = bp.take(R * m->slot_size);
-  float* q = bp.take(R * m->slot_size);
+  SlotRows r;
+  slot_rows_take(bp, r, (size_t)NB * B * m->num_slots, m->slot_size);
   if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
-  return enc_slots_chain(m, planes, noise, prev_slots, post, post_bs, kernel_dist, attn, NB, B, T, sA, sB, lat, q, (hipStream_t)stream);
+  return enc_slots_chain(m, planes, noise, prev_slots, post, post_bs, kernel_dist, attn, NB, B, T, r, (hipStream_t)stream);
 }
 
 int sf_savi_encode_f32(const sf_savi_encoder* m, const float* img, const float* noise, const float* prev_slots,
@@ -831,34 +1135,18 @@ int sf_savi_encode_pre_f32(const sf_savi_encoder* m, const float* img, const flo
                                  B, T, ws, ws_bytes, stream, nullptr);
 }
 
-// fork / join events of the forked encode, per host thread (created on first use, kept for the life of the thread: the library's
-// only host-side objects; no device memory)
-static hipEvent_t enc_fork_event(int i) {
-  // keyed by the CURRENT device: an event belongs to the device it was created on, and one host thread may drive several GPUs (engine.py keeps its
-  // side streams per device); recording a device-0 event on a device-1 stream is hipErrorInvalidHandle
-  thread_local std::map<int, std::vector<hipEvent_t>> per_dev;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::vector<hipEvent_t>& ev = per_dev[dev];
-  while ((int)ev.size() <= i) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-    ev.push_back(e);
-  }
-  return ev[i];
-}
 
 // The encode as TWO branches (side_stream != NULL).  The image features of a time step (CNN + per-pixel chain: ~420 us of dense
 // launches per step at C2) do not depend on the slots; the slot branch of a step (prologue, Slot-Attention iterations, slot updates:
 // ~140 us, half of it in seven-workgroup launches that leave the chip idle) needs only that step's features.  `stream` runs the
 // features of all T steps back to back; `side_stream` follows one step behind with the slot branches, ordered by events (fork after
-// the features of step t, join at the end: `stream` waits for the last slot update).  Captured into a hipGraph the two become parallel
-// branches of the graph.  Same kernels, same arguments, same bits.  Workspace: sf_savi_encode_fork_workspace_bytes(m, B, T).
+// the features of step t, join at the end: `stream` waits for the last slot update).
+// Captured into a hipGraph the two become parallel branches of the graph.  Same kernels, same arguments, same bits.  Workspace:
+// sf_savi_encode_fork_workspace_bytes(m, B, T).
 int sf_savi_encode_fork_f32(const sf_savi_encoder* m, const float* img, const float* feat_pre, int n_pre, const float* noise,
                             const float* prev_slots, float* lstm_h, float* lstm_c, int state_valid, float* post_slots,
                             float* kernel_dist, float* attn, int B, int T, void* ws, size_t ws_bytes, void* stream, void* side_stream) {
   SF_REQUIRE(m && img && post_slots && ws, "null pointer");
-  const bool fork = side_stream != nullptr && side_stream != stream;
   SF_REQUIRE(n_pre >= 0 && n_pre <= T && (n_pre == 0 || feat_pre != nullptr), "bad precomputed-feature arguments");
   SF_REQUIRE(B >= 1 && T >= 1, "bad batch / clip length");
   SF_REQUIRE(m->resolution == 64 || m->resolution == 128, "resolution must be 64 or 128 (savi.py:226,236)");
@@ -878,349 +1166,48 @@ int sf_savi_encode_fork_f32(const sf_savi_encoder* m, const float* img, const fl
   if (m->pred_rnn)
     SF_REQUIRE(lstm_h && lstm_c && m->pred_hidden > 0 && m->lstm_w_ih && m->lstm_w_hh && m->lstm_b_ih &&
                    m->lstm_b_hh && m->proj_w && m->proj_b, "null LSTM state / weight");
-  const int KV = fork ? enc_fork_steps(T) : 2;   // resident Slot-Attention inputs: a ring of KV time steps
-  SF_REQUIRE(ws_bytes >= enc_ws_bytes(m, B, KV), "workspace too small");
+  const EncodePlan p = plan_encode(m, B, T, n_pre, side_stream != nullptr && side_stream != stream, ws_bytes);
   for (int i = 0; i < m->enc_layers; ++i) SF_REQUIRE(m->conv_w[i] != nullptr, "null conv weight");
-
-  hipStream_t st_main = (hipStream_t)stream, st_side = fork ? (hipStream_t)side_stream : (hipStream_t)stream;
-  hipStream_t st = st_main;
-  const int HW = 64 * 64, res = m->resolution;
-  const int N = m->num_slots, D = m->slot_size, Ce = m->enc_out_channels, Hm = m->slot_mlp_size;
-  const int R = B * N, Bc = enc_chunk(B), P = sf_sa_pick_partials(HW);
-  int cmax = 0;
-  for (int i = 1; i <= m->enc_layers; ++i) cmax = m->enc_channels[i] > cmax ? m->enc_channels[i] : cmax;
-  const int hidp = m->pred_ffn_dim > 2 * D ? m->pred_ffn_dim : 2 * D;
-
   Bump bp{(char*)ws, ws_bytes};
-  float* featA = bp.take((size_t)Bc * HW * cmax);
-  float* featB = bp.take((size_t)Bc * HW * cmax);
-  float* h1 = bp.take((size_t)Bc * HW * Ce);
-  float* h2 = bp.take((size_t)Bc * HW * Ce);
-  float* kv_base = bp.take((size_t)KV * B * HW * 2 * D);
-  const size_t kv_step = (size_t)B * HW * 2 * D;
-  float* slotsA = bp.take((size_t)R * D);
-  float* slotsB = bp.take((size_t)R * D);
-  float* latents = bp.take((size_t)R * D);
-  float* q = bp.take((size_t)R * D);
-  float* lnbuf = bp.take((size_t)R * D);
-  float* px = bp.take((size_t)R * D);
-  float* kdist = bp.take((size_t)R * 2 * D);
-  float* kdtmp = bp.take((size_t)R * 2 * D);
-  float* pnum = bp.take((size_t)B * P * N * D);
-  float* pden = bp.take((size_t)B * P * N);
-  TfmWs tw;
-  bool ok = tfm_ws_take(bp, tw, R, D, hidp);
-  float* gates = bp.take((size_t)R * 4 * (m->pred_hidden > 0 ? m->pred_hidden : 1));
-  if (!ok || !bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
-  // all T steps' convolutions as one launch per layer (sf_savi_encode_batched_workspace_bytes): when the caller brought the room for it
-  float* big[3] = {nullptr, nullptr, nullptr};
-  const bool batched = !fork && n_pre == 0 && enc_batched_ok(m, B, T) && ws_bytes >= enc_ws_bytes(m, B, KV) + enc_batched_extra(m, B, T);
-  float* planes = nullptr;
-  if (batched) {
-    for (int i = 0; i < 3; ++i) big[i] = bp.take((size_t)B * T * HW * cmax);
-    planes = bp.take((size_t)B * T * HW * 128);
-    if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
-  }
-
+  EncodeWs w;
+  SF_REQUIRE(ws_bytes >= enc_ws_bytes(m, B, T, p) && enc_ws_take(bp, w, m, B, T, p), "workspace too small");
+  const hipStream_t st_main = (hipStream_t)stream, st = p.fork ? (hipStream_t)side_stream : st_main;   // st: the slot branch
+  const EncodeArgs a{m, img, feat_pre, noise, lstm_h, lstm_c, post_slots, kernel_dist, attn, B, T};
+  const int N = m->num_slots, D = m->slot_size;
   const float* prev = prev_slots;
   if (m->pred_rnn && (prev == nullptr || !state_valid)) {
     // RNNPredictorWrapper.reset(): hidden_state = None -> zeros on first use (predictor.py:132-135)
     // (a KERNEL, not hipMemsetAsync: the encode may be captured into a hipGraph, and memset nodes were seen to stop clearing
     //  after an older graph exec had been destroyed -- see zero_words_kernel above; pipeline encode graphs hit it at once)
-    const long long nz = (long long)R * m->pred_hidden;
-    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)(((nz + 3) / 4 + 255) / 256)), dim3(256), 0, st, lstm_h, lstm_c, nz);
+    const long long nz = (long long)B * N * m->pred_hidden;
+    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)(((nz + 3) / 4 + 255) / 256)), dim3(256), 0, st_main, lstm_h, lstm_c, nz);
     SF_CHECK_LAUNCH();
   }
-  const long long frame_elems = (long long)3 * res * res;
-  const float ln_eps = 1e-5f;
-  // Slot Attention on the normalised pixel features with the key / value projections folded into project_q and the GRU input
-  // matrix (include/slotformer_hip.h, sa_fold_*; widths 128 and 192); without the folded copies, or at other widths: k|v as the reference computes them
-  const bool feat192 = m->enc_channels[m->enc_layers] == 64 && Ce == 192 && m->enc_fc1_p && m->enc_fc2_p;
-  const bool fold = sf_get_precision() >= 1 && m->sa_fold_q_w && m->sa_fold_q_w_t && m->sa_fold_gru_ih_t && Ce == D &&
-                    (sf_pixel_mlp_feat_ok(m->enc_channels[m->enc_layers], Ce) || feat192);
-  const bool sa_planes = fold && !feat192 && sf_get_slot_attn_planes() && sf_slot_attn_planes_ok(HW, D, N) && m->enc_channels[m->enc_layers] == 64 &&
-                         P == HW / 256;
-  const float* q_w = fold ? m->sa_fold_q_w : m->sa_q_w;
-  const float* q_w_t = fold ? m->sa_fold_q_w_t : m->sa_q_w_t;
-  const float* gru_ih_t = fold ? m->sa_fold_gru_ih_t : m->gru_w_ih;
-  const void* q_w_p = fold ? m->sa_fold_q_w_p : m->sa_q_w_p;
-  const void* gru_ih_p = fold ? m->sa_fold_gru_ih_p : m->sa_gru_ih_p;
-
-  // slot update on the matrix cores (slot_update_mfma.hip) when the packed copies are there (slot size 128); otherwise the VALU kernel
-  const bool su_packed = sf_get_precision() >= 1 && gru_ih_p && m->sa_gru_hh_p && m->sa_mlp_w1_p && m->sa_mlp_w2_p && q_w_p;
-  const bool su_mfma = su_packed && sf_slot_update_mfma_ok(D, Hm, P);
-  const bool su_wide = su_packed && sf_slot_update_wide_ok(D, Hm, P);   // slot size 192 (slot_update_wide.hip)
-  // time-step order; forked: the features of step t are enqueued on `stream`, its slot branch on `side_stream` behind them (event),
-  // and the features of step t + KV wait for the slot branch of step t to release its ring slot
-  // the one-launch slot prologue applies (CLEVRER configuration); with packed copies of its three matrices and the matrix-core slot update, the
-  // prologue of step t + 1 runs at the tail of step t's last update (slot_update_mfma.hip, NEXT form)
-  const bool can_prologue = m->pred_type == 0 && !m->pred_rnn && m->kd_mode == 1 && m->pm_w0_t && m->pm_w2_t && m->kd_w0_t && q_w_t;
-  const bool can_fuse_next = sf_get_encode_fuse_next() && can_prologue && su_mfma && m->pm_w0_p && m->pm_w2_p && m->kd_w0_p && m->pm_ln_g && m->pm_ln_b && m->pm_b0 &&
-                             m->pm_b2 && m->kd_b0;
-  bool next_done = false;
-  const bool planes_all = false;
-  if (batched) {
-    // layer 0 per time step (the frames of one step lie T frames apart), every later layer over the B * T frames in [t][b] order; the last one
-    // leaves the features of step t at big[2] + t * B * HW * Cl
-    const long long frame_elems0 = (long long)3 * res * res;
-    const int c1 = m->enc_channels[1];
-    int rc0 = 1;
-    if (sf_get_precision() >= 1)   // one launch for the B * T frames where the first-layer kernel applies (3 -> 64 channels at 128 x 128 / 64 x 64)
-      rc0 = sf_conv_first_grouped_ex(img, (long long)T * frame_elems0, B, frame_elems0, m->conv_w[0], m->conv_b[0], nullptr, big[0], B * T, m->enc_channels[0], res,
-                                     res, c1, m->enc_ks, res == 128 ? 2 : 1, 1, st_main);
-    if (rc0 < 0 || rc0 > 1) return rc0;
-    for (int t = 0; t < T && rc0 == 1; ++t)
-      SF_TRY(sf_conv2d_nchw_in_f32(img + (long long)t * frame_elems0, (long long)T * frame_elems0, m->conv_w[0], m->conv_b[0], nullptr,
-                                   big[0] + (long long)t * B * HW * c1, B, m->enc_channels[0], res, res, c1, m->enc_ks, res == 128 ? 2 : 1, 1, st_main));
-    SF_TRY(run_cnn_layers(m, nullptr, 0, B * T, big[2], big[0], big[1], 1, m->enc_layers, st_main));
-    // (the per-pixel chain stays per time step: as ONE launch for the B * T frames it takes 333 instead of 6 x 65 us on the lane, but the Slot-Attention
-    //  iterations then read their rows from HBM instead of the cache the launch in front of them left warm: 18.9 -> 20.8 us each -- no gain, probes r06)
-    // ---- the slot branch of all T steps as ONE video-stationary launch (slot_chain.hip): the per-pixel chain of the B * T frames in one launch
-    //      (feature rows as bf16 hi | lo), the prologue of step 0, then one workgroup per video ----
-    if (sf_get_slot_chain() && enc_chain_model_ok(m)) {
-      SF_TRY(sf_pixel_mlp_feat_planes_ex(big[2], m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b, m->sa_norm_in_g,
-                                         m->sa_norm_in_b, planes, B * T * HW, ln_eps, st_main));
-      // (the chain's row buffers: the slot buffers of this function's workspace)
-      return enc_slots_chain(m, planes, noise, prev, post_slots, (long long)T * N * D, kernel_dist, attn, 1, B, T, slotsA, slotsB, latents, q, st_main);
-    }
+  if (p.chain) {   // the slot branch of all T steps as ONE video-stationary launch behind the features of the B * T frames as bf16 hi | lo rows
+    SF_TRY(enc_feature_planes(m, img, B, T, w.big, w.planes, st_main));
+    return enc_slots_chain(m, w.planes, noise, prev, post_slots, (long long)T * N * D, kernel_dist, attn, 1, B, T, w.rows, st_main);
   }
+  // (the per-pixel chain stays per time step: as ONE launch for the B * T frames it takes 333 instead of 6 x 65 us on the lane, but the Slot-Attention
+  //  iterations then read their rows from HBM instead of the cache the launch in front of them left warm: 18.9 -> 20.8 us each -- no gain, probes r06)
+  if (p.batched) SF_TRY(enc_cnn_all_steps(m, img, B, T, w.big, st_main));
+  bool next_done = false;   // the slot prologue of step t ran at the tail of step t - 1's last slot update
   for (int t = 0; t < T; ++t) {
-    float* kv = planes_all ? (float*)((char*)planes + (size_t)t * B * HW * 512) : kv_base + (size_t)(t % KV) * kv_step;
-    // ---- CNN encoder + per-pixel MLP + K/V for the B frames of step t ---------------------
-    st = st_main;
-    if (fork && t >= KV) {   // the ring slot is free once the slot branch of step t - KV has read it
-      if (hipStreamWaitEvent(st_main, enc_fork_event(T + 1 + (t - KV)), 0) != hipSuccess) return sf_set_err((int)hipGetLastError(), "hipStreamWaitEvent", __FILE__, __LINE__);
+    float* kv = w.kv + (size_t)(t % p.KV) * B * ENC_HW * 2 * D;
+    if (p.fork && t >= p.KV) SF_TRY(enc_fork_wait(T + 1 + (t - p.KV), st_main));   // the ring slot, once the slot branch of step t - KV has read it
+    SF_TRY(enc_step_features(a, p, w, t, kv, st_main));
+    if (p.fork) {   // the slot branch of step t behind its features
+      SF_TRY(enc_fork_record(t, st_main));
+      SF_TRY(enc_fork_wait(t, st));
     }
-    for (int b0 = 0; b0 < B && !planes_all; b0 += Bc) {
-      const int nb = (B - b0 < Bc) ? (B - b0) : Bc;
-      const int Cl0 = m->enc_channels[m->enc_layers];
-      const float* cur;
-      if (t < n_pre) {
-        cur = feat_pre + ((long long)t * B + b0) * HW * Cl0;   // computed ahead of time by sf_savi_cnn_f32
-      } else if (batched) {
-        cur = big[2] + ((long long)t * B + b0) * HW * Cl0;
-      } else {
-        float* dstf = (m->enc_layers & 1) ? featA : featB;   // the buffer the last conv does not read
-        SF_TRY(run_cnn(m, img + ((long long)b0 * T + t) * frame_elems, (long long)T * frame_elems, nb, dstf, featA, featB, st));
-        cur = dstf;
-      }
-      const int Cl = m->enc_channels[m->enc_layers];
-      const int Mp = nb * HW;
-      // encoder_out_layer (LN -> Linear -> ReLU -> Linear, savi.py:245-250) and k|v = [Wk;Wv] LN(inputs)
-      // (savi.py:66-70): one fused kernel per 128-pixel tile in split-bf16 mode (pixel_mlp.hip), else three GEMMs
-      if (fold && feat192) {
-        SF_TRY(sf_pixel_mlp_feat192_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_p, m->enc_fc1_b, m->enc_fc2_p, m->enc_fc2_b,
-                                       m->sa_norm_in_g, m->sa_norm_in_b, kv + (long long)b0 * HW * Ce, Mp, ln_eps, st));
-        continue;
-      }
-      if (fold && sa_planes) {   // rows of 512 B (bf16 hi | lo): what sa_attn_planes_kernel streams
-        SF_TRY(sf_pixel_mlp_feat_planes_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b, m->sa_norm_in_g, m->sa_norm_in_b,
-                                           (char*)kv + (size_t)b0 * HW * 512, Mp, ln_eps, st));
-        continue;
-      }
-      if (fold) {
-        SF_TRY(sf_pixel_mlp_feat_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w, m->enc_fc2_b,
-                                    m->sa_norm_in_g, m->sa_norm_in_b, kv + (long long)b0 * HW * Ce, Mp, ln_eps, st));
-        continue;
-      }
-      float* kv_dst = kv + (long long)b0 * HW * 2 * D;
-      int fused = 1;
-      if (sf_get_precision() >= 1)
-        fused = sf_pixel_mlp_kv_ex(cur, m->enc_ln_g, m->enc_ln_b, m->enc_fc1_w, m->enc_fc1_b, m->enc_fc2_w,
-                                   m->enc_fc2_b, m->sa_norm_in_g, m->sa_norm_in_b, m->sa_kv_w, kv_dst, Mp, Cl, Ce,
-                                   2 * D, ln_eps, st);
-      if (fused < 0 || fused > 1) return fused;
-      if (fused == 1) {
-        SF_TRY(sf_linear_ex(cur, sf_rows(Cl), m->enc_fc1_w, m->enc_fc1_b, m->enc_ln_g, m->enc_ln_b, ln_eps, nullptr,
-                            sf_rows(Ce), 0, h1, sf_rows(Ce), Mp, Ce, Cl, 1, st));
-        SF_TRY(sf_linear_ex(h1, sf_rows(Ce), m->enc_fc2_w, m->enc_fc2_b, nullptr, nullptr, ln_eps, nullptr,
-                            sf_rows(Ce), 0, h2, sf_rows(Ce), Mp, Ce, Ce, 0, st));
-        SF_TRY(sf_linear_ex(h2, sf_rows(Ce), m->sa_kv_w, nullptr, m->sa_norm_in_g, m->sa_norm_in_b, ln_eps, nullptr,
-                            sf_rows(2 * D), 0, kv_dst, sf_rows(2 * D), Mp, 2 * D, Ce, 0, st));
-      }
-    }
-    if (fork) {
-      hipEvent_t e = enc_fork_event(t);
-      SF_REQUIRE(e != nullptr, "hipEventCreate failed");
-      if (hipEventRecord(e, st_main) != hipSuccess || hipStreamWaitEvent(st_side, e, 0) != hipSuccess)
-        return sf_set_err((int)hipGetLastError(), "fork event", __FILE__, __LINE__);
-      st = st_side;
-    }
-    // ---- one-launch slot prologue (CLEVRER configuration: residual-MLP predictor without LSTM, single-Linear kernel
-    //      distribution): init / predictor -> kernel_dist -> sampling -> q of the first iteration (slot_attn.hip) ----
-    float* s_in = slotsA;
-    float* s_out = slotsB;
-    int prologue = 1;
-    if (next_done) {   // computed at the tail of the previous step's last slot update (NEXT form below)
-      prologue = 0;
-      next_done = false;
-    } else if (can_prologue)
-      prologue = sf_slot_prologue_ex(prev, m->init_latents, m->pm_ln_g, m->pm_ln_b, m->pm_w0_t, m->pm_b0, m->pm_w2_t, m->pm_b2,
-                                     m->pred_norm_first, m->kd_w0_t, m->kd_b0, noise ? noise + (long long)t * N * D : nullptr,
-                                     (long long)T * N * D, kernel_dist ? kernel_dist + (long long)t * N * 2 * D : nullptr,
-                                     (long long)T * N * 2 * D, m->sa_q_ln_g, m->sa_q_ln_b, q_w_t, s_in, q, B, N, D, ln_eps,
-                                     st);
-    if (prologue < 0 || prologue > 1) return prologue;
-    if (prologue == 1) {
-      // ---- slot initialisation: init_latents or predictor(prev_slots)  (savi.py:393-398) ------
-      const float* lat;
-      if (prev == nullptr) {
-        SF_TRY(sf_copy_rows_ex(m->init_latents, sf_rows_batched(D, N, 0, 0), latents, sf_rows(D), R, D, st));
-        lat = latents;
-      } else {
-        // Transformer predictor (+ LSTM wrapper) in one launch (pred_step.hip) when its packed weights are there
-        int pstep = 1;
-        if (m->pred_type == 1 && m->pred_packed && sf_get_precision() >= 1)
-          pstep = sf_pred_step_ex(prev, m->pred_layers, m->pred_num_layers, m->pred_num_heads, m->pred_ffn_dim, m->pred_norm_first,
-                                  m->pred_packed, m->lstm_b_ih, m->lstm_b_hh, m->proj_b, m->pred_hidden, m->pred_rnn ? lstm_h : nullptr,
-                                  m->pred_rnn ? lstm_c : nullptr, latents, B, N, D, 1e-5f, st);
-        if (pstep < 0 || pstep > 1) return pstep;
-        if (pstep == 0) {
-          lat = latents;
-        } else {
-          const float* pout;
-          if (m->pred_type == 0) {
-            // ResidualMLPPredictor (predictor.py:65-73)
-            SF_TRY(sf_layernorm_ex(prev, sf_rows(D), m->pm_ln_g, m->pm_ln_b, lnbuf, sf_rows(D), R, D, ln_eps, st));
-            SF_TRY(sf_linear_ex(lnbuf, sf_rows(D), m->pm_w0, m->pm_b0, nullptr, nullptr, ln_eps, nullptr, sf_rows(D), 0,
-                                tw.hid, sf_rows(2 * D), R, 2 * D, D, 1, st));
-            SF_TRY(sf_linear_ex(tw.hid, sf_rows(2 * D), m->pm_w2, m->pm_b2, nullptr, nullptr, ln_eps,
-                                m->pred_norm_first ? lnbuf : prev, sf_rows(D), 0, px, sf_rows(D), R, D, 2 * D, 0, st));
-            pout = px;
-          } else {
-            // TransformerPredictor over the N slots (predictor.py:20-44)
-            SF_TRY(sf_copy_rows_ex(prev, sf_rows(D), px, sf_rows(D), R, D, st));
-            float* cur = px;
-            for (int l = 0; l < m->pred_num_layers; ++l) {
-              float* outp = nullptr;
-              SF_TRY(tfm_layer(m->pred_layers[l], cur, tw, B, N, N, D, m->pred_num_heads, m->pred_ffn_dim,
-                               m->pred_norm_first, st, &outp));
-              cur = outp;
-            }
-            pout = cur;
-          }
-          if (m->pred_rnn) {
-            // nn.LSTM, seq len 1, batch B*N (predictor.py:113-120)
-            const int Hh = m->pred_hidden;
-            SF_TRY(sf_linear_ex(pout, sf_rows(D), m->lstm_w_ih, m->lstm_b_ih, nullptr, nullptr, ln_eps, nullptr,
-                                sf_rows(4 * Hh), 0, gates, sf_rows(4 * Hh), R, 4 * Hh, D, 0, st));
-            SF_TRY(sf_linear_ex(lstm_h, sf_rows(Hh), m->lstm_w_hh, m->lstm_b_hh, nullptr, nullptr, ln_eps, gates,
-                                sf_rows(4 * Hh), 0, gates, sf_rows(4 * Hh), R, 4 * Hh, Hh, 0, st));
-            SF_TRY(sf_lstm_pointwise_ex(gates, lstm_c, lstm_h, lstm_c, R, Hh, st));
-            SF_TRY(sf_linear_ex(lstm_h, sf_rows(Hh), m->proj_w, m->proj_b, nullptr, nullptr, ln_eps, nullptr,
-                                sf_rows(D), 0, latents, sf_rows(D), R, D, Hh, 0, st));
-            lat = latents;
-          } else {
-            lat = pout;
-          }
-        }
-      }
-      // ---- kernel distribution + sampling (savi.py:401-402) --------------------------------------
-      if (m->kd_mode == 0) {
-        SF_TRY(sf_copy_rows_ex(lat, sf_rows(D), s_in, sf_rows(D), R, D, st));
-      } else {
-        if (m->kd_mode == 1) {
-          SF_TRY(sf_linear_ex(lat, sf_rows(D), m->kd_w0, m->kd_b0, nullptr, nullptr, ln_eps, nullptr, sf_rows(2 * D), 0,
-                              kdist, sf_rows(2 * D), R, 2 * D, D, 0, st));
-        } else {
-          SF_TRY(sf_linear_ex(lat, sf_rows(D), m->kd_w0, m->kd_b0, nullptr, nullptr, ln_eps, nullptr, sf_rows(2 * D), 0,
-                              kdtmp, sf_rows(2 * D), R, 2 * D, D, 0, st));
-          SF_TRY(sf_linear_ex(kdtmp, sf_rows(2 * D), m->kd_w3, m->kd_b3, m->kd_ln_g, m->kd_ln_b, ln_eps, nullptr,
-                              sf_rows(2 * D), 0, kdist, sf_rows(2 * D), R, 2 * D, 2 * D, 0, st, /*ln_relu=*/1));
-        }
-        const SfRowMap nmap = sf_rows_batched(D, N, (long long)T * N * D, (long long)t * N * D);
-        SF_TRY(sf_sample_dist_ex(kdist, noise, nmap, s_in, R, D, st));
-        if (kernel_dist)
-          SF_TRY(sf_copy_rows_ex(kdist, sf_rows(2 * D), kernel_dist,
-                                 sf_rows_batched(2 * D, N, (long long)T * N * 2 * D, (long long)t * N * 2 * D), R,
-                                 2 * D, st));
-      }
-      // q of the first iteration: LN-fused GEMM; every later q comes out of the slot-update kernel, which also writes the
-      // last iteration's result straight into post_slots[:, t]
-      SF_TRY(sf_linear_ex(s_in, sf_rows(D), q_w, nullptr, m->sa_q_ln_g, m->sa_q_ln_b, ln_eps, nullptr,
-                          sf_rows(D), 0, q, sf_rows(D), R, D, D, 0, st));
-    }
-    // ---- Slot Attention iterations (savi.py:76-100) -------------------------------------------
-    const float scale = 1.0f / sqrtf((float)D);
-    for (int it = 0; it < m->num_iterations; ++it) {
-      const bool last_it = (it == m->num_iterations - 1);
-      float* aout = (attn && last_it) ? attn + (long long)t * N * HW : nullptr;
-      if (fold && sa_planes)   // the same iteration on the bf16 hi | lo rows (split-bf16 MFMAs; the same records)
-        SF_TRY(sf_slot_attn_planes_ex(kv, HW, q, pnum, pden, aout, (long long)T * N * HW, B, HW, N, scale, m->sa_eps, st));
-      else if (fold)   // keys = values = the normalised features (q is Wk^T q here, the GRU input matrix is W_ih Wv)
-        SF_TRY(sf_slot_attn_iter_ex(kv, kv, Ce, (long long)HW * Ce, q, pnum, pden, aout, (long long)T * N * HW, B, HW, N, D, scale,
-                                    m->sa_eps, st));
-      else
-        SF_TRY(sf_slot_attn_iter_ex(kv, kv + D, 2 * D, (long long)HW * 2 * D, q, pnum, pden, aout,
-                                    (long long)T * N * HW, B, HW, N, D, scale, m->sa_eps, st));
-      if (su_mfma) {
-        bool rode = false;
-        // (the one-pass Slot-Attention kernel leaves every second partial record zero: the update reads the others -- eight, one round of requests)
-        const int p_step = (fold && P == HW / 256 && (sa_planes || sf_slot_attn_sparse_records(kv, kv, HW, D))) ? 2 : 1;
-        const bool fuse_next = can_fuse_next && last_it && t + 1 < T && prologue == 0;
-        if (fuse_next) {
-          SfNextStep nx;
-          nx.pm_ln_g = m->pm_ln_g; nx.pm_ln_b = m->pm_ln_b; nx.pm_w0_p = m->pm_w0_p; nx.pm_b0 = m->pm_b0; nx.pm_w2_p = m->pm_w2_p; nx.pm_b2 = m->pm_b2;
-          nx.norm_first = m->pred_norm_first; nx.kd_w_p = m->kd_w0_p; nx.kd_b = m->kd_b0;
-          nx.noise = noise ? noise + (long long)(t + 1) * N * D : nullptr; nx.noise_bs = (long long)T * N * D;
-          nx.kdist_out = kernel_dist ? kernel_dist + (long long)(t + 1) * N * 2 * D : nullptr; nx.kdist_bs = (long long)T * N * 2 * D;
-          nx.slots = slotsA;   // where the next step's iterations start
-          // (the finished rows of step t go to post_slots[:, t]; their ping-pong copy is not read again, and must not alias the sampled slots)
-          SF_TRY(sf_slot_update_mfma_ex(pnum, pden, P, s_in, gru_ih_p, m->sa_gru_hh_p, m->gru_b_ih, m->gru_b_hh, m->mlp_ln_g, m->mlp_ln_b,
-                                        m->sa_mlp_w1_p, m->mlp_b1, m->sa_mlp_w2_p, m->mlp_b2, s_out == slotsA ? latents : s_out,
-                                        post_slots + (long long)t * N * D, (long long)T * N * D, m->sa_q_ln_g, m->sa_q_ln_b, q_w_p, q, B, N, ln_eps, st,
-                                        &nx, p_step));
-          next_done = true;
-          rode = true;
-        }
-        if (!rode)
-          SF_TRY(sf_slot_update_mfma_ex(pnum, pden, P, s_in, gru_ih_p, m->sa_gru_hh_p, m->gru_b_ih, m->gru_b_hh, m->mlp_ln_g,
-                                        m->mlp_ln_b, m->sa_mlp_w1_p, m->mlp_b1, m->sa_mlp_w2_p, m->mlp_b2, s_out,
-                                        last_it ? post_slots + (long long)t * N * D : nullptr, (long long)T * N * D, m->sa_q_ln_g,
-                                        m->sa_q_ln_b, q_w_p, last_it ? nullptr : q, B, N, ln_eps, st, nullptr, p_step));
-        float* tmp = s_in;
-        s_in = s_out;
-        s_out = tmp;
-        continue;
-      }
-      if (su_wide) {
-        SF_TRY(sf_slot_update_wide_ex(pnum, pden, P, s_in, gru_ih_p, m->sa_gru_hh_p, m->gru_b_ih, m->gru_b_hh, m->mlp_ln_g, m->mlp_ln_b,
-                                      m->sa_mlp_w1_p, m->mlp_b1, m->sa_mlp_w2_p, m->mlp_b2, s_out,
-                                      last_it ? post_slots + (long long)t * N * D : nullptr, (long long)T * N * D, m->sa_q_ln_g, m->sa_q_ln_b,
-                                      q_w_p, last_it ? nullptr : q, B, N, ln_eps, st));
-        float* tmp = s_in;
-        s_in = s_out;
-        s_out = tmp;
-        continue;
-      }
-      SF_TRY(sf_slot_update_ex(pnum, pden, P, s_in, gru_ih_t, m->gru_w_hh, m->gru_b_ih, m->gru_b_hh, m->mlp_ln_g,
-                               m->mlp_ln_b, m->mlp_w1, m->mlp_b1, m->mlp_w2, m->mlp_b2, s_out,
-                               last_it ? post_slots + (long long)t * N * D : nullptr, (long long)T * N * D,
-                               m->sa_q_ln_g, m->sa_q_ln_b, q_w_t, (last_it || !q_w_t) ? nullptr : q, B, N, D, Hm, ln_eps,
-                               st));
-      if (!last_it && !q_w_t)   // no transposed copy of project_q given: the LN-fused GEMM produces q
-        SF_TRY(sf_linear_ex(s_out, sf_rows(D), q_w, nullptr, m->sa_q_ln_g, m->sa_q_ln_b, ln_eps, nullptr, sf_rows(D), 0, q,
-                            sf_rows(D), R, D, D, 0, st));
-      float* tmp = s_in;
-      s_in = s_out;
-      s_out = tmp;
-    }
-    // s_in now holds post_slots of step t (also written to post_slots[:, t] by the last slot update)
-    // prev_slots for the next step must not alias the ping-pong buffers that step overwrites:
-    // keep it in `lnbuf`-independent storage (q is rewritten first, so use latents' twin `px`?)
-    // -> simplest: the next step reads `prev` only before it writes slotsA/slotsB.
-    prev = s_in;
-    if (fork && t + KV < T) {   // the features of step t + KV may overwrite this step's ring slot now
-      hipEvent_t e = enc_fork_event(T + 1 + t);
-      SF_REQUIRE(e != nullptr, "hipEventCreate failed");
-      if (hipEventRecord(e, st_side) != hipSuccess) return sf_set_err((int)hipGetLastError(), "hipEventRecord", __FILE__, __LINE__);
-    }
+    bool one_launch = next_done;
+    if (!next_done) SF_TRY(enc_slot_init(a, p, w, prev, t, st, &one_launch));
+    next_done = p.fuse_next && one_launch && t + 1 < T;
+    SF_TRY(enc_iterations(a, p, w, kv, t, next_done, st, &prev));
+    if (p.fork && t + p.KV < T) SF_TRY(enc_fork_record(T + 1 + t, st));
   }
-  if (fork) {   // join: the calling stream continues behind the last slot update
-    hipEvent_t e = enc_fork_event(T);
-    SF_REQUIRE(e != nullptr, "hipEventCreate failed");
-    if (hipEventRecord(e, st_side) != hipSuccess || hipStreamWaitEvent(st_main, e, 0) != hipSuccess)
-      return sf_set_err((int)hipGetLastError(), "fork join", __FILE__, __LINE__);
+  if (p.fork) {   // join: the calling stream continues behind the last slot update
+    SF_TRY(enc_fork_record(T, st));
+    SF_TRY(enc_fork_wait(T, st_main));
   }
   return 0;
 }

@@ -776,8 +776,8 @@ def _batched_encode_is_bit_identical(dev, name):
 
 @torch.no_grad()
 def test_slot_chain_matches_the_per_iteration_launches(dev):
-    """The slot branch of a batched encode as ONE video-stationary launch (csrc/slot_chain.hip: sf_set_slot_chain(1), the default) against the per-iteration
-    launches over the batch (0): Slot Attention as split-bf16 products on feature rows kept as bf16 hi | lo there, exact-f32 products on f32 rows
+    """The slot branch of a batched encode as ONE video-stationary launch (csrc/slot_chain.hip: sf_set_slot_chain(1), opt-in) against the per-iteration
+    launches over the batch (0, the default): Slot Attention as split-bf16 products on feature rows kept as bf16 hi | lo there, exact-f32 products on f32 rows
     here -- split-bf16 rounding apart (both inside the fixture tolerance: test_savi_golden runs the default).  B = 1 / 5 / 32, T = 2 .. 6, injected
     noise, carried state (prev_slots: the chunked encode), post slots / kernel distribution / attention maps compared; plain and CU-masked streams."""
     import ctypes as C
