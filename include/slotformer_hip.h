@@ -442,7 +442,11 @@ int sf_linear_bwd_f32(const float* x, const float* W, const float* y, float* dy,
                       int N, int K, int relu, void* ws, size_t ws_bytes, void* stream);
 /* Attention core of nn.MultiheadAttention under autograd (predictor.py:33-38 in train mode): qkv [B*L, 3d] (q|k|v) -> ctx
  * [B*L, d]; dropout on the softmax weights with masks that are a pure function of (seed, element); the backward call
- * recomputes the probabilities.  L <= 128, head_dim <= 64. */
+ * recomputes the probabilities.  Accepted: L <= 128 and head_dim <= 64 where the backward kernel's tile fits the 160 KB of
+ * LDS, the same range for both calls.  Head dim 32 / 64 with L <= 96 runs on the MFMA kernels, whose tiles pad L to Lp (a
+ * multiple of 32): 4 Lp (hd + 1) + 2 Lp (Lp + 1) floats; every other shape on the scalar kernels, 4 L (hd + 1) + 2 L (L + 1)
+ * floats.  So head dim 64 stops at L = 64 and head dim 32 at L = 113; head dim 16 reaches L = 126, head dim 48 L = 101.
+ * Other shapes return an argument error before any launch. */
 int sf_mha_train_fwd_f32(const float* qkv, float* ctx, int B, int L, int d_model, int num_heads, float dropout_p,
                          unsigned long long seed, void* stream);
 int sf_mha_train_bwd_f32(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int d_model, int num_heads,

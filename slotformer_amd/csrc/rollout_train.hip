@@ -948,6 +948,20 @@ inline size_t tn_partial_floats(const Dims& D) {
   return best > cs ? best : cs;
 }
 
+inline bool attn_use_mfma(int L, int hd) {
+  return (hd == 32 || hd == 64) && L <= 96;
+}
+// dynamic LDS of the training-attention kernel that launch_attn_fwd / launch_attn_bwd pick for (L, hd): the MFMA kernels
+// keep zero-padded tiles of Lp = L rounded up to 32 rows, the scalar ones L rows
+size_t attn_lds_bytes(int L, int hd, bool bwd) {
+  const size_t l = attn_use_mfma(L, hd) ? (size_t)((L + 31) & ~31) : (size_t)L;
+  return ((bwd ? 4 : 3) * l * (hd + 1) + (bwd ? 2 : 1) * l * (l + 1)) * sizeof(float);
+}
+constexpr size_t kAttnLdsMax = (size_t)160 * 1024;   // the LDS of one CU: the most one workgroup can get
+// the (L, head_dim) a training attention accepts: both of its kernels fit the LDS (the backward needs more)
+inline bool attn_shape_fits(int L, int hd) {
+  return L >= 1 && L <= 128 && hd >= 1 && hd <= 64 && attn_lds_bytes(L, hd, true) <= kAttnLdsMax;
+}
 int check_model(const sf_rollouter* m, Dims& D, int B, int pred_len) {
   SF_REQUIRE(m && m->layers, "null model");
   SF_REQUIRE(m->norm_first, "training needs norm_first layers (all reference configurations)");
@@ -961,6 +975,7 @@ int check_model(const sf_rollouter* m, Dims& D, int B, int pred_len) {
   SF_REQUIRE(D.d <= 1024, "d_model <= 1024");
   SF_REQUIRE(D.d % D.H == 0 && D.d / D.H <= 64, "head_dim <= 64");
   SF_REQUIRE(D.L <= 128, "window of at most 128 tokens");
+  SF_REQUIRE(attn_shape_fits(D.L, D.d / D.H), "attention tile does not fit the 160 KB of LDS");   // (the largest window needs the most)
   return 0;
 }
 
@@ -975,25 +990,19 @@ int gemm(const float* A, const float* W, const float* bias, const float* res, fl
   return sf_linear_ex(A, sf_rows(K), W, bias, nullptr, nullptr, 0.f, res, sf_rows(N), 0, Cc, sf_rows(N), M, N, K, relu, st);
 }
 
-int attn_lds_bytes(int L, int hd, bool bwd) {
-  return (int)(((bwd ? 4 : 3) * L * (hd + 1) + (bwd ? 2 : 1) * L * (L + 1)) * sizeof(float));
-}
-
-inline bool attn_use_mfma(int L, int hd) {
-  return (hd == 32 || hd == 64) && L <= 96;
-}
 template <class Kern>
 int set_lds(Kern kern, size_t bytes) {
   if (bytes <= 64 * 1024) return 0;
-  return sf_ensure_dyn_lds((const void*)kern, (size_t)160 * 1024);
+  return sf_ensure_dyn_lds((const void*)kern, kAttnLdsMax);
 }
 int launch_attn_fwd(const float* qkv, float* ctx, int B, int H, int L, int d, uint32_t sseed, uint32_t thr, float inv_keep,
                     hipStream_t st) {
   const int hd = d / H;
   const float scale = 1.f / sqrtf((float)hd);
+  const size_t bytes = attn_lds_bytes(L, hd, false);
+  SF_REQUIRE(bytes <= kAttnLdsMax, "attention tile does not fit the 160 KB of LDS");
   if (attn_use_mfma(L, hd)) {
     const int Lp = (L + 31) & ~31;
-    const size_t bytes = ((size_t)3 * Lp * (hd + 1) + (size_t)Lp * (Lp + 1)) * sizeof(float);
     if (hd == 32) {
       SF_TRY(set_lds(attn_train_fwd_mfma_kernel<32>, bytes));
       hipLaunchKernelGGL(attn_train_fwd_mfma_kernel<32>, dim3(H, B), dim3(256), bytes, st, qkv, ctx, L, Lp, d, scale, sseed, thr,
@@ -1004,8 +1013,8 @@ int launch_attn_fwd(const float* qkv, float* ctx, int B, int H, int L, int d, ui
                          inv_keep);
     }
   } else {
-    hipLaunchKernelGGL(attn_train_fwd_kernel, dim3(H, B), dim3(256), attn_lds_bytes(L, hd, false), st, qkv, ctx, L, d, hd, scale,
-                       sseed, thr, inv_keep);
+    SF_TRY(set_lds(attn_train_fwd_kernel, bytes));
+    hipLaunchKernelGGL(attn_train_fwd_kernel, dim3(H, B), dim3(256), bytes, st, qkv, ctx, L, d, hd, scale, sseed, thr, inv_keep);
   }
   SF_CHECK_LAUNCH();
   return 0;
@@ -1014,9 +1023,10 @@ int launch_attn_bwd(const float* qkv, const float* dctx, float* dqkv, int B, int
                     float inv_keep, hipStream_t st) {
   const int hd = d / H;
   const float scale = 1.f / sqrtf((float)hd);
+  const size_t bytes = attn_lds_bytes(L, hd, true);
+  SF_REQUIRE(bytes <= kAttnLdsMax, "attention tile does not fit the 160 KB of LDS");
   if (attn_use_mfma(L, hd)) {
     const int Lp = (L + 31) & ~31;
-    const size_t bytes = ((size_t)4 * Lp * (hd + 1) + (size_t)2 * Lp * (Lp + 1)) * sizeof(float);
     if (hd == 32) {
       SF_TRY(set_lds(attn_train_bwd_mfma_kernel<32>, bytes));
       hipLaunchKernelGGL(attn_train_bwd_mfma_kernel<32>, dim3(H, B), dim3(256), bytes, st, qkv, dctx, dqkv, L, Lp, d, scale, sseed,
@@ -1027,8 +1037,9 @@ int launch_attn_bwd(const float* qkv, const float* dctx, float* dqkv, int B, int
                          thr, inv_keep);
     }
   } else {
-    hipLaunchKernelGGL(attn_train_bwd_kernel, dim3(H, B), dim3(256), attn_lds_bytes(L, hd, true), st, qkv, dctx, dqkv, L, d, hd,
-                       scale, sseed, thr, inv_keep);
+    SF_TRY(set_lds(attn_train_bwd_kernel, bytes));
+    hipLaunchKernelGGL(attn_train_bwd_kernel, dim3(H, B), dim3(256), bytes, st, qkv, dctx, dqkv, L, d, hd, scale, sseed, thr,
+                       inv_keep);
   }
   SF_CHECK_LAUNCH();
   return 0;
@@ -1168,6 +1179,7 @@ int sf_mha_train_fwd_f32(const float* qkv, float* ctx, int B, int L, int d_model
                          unsigned long long seed, void* stream) {
   SF_REQUIRE(qkv && ctx && B > 0 && L > 0 && L <= 128 && num_heads > 0 && d_model % num_heads == 0 && d_model / num_heads <= 64,
              "bad attention shape");
+  SF_REQUIRE(attn_shape_fits(L, d_model / num_heads), "attention tile does not fit the 160 KB of LDS");
   SF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p in [0, 1)");
   return launch_attn_fwd(qkv, ctx, B, num_heads, L, d_model, site_seed(seed, 0, 0, SITE_ATTN_P), drop_thresh(dropout_p),
                          1.f / (1.f - dropout_p), (hipStream_t)stream);
@@ -1176,6 +1188,7 @@ int sf_mha_train_bwd_f32(const float* qkv, const float* d_ctx, float* d_qkv, int
                          float dropout_p, unsigned long long seed, void* stream) {
   SF_REQUIRE(qkv && d_ctx && d_qkv && B > 0 && L > 0 && L <= 128 && num_heads > 0 && d_model % num_heads == 0 &&
                  d_model / num_heads <= 64, "bad attention shape");
+  SF_REQUIRE(attn_shape_fits(L, d_model / num_heads), "attention tile does not fit the 160 KB of LDS");
   return launch_attn_bwd(qkv, d_ctx, d_qkv, B, num_heads, L, d_model, site_seed(seed, 0, 0, SITE_ATTN_P), drop_thresh(dropout_p),
                          1.f / (1.f - dropout_p), (hipStream_t)stream);
 }
@@ -1220,6 +1233,7 @@ size_t sf_layernorm_bwd_workspace_bytes(int D) { return ((size_t)513 * 2 * D + 1
 int sf_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta, long long rows,
                          int D, float eps, void* ws, size_t ws_bytes, void* stream) {
   SF_REQUIRE(x && dy && gamma && dx && dgamma && dbeta && ws && rows > 0, "null pointer");
+  SF_REQUIRE(D > 0 && D % 4 == 0 && D <= 1024, "LayerNorm width");   // (before the parameter-gradient launch, which assumes it too)
   SF_REQUIRE(ws_bytes >= sf_layernorm_bwd_workspace_bytes(D), "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
@@ -1247,8 +1261,6 @@ int sf_rollout_train_fwd_f32(const sf_rollouter* m, const float* x, float* pred,
   const uint32_t thr = drop_thresh(dropout_p);
   const float inv_keep = 1.f / (1.f - dropout_p);
   const float scale = 1.f / sqrtf((float)hd);
-  const int albytes = attn_lds_bytes(D.L, hd, false);
-  SF_REQUIRE(albytes <= 64 * 1024, "attention tile does not fit LDS");
 
   // burn-in frames -> frame-major slots_all, then their in-projections
   for (int t = 0; t < D.hist; ++t)
@@ -1313,8 +1325,6 @@ int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* 
   const uint32_t thr = drop_thresh(dropout_p);
   const float inv_keep = 1.f / (1.f - dropout_p);
   const float scale = 1.f / sqrtf((float)hd);
-  const int albytes = attn_lds_bytes(D.L, hd, true);
-  SF_REQUIRE(albytes <= 64 * 1024, "attention tile does not fit LDS");
 
   // transposed weight copies: the data-gradient GEMMs run on the forward core (C = A . W^T)
   for (int l = 0; l < D.nl; ++l) {

@@ -133,6 +133,38 @@ def test_rollout_grads_c2_vs_oracle(dev, precision, B, S):
     assert l2_err(d_slots, od) < L2TOL[precision]
 
 
+def _double(t):
+    return t.double() if t.dtype.is_floating_point else t
+
+
+@pytest.mark.parametrize('name,cfg_name,seed,B,S', [
+    # the reference's Physion window (slotformer_physion_params.py: 15 burn-in frames x 6 slots = 90 tokens, 8 layers): MFMA
+    # attention on 96-token tiles, past 64 KB of LDS
+    ('roll_c4_ref', 'C4_ROLL_REF', 214, 2, 2),
+    # OBJ3D (d_model 128, 8 heads of 16): the scalar attention kernels
+    ('roll_c1', 'C1_ROLL', 201, 3, 3),
+    # CLEVRER at tools/bench_train.py's training batch, oracle in float64
+    ('roll_c2', 'C2_ROLL', 202, 32, 10),
+])
+def test_rollout_grads_reference_shapes_vs_oracle(dev, precision, name, cfg_name, seed, B, S):
+    cfg = {**getattr(gu, cfg_name), 'loss_dict': dict(rollout_len=S, use_img_recon_loss=False)}
+    m, sd = build(cfg, gu.load_golden(name), seed, dev, vp=True)
+    m.train()
+    _no_dropout(m)
+    rd = cfg['rollout_dict']
+    slots = gu.seeded_normal((B, rd['history_len'] + S, rd['num_slots'], rd['slot_size']), 910 + B)
+    loss, pred, grads, d_slots = _engine_grads(m, slots, 1.0, dev)
+    oloss, opred, ograds, od = _oracle_grads(slots.double(), {k: _double(v) for k, v in sd.items()}, cfg, S, 1.0, set(grads))
+    worst = max((l2_err(grads[n], ograds[n]), n) for n in grads)
+    print(name, precision, f'loss {abs(loss - oloss) / abs(oloss):.2e} pred {rel_err(pred, opred):.2e} worst grad {worst[0]:.2e} ({worst[1]})',
+          f'd_slots {l2_err(d_slots, od):.2e} (bound {L2TOL[precision]:.0e})')
+    assert abs(loss - oloss) < 1e-5 * abs(oloss)
+    assert rel_err(pred, opred) < 1e-4
+    for n in grads:
+        assert l2_err(grads[n], ograds[n]) < L2TOL[precision], n
+    assert l2_err(d_slots, od) < L2TOL[precision]
+
+
 def test_rollout_dropout_masks_vs_oracle(dev):
     """Train mode with the layer's default dropout (p = 0.1): the library's masks are a pure function of
     (seed, step, layer, site, element), rebuilt here on the host and fed to the oracle."""
