@@ -309,7 +309,8 @@ typedef struct {
   /* optional, same rule: sf_pack_attn_weights() copies of in_proj_w / out_proj_w */
   const void *attn_in_packed, *attn_out_packed;
   /* optional: sf_pack_layer_tok_weights() copy of all four matrices (the layer's fragments in consumption order) -- with it the rollout runs the layers
-   * before the last as ONE token-stationary launch each (csrc/layer_tok.hip; sf_rollout_opts.layer_tok) */
+   * before the last as ONE token-stationary launch each (csrc/layer_tok.hip, csrc/layer_tok128.hip; sf_rollout_opts.layer_tok).  A blob belongs to
+   * the (d_model, heads, ffn) it was packed for: (256, 8, 1024) or (128, 8, 512) */
   const void* tok_packed;
 } sf_tfm_layer;
 
@@ -351,10 +352,18 @@ int sf_ffn_block_rows_f32(const sf_tfm_layer* w, const float* x2, float* y, int 
  * workgroup, only a head's keys / values cross waves; `nl` (1..8) consecutive layers w[0..nl) run in ONE launch (the rows never leave the registers
  * between them).  tok_packed: sf_pack_layer_tok_weights copy of a layer (sf_layer_tok_packed_bytes() bytes: its four matrices as fragments in consumption
  * order + its eight vectors).  A sequence's result does not depend on the other sequences of the call; it may differ in the last bits with its position
- * modulo the sequences per workgroup. */
+ * modulo the sequences per workgroup.
+ * Two shapes (d_model, heads, ffn) are covered: (256, 8, 1024) and (128, 8, 512) -- the OBJ3D Transformer, heads of 16, x, y [B][L][128]
+ * (csrc/layer_tok128.hip: the same workgroup / wave geometry and window rules; an attention stage carries a PAIR of heads).  sf_pack_layer_tok_weights
+ * takes either and refuses every other shape; the blob it writes (sf_layer_tok_packed_bytes_ex(d_model, heads, ffn) bytes; 0 = shape not covered;
+ * sf_layer_tok_packed_bytes() is the (256, 8, 1024) size) is only valid for the kernel of that shape.  sf_layer_tok_block_f32 is the (256, 8, 1024)
+ * entry; sf_layer_tok_block_ex_f32 names the shape w[].tok_packed was packed for and runs that shape's kernel.  Both return an argument error without a
+ * launch for L > 96, nl outside 1..8, an uncovered shape or a process precision other than split-bf16. */
 size_t sf_layer_tok_packed_bytes(void);
+size_t sf_layer_tok_packed_bytes_ex(int d_model, int num_heads, int ffn);
 int sf_pack_layer_tok_weights(const sf_tfm_layer* w, void* packed, int d_model, int num_heads, int ffn, void* stream);
 int sf_layer_tok_block_f32(const sf_tfm_layer* w, int nl, const float* x, float* y, int B, int L, void* stream);
+int sf_layer_tok_block_ex_f32(const sf_tfm_layer* w, int nl, int d_model, int num_heads, int ffn, const float* x, float* y, int B, int L, void* stream);
 int sf_debug_read_ts_layer_tok(long long* out16);   /* wall-clock stamps (10 ns) of workgroup 0 with SF_DBG=lt */
 size_t sf_attn_rows_planes_bytes(int B);
 int sf_attn_block_rows_f32(const sf_tfm_layer* w, const float* x, float* out, void* planes, int B, int L, int Lq, void* stream);
@@ -412,7 +421,12 @@ typedef struct {
                       * of <= 96 tokens; 65..96 -- the reference's Physion window of 15 frames x 6 slots -- outside the pipeline's units): those layers run as ONE token-stationary launch each (csrc/layer_tok.hip) -- a 128-token workgroup owns whole
                       * videos, every product of the layer keeps its activations in registers -- instead of an attention-core launch per video plus an
                       * FFN + q|k|v launch per 64-row tile; the row-pruned last layer keeps the row-tile forms.  Not bit-identical to the other forms
-                      * (one accumulator per output block instead of per-chunk partial sums): 1e-6-level differences per layer */
+                      * (one accumulator per output block instead of per-chunk partial sums): 1e-6-level differences per layer.
+                      * A rollouter of d_model 128, 8 heads, ffn 512 (OBJ3D; the generic GEMM path) takes the same option: with tok_packed on the layers
+                      * before the last, norm_first, split-bf16 mode and a sliding window of <= 96 tokens those layers run as ONE launch of
+                      * csrc/layer_tok128.hip per step, the last layer stays on the GEMM core (sf_rollout_tok_layers tells which).  Measured
+                      * (profiles/layer_tok_d128.md, 6 + 10 frames): FASTER than the GEMM path from 64 videos up (1.43 x at 192, 2.5 x at 512), SLOWER at 32
+                      * (188 against 175 us per step: the launch costs about the same whatever it holds) -- pick per batch size */
 } sf_rollout_opts;
 int sf_set_layer_tok(int on);   /* process default of sf_rollout_opts.layer_tok == 0 */
 int sf_get_layer_tok(void);
@@ -425,6 +439,11 @@ int sf_rollout_is_fused(const sf_rollouter* m);
 /* 1 when the layers before the last can run as token-stationary launches (sf_rollout_opts.layer_tok): fused-layer path, tok_packed on those layers,
  * every window of the rollout within the kernel's limits (whether layer_tok is on is not asked) */
 int sf_rollout_tok_ok(const sf_rollouter* m);
+/* How many leading layers a rollout of B videos with these options (NULL: the process defaults) runs as token-stationary launches, on whatever path:
+ * 0 or num_layers - 1.  Unlike sf_rollout_tok_ok it asks whether layer_tok is ON for the call and counts every path that takes the launches: the
+ * fused-layer path, the long-window path (65..96 tokens) and the generic path at (128, 8, 512), for which sf_rollout_tok_ok and sf_rollout_is_fused
+ * stay 0.  Reads no weight and needs no GPU. */
+int sf_rollout_tok_layers(const sf_rollouter* m, int B, const sf_rollout_opts* opts);
 /* 1 when sf_rollout_f32 may run seam launches for this model / batch with the calling thread's defaults: the fused-layer path with
  * packed in/out projections in split-bf16 mode, seams on, head-pair attention (attn_heads_per_wg 8, attn_qkv_rows and the
  * token-stationary layers take other forms), a grid that fits the CUs, and a window of some step after the first that a seam launch

@@ -171,14 +171,17 @@ SIGNATURES = {
     'sf_rollout_uses_seam_opts': (I, [C.POINTER(sf_rollouter), I, C.POINTER(sf_rollout_opts)]),
     'sf_rollout_is_fused': (I, [C.POINTER(sf_rollouter)]),
     'sf_rollout_tok_ok': (I, [C.POINTER(sf_rollouter)]),
+    'sf_rollout_tok_layers': (I, [C.POINTER(sf_rollouter), I, C.POINTER(sf_rollout_opts)]),
     'sf_ffn_chunk_partials_f32': (I, [C.POINTER(sf_tfm_layer), FP, LL, FP, LL, I, I, I, VP]),
     'sf_attn_block_f32': (I, [C.POINTER(sf_tfm_layer), FP, FP, I, I, I, I, VP]),
     'sf_ffn_block_rows_f32': (I, [C.POINTER(sf_tfm_layer), FP, FP, I, I, VP]),
     'sf_set_layer_tok': (I, [I]),
     'sf_get_layer_tok': (I, []),
     'sf_layer_tok_packed_bytes': (SZ, []),
+    'sf_layer_tok_packed_bytes_ex': (SZ, [I, I, I]),
     'sf_pack_layer_tok_weights': (I, [C.POINTER(sf_tfm_layer), VP, I, I, I, VP]),
     'sf_layer_tok_block_f32': (I, [C.POINTER(sf_tfm_layer), I, FP, FP, I, I, VP]),
+    'sf_layer_tok_block_ex_f32': (I, [C.POINTER(sf_tfm_layer), I, I, I, I, FP, FP, I, I, VP]),
     'sf_debug_read_ts_layer_tok': (I, [C.POINTER(C.c_longlong)]),
     'sf_attn_rows_planes_bytes': (SZ, [I]),
     'sf_attn_block_rows_f32': (I, [C.POINTER(sf_tfm_layer), FP, FP, VP, I, I, I, VP]),

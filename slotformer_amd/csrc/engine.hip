@@ -145,7 +145,8 @@ void step_window(const sf_rollouter* m, int s, int& nf, int& f0) {
 // How sf_rollout_f32 runs a model, chosen once per call from its shape, which packed weight copies it has (their presence only: no
 // weight is read, so a plan is made without a GPU), the process defaults and the call's options
 struct RolloutPlan {
-  // GENERIC: GEMM-core layers (tfm_layer).  LONG_WINDOW (65..128 tokens): tfm_layer on LN1 + q|k|v + attention in one launch
+  // GENERIC: GEMM-core layers (tfm_layer); at d_model 128 / 8 heads / ffn 512 with layer_tok on, the layers before the last as token-stationary
+  // launches (layer_tok128.hip) on x = in_proj(window) + PE, the row-pruned last layer still tfm_layer.  LONG_WINDOW (65..128 tokens): tfm_layer on LN1 + q|k|v + attention in one launch
   // (attn_fused.hip), the out-projection GEMM and the fused FFN kernel.  FUSED_*: the two-launch layers of layer_fused.hip on
   // x = in_proj(window) + PE (ROWS), or on the ring of cached in-projections with one launch per step boundary (RING)
   enum Path { GENERIC, LONG_WINDOW, FUSED_ROWS, FUSED_RING } path = GENERIC;
@@ -192,6 +193,10 @@ RolloutPlan plan_rollout(const sf_rollouter* m, int B, const SfThreadOpts& o) {
   } else if (fusable && sf_layer_fused_ok(d, m->num_heads, m->ffn_dim, 1) && Lmax > 64 && sf_ffn_tiles(B * Lmax) <= 1024) {
     p.path = RolloutPlan::LONG_WINDOW;
     if (tok_on && Lmax <= 96 && !m->single_step && sf_layer_tok_ok(Lmax)) p.tok_layers = nl - 1;   // one video per workgroup
+  } else if (tok_on && !plain_gemms(o) && precision >= 1 && m->norm_first && sf_layer_tok128_shape(d, m->num_heads, m->ffn_dim) && !m->single_step &&
+             sf_layer_tok_ok(Lmax)) {
+    // the OBJ3D Transformer: the sliding window has one size (the single-step rollouter has no configuration of this shape and is not taken)
+    p.tok_layers = nl - 1;
   }
   return p;
 }
@@ -362,6 +367,8 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
       float* xo = (cin == w.xa) ? w.xb2 : w.xa;
       if (ring_in)
         SF_TRY(sf_layer_tok_ex(l == 0 ? 1 : 0, cin, w.ring, RF, N, f0, pe, m->layers + l, nlt, eps, xo, B, L, st));
+      else if (sf_layer_tok128_shape(d, m->num_heads, m->ffn_dim))   // (the kernel follows the MODEL's shape: its tok_packed blobs are that shape's)
+        SF_TRY(sf_layer_tok128_ex(cin, m->layers + l, nlt, eps, xo, B, L, st));
       else
         SF_TRY(sf_layer_tok_ex(0, cin, nullptr, 1, 1, 0, nullptr, m->layers + l, nlt, eps, xo, B, L, st));
       cin = xo;
@@ -550,6 +557,13 @@ int sf_rollout_tok_ok(const sf_rollouter* m) {
   o.layer_tok = 1;
   const RolloutPlan p = plan_rollout(m, 1, o);
   return p.fused() && p.tok_layers > 0;
+}
+
+// How many leading layers sf_rollout_f32 with these options (NULL: the thread's defaults) runs as token-stationary launches, on whatever path: 0 or
+// num_layers - 1
+int sf_rollout_tok_layers(const sf_rollouter* m, int B, const sf_rollout_opts* opts) {
+  if (B <= 0) return 0;
+  return plan_rollout(m, B, rollout_thread_opts(opts)).tok_layers;
 }
 
 // 1 when sf_rollout_f32 with these options may launch seams for this model / batch (a caller that wants to verify

@@ -33,6 +33,11 @@ int sf_ffn_tile_ex(const float* x2, const sf_tfm_layer& w, float eps, float* y, 
 // rollout step, x = ring rows + position table
 bool sf_layer_tok_ok(int L);
 int sf_layer_tok_vpw(int L);   // videos per 128-token workgroup for sequences of L tokens (0: refused)
+// the same layers at d_model 128, 8 heads of 16, ffn 512 (layer_tok128.hip): rows in, rows out; the window rules are sf_layer_tok_vpw's
+bool sf_layer_tok128_shape(int d_model, int num_heads, int ffn);
+size_t sf_layer_tok128_packed_bytes();
+int sf_pack_layer_tok128(const sf_tfm_layer* w, void* packed, hipStream_t st);
+int sf_layer_tok128_ex(const float* xin, const sf_tfm_layer* layers, int nl, float eps, float* y, int B, int L, hipStream_t st);
 int sf_layer_tok_ex(int mode, const float* xin, const float* ring, int ring_frames, int nslots, int f0, const float* pe, const sf_tfm_layer* layers, int nl,
                     float eps, float* y, int B, int L, hipStream_t st);
 // row-tile form (attn_rows.hip): q|k|v projection on 128-row tiles of the batch + one core / out-projection workgroup per video;

@@ -129,10 +129,12 @@ def _tfm_layers(plan, encoder, pack_ffn=False):
         a.norm2_g, a.norm2_b = plan.dp(l.norm2.weight), plan.dp(l.norm2.bias)
         a.lin1_w, a.lin1_b = plan.dp(l.linear1.weight), plan.dp(l.linear1.bias)
         a.lin2_w, a.lin2_b = plan.dp(l.linear2.weight), plan.dp(l.linear2.bias)
-        if a.attn_in_packed:
-            # all four matrices as the fragment stream of the token-stationary layer launch + the layer's vectors (layer_tok.hip)
-            tp = torch.empty(lib().sf_layer_tok_packed_bytes(), dtype=torch.uint8, device=l.linear1.weight.device)
-            check(lib().sf_pack_layer_tok_weights(C.byref(a), tp.data_ptr(), d, 8, ffn, torch.cuda.current_stream().cuda_stream))
+        heads = l.self_attn.num_heads
+        if a.attn_in_packed or (pack_ffn and (d, heads, ffn) == (128, 8, 512) and l.linear1.weight.is_cuda):
+            # all four matrices as the fragment stream of the token-stationary layer launch + the layer's vectors (layer_tok.hip; layer_tok128.hip
+            # for the OBJ3D shape, which has no other packed copy)
+            tp = torch.empty(lib().sf_layer_tok_packed_bytes_ex(d, heads, ffn), dtype=torch.uint8, device=l.linear1.weight.device)
+            check(lib().sf_pack_layer_tok_weights(C.byref(a), tp.data_ptr(), d, heads, ffn, torch.cuda.current_stream().cuda_stream))
             plan.keep.append(tp)
             a.tok_packed = tp.data_ptr()
     plan.keep.append(arr)
