@@ -139,6 +139,39 @@ int sf_decode_combine_seg_f32(const float* dec, float* recon_combined, float* re
 int sf_postproc_mask_f32(const float* masks, long long* seg_i64, unsigned char* seg_u8, float fg_thre, unsigned* slot_max, int F, int N,
                          int HW, void* stream);
 
+/* ---- video-prediction metrics (vp_utils.py:44-344 as test_vp.py:149-160 calls them; csrc/vp_metrics.hip) ---------------------------------
+ * F = B * T frames, frame (b, t) at index b * T + t.  Every score is a double; every sum has a fixed order, so equal inputs give equal bits.
+ * Bytes of workspace for the calls below on F frames of H x W (0 for a shape they reject). */
+size_t sf_vp_metrics_workspace_bytes(int F, int H, int W);
+/* MSE / PSNR / SSIM per frame in one pass over both clips (vp_utils.py:72-106, 323-333).  gt, pred [F,3,H,W] float32; to_rgb = 1: in the model's
+ * [-1, 1] range, to_rgb_from_tensor (x * 0.5 + 0.5, clamped to [0, 1]) is applied on load; to_rgb = 0: already in [0, 1], taken as they are.  mse [F]: squared error summed over H and W, averaged over the channels.
+ * psnr [F]: peak_signal_noise_ratio at data range 1 (+inf for equal frames).  ssim [F]: structural_similarity(channel_axis=0, gaussian_weights=True,
+ * sigma=1.5, use_sample_covariance=False) -- 11 normalised Gaussian taps, K1 0.01, K2 0.03, the map cropped by 5 pixels and averaged over crop and
+ * channels -- evaluated at data range 1, which is the same function as the reference's data range 255 on the x 255 images.  The crop equals the
+ * filter radius, so no kept map pixel reads across the image edge.  Any H, W >= 11. */
+int sf_vp_image_metrics_f32(const float* gt, const float* pred, double* mse, double* psnr, double* ssim, int F, int H, int W, int to_rgb,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* ARI / FG-ARI / mIoU per frame (vp_utils.py:114-177, 225-255).  gt_mask [F,H*W] int64; pred_mask [F,H*W] int64, or uint8 with pred_is_u8 = 1; ids
+ * in [0, num_classes) for pred_mask and [0, 16) for gt_mask, num_classes <= 16.  A pixel with an id outside is left out and sets *flag to 1 (flag: one
+ * device word, zeroed by the call).  tables [F,16,16] uint32 (ground truth x predicted counts; NULL: kept in the workspace), pred_boxes [F,16,4]
+ * float32 or NULL (as sf_masks_to_boxes).  ari / fari [F]: adjusted_rand_index without / with ignore_background, 1 where the denominator is 0;
+ * miou [F]: the maximum-weight assignment over intersect / (union + 1e-8) of the ground-truth ids 1 .. N against the predicted ids, divided by
+ * N = the largest ground-truth id of the frame; NaN without a foreground pixel. */
+int sf_vp_mask_metrics(const long long* gt_mask, const void* pred_mask, int pred_is_u8, unsigned* tables, float* pred_boxes, double* ari,
+                       double* fari, double* miou, unsigned* flag, int F, int H, int W, int num_classes, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* bbox_precision_recall per frame at IoU >= ovthresh (vp_utils.py:180-222).  gt_bbox [F,N,4], pred_bbox [F,M,4] float32 as [x1,y1,x2,y2];
+ * gt_pres_mask [F,N] bytes (torch.bool) selects the ground-truth rows, predicted rows count where x1 >= 0; N, M <= 64.  Greedy in ground-truth order,
+ * first maximum on ties, each predicted box used once; box IoU = inter / (area_a + area_b - inter), areas (x2 - x1)(y2 - y1), in double.  ap [F] =
+ * tp / predicted boxes, ar [F] = tp / present boxes; NaN for a frame without a present or without a predicted box (the reference divides by zero). */
+int sf_vp_bbox_pr_f32(const float* gt_bbox, const unsigned char* gt_pres_mask, const float* pred_bbox, double* ap, double* ar, int F, int N, int M,
+                      float ovthresh, void* stream);
+/* masks_to_boxes (vp_utils.py:44-69): masks [F,H*W] int64 (or uint8 with is_u8 = 1) -> boxes [F,num_boxes,4] float32 [min x, min y, max x, max y] of
+ * every id below num_boxes <= 16, -1 for an id without a pixel.  flag (may be NULL): set to 1 by an id outside [0, num_boxes). */
+int sf_masks_to_boxes(const void* masks, int is_u8, float* boxes, unsigned* flag, int F, int H, int W, int num_boxes, void* stream);
+/* out [K,T] = the mean over the B videos of per_video [K,B,T] (np.mean over the batch, vp_utils.py:88,106,222,255), summed in order. */
+int sf_vp_mean_over_videos_f64(const double* per_video, double* out, int K, int B, int T, void* stream);
+
 /* table[HW,C] = dense(grid)  (SoftPositionEmbed, utils.py:52-63; grid [HW,4]). */
 int sf_pos_embed_table_f32(const float* grid, const float* dense_w, const float* dense_b, float* table, int HW,
                            int C, void* stream);

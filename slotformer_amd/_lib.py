@@ -154,6 +154,12 @@ SIGNATURES = {
     'sf_savi_decode_seg_f32': (I, [C.POINTER(sf_savi_decoder), FP, FP, FP, FP, VP, VP, F32, I, VP, SZ, VP]),
     'sf_decode_combine_seg_f32': (I, [FP, FP, FP, FP, VP, VP, F32, VP, I, I, I, VP]),
     'sf_postproc_mask_f32': (I, [FP, VP, VP, F32, VP, I, I, I, VP]),
+    'sf_vp_metrics_workspace_bytes': (SZ, [I, I, I]),
+    'sf_vp_image_metrics_f32': (I, [FP, FP, VP, VP, VP, I, I, I, I, VP, SZ, VP]),
+    'sf_vp_mask_metrics': (I, [VP, VP, I, VP, FP, VP, VP, VP, VP, I, I, I, I, VP, SZ, VP]),
+    'sf_vp_bbox_pr_f32': (I, [FP, VP, FP, VP, VP, I, I, I, F32, VP]),
+    'sf_masks_to_boxes': (I, [VP, I, FP, VP, I, I, I, I, VP]),
+    'sf_vp_mean_over_videos_f64': (I, [VP, VP, I, I, I, VP]),
     'sf_pos_embed_table_f32': (I, [FP, FP, FP, FP, I, I, VP]),
     'sf_slot_attn_num_partials': (I, [I]),
     'sf_slot_attn_iter_f32': (I, [FP, FP, I, LL, FP, FP, FP, FP, I, I, I, I, F32, F32, VP]),
