@@ -510,6 +510,29 @@ int sf_dropout_f32(const float* x, const float* res, float* y, long long n, floa
  * weight decay, no amsgrad) over one flat fp32 bucket of n elements; step is the 1-based step count. */
 int sf_adam_flat_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr,
                      float beta1, float beta2, float eps, void* stream);
+/* Gradient clipping by global norm on the flat bucket (torch.nn.utils.clip_grad_norm_; clip_grad = 0.05 in the StoSAVi,
+ * SAVi and STEVE configurations, base_slots/method.py).  ONE launch, nothing read back: out3 (device, 3 floats) receives
+ * the L2 norm of grad[0..n), the coefficient min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0) and 1.0 / 0.0 for
+ * "some element is NaN or +-Inf".  Elements are accumulated in fp32 per thread and in double from the wave on; the result
+ * is bit-identical from call to call.  ws: the workspace query's bytes, 16-byte aligned, ZERO-FILLED before its first use;
+ * every call leaves its arrival counter (the first 4 bytes) at zero again, so one workspace serves any later n it is large enough for. */
+size_t sf_grad_norm_workspace_bytes(long long n);
+int sf_grad_clip_coef_f32(const float* grad, long long n, float max_norm, float* out3, void* ws, size_t ws_bytes,
+                          void* stream);
+/* Adam as above with parameter groups (torch.optim.Adam's param_groups; STEVE's lr / dec_lr, base_slots/method.py:237-276):
+ * group k owns the elements from groups[k].begin up to the next group's begin (the last one up to n) and steps at groups[k].lr.
+ * groups: HOST array, begins ascending, groups[0].begin == 0, at most SF_ADAM_MAX_GROUPS of them.  grad_scale: NULL, or a
+ * DEVICE pointer to one float that every gradient element is multiplied by before it enters the moments -- the coefficient
+ * written by the clip call above (out3 + 1), so clipping costs no pass and no host round trip; grad itself is not modified.
+ * With one group and grad_scale == NULL the result equals the plain entry point's bit for bit. */
+#define SF_ADAM_MAX_GROUPS 8
+typedef struct {
+  long long begin;
+  float lr;
+} sf_adam_group;
+int sf_adam_flat_groups_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, int step,
+                            const sf_adam_group* groups, int num_groups, float beta1, float beta2, float eps,
+                            const float* grad_scale, void* stream);
 /* Backward of nn.LayerNorm over the last dimension (D <= 1024, D % 4 == 0). */
 size_t sf_layernorm_bwd_workspace_bytes(int D);
 int sf_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta,

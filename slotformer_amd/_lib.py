@@ -54,6 +54,10 @@ class sf_slot_attention_grads(C.Structure):
     _fields_ = [(n, FP) for n in _SA_LEAVES]
 
 
+class sf_adam_group(C.Structure):
+    _fields_ = [('begin', C.c_longlong), ('lr', C.c_float)]
+
+
 class sf_savi_decoder_grads(C.Structure):
     _fields_ = [('deconv_w', FP * 8), ('deconv_b', FP * 8)] + [(n, FP) for n in ('out_w', 'out_b', 'pos_w', 'pos_b')]
 
@@ -210,6 +214,9 @@ SIGNATURES = {
     'sf_mha_train_bwd_f32': (I, [FP, FP, FP, I, I, I, I, F32, C.c_ulonglong, VP]),
     'sf_dropout_f32': (I, [FP, FP, FP, LL, F32, C.c_ulonglong, VP]),
     'sf_adam_flat_f32': (I, [FP, FP, FP, FP, LL, I, F32, F32, F32, F32, VP]),
+    'sf_grad_norm_workspace_bytes': (SZ, [LL]),
+    'sf_grad_clip_coef_f32': (I, [FP, LL, F32, FP, VP, SZ, VP]),
+    'sf_adam_flat_groups_f32': (I, [FP, FP, FP, FP, LL, I, C.POINTER(sf_adam_group), I, F32, F32, F32, FP, VP]),
     'sf_layernorm_bwd_workspace_bytes': (SZ, [I]),
     'sf_layernorm_bwd_f32': (I, [FP, FP, FP, FP, FP, FP, LL, I, F32, VP, SZ, VP]),
     'sf_rollout_train_workspace_bytes': (SZ, [C.POINTER(sf_rollouter), I, I]),

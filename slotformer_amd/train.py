@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as tnf
 
 from ._lib import sf_savi_features, sf_savi_features_grads, sf_savi_decoder_grads
+from ._lib import sf_adam_group
 from ._lib import lib, check, sf_rollouter_grads, sf_tfm_layer_grads, sf_slot_attention, sf_slot_attention_grads, _SA_LEAVES
 from . import engine, parallel
 
@@ -832,17 +833,62 @@ def conv3x3_nhwc(x, weight):
     return linear_weight(cols, w2)
 
 
+def flat_bucket_layout(param_groups):
+    """Where the parameter groups of a FlatAdam sit in its bucket.  param_groups: a list of dicts with 'params' (as
+    torch.optim takes them).  Each group's parameters that require a gradient lie contiguously, in group order: returns
+    (params, begins) -- the flat parameter list and the element offset at which each group begins (ascending, begins[0] == 0)."""
+    params, begins, off = [], [], 0
+    for g in param_groups:
+        begins.append(off)
+        for p in g['params']:
+            if p.requires_grad:
+                params.append(p)
+                off += p.numel()
+    return params, begins
+
+
+def grad_norm_grid(n):
+    """Workgroups of the sf_grad_clip_coef_f32 launch over a bucket of n elements (its workspace holds a 16-byte counter and 16
+    bytes per workgroup)."""
+    return (int(lib().sf_grad_norm_workspace_bytes(n)) - 16) // 16
+
+
 class FlatAdam:
     """Adam (torch.optim.Adam defaults: betas (0.9, 0.999), eps 1e-8, no weight decay -- the reference's optimiser) over ONE
     flat bucket.  The parameters are re-pointed at views of a single fp32 tensor (their values are kept), gradients are
     gathered into a matching flat tensor, and a step is one `sf_adam_flat_f32` launch -- plus, under data parallelism
-    (`allreduce=True`), one RCCL all-reduce of that gradient bucket first.  `lr` may be changed between steps (schedules)."""
+    (`allreduce=True`), one RCCL all-reduce of that gradient bucket first.  `lr` may be changed between steps (schedules:
+    `warmup_cosine_lr`).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, allreduce=False):
-        self.params = [p for p in params if p.requires_grad]
+    params: an iterable of tensors, or a list of dicts {'params': [...], 'lr': optional} as torch.optim.Adam takes them (STEVE's
+    two rates: `steve_param_groups`).  Each group is contiguous in the bucket, in group order (`flat_bucket_layout`), and
+    `param_groups` is the list of dicts with 'params' and a mutable 'lr' that a schedule written for torch.optim assigns to;
+    `lr` is group 0's rate.  With more than one group the step is one `sf_adam_flat_groups_f32` launch.
+
+    clip_grad: clip the gradient's global L2 norm to this value, torch.nn.utils.clip_grad_norm_'s rule (the reference's
+    `clip_grad`, base_slots/method.py), applied to the all-reduced gradient as under DDP.  It adds ONE launch
+    (`sf_grad_clip_coef_f32`) whose coefficient the update reads from device memory: no pass over the gradients, no host round
+    trip, nothing allocated per step.  `p.grad` is left UNCLIPPED (clip_grad_norm_ rescales it in place; here the scale is
+    applied inside the update).  `grad_norm` is a one-element device view of the norm before clipping (what the reference
+    logs), `grad_nonfinite` one of a flag that is 1.0 when some gradient element was NaN or +-Inf.  As with torch a non-finite
+    gradient propagates into the parameters; the flag is there for the caller to look at when it chooses."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, allreduce=False, clip_grad=None):
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            groups = [{'params': list(g['params']), 'lr': float(g.get('lr', lr))} for g in params]
+        else:
+            groups = [{'params': params, 'lr': float(lr)}]
+        if not 1 <= len(groups) <= 8:
+            raise ValueError('slotformer_amd: FlatAdam takes 1 to 8 parameter groups')
+        self.params, begins = flat_bucket_layout(groups)
+        for g in groups:
+            g['params'] = [p for p in g['params'] if p.requires_grad]
+        self.param_groups = groups
         if not self.params or not self.params[0].is_cuda:
             raise RuntimeError('slotformer_amd: FlatAdam needs parameters on a HIP device; there is no CPU fallback')
-        self.lr, self.betas, self.eps, self.allreduce, self.steps = float(lr), betas, float(eps), allreduce, 0
+        self.betas, self.eps, self.allreduce, self.steps = betas, float(eps), allreduce, 0
+        self.clip_grad = float(clip_grad) if clip_grad else None
         n = sum(p.numel() for p in self.params)
         dev = self.params[0].device
         self.flat = torch.empty(n, dtype=torch.float32, device=dev)
@@ -855,6 +901,23 @@ class FlatAdam:
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros_like(self.grad)
         self.exp_avg_sq = torch.zeros_like(self.grad)
+        self._groups = (sf_adam_group * len(groups))()
+        for g, b in zip(self._groups, begins):
+            g.begin = b
+        self.grad_norm = self.grad_nonfinite = None
+        if self.clip_grad:
+            # norm, coefficient, non-finite flag; the workspace's arrival counter starts at zero and every call leaves it there
+            self._clip_out = torch.zeros(3, dtype=torch.float32, device=dev)
+            self._clip_ws = torch.zeros(int(lib().sf_grad_norm_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+            self.grad_norm, self.grad_nonfinite = self._clip_out[0:1], self._clip_out[2:3]
+
+    @property
+    def lr(self):
+        return self.param_groups[0]['lr']
+
+    @lr.setter
+    def lr(self, value):
+        self.param_groups[0]['lr'] = float(value)
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -872,14 +935,52 @@ class FlatAdam:
         if self.allreduce:
             parallel.allreduce_flat(self.grad)
         self.steps += 1
-        check(lib().sf_adam_flat_f32(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                     self.flat.numel(), self.steps, self.lr, float(self.betas[0]), float(self.betas[1]), self.eps,
-                                     torch.cuda.current_stream().cuda_stream))
+        st = torch.cuda.current_stream().cuda_stream
+        scale = None
+        if self.clip_grad:
+            check(lib().sf_grad_clip_coef_f32(self.grad.data_ptr(), self.grad.numel(), self.clip_grad, self._clip_out.data_ptr(),
+                                              self._clip_ws.data_ptr(), self._clip_ws.numel(), st))
+            scale = self._clip_out.data_ptr() + 4
+        if scale is None and len(self.param_groups) == 1:
+            check(lib().sf_adam_flat_f32(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                         self.flat.numel(), self.steps, float(self.lr), float(self.betas[0]), float(self.betas[1]), self.eps, st))
+        else:
+            for g, d in zip(self._groups, self.param_groups):
+                g.lr = float(d['lr'])
+            check(lib().sf_adam_flat_groups_f32(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
+                                                self.exp_avg_sq.data_ptr(), self.flat.numel(), self.steps, self._groups, len(self._groups),
+                                                float(self.betas[0]), float(self.betas[1]), self.eps, scale, st))
         # The kernel wrote the parameters through a raw pointer: tell torch (and, through `_version`, every plan cache
         # in engine.py that is keyed on (data_ptr, _version)) that their contents changed -- otherwise derived / packed
         # weight copies built before this step would keep being served.
         for p in self.params:
             torch._C._increment_version(p)
+
+
+def warmup_cosine_lr(step, total_steps, warmup_steps, max_lr, min_lr=0.):
+    """Learning rate at `step` of the schedule every reference configuration names: linear warm-up, then cosine
+    (base_slots/method.py: min_lr = lr / 100 for the slot models, 0 for STEVE; once per group for STEVE's two rates).
+    Linear from min_lr to max_lr over the first `warmup_steps` steps, then
+    min_lr + (max_lr - min_lr) * (1 + cos(pi * (step - warmup_steps) / (total_steps - warmup_steps))) / 2.
+    A plain host function: assign its value to `FlatAdam.param_groups[k]['lr']` before the step.  The reference takes
+    nerv's CosineAnnealingWarmupRestarts, which is not available here: this is the common single-cycle form and is NOT
+    pinned against nerv."""
+    import math
+    if step < warmup_steps:
+        return min_lr + (max_lr - min_lr) * step / warmup_steps
+    if total_steps <= warmup_steps:
+        return max_lr
+    t = min(max((step - warmup_steps) / (total_steps - warmup_steps), 0.), 1.)
+    return min_lr + (max_lr - min_lr) * (1. + math.cos(math.pi * t)) / 2.
+
+
+def steve_param_groups(model, lr, dec_lr):
+    """The two Adam groups STEVE trains with (base_slots/method.py:245-261): every trainable parameter whose name does not
+    contain 'trans_decoder' at `lr`, the Transformer decoder's at `dec_lr`.  The frozen dVAE is in neither, nor are the decoder's
+    fixed attention masks (parameters without a gradient, which torch.optim.Adam would carry along and never touch)."""
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    return [{'params': [p for n, p in named if 'trans_decoder' not in n], 'lr': lr},
+            {'params': [p for n, p in named if 'trans_decoder' in n], 'lr': dec_lr}]
 
 
 class amp_bf16:

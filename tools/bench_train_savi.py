@@ -65,6 +65,7 @@ def main():
     ap.add_argument('--eager', action='store_true')
     ap.add_argument('--flat-adam', action='store_true', help='train.FlatAdam (one HIP launch per step) instead of torch.optim.Adam')
     ap.add_argument('--amp', action='store_true', help='AMP-bf16 policy: library precision mode 2 (train.amp_bf16)')
+    ap.add_argument('--clip', type=float, default=0., help='clip the gradient norm (stosavi_clevrer_params: 0.05); 0 = off')
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     if a.amp:
@@ -81,9 +82,10 @@ def main():
     data = {'img': img, 'noise': noise}
     if a.flat_adam:
         from slotformer_amd import train as sf_train
-        opt = sf_train.FlatAdam([p for p in m.parameters() if p.requires_grad], lr=1e-4)
+        opt = sf_train.FlatAdam([p for p in m.parameters() if p.requires_grad], lr=1e-4, clip_grad=a.clip or None)
     else:
         opt = torch.optim.Adam([p for p in m.parameters() if p.requires_grad], lr=1e-4)
+    clip_params = [p for p in m.parameters() if p.requires_grad] if a.clip and not a.flat_adam else None
     kld_w = 1e-4
 
     def step():
@@ -91,13 +93,15 @@ def main():
         out = m(data)
         terms = m.calc_train_loss(data, out)
         (terms['post_recon_loss'] + kld_w * terms['kld_loss']).backward()
+        if clip_params:
+            torch.nn.utils.clip_grad_norm_(clip_params, a.clip)
         opt.step()
 
     ms = time_loop(step, a.steps, a.warmup)
     res = {'metric': 'stosavi_training_iterations_per_sec', 'value': round(1e3 / ms, 2), 'unit': 'it/s', 'ms_per_iter': round(ms, 2),
            'frames_per_sec': round(B * T * 1e3 / ms, 1),
            'config': {'workload': f'StoSAVi CLEVRER training step, B={B}, T={T}, 64x64, 7 slots, 2 SA iterations, MLP predictor, '
-                                  'recon + KLD loss, Adam', 'dtype': 'f32 storage, single-pass bf16 MFMA (AMP policy)' if a.amp else 'f32 (split-bf16 MFMA)'}}
+                                  'recon + KLD loss, Adam' + (f', clip_grad {a.clip}' if a.clip else ''), 'dtype': 'f32 storage, single-pass bf16 MFMA (AMP policy)' if a.amp else 'f32 (split-bf16 MFMA)'}}
     if a.eager:
         def estep():
             opt.zero_grad(set_to_none=True)

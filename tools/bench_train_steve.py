@@ -2,7 +2,7 @@
 12 clips per GPU x 6 frames at 128x128, 6 slots of 192, Transformer + LSTM predictor, frozen dVAE with 4096 tokens on a
 32x32 grid, 4-block Transformer decoder of width 192, token cross-entropy, Adam).
 
-  python tools/bench_train_steve.py [--batch 12] [--steps 5] [--warmup 1] [--eager]
+  python tools/bench_train_steve.py [--batch 12] [--steps 5] [--warmup 1] [--eager] [--clip 0.05] [--dec-lr 3e-4]
 
 One JSON line: ms per iteration of the HIP path (forward + loss + backward + optimiser); --eager adds the same step with torch
 ops (autograd) on the same GPU, sharing the parameters and the (inference-path) dVAE tokens.
@@ -103,6 +103,8 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--eager', action='store_true')
+    ap.add_argument('--clip', type=float, default=0., help='clip the gradient norm inside FlatAdam (steve_physion_params: 0.05); 0 = off')
+    ap.add_argument('--dec-lr', type=float, default=0., help="the Transformer decoder's own rate (steve_physion_params: 3e-4); 0 = one group")
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     from slotformer_amd.base_slots import build_model
@@ -115,7 +117,8 @@ def main():
     with torch.no_grad():
         tok = m.dvae.tokenize(img, one_hot=False).flatten(2, 3)           # [B,T,1024] targets from the frozen dVAE
     data = {'img': img, 'token_id': tok}
-    opt = train.FlatAdam([p for p in m.parameters() if p.requires_grad], lr=1e-4)
+    params = train.steve_param_groups(m, 1e-4, a.dec_lr) if a.dec_lr else [p for p in m.parameters() if p.requires_grad]
+    opt = train.FlatAdam(params, lr=1e-4, clip_grad=a.clip or None)
 
     def step():
         opt.zero_grad()
@@ -127,7 +130,8 @@ def main():
     res = {'metric': 'steve_training_iterations_per_sec', 'value': round(1e3 / ms, 2), 'unit': 'it/s', 'ms_per_iter': round(ms, 1),
            'frames_per_sec': round(B * T * 1e3 / ms, 1),
            'config': {'workload': f'STEVE Physion training step, B={B}, T={T}, 128x128, 6 slots of 192, 1025-token decoder (4 blocks, '
-                                  'width 192, vocab 4096), all dropouts on, token cross-entropy, Adam', 'dtype': 'f32 (split-bf16 MFMA)'}}
+                                  'width 192, vocab 4096), all dropouts on, token cross-entropy, Adam' + (f', clip_grad {a.clip}' if a.clip else '') +
+                                  (f', decoder rate {a.dec_lr}' if a.dec_lr else ''), 'dtype': 'f32 (split-bf16 MFMA)'}}
     if a.eager:
         tgt = tok.flatten(0, 1).long()
 
