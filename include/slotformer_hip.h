@@ -172,6 +172,29 @@ int sf_masks_to_boxes(const void* masks, int is_u8, float* boxes, unsigned* flag
 /* out [K,T] = the mean over the B videos of per_video [K,B,T] (np.mean over the batch, vp_utils.py:88,106,222,255), summed in order. */
 int sf_vp_mean_over_videos_f64(const double* per_video, double* out, int K, int B, int T, void* stream);
 
+/* ---- ingest: the decoder's uint8 frames -> the encoder's input (base_slots/datasets/utils.py:15-43 BaseTransforms; csrc/ingest.hip) -------------
+ * Source coordinates and weights are tables built on the HOST in float64, one per (H0, W0, H, W, mode): per output row and per output column the
+ * first source index, the tap count and float32 weights (the kernels do no coordinate arithmetic, so they carry no float32 coordinate rounding).
+ * mode 0: bilinear, align_corners=False, edge-clamped (what the reference's pinned torchvision does to a tensor); 1: the separable triangle filter of
+ * F.interpolate(..., antialias=True), support max(in / out, 1) per axis; 2: nearest as F.interpolate(mode='nearest') picks it: floor(dst * in / out)
+ * clamped to in - 1, evaluated like ATen with a float32 ratio.  Sizes in [1, 16384].
+ * sf_ingest_tables_bytes: bytes of the table (0 for sizes or a mode it rejects).  sf_ingest_tables_host fills `tables` (HOST memory, `bytes` long);
+ * the caller uploads it once and passes the device copy to the two kernels below.  Layout (32-bit words): 8 header words {magic, H0, W0, H, W, mode,
+ * tapsY, tapsX}, then first[H], count[H], weight[H][tapsY] of the rows and first[W], count[W], weight[W][tapsX] of the columns (weights beyond
+ * count are 0; the taps of an output sum to 1 to float32 rounding). */
+size_t sf_ingest_tables_bytes(int H0, int W0, int H, int W, int mode);
+int sf_ingest_tables_host(void* tables, size_t bytes, int H0, int W0, int H, int W, int mode);
+/* src [F,H0,W0,3] uint8 (HWC, as decoded; any byte alignment) -> out [F,3,H,W] float32 = resize((x / 255 - mean_c) / std_c), antialias 0 / 1 = table
+ * modes 0 / 1.  With a palette [K,3] uint8 (device; 1 <= K <= 256) src is [F,H0,W0] uint8 colour indices instead (datasets/phyre.py:50); an index
+ * >= K takes colour K - 1.  palette NULL: K = 0.  tables: the DEVICE copy of the table for these sizes and this mode.  mean3 / std3: three HOST
+ * floats each.  max_blocks: 0 = one workgroup per (frame, band of output rows); > 0 caps the grid (the workgroups loop). */
+int sf_ingest_frames_u8(const unsigned char* src, const unsigned char* palette, int K, const void* tables, const float* mean3,
+                        const float* std3, float* out, int F, int H0, int W0, int H, int W, int antialias, int max_blocks, void* stream);
+/* BaseTransforms.process_mask: src [F,H0,W0] int64 (or uint8 with src_is_u8 = 1) -> [F,H,W] as int64 and / or uint8 (either may be NULL; ids are
+ * copied, uint8 output keeps the low byte).  tables: the DEVICE copy of the mode-2 table for these sizes. */
+int sf_resize_masks_nearest(const void* src, int src_is_u8, const void* tables, long long* out_i64, unsigned char* out_u8, int F, int H0,
+                            int W0, int H, int W, void* stream);
+
 /* table[HW,C] = dense(grid)  (SoftPositionEmbed, utils.py:52-63; grid [HW,4]). */
 int sf_pos_embed_table_f32(const float* grid, const float* dense_w, const float* dense_b, float* table, int HW,
                            int C, void* stream);

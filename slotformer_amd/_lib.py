@@ -164,6 +164,10 @@ SIGNATURES = {
     'sf_vp_bbox_pr_f32': (I, [FP, VP, FP, VP, VP, I, I, I, F32, VP]),
     'sf_masks_to_boxes': (I, [VP, I, FP, VP, I, I, I, I, VP]),
     'sf_vp_mean_over_videos_f64': (I, [VP, VP, I, I, I, VP]),
+    'sf_ingest_tables_bytes': (SZ, [I, I, I, I, I]),
+    'sf_ingest_tables_host': (I, [VP, SZ, I, I, I, I, I]),
+    'sf_ingest_frames_u8': (I, [VP, VP, I, VP, FP, FP, FP, I, I, I, I, I, I, I, VP]),
+    'sf_resize_masks_nearest': (I, [VP, I, VP, VP, VP, I, I, I, I, I, VP]),
     'sf_pos_embed_table_f32': (I, [FP, FP, FP, FP, I, I, VP]),
     'sf_slot_attn_num_partials': (I, [I]),
     'sf_slot_attn_iter_f32': (I, [FP, FP, I, LL, FP, FP, FP, FP, I, I, I, I, F32, F32, VP]),

@@ -100,7 +100,7 @@ def release_pipelines():
 
 @torch.no_grad()
 def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises=None, pipelined=True, to_host=False, decoder=None,
-                        seg_dtype=torch.uint8, encode_group=None, **pipe_kw):
+                        seg_dtype=torch.uint8, encode_group=None, ingest=None, **pipe_kw):
     """Whole hot path over many videos: SAVi slot extraction of the burn-in frames followed by the SlotFormer rollout
     (extract_slots.py:19-38 + rollout_clevrer_slots.py:20-65 / test_phyre_planning.py:159-174 as one on-device call).
 
@@ -115,12 +115,20 @@ def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises
     draws it; ignored by models that sample nothing).
     decoder: a module holding the SAVi decoder (the StoSAVi, or the SlotFormer that copied its weights) -- the PREDICTED frames are then
     also decoded behind their rollout (test_vp.py:55-63,145-146: reconstruction + postproc_mask segmentation) and the call returns
-    (slots, {'recon': [V, pred_len, 3, R, R] float32, 'seg': [V, pred_len, R, R] seg_dtype}) on the device."""
+    (slots, {'recon': [V, pred_len, 3, R, R] float32, 'seg': [V, pred_len, R, R] seg_dtype}) on the device.
+    ingest: an `ingest.FrameIngest` -- `videos` is then the decoder's RAW uint8 clips [V, T_burn, H0, W0, 3] ([V, T_burn, H0, W0] colour indices with
+    a palette), on the device or on the host: normalising and resizing (the reference's BaseTransforms) run on the device, batch by batch on the
+    pipeline's copy stage, and the uploads carry uint8 at source size.  Anything but uint8 raises ValueError."""
     from . import engine
     if decoder is not None and to_host:
         raise RuntimeError('slotformer_amd: decoder= keeps its outputs on the device (to_host=False)')
     dev = next(rollouter.parameters()).device
-    videos = videos.float()
+    if ingest is None:
+        videos = videos.float()
+    else:
+        ingest.output_shape(videos)   # (raises for anything but contiguous uint8 frames: no silent 0..255 floats)
+        if videos.dim() != (4 if ingest.palette is not None else 5):
+            raise ValueError(f'slotformer_amd: ingest= takes clips [V, T, H0, W0, 3] ([V, T, H0, W0] with a palette), got {tuple(videos.shape)}')
     host_in = not videos.is_cuda
     if host_in:
         videos = videos.contiguous()   # (pageable input is staged batch by batch through the pipeline's ring of page-locked buffers)
@@ -153,12 +161,15 @@ def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises
         imgs = [videos[j * batch_size:(j + 1) * batch_size] for j in range(nfull)]
         nz = None if noises is None else [noises[j * batch_size:(j + 1) * batch_size].float().to(dev).contiguous() for j in range(nfull)]
         dv = None if dec is None else {k: v[:nfull * batch_size].view(nfull, batch_size, *v.shape[1:]) for k, v in dec.items()}
-        pipe.run(imgs, nz, out=out[:nfull * batch_size].view(nfull, batch_size, T + pred_len, N, D), serial=not pipelined or nfull < 2, decoded=dv)
+        pipe.run(imgs, nz, out=out[:nfull * batch_size].view(nfull, batch_size, T + pred_len, N, D), serial=not pipelined or nfull < 2, decoded=dv, ingest=ingest)
     r0 = nfull * batch_size
     if r0 < V:
         nz = None if noises is None else noises[r0:].float().to(dev).contiguous()
         nz = engine.kernel_noise(savi, nz, V - r0, T, dev)   # None for models that sample nothing (kld_method 'none')
-        post, _, _ = engine.savi_encode(savi, videos[r0:].to(dev).contiguous(), noise=nz)
+        tail_in = videos[r0:].to(dev).contiguous()
+        if ingest is not None:
+            tail_in = ingest(tail_in)
+        post, _, _ = engine.savi_encode(savi, tail_in, noise=nz)
         tail = torch.zeros(V - r0, T + pred_len, N, D, device=dev)
         tail[:, :T] = post
         engine.rollout(rollouter, tail, T, pred_len, opts=tail_opts)

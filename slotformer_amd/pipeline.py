@@ -482,6 +482,7 @@ class EncodeRolloutPipeline:
             self.pre_steal = []
         self.feat_bufs = None
         self._stage, self._s_copy, self._s_out = None, None, None   # staging ring + copy streams for host-resident inputs / outputs
+        self._stage_u8, self._pin_u8 = None, None                   # ingest=: the device / page-locked rings of uint8 frames at source size
         self.completion_events = []      # one event per unit of the last run() ...
         self.completion_batches = []     # ... and the number of batches it completed
         # the encode graphs hold raw pointers into the SAVi encoder's plan (packed conv weights, folded Slot-Attention matrices,
@@ -622,6 +623,12 @@ class EncodeRolloutPipeline:
         with _STREAMS_LOCK:
             _STREAMS[key] = tuple(picked)
         return picked
+
+    @property
+    def stage_slots(self):
+        """Slots of the staging rings of run() (host-resident and / or ingested inputs): far enough ahead of the consumers for the work stealing,
+        which reads the frames of a batch lead * G + G batches before its encode."""
+        return self.lead * self.G + self.G + 2
 
     def _close_streams(self):
         pass   # (the streams belong to the process-wide pool and live as long as the process)
@@ -889,13 +896,17 @@ class EncodeRolloutPipeline:
                            out_recon=recon.view(self.B * self.H, *recon.shape[2:]), out_seg=seg.view(self.B * self.H, *seg.shape[2:]))
 
     @torch.no_grad()
-    def run(self, imgs, noises=None, out=None, serial=False, decoded=None):
+    def run(self, imgs, noises=None, out=None, serial=False, decoded=None, ingest=None):
         """imgs: sequence of n device tensors [B, burn_in, 3, H, W]; noises: None or n tensors [B, burn_in, N, D]
         (the kernel noise of every frame, for reproducible runs).  Returns out [n, B, burn_in + pred_len, N, D]; the
         pipelined schedule returns when the last batch is finished (the host waits for it, see the end of this function).
         serial=True runs the same calls back to back on the calling stream (reference schedule for the tests).
         decoded: None, or a dict the decode stage fills (pipeline built with decoder=...): 'recon' [n, B, pred_len, 3, R, R] and
-        'seg' [n, B, pred_len, R, R] of the PREDICTED frames (test_vp.py's `pred` / `pred_mask`)."""
+        'seg' [n, B, pred_len, R, R] of the PREDICTED frames (test_vp.py's `pred` / `pred_mask`).
+        ingest: None, or an `ingest.FrameIngest` -- the batches are then RAW uint8 frames [B, burn_in, H0, W0, 3] ([B, burn_in, H0, W0] colour
+        indices with a palette) on the device, in pinned or in pageable host memory: the staging rings hold uint8 at source size (a quarter of the
+        float32 bytes at equal size), and the ingest kernel runs on the copy stream behind each upload, writing the float32 stage buffer the encodes
+        read.  Device-resident batches take the same ring without the copy."""
         n = len(imgs)
         B = self.B
         rc_all, sg_all = self._decoded_buffers(decoded, n) if decoded is not None else (None, None)
@@ -903,7 +914,12 @@ class EncodeRolloutPipeline:
             raise RuntimeError('slotformer_amd: the decode stage reads the slots from a device-resident `out`')
         host_in = n > 0 and not imgs[0].is_cuda
         for im in imgs:
-            if tuple(im.shape[:2]) != (B, self.T) or im.is_cuda == host_in or im.dtype != torch.float32:
+            if ingest is not None:
+                fshape = ingest.output_shape(im)   # (ValueError for anything but contiguous uint8 frames)
+                if tuple(im.shape[:2]) != (B, self.T) or im.is_cuda == host_in or im.shape != imgs[0].shape or len(fshape) != 5:
+                    raise RuntimeError(f'ingest=: every batch must be a uint8 tensor [{B},{self.T},H0,W0,3] ([{B},{self.T},H0,W0] with a palette), all '
+                                       f'of one size, all on the device or all in host memory, got {tuple(im.shape)} {im.dtype} on {im.device}')
+            elif tuple(im.shape[:2]) != (B, self.T) or im.is_cuda == host_in or im.dtype != torch.float32:
                 raise RuntimeError(f'every batch must be a float32 tensor [{B},{self.T},3,H,W], all on the device or all in (pinned) host '
                                    f'memory, got {tuple(im.shape)} {im.dtype} on {im.device}')
         if out is None:
@@ -916,6 +932,8 @@ class EncodeRolloutPipeline:
             for u0, nb, u, _ in units:
                 for h in range(nb):
                     im = imgs[u0 + h].to(self.dev, non_blocking=True) if host_in else imgs[u0 + h]
+                    if ingest is not None:
+                        im = ingest(im)
                     # (on the calling stream the encode has the whole chip: the fill graph -- one persistent convolution workgroup per CU of the
                     #  device -- not the lane's, which is sized for the encode partition)
                     whole = ('fill', 0) if (self.encode_graph and self.cu_split and self.fill_whole_chip and self.s_free and self.fill_par > 1) else 0
@@ -964,24 +982,38 @@ class EncodeRolloutPipeline:
         # host-resident inputs (pinned): an upload stage on its own stream runs ahead of the consumers -- far enough for the
         # work stealing, which reads the frames of a batch lead * G + G batches before its encode (extract_slots.py:19-38 reads
         # its videos from a DataLoader; this is the device side of that hand-over)
-        NS = NF + 2
+        NS = self.stage_slots
+        assert NS == NF + 2
         ev_up, up_next = [], [0]
         pinned_in = host_in and all(im.is_pinned() for im in imgs)
-        if host_in:
-            if self._stage is None or self._stage[0].shape != imgs[0].shape:
-                self._stage = [torch.empty(imgs[0].shape, device=self.dev) for _ in range(NS)]
+        staged = host_in or ingest is not None
+        pin = None
+        if staged:
+            fshape = imgs[0].shape if ingest is None else ingest.output_shape(imgs[0])
+            if self._stage is None or self._stage[0].shape != fshape:
+                self._stage = [torch.empty(fshape, device=self.dev) for _ in range(NS)]
                 self._s_copy = self._pool_stream('copy')
                 self._pin = None
-            if not pinned_in and getattr(self, '_pin', None) is None:
-                # pageable input: batches pass through a ring of NS page-locked staging buffers (never the whole set page-locked at once;
-                # the host pays one memcpy per batch -- pre-pinned input skips it)
-                self._pin = [torch.empty(imgs[0].shape, pin_memory=True) for _ in range(NS)]
+            if ingest is None:
+                if not pinned_in and getattr(self, '_pin', None) is None:
+                    # pageable input: batches pass through a ring of NS page-locked staging buffers (never the whole set page-locked at once;
+                    # the host pays one memcpy per batch -- pre-pinned input skips it)
+                    self._pin = [torch.empty(imgs[0].shape, pin_memory=True) for _ in range(NS)]
+                pin = self._pin
+            elif host_in:
+                # ingest=: both rings hold the decoder's uint8 frames at source size; self._stage is what the ingest kernel writes
+                if self._stage_u8 is None or self._stage_u8[0].shape != imgs[0].shape:
+                    self._stage_u8 = [torch.empty(imgs[0].shape, dtype=torch.uint8, device=self.dev) for _ in range(NS)]
+                    self._pin_u8 = None
+                if not pinned_in and self._pin_u8 is None:
+                    self._pin_u8 = [torch.empty(imgs[0].shape, dtype=torch.uint8, pin_memory=True) for _ in range(NS)]
+                pin = self._pin_u8
             self._s_copy.wait_stream(cur)
             ev_up = [torch.cuda.Event() for _ in range(n)]
 
         def img_of(j, stream):
             """the frames of batch j as a device tensor `stream` may read"""
-            if not host_in:
+            if not staged:
                 return imgs[j]
             while up_next[0] <= min(j, n - 1):
                 k = up_next[0]
@@ -993,12 +1025,19 @@ class EncodeRolloutPipeline:
                         for e in ev_enc[k - NS]:
                             e.synchronize()
                     src = imgs[k]
-                    if not pinned_in:
+                    if host_in and not pinned_in:
                         if k >= NS:
                             ev_up[k - NS].synchronize()   # the upload out of this page-locked slot is done
-                        self._pin[k % NS].copy_(src)
-                        src = self._pin[k % NS]
-                    self._stage[k % NS].copy_(src, non_blocking=True)
+                        pin[k % NS].copy_(src)
+                        src = pin[k % NS]
+                    if ingest is None:
+                        self._stage[k % NS].copy_(src, non_blocking=True)
+                    else:
+                        if host_in:
+                            # (the slot's previous frames were read by the ingest launch of batch k - NS, earlier on this stream)
+                            self._stage_u8[k % NS].copy_(src, non_blocking=True)
+                            src = self._stage_u8[k % NS]
+                        ingest(src, out=self._stage[k % NS])   # on the copy stream, behind the upload
                     ev_up[k].record(self._s_copy)
                 up_next[0] += 1
             stream.wait_event(ev_up[j])
@@ -1187,7 +1226,7 @@ class EncodeRolloutPipeline:
             cur.wait_stream(self._s_dec)
         for st, _, _ in lanes:
             cur.wait_stream(st)
-        for st in rolls + list(self.s_free) + ([self._s_copy] if host_in else []) + ([self._s_out] if not out.is_cuda else []):
+        for st in rolls + list(self.s_free) + ([self._s_copy] if staged else []) + ([self._s_out] if not out.is_cuda else []):
             cur.wait_stream(st)
         self.completion_events = ev_roll
         self.completion_batches = [nb for _, nb, _, _ in units]
