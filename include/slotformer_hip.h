@@ -195,7 +195,51 @@ int sf_ingest_frames_u8(const unsigned char* src, const unsigned char* palette, 
 int sf_resize_masks_nearest(const void* src, int src_is_u8, const void* tables, long long* out_i64, unsigned char* out_u8, int F, int H0,
                             int W0, int H, int W, void* stream);
 
-/* table[HW,C] = dense(grid)  (SoftPositionEmbed, utils.py:52-63; grid [HW,4]). */
+/* ---- egress: decoded frames, slot decompositions, segment ids and boxes -> the videos a writer takes (video_prediction/vp_vis.py make_video /
+ * draw_bbox, base_slots/method.py _make_video_grid, the `(video * 255.).astype(np.uint8)` of _save_video; csrc/egress.hip) -----------------------
+ * The float work is the reference's float32 operations in their order, each rounded once (nothing is contracted into an fma except x * 0.5 + 0.5,
+ * whose product is exact), so the results are held to EXACT equality with the same torch operations on the CPU.  Inputs are assumed FINITE (a NaN
+ * or an infinity gives an unspecified byte).  All pointers are device pointers unless stated; float32 tensors 4-byte aligned, contiguous. */
+enum { SF_EGRESS_TRUNC = 0, SF_EGRESS_NEAREST_EVEN = 1 };               /* rounding of v * 255: toward zero (_save_video) / torch.round (draw_bbox) */
+enum { SF_EGRESS_F32_CHW = 0, SF_EGRESS_U8_CHW = 1, SF_EGRESS_U8_HWC = 2 };   /* what a grid is written as */
+enum { SF_EGRESS_IMG = 0, SF_EGRESS_SLOTS = 1, SF_EGRESS_IDS = 2 };     /* tile kinds */
+/* x [F,3,H,W] float32 -> out uint8 [F,3,H,W] (hwc = 0) or [F,H,W,3] (hwc = 1).  to_rgb = 1: v = clamp(x * 0.5 + 0.5, 0, 1) first (x in [-1, 1]);
+ * 0: v = x (in [0, 1]).  out = rounding(clamp(v * 255.f, 0, 255)), so nothing wraps.  `x` and `out` may sit at any (4-byte / 1-byte) offset and W
+ * need not be a multiple of 4: 16-byte loads and stores where the alignment allows them, a scalar path otherwise. */
+int sf_egress_frames_u8(const float* x, unsigned char* out, long long F, int H, int W, int hwc, int to_rgb, int rounding, void* stream);
+/* One entry of a grid's tile list (HOST memory, read during the call).  IMG: a = x [T,3,H,W] float32 in [-1, 1] -> to_rgb(x).  SLOTS: a = recons
+ * [T,N,3,H,W], b = masks [T,N,1,H,W] float32 -> N consecutive tiles to_rgb(recons * masks + (1 - masks) * scale).  IDS: a = segment ids [T,H,W]
+ * uint8 (ids_i64 = 0) or int64 (1), b = palette [P,3] uint8, 1 <= P <= 256 -> to_rgb(palette[id] / 255 * 2 - 1); an id >= P takes colour P - 1.
+ * history_len: with a border, frames t < history_len get the green frame (0, 0.7, 0), the others the red one (0.7, 0, 0). */
+typedef struct {
+  int kind;
+  int N;
+  const void* a;
+  const void* b;
+  float scale;
+  int ids_i64;
+  int P;
+  int history_len;
+} sf_egress_tile;
+/* The canvas of K tiles of H x W as torchvision.utils.make_grid(tiles, nrow, padding) lays them, each tile grown by `border` pixels on every side
+ * first: xmaps = min(nrow, K), ymaps = ceil(K / xmaps), CH = ymaps * (H + 2 border + padding) + padding, CW likewise; tile k at row k / xmaps,
+ * column k % xmaps.  K == 1: the tile itself, no padding. */
+int sf_egress_grid_shape(int K, int H, int W, int nrow, int padding, int border, int* CH, int* CW);
+/* One video of grids per launch: out [T,3,CH,CW] float32 in [0, 1] (SF_EGRESS_F32_CHW, what the reference's functions return), uint8 [T,3,CH,CW] or
+ * uint8 [T,CH,CW,3] (TRUNC rounding).  The tiles of all entries in order (at most 32); pad_value and the border colours are written as they are,
+ * not passed through to_rgb.  One canvas row must fit 64 KiB of LDS. */
+int sf_egress_grid(const sf_egress_tile* tiles, int n_entries, void* out, int out_mode, int T, int H, int W, int nrow, int padding,
+                   float pad_value, int border, void* stream);
+/* Rectangle outlines IN PLACE on frames [F,3,H,W] uint8.  boxes [F,M,4] float32 (x0, y0, x1, y1), pres [F,M] uint8 or NULL, palette [P,3] uint8,
+ * M <= 256.  Per frame: keep the boxes that are present and have x0 >= 0, truncate their coordinates toward zero; the k-th KEPT box takes colour
+ * min(k, P - 1) (vp_vis.py:60-65: colors=PALETTE[:N] zipped with the surviving boxes -- not the slot index).  A pixel belongs to an outline iff it
+ * lies inside the inclusive box and within `width` pixels of one of its four sides; outlines are clipped to the image, later boxes overwrite
+ * earlier ones.  This is PIL's ImageDraw.rectangle(outline=, width=) for every box with both sides >= 2 * width; for thinner boxes PIL draws
+ * outside the box, which is not followed -- the one difference. */
+int sf_egress_draw_boxes(unsigned char* frames, const float* boxes, const unsigned char* pres, const unsigned char* palette, int P, int F, int M,
+                         int H, int W, int width, void* stream);
+
+/* table[HW,C] = dense(grid) (SoftPositionEmbed, utils.py:52-63; grid [HW,4]). */
 int sf_pos_embed_table_f32(const float* grid, const float* dense_w, const float* dense_b, float* table, int HW,
                            int C, void* stream);
 

@@ -117,6 +117,11 @@ class sf_savi_decoder(C.Structure):
                  ('pos_table', FP), ('deconv_w_flipped', FP * 8), ('deconv_w_frag', C.c_void_p * 8), ('l0_weff', FP), ('l0_posterm', FP)])
 
 
+class sf_egress_tile(C.Structure):
+    _fields_ = [('kind', C.c_int), ('N', C.c_int), ('a', C.c_void_p), ('b', C.c_void_p), ('scale', C.c_float), ('ids_i64', C.c_int), ('P', C.c_int),
+                ('history_len', C.c_int)]
+
+
 I, LL, F32, SZ, VP = C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_void_p
 
 # name -> (restype, argtypes): exactly the declarations of include/slotformer_hip.h
@@ -168,6 +173,10 @@ SIGNATURES = {
     'sf_ingest_tables_host': (I, [VP, SZ, I, I, I, I, I]),
     'sf_ingest_frames_u8': (I, [VP, VP, I, VP, FP, FP, FP, I, I, I, I, I, I, I, VP]),
     'sf_resize_masks_nearest': (I, [VP, I, VP, VP, VP, I, I, I, I, I, VP]),
+    'sf_egress_frames_u8': (I, [FP, VP, LL, I, I, I, I, I, VP]),
+    'sf_egress_grid_shape': (I, [I, I, I, I, I, I, C.POINTER(I), C.POINTER(I)]),
+    'sf_egress_grid': (I, [C.POINTER(sf_egress_tile), I, VP, I, I, I, I, I, I, F32, I, VP]),
+    'sf_egress_draw_boxes': (I, [VP, FP, VP, VP, I, I, I, I, I, I, VP]),
     'sf_pos_embed_table_f32': (I, [FP, FP, FP, FP, I, I, VP]),
     'sf_slot_attn_num_partials': (I, [I]),
     'sf_slot_attn_iter_f32': (I, [FP, FP, I, LL, FP, FP, FP, FP, I, I, I, I, F32, F32, VP]),

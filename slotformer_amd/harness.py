@@ -115,13 +115,14 @@ def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises
     draws it; ignored by models that sample nothing).
     decoder: a module holding the SAVi decoder (the StoSAVi, or the SlotFormer that copied its weights) -- the PREDICTED frames are then
     also decoded behind their rollout (test_vp.py:55-63,145-146: reconstruction + postproc_mask segmentation) and the call returns
-    (slots, {'recon': [V, pred_len, 3, R, R] float32, 'seg': [V, pred_len, R, R] seg_dtype}) on the device.
+    (slots, {'recon': [V, pred_len, 3, R, R] float32, 'seg': [V, pred_len, R, R] seg_dtype}) on the device.  With to_host=True the dict holds
+    {'recon_u8': [V, pred_len, R, R, 3] uint8, 'seg': [V, pred_len, R, R] seg_dtype} in pinned host memory instead: the frames as a video writer
+    takes them (egress.frames_to_uint8 of the reconstruction), quantised on the device and downloaded behind each decode -- a quarter of the float32
+    bytes, and no float32 buffer for the whole set anywhere.
     ingest: an `ingest.FrameIngest` -- `videos` is then the decoder's RAW uint8 clips [V, T_burn, H0, W0, 3] ([V, T_burn, H0, W0] colour indices with
     a palette), on the device or on the host: normalising and resizing (the reference's BaseTransforms) run on the device, batch by batch on the
     pipeline's copy stage, and the uploads carry uint8 at source size.  Anything but uint8 raises ValueError."""
     from . import engine
-    if decoder is not None and to_host:
-        raise RuntimeError('slotformer_amd: decoder= keeps its outputs on the device (to_host=False)')
     dev = next(rollouter.parameters()).device
     if ingest is None:
         videos = videos.float()
@@ -134,7 +135,8 @@ def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises
         videos = videos.contiguous()   # (pageable input is staged batch by batch through the pipeline's ring of page-locked buffers)
     V, T = videos.shape[:2]
     N, D = rollouter.num_slots, rollouter.in_proj.in_features
-    out = torch.empty(V, T + pred_len, N, D, pin_memory=True) if to_host else torch.empty(V, T + pred_len, N, D, device=dev)
+    # (the decode stage reads the slots from a device-resident `out`: with decoder= and to_host=True they are downloaded at the end)
+    out = torch.empty(V, T + pred_len, N, D, pin_memory=True) if to_host and decoder is None else torch.empty(V, T + pred_len, N, D, device=dev)
     # small batches are handed to the pipeline several at a time (pipeline.encode_group_for: the latency-bound slot branch of an encode costs the
     # same for 16 videos as for 32); the kernels are per video, so the slots do not depend on the grouping in the row forms
     # (token-stationary units of >= 96 videos: to ~5e-6)
@@ -148,7 +150,11 @@ def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises
     dec = None
     if decoder is not None:
         R = engine.decoder_plan(decoder).struct.resolution
-        dec = {'recon': torch.empty(V, pred_len, 3, R, R, device=dev), 'seg': torch.empty(V, pred_len, R, R, device=dev, dtype=seg_dtype)}
+        if to_host:
+            dec = {'recon_u8': torch.empty(V, pred_len, R, R, 3, dtype=torch.uint8, pin_memory=True),
+                   'seg': torch.empty(V, pred_len, R, R, dtype=seg_dtype, pin_memory=True)}
+        else:
+            dec = {'recon': torch.empty(V, pred_len, 3, R, R, device=dev), 'seg': torch.empty(V, pred_len, R, R, device=dev, dtype=seg_dtype)}
         pipe_kw = dict(pipe_kw, decoder=decoder, seg_dtype=seg_dtype)
     if nfull:
         if 'group' not in pipe_kw and pipe_kw.get('partition', 'pair') == 'pair':
@@ -174,9 +180,21 @@ def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises
         tail[:, :T] = post
         engine.rollout(rollouter, tail, T, pred_len, opts=tail_opts)
         out[r0:].copy_(tail)
-        if dec is not None:
+        if dec is not None and not to_host:
             engine.savi_decode(decoder, tail[:, T:].reshape((V - r0) * pred_len, N, D), want=('seg', ), seg_dtype=seg_dtype,
                                out_recon=dec['recon'][r0:].view((V - r0) * pred_len, 3, R, R), out_seg=dec['seg'][r0:].view((V - r0) * pred_len, R, R))
+        elif dec is not None:
+            from . import egress
+            recon = torch.empty(V - r0, pred_len, 3, R, R, device=dev)
+            seg = torch.empty(V - r0, pred_len, R, R, device=dev, dtype=seg_dtype)
+            engine.savi_decode(decoder, tail[:, T:].reshape((V - r0) * pred_len, N, D), want=('seg', ), seg_dtype=seg_dtype,
+                               out_recon=recon.view((V - r0) * pred_len, 3, R, R), out_seg=seg.view((V - r0) * pred_len, R, R))
+            dec['recon_u8'][r0:].copy_(egress.frames_to_uint8(recon), non_blocking=True)   # (the same kernel as the pipeline's decode stage)
+            dec['seg'][r0:].copy_(seg, non_blocking=True)
+    if to_host and dec is not None:
+        host = torch.empty(V, T + pred_len, N, D, pin_memory=True)
+        host.copy_(out, non_blocking=True)
+        out = host
     if to_host:
         torch.cuda.synchronize(dev)
     return out if dec is None else (out, dec)

@@ -280,6 +280,7 @@ class EncodeRolloutPipeline:
         # the (frozen) decoder weights: the StoSAVi itself or the SlotFormer that copied them (slotformer.py:203-210)
         self.decoder, self.seg_dtype = decoder, seg_dtype
         self._s_dec = None
+        self._egress = {}   # one-batch device buffers of run(decoded={'recon_u8': ...}): 'recon' float32, 'u8', 'seg'
         self.B, self.T, self.H = int(batch), int(burn_in), int(pred_len)
         p = next(rollouter.parameters())
         if not p.is_cuda:
@@ -635,7 +636,7 @@ class EncodeRolloutPipeline:
 
     def close(self):
         self._close_streams()
-        self.units, self._tails, self._enc_graphs = [], {}, {}
+        self.units, self._tails, self._enc_graphs, self._egress = [], {}, {}, {}
         engine.release_workspaces(self._key)
 
     def __del__(self):
@@ -880,6 +881,8 @@ class EncodeRolloutPipeline:
         if self.decoder is None:
             raise RuntimeError('slotformer_amd: run(decoded=...) needs a pipeline built with decoder=<module holding the SAVi decoder>')
         R = engine.decoder_plan(self.decoder).struct.resolution
+        if decoded.get('recon_u8') is not None:
+            return self._egress_buffers(decoded, n, R)
         if decoded.get('recon') is None:
             decoded['recon'] = torch.empty(n, self.B, self.H, 3, R, R, device=self.dev)
         if decoded.get('seg') is None:
@@ -887,7 +890,47 @@ class EncodeRolloutPipeline:
         rc, sg = decoded['recon'], decoded['seg']
         if tuple(rc.shape) != (n, self.B, self.H, 3, R, R) or tuple(sg.shape) != (n, self.B, self.H, R, R) or not rc.is_contiguous() or not sg.is_contiguous():
             raise RuntimeError(f'decoded buffers must be contiguous [n,{self.B},{self.H},3,{R},{R}] / [n,{self.B},{self.H},{R},{R}]')
-        return rc, sg
+        return rc, sg, None
+
+    def _egress_buffers(self, decoded, n, R):
+        """decoded['recon_u8'] [n, B, pred_len, R, R, 3] uint8, in pinned host memory or on the device: the frames as a video writer takes them
+        (egress.frames_to_uint8 of the reconstruction).  'recon' may then be absent -- the float32 reconstruction of a batch lives in ONE
+        per-pipeline buffer -- and 'seg' may be pinned host memory too; host tensors are filled from one-batch device buffers by asynchronous
+        copies behind the decode, on its stream."""
+        B, H = self.B, self.H
+        u8, rc, sg = decoded['recon_u8'], decoded.get('recon'), decoded.get('seg')
+        if sg is None:
+            sg = decoded['seg'] = torch.empty(n, B, H, R, R, device=self.dev, dtype=self.seg_dtype)
+        for name, t, shape, dtype in (('recon_u8', u8, (n, B, H, R, R, 3), torch.uint8), ('seg', sg, (n, B, H, R, R), self.seg_dtype)):
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or not (t.is_cuda or t.is_pinned()):
+                raise RuntimeError(f"decoded['{name}'] must be a contiguous {dtype} tensor {list(shape)} on the device or in pinned host memory")
+        if rc is not None and (tuple(rc.shape) != (n, B, H, 3, R, R) or not rc.is_contiguous() or not rc.is_cuda or rc.dtype != torch.float32):
+            raise RuntimeError(f"decoded['recon'] must be a contiguous float32 device tensor [n,{B},{H},3,{R},{R}]")
+        eg = self._egress
+        if rc is None and 'recon' not in eg:
+            eg['recon'] = torch.empty(B, H, 3, R, R, device=self.dev)
+        if not u8.is_cuda and 'u8' not in eg:
+            eg['u8'] = torch.empty(B, H, R, R, 3, device=self.dev, dtype=torch.uint8)
+        if not sg.is_cuda and 'seg' not in eg:
+            eg['seg'] = torch.empty(B, H, R, R, device=self.dev, dtype=self.seg_dtype)
+        return rc, sg, u8
+
+    def _decode_batch(self, j, slots_all, rc_all, sg_all, u8_all):
+        """the decode stage of batch j on the current stream; with 'recon_u8' the reconstruction is quantised behind it (csrc/egress.hip) and the
+        host-resident outputs are copied to their place, all in order on this stream -- so the one-batch buffers are free when batch j + 1 starts"""
+        if u8_all is None:
+            return self._decode(slots_all, rc_all[j], sg_all[j])
+        from . import egress
+        eg = self._egress
+        recon = rc_all[j] if rc_all is not None else eg['recon']
+        seg = sg_all[j] if sg_all.is_cuda else eg['seg']
+        self._decode(slots_all, recon, seg)
+        u8 = u8_all[j] if u8_all.is_cuda else eg['u8']
+        egress.frames_to_uint8(recon, to_rgb=True, layout='hwc', rounding='trunc', out=u8)
+        if not u8_all.is_cuda:
+            u8_all[j].copy_(u8, non_blocking=True)
+        if not sg_all.is_cuda:
+            sg_all[j].copy_(seg, non_blocking=True)
 
     def _decode(self, slots_all, recon, seg):
         """predicted frames of one batch: slots_all [B, T + H, N, D] -> recon [B, H, 3, R, R], seg [B, H, R, R] on the current stream"""
@@ -902,14 +945,17 @@ class EncodeRolloutPipeline:
         pipelined schedule returns when the last batch is finished (the host waits for it, see the end of this function).
         serial=True runs the same calls back to back on the calling stream (reference schedule for the tests).
         decoded: None, or a dict the decode stage fills (pipeline built with decoder=...): 'recon' [n, B, pred_len, 3, R, R] and
-        'seg' [n, B, pred_len, R, R] of the PREDICTED frames (test_vp.py's `pred` / `pred_mask`).
+        'seg' [n, B, pred_len, R, R] of the PREDICTED frames (test_vp.py's `pred` / `pred_mask`).  With a key 'recon_u8' -- a uint8 tensor
+        [n, B, pred_len, R, R, 3] in pinned host memory or on the device -- the stage also hands out the frames as a video writer takes them,
+        egress.frames_to_uint8(recon): 'recon' may then be absent (one float32 batch buffer per pipeline instead of the whole run's) and 'seg'
+        may be pinned host memory as well; quantising and the copies run behind each decode, in order on the decode stream.
         ingest: None, or an `ingest.FrameIngest` -- the batches are then RAW uint8 frames [B, burn_in, H0, W0, 3] ([B, burn_in, H0, W0] colour
         indices with a palette) on the device, in pinned or in pageable host memory: the staging rings hold uint8 at source size (a quarter of the
         float32 bytes at equal size), and the ingest kernel runs on the copy stream behind each upload, writing the float32 stage buffer the encodes
         read.  Device-resident batches take the same ring without the copy."""
         n = len(imgs)
         B = self.B
-        rc_all, sg_all = self._decoded_buffers(decoded, n) if decoded is not None else (None, None)
+        rc_all, sg_all, u8_all = self._decoded_buffers(decoded, n) if decoded is not None else (None, None, None)
         if decoded is not None and out is not None and not out.is_cuda:
             raise RuntimeError('slotformer_amd: the decode stage reads the slots from a device-resident `out`')
         host_in = n > 0 and not imgs[0].is_cuda
@@ -944,7 +990,9 @@ class EncodeRolloutPipeline:
                 for h in range(nb):
                     out[u0 + h].copy_(u.buf[h * B:(h + 1) * B], non_blocking=True)
                     if decoded is not None:
-                        self._decode(out[u0 + h], rc_all[u0 + h], sg_all[u0 + h])
+                        self._decode_batch(u0 + h, out[u0 + h], rc_all, sg_all, u8_all)
+            if u8_all is not None and not (u8_all.is_cuda and sg_all.is_cuda):
+                cur.synchronize()   # (the copies into the caller's pinned tensors)
             self._check_seam()
             return out
         G, NU, steal = self.G, self.NU, self.steal
@@ -1195,7 +1243,7 @@ class EncodeRolloutPipeline:
                         with torch.cuda.stream(self._s_dec):
                             self._s_dec.wait_event(ev_roll[ui])
                             for h in range(nb):
-                                self._decode(out[u0 + h], rc_all[u0 + h], sg_all[u0 + h])
+                                self._decode_batch(u0 + h, out[u0 + h], rc_all, sg_all, u8_all)
                             ev_dec.record(self._s_dec)
                 else:
                     # pinned host output: the downloads run on a torch-owned stream -- PyTorch's host allocator records an event
