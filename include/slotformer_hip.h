@@ -132,7 +132,9 @@ int sf_decode_combine_f32(const float* dec, float* recon_combined, float* recons
                           void* stream);
 /* ... followed by postproc_mask (vp_utils.py:20-41) on those masks: seg [F,H,W] = the slot with the smallest peak mask value over the frame
  * (the background) where the best mask value is below fg_thre, else the argmax over slots; as int64 (the reference's dtype) and / or
- * uint8, either may be NULL.  slot_max: [F * N] words of scratch.  recon_combined is always written; recons / masks may be NULL. */
+ * uint8, either may be NULL.  (The reference sets the background's score to 1 and takes the argmax, first index on ties: with fg_thre > 1 a
+ * slot at 1 or above still wins, and so it does here.)  slot_max: [F * N] words of scratch.  recon_combined is always written; recons /
+ * masks may be NULL. */
 int sf_decode_combine_seg_f32(const float* dec, float* recon_combined, float* recons, float* masks, long long* seg_i64,
                               unsigned char* seg_u8, float fg_thre, unsigned* slot_max, int F, int N, int HW, void* stream);
 /* postproc_mask (vp_utils.py:20-41) on given masks [F,N,HW] (any float values) -> seg [F,HW] int64 and / or uint8; slot_max: [F * N] words. */

@@ -442,8 +442,9 @@ def slot_mse_losses(pred, gt, training, loss_decay_factor=1., vid_len=None, hist
 # ---------------------------------------------------------------------------
 # "next" rows: decoder (N2), masks (M1), harness index arithmetic (H2/H3)
 # ---------------------------------------------------------------------------
-def savi_decode(slots, sd, cfg):
-    """StoSAVi.decode, savi.py:504-525.  slots [F,N,D] -> (recon [F,3,H,W], recons, masks).
+def savi_decode(slots, sd, cfg, return_logits=False):
+    """StoSAVi.decode, savi.py:504-525.  slots [F,N,D] -> (recon [F,3,H,W], recons, masks); return_logits: also the mask logits
+    [F,N,1,H,W] the softmax over slots is taken of.
 
     Deconv convention (nerv deconv_norm_act, un-vendored): ConvTranspose2d(k,
     stride, padding=k//2, output_padding=stride-1, bias=True) -> ReLU.
@@ -469,6 +470,8 @@ def savi_decode(slots, sd, cfg):
     x = F.conv2d(x, sd[f'decoder.{j}.weight'], sd[f'decoder.{j}.bias'])
     x = x.view(Fr, N, 4, res, res)
     recons, masks = x[:, :, :3], torch.softmax(x[:, :, 3:], dim=1)
+    if return_logits:
+        return (recons * masks).sum(1), recons, masks, x[:, :, 3:]
     return (recons * masks).sum(1), recons, masks
 
 

@@ -422,6 +422,8 @@ __global__ void decode_combine_kernel(const float* __restrict__ dec, float* __re
 // postproc_mask (vp_utils.py:20-41) on the decoder's own masks, recomputed from dec with the expressions of decode_combine_kernel (the
 // same bits): the slot whose peak mask value over the frame is smallest is the background (first index on ties, as torch.argmin); a
 // pixel whose best mask value is below fg_thre goes to it, every other pixel to its argmax over slots (first index on ties).
+// The reference gets there by setting the background's score to 1 before the argmax: with fg_thre > 1 (not a value of the reference, which
+// fixes 0.5) a slot at 1 or above still beats or ties it, so there the argmax is taken again with that 1 in place.
 template <int NN>
 __global__ void decode_seg_kernel(const float* __restrict__ dec, const unsigned* __restrict__ slot_max, long long* __restrict__ seg64,
                                   unsigned char* __restrict__ seg8, int F, int N, int HW, float thre) {
@@ -447,7 +449,22 @@ __global__ void decode_seg_kernel(const float* __restrict__ dec, const unsigned*
       best = n;
     }
   }
-  const int out = bestv < thre ? bg : best;
+  int out = best;
+  if (bestv < thre) {
+    out = bg;
+    if (thre > 1.f) {
+      float top = -INFINITY;
+#pragma unroll
+      for (int n = 0; n < NN; ++n) {
+        if (n >= N) break;
+        const float val = n == bg ? 1.f : m[n];
+        if (val > top) {
+          top = val;
+          out = n;
+        }
+      }
+    }
+  }
   if (seg64) seg64[idx] = out;
   if (seg8) seg8[idx] = (unsigned char)out;
 }
@@ -461,10 +478,11 @@ __global__ __launch_bounds__(256) void mask_rowmax_kernel(const float* __restric
   __shared__ float part[4];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
   __syncthreads();
-  // stored as an order-preserving key of the float (masks may be any float here): flip the sign bit / all bits
+  // stored as an order-preserving key of the float (masks may be any float here): flip the sign bit / all bits; -0.0 gets the key of +0.0
+  // (torch.argmin takes them as equal and keeps the first)
   if (threadIdx.x == 0) {
     const float r = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-    const unsigned b = __float_as_uint(r);
+    const unsigned b = r == 0.f ? 0u : __float_as_uint(r);
     slot_max[blockIdx.x] = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
   }
 }
@@ -489,7 +507,20 @@ __global__ void mask_seg_kernel(const float* __restrict__ masks, const unsigned*
       best = n;
     }
   }
-  const int out = bestv < thre ? bg : best;
+  int out = best;
+  if (bestv < thre) {
+    out = bg;
+    if (thre > 1.f) {   // the background's score becomes 1 and the argmax is taken again (see decode_seg_kernel)
+      float top = -INFINITY;
+      for (int n = 0; n < N; ++n) {
+        const float val = n == bg ? 1.f : masks[(f * N + n) * HW + pix];
+        if (val > top) {
+          top = val;
+          out = n;
+        }
+      }
+    }
+  }
   if (seg64) seg64[idx] = out;
   if (seg8) seg8[idx] = (unsigned char)out;
 }

@@ -453,7 +453,8 @@ def test_forward_with_decode_paths(dev):
 
 @torch.no_grad()
 def test_chunk_loops_and_small_batches(dev):
-    """Encoder frame chunks (B > 32), decoder frame chunks (F > 17 at 64x64x7 slots), B = 1, T = 1."""
+    """Encoder frame chunks (B > 32), a 20-frame decode (one chunk: the decoder's own chunk loop is tests/test_decode_gpu.py::test_chunk_loop_phyre),
+    B = 1, T = 1."""
     g = gu.load_golden('savi_c2')
     cfg = gu.savi_cfg(64, 7, kernel_mlp=False, pred='mlp', rnn=False, kld='none')
     shapes = gu.shapes_from_golden(g)
@@ -468,7 +469,7 @@ def test_chunk_loops_and_small_batches(dev):
     assert rel_err(one, ref[32:33]) < 5e-5
     t1 = m({'img': img[:2, :1].to(dev)})['post_slots']
     assert t1.shape == (2, 1, 7, 128) and rel_err(t1, ref[:2, :1]) < 5e-5
-    # decoder: 20 slot-frames -> two chunks
+    # decoder: 20 slot-frames in one call (one chunk: a chunk holds 146 frames of this shape)
     slots = gu.seeded_normal((20, 7, 128), 9)
     recon = m.decode(slots.to(dev))[0]
     assert rel_err(recon, oracle.savi_decode(slots, sd, cfg)[0]) < 2e-4
