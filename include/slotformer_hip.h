@@ -174,6 +174,40 @@ int sf_masks_to_boxes(const void* masks, int is_u8, float* boxes, unsigned* flag
 /* out [K,T] = the mean over the B videos of per_video [K,B,T] (np.mean over the batch, vp_utils.py:88,106,222,255), summed in order. */
 int sf_vp_mean_over_videos_f64(const double* per_video, double* out, int K, int B, int T, void* stream);
 
+/* ---- LPIPS, VGG16 (the `percept_dist` of test_vp.py:21-23, 149-160: lpips.LPIPS(net='vgg'); csrc/lpips.hip) ----------------------------------
+ * Thirteen 3x3 convolutions (stride 1, zero padding 1, bias, ReLU), four 2x2 max pools, and at the five taps (after relu1_2, relu2_2, relu3_3,
+ * relu4_3, relu5_3) the channel-normalised squared difference under the tap's 1x1 weights, averaged over the pixels and summed over the taps.
+ * Arithmetic: the first layer (3 -> 64) in f32 FMA; the other twelve on bf16 MFMA with split-bf16 operands (every f32 value = bf16 hi + bf16 lo,
+ * x_lo.w_hi + x_hi.w_lo + x_hi.w_hi, f32 accumulation).  This is the same WHATEVER sf_set_precision says: the metric has one definition.
+ * Every sum has a fixed order: a pair's score does not depend on its place in the batch, on `chunk` or on the other pairs; equal images give 0.
+ *
+ * The model: device pointers.  conv_w[0]: the first layer as f32 [27][64] (k = cin * 9 + tap); conv_w[1..12]: fragment order, a bf16 hi plane of
+ * Cout * Cin * 9 elements followed by the lo plane -- both written by sf_lpips_pack_conv_weights, Cout * Cin * 9 * 4 bytes either way.  conv_b[i]:
+ * the bias [Cout].  lin_w[s]: the tap's weights [C_s], C = 64, 128, 256, 512, 512.  shift, scale: [3], the input is (x - shift) / scale. */
+typedef struct {
+  const void* conv_w[13];
+  const float* conv_b[13];
+  const float* lin_w[5];
+  const float* shift;
+  const float* scale;
+} sf_lpips_model;
+/* w_oihw [Cout,Cin,3,3] f32 (torch's layout) -> packed.  Cin = 3 (Cout = 64): f32 [27][64].  Otherwise Cin, Cout in {64, 128, 256, 512}: for every
+ * block ct of 32 output channels and every k-step ks = tap * (Cin / 16) + cc, 64 lanes x 8 bf16, lane l holding W[32 ct + (l & 31)][16 cc + 8 (l >> 5)
+ * + 0..7][tap] -- element ((ct * 9 * Cin / 16 + ks) * 64 + l) * 8 + j of the hi plane, the lo plane (bf16 of the remainder) behind it.  The _host
+ * twin takes and fills HOST memory with the same bytes. */
+int sf_lpips_pack_conv_weights(const float* w_oihw, void* packed, int Cout, int Cin, void* stream);
+int sf_lpips_pack_conv_weights_host(const float* w_oihw, void* packed, int Cout, int Cin);
+/* Bytes of workspace for frames of H x W scored `chunk` pairs at a time (two activation buffers of 2 * chunk images at the first stage's width
+ * and the tap partials); 0 for H or W below 16, chunk outside [1, 16384], or 2 * chunk * H * W * 64 >= 2^31. */
+size_t sf_lpips_workspace_bytes(int H, int W, int chunk);
+/* x, y [F,3,H,W] f32 -> out [F] f32, the distance of every pair.  normalize = 1 first maps [0, 1] to [-1, 1] (2 v - 1).  The frames go through
+ * the network `chunk` pairs at a time, x and y of a chunk as one batch (a layer's weights are read once for both). */
+int sf_lpips_f32(const sf_lpips_model* m, const float* x, const float* y, float* out, int F, int H, int W, int chunk, int normalize,
+                 void* workspace, size_t workspace_bytes, void* stream);
+/* scores [B,T] f32 (the out of sf_lpips_f32 on B videos of T steps) -> per_video [B,T] doubles (may be NULL) and mean [T], the mean over the videos
+ * of every step, summed in the order of b. */
+int sf_lpips_mean_over_videos_f32(const float* scores, double* per_video, double* mean, int B, int T, void* stream);
+
 /* ---- ingest: the decoder's uint8 frames -> the encoder's input (base_slots/datasets/utils.py:15-43 BaseTransforms; csrc/ingest.hip) -------------
  * Source coordinates and weights are tables built on the HOST in float64, one per (H0, W0, H, W, mode): per output row and per output column the
  * first source index, the tap count and float32 weights (the kernels do no coordinate arithmetic, so they carry no float32 coordinate rounding).

@@ -122,6 +122,10 @@ class sf_egress_tile(C.Structure):
                 ('history_len', C.c_int)]
 
 
+class sf_lpips_model(C.Structure):
+    _fields_ = [('conv_w', C.c_void_p * 13), ('conv_b', FP * 13), ('lin_w', FP * 5), ('shift', FP), ('scale', FP)]
+
+
 I, LL, F32, SZ, VP = C.c_int, C.c_longlong, C.c_float, C.c_size_t, C.c_void_p
 
 # name -> (restype, argtypes): exactly the declarations of include/slotformer_hip.h
@@ -169,6 +173,11 @@ SIGNATURES = {
     'sf_vp_bbox_pr_f32': (I, [FP, VP, FP, VP, VP, I, I, I, F32, VP]),
     'sf_masks_to_boxes': (I, [VP, I, FP, VP, I, I, I, I, VP]),
     'sf_vp_mean_over_videos_f64': (I, [VP, VP, I, I, I, VP]),
+    'sf_lpips_pack_conv_weights': (I, [FP, VP, I, I, VP]),
+    'sf_lpips_pack_conv_weights_host': (I, [VP, VP, I, I]),
+    'sf_lpips_workspace_bytes': (SZ, [I, I, I]),
+    'sf_lpips_f32': (I, [C.POINTER(sf_lpips_model), FP, FP, FP, I, I, I, I, I, VP, SZ, VP]),
+    'sf_lpips_mean_over_videos_f32': (I, [FP, VP, VP, I, I, VP]),
     'sf_ingest_tables_bytes': (SZ, [I, I, I, I, I]),
     'sf_ingest_tables_host': (I, [VP, SZ, I, I, I, I, I]),
     'sf_ingest_frames_u8': (I, [VP, VP, I, VP, FP, FP, FP, I, I, I, I, I, I, I, VP]),

@@ -401,24 +401,38 @@ def _device_step_ok(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bb
             1 <= gt_bbox.shape[2] <= 64 and 1 <= pred_bbox.shape[2] <= 64)
 
 
-def _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj):
-    """The launches of pred_eval_step_device; returns the shape's buffers."""
+def _is_device_lpips(fn):
+    from slotformer_amd.lpips import LPIPS
+    return isinstance(fn, LPIPS)
+
+
+def _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj, lpips=None):
+    """The launches of pred_eval_step_device; returns the shape's buffers.  With `lpips` (slotformer_amd.lpips.LPIPS) the buffers of the shape
+    carry the perceptual distance as well: its per-step means [T] behind the flag word (inside 'head', so they ride in the same download), its
+    per-video scores [B,T] and the float32 scores of the B * T pairs at the end; everything before them lies where it lies without."""
     assert gt.shape == pred.shape
     L = _lib()
     lib = L.lib()
     B, T, _, H, W = gt.shape
     F = B * T
     dev = gt.device
-    key = (dev.index, B, T, H, W, bool(eval_traj))
+    key = (dev.index, B, T, H, W, bool(eval_traj)) + (('lpips', ) if lpips is not None else ())
     buf = _STEP_BUFFERS.get(key)
     if buf is None:
         K = len(METRICS)
+        P = T if lpips is not None else 0   # doubles of the perceptual distance's means, behind the flag word
         # one allocation: the means [K,T] and the flag word lie together (pred_eval_step downloads them in one copy), the per-video scores behind
-        raw = torch.zeros((K * T + 1 + K * F) * 8, dtype=torch.uint8, device=dev)
-        head = raw[:(K * T + 1) * 8]
-        buf = {'raw': raw, 'head': head, 'mean': head[:K * T * 8].view(torch.float64).view(K, T), 'flag': head[K * T * 8:].view(torch.int32)[:1],
-               'per': raw[(K * T + 1) * 8:].view(torch.float64).view(K, B, T),
+        raw = torch.zeros((K * T + 1 + P + K * F) * 8 + (F * 12 if lpips is not None else 0), dtype=torch.uint8, device=dev)
+        head = raw[:(K * T + 1 + P) * 8]
+        buf = {'raw': raw, 'head': head, 'mean': head[:K * T * 8].view(torch.float64).view(K, T),
+               'flag': head[K * T * 8:(K * T + 1) * 8].view(torch.int32)[:1],
+               'per': raw[(K * T + 1 + P) * 8:(K * T + 1 + P + K * F) * 8].view(torch.float64).view(K, B, T),
                'ws': torch.empty(max(int(lib.sf_vp_metrics_workspace_bytes(F, H, W)), 256), dtype=torch.uint8, device=dev)}
+        if lpips is not None:
+            tail = raw[(K * T + 1 + P + K * F) * 8:]
+            buf['lp_mean'] = head[(K * T + 1) * 8:].view(torch.float64)
+            buf['lp_per'] = tail[:F * 8].view(torch.float64).view(B, T)
+            buf['lp_scores'] = tail[F * 8:].view(torch.float32)
         _STEP_BUFFERS[key] = buf
     per, ws, st = buf['per'], buf['ws'], _stream(gt)
     gt, pred = gt.contiguous(), pred.contiguous()
@@ -434,11 +448,14 @@ def _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bb
         L.check(lib.sf_vp_bbox_pr_f32(gb.data_ptr(), pres.data_ptr(), pb.data_ptr(), per[6].data_ptr(), per[7].data_ptr(), F, gb.shape[2], pb.shape[2],
                                       0.5, st))
     L.check(lib.sf_vp_mean_over_videos_f64(per.data_ptr(), buf['mean'].data_ptr(), len(METRICS), B, T, st))
+    if lpips is not None:
+        lpips.distances(gt.view(F, 3, H, W), pred.view(F, 3, H, W), out=buf['lp_scores'])
+        L.check(lib.sf_lpips_mean_over_videos_f32(buf['lp_scores'].data_ptr(), buf['lp_per'].data_ptr(), buf['lp_mean'].data_ptr(), B, T, st))
     return buf
 
 
 @torch.no_grad()
-def pred_eval_step_device(gt, pred, gt_mask=None, pred_mask=None, gt_pres_mask=None, gt_bbox=None, pred_bbox=None, eval_traj=True):
+def pred_eval_step_device(gt, pred, gt_mask=None, pred_mask=None, gt_pres_mask=None, gt_bbox=None, pred_bbox=None, eval_traj=True, lpips=None):
     """pred_eval_step without its host half: gt / pred [B,T,3,H,W] device float32 in [-1, 1] (e.g. the `recon` of
     `harness.extract_and_rollout(decoder=...)`), gt_mask [B,T,H,W] int64, pred_mask [B,T,H,W] int64 or uint8 (its `seg`), gt_pres_mask [B,T,N]
     bool, gt_bbox [B,T,N,4], pred_bbox [B,T,M,4] float32.  Returns float64 device tensors: 'mse', 'psnr', 'ssim', 'ari', 'fari', 'miou', 'ap', 'ar'
@@ -447,13 +464,21 @@ def pred_eval_step_device(gt, pred, gt_mask=None, pred_mask=None, gt_pres_mask=N
 
     Six launches on torch's current stream, whatever B and T; no synchronisation and no host round trip, so the call can be captured into a graph.
     The result tensors and the workspace are kept per shape: nothing is allocated after the first call of a shape, and the next call of that shape
-    overwrites them (copy what must outlive it)."""
+    overwrites them (copy what must outlive it).
+
+    lpips: a `slotformer_amd.lpips.LPIPS` on the frames' device (H, W >= 16).  The result then has 'percept_dist' [T] and 'percept_dist_per_video'
+    [B,T] as well -- the perceptual distance of the B * T pairs from one batched pass through the network, chunked by the module's `chunk` -- at
+    the price of its launches (about twenty per chunk)."""
+    if lpips is not None and not (_is_device_lpips(lpips) and torch.is_tensor(gt) and gt.dim() == 5 and min(gt.shape[3:]) >= 16):
+        raise RuntimeError('pred_eval_step_device: lpips= takes a slotformer_amd.lpips.LPIPS and frames of at least 16 x 16')
     if not _device_step_ok(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj):
         raise RuntimeError('pred_eval_step_device: device float32 frames [B,T,3,H,W] with H, W >= 11 (and, with eval_traj, device int64 / uint8 masks, '
                            'bool presence and float32 boxes, at most 64 per frame) are required; pred_eval_step takes everything else')
-    buf = _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj)
+    buf = _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj, lpips)
     out = {m: buf['mean'][i] for i, m in enumerate(METRICS)}
     out.update({m + '_per_video': buf['per'][i] for i, m in enumerate(METRICS)})
+    if lpips is not None:
+        out['percept_dist'], out['percept_dist_per_video'] = buf['lp_mean'], buf['lp_per']
     out['id_out_of_range'] = buf['flag']
     return out
 
@@ -463,7 +488,9 @@ def pred_eval_step(gt, pred, lpips_fn, gt_mask=None, pred_mask=None, gt_pres_mas
     """gt / pred [B,T,C,H,W] in [-1, 1]; masks [B,T,H,W]; gt_pres_mask [B,T,N]; boxes [B,T,N/M,4].  Every metric for every time step: a dict of
     nine lists of T Python floats ('mse', 'ssim', 'psnr', 'percept_dist', 'ari', 'fari', 'miou', 'ap', 'ar').  'percept_dist' is lpips_fn applied per
     step, 0.0 without one; eval_traj=False gives zeros for the mask and box metrics.  Device inputs are scored by the library with ONE download at
-    the end; a mask id outside [0, 16) raises there."""
+    the end; a mask id outside [0, 16) raises there.  When lpips_fn is a `slotformer_amd.lpips.LPIPS` and the frames are device float32 of at
+    least 16 x 16, 'percept_dist' of all T steps comes from one batched call over the B * T pairs, its per-step means are taken on the device and
+    ride in that one download; any other callable is applied per step as before."""
     assert len(gt.shape) == len(pred.shape) == 5
     assert gt.shape == pred.shape
     assert gt.shape[2] == 3
@@ -473,14 +500,18 @@ def pred_eval_step(gt, pred, lpips_fn, gt_mask=None, pred_mask=None, gt_pres_mas
         assert len(gt_pres_mask.shape) == 3
         assert len(gt_bbox.shape) == len(pred_bbox.shape) == 4
     T = gt.shape[1]
-    percept = [0. if lpips_fn is None else float(perceptual_dist(gt[:, t], pred[:, t], lpips_fn)) for t in range(T)]
-    if _device_step_ok(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj):
-        head = _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj)['head'].cpu()   # the one copy: [8,T] means + the flag word
-        if int(head[-8:].view(torch.int32)[0]):
+    on_device = _device_step_ok(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj)
+    fused = on_device and lpips_fn is not None and _is_device_lpips(lpips_fn) and min(gt.shape[3:]) >= 16
+    percept = None if fused else [0. if lpips_fn is None else float(perceptual_dist(gt[:, t], pred[:, t], lpips_fn)) for t in range(T)]
+    if on_device:
+        # the one copy: [8,T] means + the flag word (+ the [T] means of the perceptual distance)
+        head = _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bbox, eval_traj, lpips_fn if fused else None)['head'].cpu()
+        nm = len(METRICS) * T * 8
+        if int(head[nm:nm + 8].view(torch.int32)[0]):
             raise RuntimeError('pred_eval_step: a mask id outside [0, 16)')
-        mean = head[:-8].view(torch.float64).view(len(METRICS), T)
+        mean = head[:nm].view(torch.float64).view(len(METRICS), T)
         out = {m: [float(v) for v in mean[i]] for i, m in enumerate(METRICS)}
-        out['percept_dist'] = percept
+        out['percept_dist'] = [float(v) for v in head[nm + 8:].view(torch.float64)] if fused else percept
         return out
     out = {m: [] for m in METRICS}
     out['percept_dist'] = percept
