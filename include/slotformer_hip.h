@@ -292,16 +292,31 @@ int sf_slot_attn_iter_f32(const float* k, const float* v, int ld, long long batc
  * ~2e-3 relative on the updates (tests/test_kernels_gpu.py) -- outside the encode path's 5e-5, hence an option only. */
 int sf_slot_attn_iter_bf16(const void* k, const void* v, int ld, long long batch_stride, const float* q, float* part_num,
                            float* part_den, float* attn_out, int B, int HW, int N, int D, float scale, float eps, void* stream);
+/* Both take 1 <= N <= 16 slots.  N <= 8 runs the 8-slot instantiation of the iteration kernel, 9 .. 16 the 16-slot one (same
+ * three forms: VALU, two-pass MFMA, one-pass tile for keys == values at slot_size 128).  At 9 .. 16 slots the one-pass form
+ * holds 84,480 B of LDS -- one workgroup per CU; sf_set_slot_attn_tile16(0) sends those shapes to the two-pass form instead
+ * (process-wide, default 1; profiles/slots16.md). */
+int sf_set_slot_attn_tile16(int on);
+int sf_get_slot_attn_tile16(void);
 
 /* Backward of sf_slot_attn_iter_f32 (row N1: savi.py:82-94 under autograd).  Inputs of the forward call (k, v, q, the
  * partial records it produced) plus d_updates [B,N,D], the gradient w.r.t. updates = sum(num) / sum(den).  Writes
  * dq [B,N,D] and dk / dv (same row layout as k / v); accumulate != 0 adds into dk / dv instead (the iterations of one
- * frame share k and v).  slot_size 64 / 128 / 192 / 256, at most 8 slots. */
+ * frame share k and v).  slot_size 64 / 128 / 192 / 256, at most 8 slots (9 .. 16: sf_slot_attn_iter_bwd16_f32 below). */
 size_t sf_slot_attn_iter_bwd_workspace_bytes(int B, int HW, int N, int D);
 int sf_slot_attn_iter_bwd_f32(const float* k, const float* v, int ld, long long batch_stride, const float* q,
                               const float* part_num, const float* part_den, int P, const float* d_updates, float* dk,
                               float* dv, int accumulate, float* dq, int B, int HW, int N, int D, float scale, float eps,
                               void* ws, size_t ws_bytes, void* stream);
+/* The same backward for 1 <= N <= 16 slots, same arguments and workspace layout.  N <= 8 runs the kernel above (same bits);
+ * 9 .. 16 slots run it as two launches that share the softmax over all the slots: the first writes dk / dv and the dq partials
+ * of slots 0..7, the second reads the rows again for the dq partials of slots 8..15 (16 slots of running dq sums do not fit
+ * the registers at slot_size 256).  dq stays a fixed-order sum of per-workgroup partials. */
+size_t sf_slot_attn_iter_bwd16_workspace_bytes(int B, int HW, int N, int D);
+int sf_slot_attn_iter_bwd16_f32(const float* k, const float* v, int ld, long long batch_stride, const float* q,
+                                const float* part_num, const float* part_den, int P, const float* d_updates, float* dk,
+                                float* dv, int accumulate, float* dq, int B, int HW, int N, int D, float scale, float eps,
+                                void* ws, size_t ws_bytes, void* stream);
 
 /* Slot update (savi.py:95-100): updates = sum(num)/sum(den); GRUCell (r,z,n); slots + MLP(LN(slots)).
  * The four weight MATRICES are passed transposed ([in,out] = torch weight.t().contiguous()):
@@ -670,7 +685,7 @@ int sf_savi_features_train_bwd_f32(const sf_savi_features* m, const float* img, 
 /* ---- training of the Slot-Attention module ------------------------------------------------
  * SlotAttention (savi.py:36-102) under autograd: parameters in torch layouts, gradients with the same shapes (written,
  * not accumulated).  The forward keeps its activations in the caller's workspace for the backward call.
- * slot_size 64 / 128 / 192 / 256, in_features and mlp_hidden multiples of 64, at most 8 slots and 8 iterations. */
+ * slot_size 64 / 128 / 192 / 256, in_features and mlp_hidden multiples of 64, at most 16 slots and 8 iterations. */
 typedef struct {
   int in_features, slot_size, mlp_hidden, num_slots;
   const float *norm_in_g, *norm_in_b, *wk, *wv;                  /* norm_inputs, project_k / project_v [D, in] */

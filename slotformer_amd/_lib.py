@@ -219,6 +219,10 @@ SIGNATURES = {
     'sf_attn_block_rows_f32': (I, [C.POINTER(sf_tfm_layer), FP, FP, VP, I, I, I, VP]),
     'sf_slot_attn_iter_bwd_workspace_bytes': (SZ, [I, I, I, I]),
     'sf_slot_attn_iter_bwd_f32': (I, [FP, FP, I, LL, FP, FP, FP, I, FP, FP, FP, I, FP, I, I, I, I, F32, F32, VP, SZ, VP]),
+    'sf_slot_attn_iter_bwd16_workspace_bytes': (SZ, [I, I, I, I]),
+    'sf_slot_attn_iter_bwd16_f32': (I, [FP, FP, I, LL, FP, FP, FP, I, FP, FP, FP, I, FP, I, I, I, I, F32, F32, VP, SZ, VP]),
+    'sf_set_slot_attn_tile16': (I, [I]),
+    'sf_get_slot_attn_tile16': (I, []),
     'sf_slot_attention_train_workspace_bytes': (SZ, [C.POINTER(sf_slot_attention), I, I, I]),
     'sf_slot_attention_train_fwd_f32': (I, [C.POINTER(sf_slot_attention), FP, FP, I, I, I, FP, VP, SZ, VP]),
     'sf_slot_attention_train_bwd_f32': (I, [C.POINTER(sf_slot_attention), FP, FP, FP, FP, C.POINTER(sf_slot_attention_grads), I, I, I,

@@ -715,7 +715,7 @@ EncodePlan plan_encode(const sf_savi_encoder* m, int B, int T, int n_pre, bool f
   p.update = !su_packed ? EncodePlan::VALU : sf_slot_update_mfma_ok(D, Hm, P) ? EncodePlan::MFMA
             : sf_slot_update_wide_ok(D, Hm, P) ? EncodePlan::WIDE : EncodePlan::VALU;
   // (the folded iterations read keys == values)
-  if (fold && P == HW / 256 && (planes || sf_slot_attn_sparse_records(nullptr, nullptr, HW, D))) p.p_step = 2;
+  if (fold && P == HW / 256 && (planes || sf_slot_attn_sparse_records_n(nullptr, nullptr, HW, D, N))) p.p_step = 2;
   p.pred_step = m->pred_type == 1 && m->pred_packed && precision >= 1;
   p.prologue = m->pred_type == 0 && !m->pred_rnn && m->kd_mode == 1 && m->pm_w0_t && m->pm_w2_t && m->kd_w0_t && p.q_w_t;
   p.fuse_next = p.prologue && p.update == EncodePlan::MFMA && m->pm_w0_p && m->pm_w2_p && m->kd_w0_p && m->pm_ln_g && m->pm_ln_b && m->pm_b0 &&
@@ -1165,7 +1165,7 @@ int sf_savi_encode_fork_f32(const sf_savi_encoder* m, const float* img, const fl
   SF_REQUIRE(B >= 1 && T >= 1, "bad batch / clip length");
   SF_REQUIRE(m->resolution == 64 || m->resolution == 128, "resolution must be 64 or 128 (savi.py:226,236)");
   SF_REQUIRE(m->enc_layers >= 1 && m->enc_layers <= 8 && m->enc_channels[0] > 0 && (m->enc_ks & 1), "bad CNN config");
-  SF_REQUIRE(m->num_slots >= 1 && m->num_slots <= 8 && m->num_iterations >= 1, "bad slot config");
+  SF_REQUIRE(m->num_slots >= 1 && m->num_slots <= 16 && m->num_iterations >= 1, "bad slot config (1 <= num_slots <= 16)");
   SF_REQUIRE(m->pos_table && m->enc_ln_g && m->enc_ln_b && m->enc_fc1_w && m->enc_fc1_b && m->enc_fc2_w &&
                  m->enc_fc2_b && m->sa_norm_in_g && m->sa_norm_in_b && m->sa_q_ln_g && m->sa_q_ln_b &&
                  m->sa_q_w && m->sa_kv_w && m->init_latents, "null encoder weight");

@@ -65,6 +65,8 @@ int sf_slot_update_mfma_ex(const float* part_num, const float* part_den, int P, 
                            float ln_eps, hipStream_t st, const SfNextStep* next = nullptr, int p_step = 1);
 // 1 when sf_slot_attn_iter_ex takes its one-pass tile kernel for this shape (sums in the even partial records, zeros in the odd ones)
 bool sf_slot_attn_sparse_records(const float* k, const float* v, int HW, int D);
+// ... for N slots: beyond 8 the tile kernel is taken only under sf_set_slot_attn_tile16 (the default)
+bool sf_slot_attn_sparse_records_n(const float* k, const float* v, int HW, int D, int N);
 // the same update at slot size 192 / slot MLP 384 (slot_update_wide.hip); operands as for sf_slot_update_mfma_ex
 bool sf_slot_update_wide_ok(int D, int H, int P);
 int sf_slot_update_wide_ex(const float* part_num, const float* part_den, int P, const float* slots_prev, const void* gru_ih_p, const void* gru_hh_p,

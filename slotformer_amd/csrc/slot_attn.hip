@@ -14,7 +14,8 @@
 #include "sf_internal.h"
 #include <stdlib.h>
 
-#define SA_NMAX 8
+#define SA_NMAX 8     // the slot bound of the first instantiation of each iteration kernel: every N <= 8 runs it, as before the second existed
+#define SA_NMAX16 16  // 9 .. 16 slots: the second instantiation of each iteration kernel (the 16-lane accumulator row of the tile kernel, full)
 #define SA_DMAX 256
 #define SA_HMAX 512
 
@@ -35,7 +36,7 @@ __device__ __forceinline__ float wave_allsum(float v) {
   return v;
 }
 
-template <int VPT>
+template <int VPT, int NS = SA_NMAX>
 __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
     const float* __restrict__ k, const float* __restrict__ v, int ld, long long batch_stride,
     const float* __restrict__ q, float scale, float eps, float* __restrict__ part_num,
@@ -47,9 +48,9 @@ __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
   const int pix_per_wg = HW / P, pix_per_wave = pix_per_wg / 4;
   const int pix0 = chunk * pix_per_wg + wave * pix_per_wave;
 
-  float qr[SA_NMAX][VPT], num[SA_NMAX][VPT], den[SA_NMAX];
+  float qr[NS][VPT], num[NS][VPT], den[NS];
 #pragma unroll
-  for (int n = 0; n < SA_NMAX; ++n) {
+  for (int n = 0; n < NS; ++n) {
 #pragma unroll
     for (int j = 0; j < VPT; ++j) {
       qr[n][j] = (n < N) ? q[((long long)b * N + n) * D + lane * VPT + j] * scale : 0.f;
@@ -60,8 +61,8 @@ __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
   const float* kb = k + (long long)b * batch_stride + lane * VPT;
   const float* vb = v + (long long)b * batch_stride + lane * VPT;
 
-  __shared__ float s_attn[4][SA_NMAX][64];  // attn staging for coalesced mask rows
-  __shared__ float s_red[4][SA_NMAX][D + 1];
+  __shared__ float s_attn[4][NS][64];  // attn staging for coalesced mask rows
+  __shared__ float s_red[4][NS][D + 1];
 
   constexpr int U = 4;
   for (int p0 = 0; p0 < pix_per_wave; p0 += U) {
@@ -77,30 +78,30 @@ __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      float s[SA_NMAX];
+      float s[NS];
 #pragma unroll
-      for (int n = 0; n < SA_NMAX; ++n) {
+      for (int n = 0; n < NS; ++n) {
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < VPT; ++j) acc = fmaf(kx[u][j], qr[n][j], acc);
         s[n] = acc;
       }
 #pragma unroll
-      for (int n = 0; n < SA_NMAX; ++n)
+      for (int n = 0; n < NS; ++n)
         if (n < N) s[n] = wave_allsum(s[n]);
       float mx = s[0];
 #pragma unroll
-      for (int n = 1; n < SA_NMAX; ++n)
+      for (int n = 1; n < NS; ++n)
         if (n < N) mx = fmaxf(mx, s[n]);
       float sum = 0.f;
 #pragma unroll
-      for (int n = 0; n < SA_NMAX; ++n) {
+      for (int n = 0; n < NS; ++n) {
         s[n] = (n < N) ? expf(s[n] - mx) : 0.f;
         sum += s[n];
       }
       const float inv = 1.0f / sum;
 #pragma unroll
-      for (int n = 0; n < SA_NMAX; ++n) {
+      for (int n = 0; n < NS; ++n) {
         if (n < N) {
           const float a0 = s[n] * inv;
           if (attn_out) {
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
 
   // cross-wave reduction, then one partial per workgroup
 #pragma unroll
-  for (int n = 0; n < SA_NMAX; ++n) {
+  for (int n = 0; n < NS; ++n) {
 #pragma unroll
     for (int j = 0; j < VPT; ++j) s_red[wave][n][lane * VPT + j] = num[n][j];
     if (lane == 0) s_red[wave][n][D] = den[n];
@@ -163,19 +164,21 @@ __device__ __forceinline__ f32x4v sa_load4(const KT* p) {
   }
 }
 
-template <int D, typename KT = float>
-__global__ __launch_bounds__(256) void sa_attn_mfma_kernel(
+template <int D, typename KT = float, int NS = SA_NMAX>
+__global__ __launch_bounds__(256, (NS > SA_NMAX && D <= 128 ? 2 : 1)) void sa_attn_mfma_kernel(
     const KT* __restrict__ k, const KT* __restrict__ v, int ld, long long batch_stride,
     const float* __restrict__ q, float scale, float eps, float* __restrict__ part_num,
     float* __restrict__ part_den, float* __restrict__ attn_out, long long attn_bs, int HW, int N, int P) {
   constexpr int DB = D / 16;  // channel blocks of the MFMA (each 16 channels wide, strided by DB)
-  constexpr int NS = SA_NMAX;
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int pix0 = chunk * 256 + wave * 64;  // 64 pixels per wave
   __shared__ __attribute__((aligned(16))) float s_q[NS][D];
   __shared__ float s_a[4][64][NS + 1];
-  __shared__ float s_red[4][NS][D + 1];
+  // 16 slots at D <= 128: a wave's reduction rows (NS * (D + 1) floats) lie over ITS slab of s_k, dead after phase 1 -- 62.5 instead of 95.5 KB at
+  // D = 128, two workgroups per CU as the 8-slot instantiation has (one per CU: 52 us for 32 frames against 27 at 8 slots, profiles/slots16.md)
+  constexpr bool RED_OVER_K = NS > SA_NMAX && NS * (D + 1) <= 64 * 36;
+  __shared__ float s_red[RED_OVER_K ? 1 : 4][RED_OVER_K ? 1 : NS][D + 1];
   for (int idx = threadIdx.x; idx < NS * D; idx += 256) {
     const int n = idx / D, d = idx - n * D;
     s_q[n][d] = n < N ? q[((long long)b * N + n) * D + d] * scale : 0.f;
@@ -187,6 +190,10 @@ __global__ __launch_bounds__(256) void sa_attn_mfma_kernel(
   //      its 64 rows with 8 lanes per row (8 x 128 B contiguous per instruction), parks it in LDS and every lane reads
   //      ITS row back; the next slab is requested before the current one is consumed. ----
   __shared__ __attribute__((aligned(16))) float s_k[4][64][36];
+  auto red = [&](int w, int n, int d) -> float& {
+    if constexpr (RED_OVER_K) return (&s_k[w][0][0])[n * (D + 1) + d];
+    else return s_red[w][n][d];
+  };
   const KT* kslab = k + (long long)b * batch_stride + (long long)(pix0 + (lane >> 3)) * ld + 4 * (lane & 7);
   float s[NS];
 #pragma unroll
@@ -280,16 +287,16 @@ __global__ __launch_bounds__(256) void sa_attn_mfma_kernel(
 #pragma unroll
     for (int j = 0; j < DB; ++j)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) s_red[wave][li][DB * (4 * lk + r) + j] = acc[j][r];
+      for (int r = 0; r < 4; ++r) red(wave, li, DB * (4 * lk + r) + j) = acc[j][r];
   }
   if (lane == 0) {
 #pragma unroll
-    for (int n = 0; n < NS; ++n) s_red[wave][n][D] = den[n];
+    for (int n = 0; n < NS; ++n) red(wave, n, D) = den[n];
   }
   __syncthreads();
   for (int idx = threadIdx.x; idx < N * (D + 1); idx += 256) {
     const int n = idx / (D + 1), d = idx - n * (D + 1);
-    const float t = s_red[0][n][d] + s_red[1][n][d] + s_red[2][n][d] + s_red[3][n][d];
+    const float t = red(0, n, d) + red(1, n, d) + red(2, n, d) + red(3, n, d);
     if (d < D)
       part_num[(((long long)b * P + chunk) * N + n) * D + d] = t;
     else
@@ -732,7 +739,7 @@ extern "C" int sf_slot_attn_iter_bf16(const void* k, const void* v, int ld, long
                                       float* part_num, float* part_den, float* attn_out, int B, int HW, int N, int D, float scale,
                                       float eps, void* stream) {
   SF_REQUIRE(k && v && q && part_num && part_den, "null pointer");
-  SF_REQUIRE(B >= 0 && HW > 0 && (HW % 256) == 0 && N >= 1 && N <= SA_NMAX, "need 1 <= num_slots <= 8 and HW % 256 == 0");
+  SF_REQUIRE(B >= 0 && HW > 0 && (HW % 256) == 0 && N >= 1 && N <= SA_NMAX16, "need 1 <= num_slots <= 16 and HW % 256 == 0");
   SF_REQUIRE(D == 64 || D == 128 || D == 192 || D == 256, "slot_size must be 64/128/192/256");
   SF_REQUIRE(ld >= D && (ld % 4) == 0 && (batch_stride % 4) == 0, "k/v rows must be 8-byte aligned");
   if (B == 0) return 0;
@@ -743,14 +750,23 @@ extern "C" int sf_slot_attn_iter_bf16(const void* k, const void* v, int ld, long
   const __bf16* vb = (const __bf16*)v;
   const long long abs_ = (long long)N * HW;
   sf_prof_begin(SF_K_SA_ITER, st, 2.0 * (double)B * HW * D * sizeof(__bf16));
-#define SA_LAUNCHB(DD)                                                                                                   \
-  hipLaunchKernelGGL((sa_attn_mfma_kernel<DD, __bf16>), grid, block, 0, st, kb, vb, ld, batch_stride, q, scale, eps, part_num, \
+#define SA_LAUNCHB(DD, NN)                                                                                                   \
+  hipLaunchKernelGGL((sa_attn_mfma_kernel<DD, __bf16, NN>), grid, block, 0, st, kb, vb, ld, batch_stride, q, scale, eps, part_num, \
                      part_den, attn_out, abs_, HW, N, P)
-  switch (D / 64) {
-    case 1: SA_LAUNCHB(64); break;
-    case 2: SA_LAUNCHB(128); break;
-    case 3: SA_LAUNCHB(192); break;
-    default: SA_LAUNCHB(256); break;
+  if (N <= SA_NMAX) {
+    switch (D / 64) {
+      case 1: SA_LAUNCHB(64, SA_NMAX); break;
+      case 2: SA_LAUNCHB(128, SA_NMAX); break;
+      case 3: SA_LAUNCHB(192, SA_NMAX); break;
+      default: SA_LAUNCHB(256, SA_NMAX); break;
+    }
+  } else {
+    switch (D / 64) {
+      case 1: SA_LAUNCHB(64, SA_NMAX16); break;
+      case 2: SA_LAUNCHB(128, SA_NMAX16); break;
+      case 3: SA_LAUNCHB(192, SA_NMAX16); break;
+      default: SA_LAUNCHB(256, SA_NMAX16); break;
+    }
   }
 #undef SA_LAUNCHB
   sf_prof_end(SF_K_SA_ITER, st);
@@ -767,7 +783,8 @@ extern "C" int sf_slot_attn_iter_bf16(const void* k, const void* v, int ld, long
 //   * logits: X . Q^T on v_mfma_f32_16x16x4_f32 -- the tile rows are the A operand, the scaled queries (zero beyond N slots) sit in
 //     registers as the B operand.  One 16-byte LDS read feeds four MFMAs: MFMA e of a read contracts channels {16 s + 4 g + e}, g = lane >> 4
 //     (the contraction runs over all channels, so which instruction takes which channel is free as long as both operands agree);
-//   * softmax over slots: the 8 slots of a pixel are lanes 0..7 of a 16-lane row of the accumulator: two DPP all-reduces (max, sum);
+//   * softmax over slots: the 8 slots of a pixel are lanes 0..7 of a 16-lane row of the accumulator: two DPP all-reduces (max, sum) -- NS = 16
+//     (9 .. 16 slots): all 16 lanes of the row, one DPP step more; 8 * 128 more floats of queries in LDS: 84,480 B, one workgroup per CU;
 //   * weighted sums: A^T . X with the attention tile (through 2 KB of LDS, transposed) as A operand and the SAME LDS tile as B operand,
 //     again four MFMAs per 16-byte read (output column j of MFMA (h, e) is channel 64 h + 4 j + e).
 // 128 MFMAs of 32 cycles per wave and 32 pixels: 9.7 TB/s of rows at two waves per SIMD on the whole chip -- above the HBM roof.
@@ -776,7 +793,7 @@ extern "C" int sf_slot_attn_iter_bf16(const void* k, const void* v, int ld, long
 __device__ long long sa_ts[16];   // phase stamps of workgroup (0, 0), wave 0 (sf_debug_sa_stamps(1); sf_debug_read_ts_sa)
 __device__ int sa_dbg_on;
 #define SATS(i) do { if (dbg && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) sa_ts[i] = wall_clock64(); } while (0)
-template <int D>
+template <int D, int NS = SA_NMAX>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void sa_attn_tile_kernel(
     const float* __restrict__ x, int ld, long long batch_stride, const float* __restrict__ q, float scale, float eps,
     float* __restrict__ part_num, float* __restrict__ part_den, float* __restrict__ attn_out, long long attn_bs, int HW, int N, int P) {
@@ -786,7 +803,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // (single-shot tiles -- every workgroup loads, then computes -- ran the chip in lockstep phases at 2.5 TB/s, profiles/r04_probes.txt section 3)
   const int dbg = sa_dbg_on;
   SATS(0);
-  constexpr int NS = SA_NMAX, XP = D + 4, NW = 8, TP = 16, NT4 = 4;   // tile pitch, waves, pixels per tile, tiles per wave
+  constexpr int XP = D + 4, NW = 8, TP = 16, NT4 = 4;   // tile pitch, waves, pixels per tile, tiles per wave
   constexpr int NSLAB = D / 16, NH = D / 64;
   extern __shared__ __attribute__((aligned(16))) float sa_lds[];
   float* s_x = sa_lds;                          // [NW][TP][XP]
@@ -827,12 +844,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       for (int u = 0; u < 8; ++u) stage[u] = *(const f32x4v*)(xs + (long long)(TP * (ti + 1) + 2 * u) * ld);
     }
     __builtin_amdgcn_wave_barrier();
-    // ---- logits[pixel][slot]: A = tile rows (i = li: pixel, k = lg), B (k = lg, j = li: slot) = the scaled queries from LDS (zero beyond 8) ----
+    // ---- logits[pixel][slot]: A = tile rows (i = li: pixel, k = lg), B (k = lg, j = li: slot) = the scaled queries from LDS (zero beyond NS) ----
     f32x4a acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int sl = 0; sl < NSLAB; ++sl) {
       const f32x4v xa = *(const f32x4v*)(tile + li * XP + 16 * sl + 4 * lg);
-      f32x4v qb = *(const f32x4v*)(s_q + (li & 7) * D + 16 * sl + 4 * lg);
+      f32x4v qb = *(const f32x4v*)(s_q + (li & (NS - 1)) * D + 16 * sl + 4 * lg);
       if (li >= NS) qb = f32x4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], qb[e], acc, 0, 0, 0);
@@ -842,9 +859,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int r = 0; r < 4; ++r) {
       const bool live = li < N;
       const float v = live ? acc[r] : -INFINITY;
-      const float mx = sf_max8(li < 8 ? v : -INFINITY);
+      // (16 slots: the softmax spans the whole 16-lane row; lanes n >= N hold -inf / 0 and add exactly nothing to max, sum, den and the products)
+      const float mx = NS == 8 ? sf_max8(li < 8 ? v : -INFINITY) : sf_max16(v);
       const float ex = live ? expf(v - mx) : 0.f;
-      const float sum = sf_sum8(li < 8 ? ex : 0.f);
+      const float sum = NS == 8 ? sf_sum8(li < 8 ? ex : 0.f) : sf_sum16(ex);
       const float a0 = ex / sum;
       const int pix = 4 * lg + r;
       if (attn_out && live) attn_out[(long long)b * attn_bs + (long long)li * HW + pix0 + TP * ti + pix] = a0;
@@ -871,9 +889,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // den: the slot's sum over this wave's pixels = over the lanes with the same li
   den += __shfl_xor(den, 16, 64);
   den += __shfl_xor(den, 32, 64);
-  // ---- cross-wave reduction over the dead tiles: nacc[h][e][r] = num[slot 4 lg + r][channel 64 h + 4 li + e] (slots < 8: lg < 2) ----
+  // ---- cross-wave reduction over the dead tiles: nacc[h][e][r] = num[slot 4 lg + r][channel 64 h + 4 li + e] (slots < NS: lg < NS / 4) ----
   __syncthreads();
-  if (lg < 2) {
+  if (lg < NS / 4) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -906,11 +924,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
 bool sf_slot_attn_sparse_records(const float* k, const float* v, int HW, int D) { return HW % 512 == 0 && k == v && D == 128; }
 
+// 9 .. 16 slots, keys == values: the one-pass tile kernel (default; at 84,480 B of LDS ONE workgroup per CU) or, sf_set_slot_attn_tile16(0), the
+// two-pass kernel.  The record structure follows the kernel (sf_slot_attn_sparse_records_n): engine.hip's plan asks before it lets the slot update
+// skip the odd records.  profiles/slots16.md has the measurement behind the default.
+static int g_sa_tile16 = 1;
+extern "C" int sf_set_slot_attn_tile16(int on) { g_sa_tile16 = on ? 1 : 0; return 0; }
+extern "C" int sf_get_slot_attn_tile16(void) { return g_sa_tile16; }
+bool sf_slot_attn_sparse_records_n(const float* k, const float* v, int HW, int D, int N) {
+  return sf_slot_attn_sparse_records(k, v, HW, D) && (N <= SA_NMAX || g_sa_tile16);
+}
+
 int sf_slot_attn_iter_ex(const float* k, const float* v, int ld, long long batch_stride, const float* q,
                          float* part_num, float* part_den, float* attn_out, long long attn_batch_stride, int B,
                          int HW, int N, int D, float scale, float eps, hipStream_t st) {
   SF_REQUIRE(k && v && q && part_num && part_den, "null pointer");
-  SF_REQUIRE(B >= 0 && HW > 0 && N >= 1 && N <= SA_NMAX, "need 1 <= num_slots <= 8");
+  SF_REQUIRE(B >= 0 && HW > 0 && N >= 1 && N <= SA_NMAX16, "need 1 <= num_slots <= 16");
   SF_REQUIRE(D == 64 || D == 128 || D == 192 || D == 256, "slot_size must be 64/128/192/256");
   SF_REQUIRE(ld >= D, "bad leading dimension");
   const int P = sf_sa_pick_partials(HW);
@@ -928,7 +956,38 @@ int sf_slot_attn_iter_ex(const float* k, const float* v, int ld, long long batch
   //  profiles/r03_probes.txt)
   // (round 4, for keys == values at width 128.  32 frames: 21.3 vs 26.4 us on the whole chip, 31.2 vs 35.5
   //  on a 128-CU mask, 67 instead of 120-132 MB fetched; its single-shot forms -- one tile per wave -- were no faster: profiles/r04_probes.txt section 3)
-  if (HW % 512 == 0 && k == v && D == 128 && P == HW / 256) {
+  if (N > SA_NMAX) {
+    // 9 .. 16 slots: the same three forms at the 16-slot bound (the instantiations below this branch are the 8-slot ones, for N <= 8)
+    if (sf_slot_attn_sparse_records_n(k, v, HW, D, N) && P == HW / 256) {
+      constexpr size_t LDS16 = (size_t)(8 * 16 * (128 + 4) + 8 * 16 * 17 + SA_NMAX16 * 128) * sizeof(float);   // 84,480 B: one workgroup per CU
+      static_assert(LDS16 <= 160 * 1024, "one-pass Slot Attention, 16 slots");
+      SF_TRY(sf_ensure_dyn_lds((const void*)sa_attn_tile_kernel<128, SA_NMAX16>, LDS16));
+      hipLaunchKernelGGL((sa_attn_tile_kernel<128, SA_NMAX16>), dim3(HW / 512, B), dim3(512), LDS16, st, k, ld, batch_stride, q, scale, eps, part_num,
+                         part_den, attn_out, attn_batch_stride, HW, N, P);
+    } else if (HW % 256 == 0) {
+#define SA_LAUNCH2(DD)                                                                                                  \
+  hipLaunchKernelGGL((sa_attn_mfma_kernel<DD, float, SA_NMAX16>), grid, block, 0, st, k, v, ld, batch_stride, q, scale, eps, \
+                     part_num, part_den, attn_out, attn_batch_stride, HW, N, P)
+      switch (D / 64) {
+        case 1: SA_LAUNCH2(64); break;
+        case 2: SA_LAUNCH2(128); break;
+        case 3: SA_LAUNCH2(192); break;
+        default: SA_LAUNCH2(256); break;
+      }
+#undef SA_LAUNCH2
+    } else {
+#define SA_LAUNCH16(VPT)                                                                                        \
+  hipLaunchKernelGGL((sa_attn_partial_kernel<VPT, SA_NMAX16>), grid, block, 0, st, k, v, ld, batch_stride, q, \
+                     scale, eps, part_num, part_den, attn_out, attn_batch_stride, HW, N, P)
+      switch (D / 64) {
+        case 1: SA_LAUNCH16(1); break;
+        case 2: SA_LAUNCH16(2); break;
+        case 3: SA_LAUNCH16(3); break;
+        default: SA_LAUNCH16(4); break;
+      }
+#undef SA_LAUNCH16
+    }
+  } else if (HW % 512 == 0 && k == v && D == 128 && P == HW / 256) {
     // keys == values: every row read once, both products on the matrix cores (sa_attn_tile_kernel: 512 pixels per workgroup)
     constexpr size_t LDS = (size_t)(8 * 16 * (128 + 4) + 8 * 16 * 17 + SA_NMAX * 128) * sizeof(float);   // 80,384 B: two workgroups per CU
     static_assert(2 * LDS <= 160 * 1024, "one-pass Slot Attention: two workgroups per CU");

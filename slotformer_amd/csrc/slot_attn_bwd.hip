@@ -18,7 +18,8 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 
-#define SAB_NMAX 8
+#define SAB_NMAX 8      // the first instantiation: every N <= 8, as before the second existed
+#define SAB_NMAX16 16   // 9 .. 16 slots (sf_slot_attn_iter_bwd16_f32)
 #define SAB_PIX 256   // pixels per workgroup
 
 // g = dU / den, c = dU.U / den per (frame, slot); one wave per (b, n)
@@ -41,7 +42,11 @@ __global__ __launch_bounds__(64) void sa_bwd_prep_kernel(const float* __restrict
   if (lane == 0) c[(long long)b * N + n] = dot * inv;
 }
 
-template <int D>
+// NS: the slot bound of the softmax (all the frame's slots, in registers).  G: which group of 8 slots this launch keeps running dq sums for.
+// 16 slots x D / 64 float4 of dq do not fit the registers at D = 256, so the 16-slot form runs as TWO launches that share the softmax (each
+// recomputes the 16 logits of a pixel): G = 0 writes dk / dv and the dq partials of slots 0..7 exactly as the 8-slot kernel does, G = 1 reads the
+// rows again and emits only the dq partials of slots 8..15.  Every partial is still one workgroup's sum in a fixed order.
+template <int D, int NS = SAB_NMAX, int G = 0>
 __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void sa_iter_bwd_kernel(const float* __restrict__ k, const float* __restrict__ v, int ld,
                                                           long long batch_stride, const float* __restrict__ q,
                                                           const float* __restrict__ g, const float* __restrict__ c,
@@ -53,17 +58,18 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void sa_iter_bwd_kernel(co
   const int tid = threadIdx.x, j = tid & 15, grp = tid >> 4;   // 16 pixel groups per workgroup
   // red: [16][D] floats for the final dq reduction, then qs [NMAX][D] (scaled queries) and gg [NMAX][D]
   float* qsl = red + 16 * D;
-  float* ggl = qsl + SAB_NMAX * D;
-  for (int i = tid; i < SAB_NMAX * D; i += 256) {
+  float* ggl = qsl + NS * D;
+  for (int i = tid; i < NS * D; i += 256) {
     const int n = i / D;
     qsl[i] = n < N ? q[(long long)b * N * D + i] * scale : 0.f;
     ggl[i] = n < N ? g[(long long)b * N * D + i] : 0.f;
   }
-  float4 dqa[SAB_NMAX][C4];
-  float cc[SAB_NMAX];
+  float4 dqa[SAB_NMAX][C4];   // slots 8 G .. 8 G + 7
+  float cc[NS];
+#pragma unroll
+  for (int n = 0; n < NS; ++n) cc[n] = n < N ? c[(long long)b * N + n] : 0.f;
 #pragma unroll
   for (int n = 0; n < SAB_NMAX; ++n) {
-    cc[n] = n < N ? c[(long long)b * N + n] : 0.f;
 #pragma unroll
     for (int i = 0; i < C4; ++i) dqa[n][i] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
@@ -99,7 +105,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void sa_iter_bwd_kernel(co
       }
     }
     float4 ok[C4], ov[C4];
-    if (accumulate && p < HW) {
+    if (G == 0 && accumulate && p < HW) {
 #pragma unroll
       for (int i = 0; i < C4; ++i) {
         ok[i] = *reinterpret_cast<const float4*>(dk + row(p) + 64 * i);
@@ -109,10 +115,10 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void sa_iter_bwd_kernel(co
 #pragma unroll
       for (int i = 0; i < C4; ++i) ok[i] = ov[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    float s[SAB_NMAX], t[SAB_NMAX];
+    float s[NS], t[NS];
     float mx = -INFINITY;
 #pragma unroll
-    for (int n = 0; n < SAB_NMAX; ++n) {
+    for (int n = 0; n < NS; ++n) {
       float a = 0.f, e = 0.f;
 #pragma unroll
       for (int i = 0; i < C4; ++i) {
@@ -126,31 +132,37 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void sa_iter_bwd_kernel(co
     }
     float sum = 0.f;
 #pragma unroll
-    for (int n = 0; n < SAB_NMAX; ++n) {
+    for (int n = 0; n < NS; ++n) {
       s[n] = n < N ? __expf(s[n] - mx) : 0.f;
       sum += s[n];
     }
     const float inv = 1.f / sum;
+    if constexpr (NS != SAB_NMAX) __builtin_amdgcn_sched_barrier(0);   // (16 slots: the dq products are not scheduled into the logits -- registers)
     float dot = 0.f;
 #pragma unroll
-    for (int n = 0; n < SAB_NMAX; ++n) {
+    for (int n = 0; n < NS; ++n) {
       s[n] *= inv;            // a[p,n]
       t[n] -= cc[n];          // da'[p,n]
       dot += s[n] * t[n];
     }
 #pragma unroll
-    for (int n = 0; n < SAB_NMAX; ++n) {
+    for (int n = 0; n < NS; ++n) {
       const float dl = s[n] * (t[n] - dot);
       const float ap = n < N ? s[n] + eps : 0.f;
 #pragma unroll
       for (int i = 0; i < C4; ++i) {
-        const float4 qv = QS(n, i), gv = GG(n, i);
-        ok[i].x += dl * qv.x; ok[i].y += dl * qv.y; ok[i].z += dl * qv.z; ok[i].w += dl * qv.w;
-        ov[i].x += ap * gv.x; ov[i].y += ap * gv.y; ov[i].z += ap * gv.z; ov[i].w += ap * gv.w;
-        dqa[n][i].x += dl * kc[i].x; dqa[n][i].y += dl * kc[i].y; dqa[n][i].z += dl * kc[i].z; dqa[n][i].w += dl * kc[i].w;
+        if constexpr (G == 0) {
+          const float4 qv = QS(n, i), gv = GG(n, i);
+          ok[i].x += dl * qv.x; ok[i].y += dl * qv.y; ok[i].z += dl * qv.z; ok[i].w += dl * qv.w;
+          ov[i].x += ap * gv.x; ov[i].y += ap * gv.y; ov[i].z += ap * gv.z; ov[i].w += ap * gv.w;
+        }
+        if (n >= SAB_NMAX * G && n < SAB_NMAX * (G + 1)) {   // (n is a compile-time constant of the unrolled loop)
+          float4& dq4 = dqa[(n - SAB_NMAX * G) & (SAB_NMAX - 1)][i];
+          dq4.x += dl * kc[i].x; dq4.y += dl * kc[i].y; dq4.z += dl * kc[i].z; dq4.w += dl * kc[i].w;
+        }
       }
     }
-    if (p < HW) {
+    if (G == 0 && p < HW) {
 #pragma unroll
       for (int i = 0; i < C4; ++i) {
         *reinterpret_cast<float4*>(dk + row(p) + 64 * i) = ok[i];
@@ -159,14 +171,14 @@ __global__ __launch_bounds__(256, (D <= 128 ? 2 : 1)) void sa_iter_bwd_kernel(co
     }
   }
   // dq partial of this workgroup: sum the 16 pixel groups through LDS, slot by slot ([16][D] floats at a time)
-  for (int n = 0; n < N; ++n) {
+  for (int n = SAB_NMAX * G; n < N && n < SAB_NMAX * (G + 1); ++n) {
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < C4; ++i) {
       float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int m = 0; m < SAB_NMAX; ++m)
-        if (m == n) val = dqa[m][i];
+        if (m + SAB_NMAX * G == n) val = dqa[m][i];
       *reinterpret_cast<float4*>(&red[grp * D + 4 * (j + 16 * i)]) = val;
     }
     __syncthreads();
@@ -189,22 +201,21 @@ __global__ __launch_bounds__(256) void sa_bwd_dq_reduce_kernel(const float* __re
   dq[(long long)b * ND + i] = a * scale;
 }
 
-extern "C" {
-
-size_t sf_slot_attn_iter_bwd_workspace_bytes(int B, int HW, int N, int D) {
+static size_t sab_workspace_bytes(int B, int HW, int N, int D) {
   const size_t nchunks = (size_t)(HW + SAB_PIX - 1) / SAB_PIX;
   return ((size_t)B * N * D + (size_t)B * N + (size_t)B * nchunks * N * D) * sizeof(float) + 256;
 }
 
-int sf_slot_attn_iter_bwd_f32(const float* k, const float* v, int ld, long long batch_stride, const float* q,
-                              const float* part_num, const float* part_den, int P, const float* d_updates, float* dk, float* dv,
-                              int accumulate, float* dq, int B, int HW, int N, int D, float scale, float eps, void* ws,
-                              size_t ws_bytes, void* stream) {
+// both entry points: nmax = 8 (sf_slot_attn_iter_bwd_f32, whose callers rely on 9 slots being refused) or 16 (sf_slot_attn_iter_bwd16_f32)
+static int sab_run(const float* k, const float* v, int ld, long long batch_stride, const float* q, const float* part_num,
+                   const float* part_den, int P, const float* d_updates, float* dk, float* dv, int accumulate, float* dq, int B, int HW,
+                   int N, int D, float scale, float eps, void* ws, size_t ws_bytes, void* stream, int nmax) {
   SF_REQUIRE(k && v && q && part_num && part_den && d_updates && dk && dv && dq && ws, "null pointer");
-  SF_REQUIRE(B >= 0 && HW > 0 && N >= 1 && N <= SAB_NMAX && P >= 1, "need 1 <= num_slots <= 8");
+  SF_REQUIRE(nmax != SAB_NMAX || (N >= 1 && N <= SAB_NMAX), "need 1 <= num_slots <= 8");
+  SF_REQUIRE(B >= 0 && HW > 0 && N >= 1 && N <= SAB_NMAX16 && P >= 1, "need 1 <= num_slots <= 16");
   SF_REQUIRE(D == 64 || D == 128 || D == 192 || D == 256, "slot_size must be 64 / 128 / 192 / 256");
   SF_REQUIRE(ld >= D && (ld % 4) == 0 && (batch_stride % 4) == 0, "k/v rows must be 16-byte aligned");
-  SF_REQUIRE(ws_bytes >= sf_slot_attn_iter_bwd_workspace_bytes(B, HW, N, D), "workspace too small");
+  SF_REQUIRE(ws_bytes >= sab_workspace_bytes(B, HW, N, D), "workspace too small");
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   float* g = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
@@ -213,21 +224,63 @@ int sf_slot_attn_iter_bwd_f32(const float* k, const float* v, int ld, long long 
   const int nchunks = (HW + SAB_PIX - 1) / SAB_PIX;
   hipLaunchKernelGGL(sa_bwd_prep_kernel, dim3(N, B), dim3(64), 0, st, part_num, part_den, P, d_updates, g, c, N, D);
   SF_CHECK_LAUNCH();
-  const size_t lds = (size_t)(16 + 2 * SAB_NMAX) * D * sizeof(float);
+  if (N <= SAB_NMAX) {
+    const size_t lds = (size_t)(16 + 2 * SAB_NMAX) * D * sizeof(float);
 #define SAB_LAUNCH(DD)                                                                                                       \
   hipLaunchKernelGGL(sa_iter_bwd_kernel<DD>, dim3(nchunks, B), dim3(256), lds, st, k, v, ld, batch_stride, q, g, c, dk, dv, \
                      accumulate, part, HW, N, scale, eps)
-  switch (D) {
-    case 64: SAB_LAUNCH(64); break;
-    case 128: SAB_LAUNCH(128); break;
-    case 192: SAB_LAUNCH(192); break;
-    default: SAB_LAUNCH(256); break;
-  }
+    switch (D) {
+      case 64: SAB_LAUNCH(64); break;
+      case 128: SAB_LAUNCH(128); break;
+      case 192: SAB_LAUNCH(192); break;
+      default: SAB_LAUNCH(256); break;
+    }
 #undef SAB_LAUNCH
-  SF_CHECK_LAUNCH();
+    SF_CHECK_LAUNCH();
+  } else {
+    // 9 .. 16 slots: two launches that share the softmax (see sa_iter_bwd_kernel); the second touches neither dk nor dv
+    const size_t lds = (size_t)(16 + 2 * SAB_NMAX16) * D * sizeof(float);   // at most 48 KB
+#define SAB_LAUNCH16(DD, GG)                                                                                                           \
+  do {                                                                                                                                 \
+    SF_TRY(sf_ensure_dyn_lds((const void*)sa_iter_bwd_kernel<DD, SAB_NMAX16, GG>, lds));                                               \
+    hipLaunchKernelGGL((sa_iter_bwd_kernel<DD, SAB_NMAX16, GG>), dim3(nchunks, B), dim3(256), lds, st, k, v, ld, batch_stride, q, g, c, \
+                       dk, dv, accumulate, part, HW, N, scale, eps);                                                                   \
+    SF_CHECK_LAUNCH();                                                                                                                 \
+  } while (0)
+    switch (D) {
+      case 64: SAB_LAUNCH16(64, 0); SAB_LAUNCH16(64, 1); break;
+      case 128: SAB_LAUNCH16(128, 0); SAB_LAUNCH16(128, 1); break;
+      case 192: SAB_LAUNCH16(192, 0); SAB_LAUNCH16(192, 1); break;
+      default: SAB_LAUNCH16(256, 0); SAB_LAUNCH16(256, 1); break;
+    }
+#undef SAB_LAUNCH16
+  }
   hipLaunchKernelGGL(sa_bwd_dq_reduce_kernel, dim3((N * D + 255) / 256, B), dim3(256), 0, st, part, dq, nchunks, N * D, scale);
   SF_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" {
+
+size_t sf_slot_attn_iter_bwd_workspace_bytes(int B, int HW, int N, int D) { return sab_workspace_bytes(B, HW, N, D); }
+
+int sf_slot_attn_iter_bwd_f32(const float* k, const float* v, int ld, long long batch_stride, const float* q,
+                              const float* part_num, const float* part_den, int P, const float* d_updates, float* dk, float* dv,
+                              int accumulate, float* dq, int B, int HW, int N, int D, float scale, float eps, void* ws,
+                              size_t ws_bytes, void* stream) {
+  return sab_run(k, v, ld, batch_stride, q, part_num, part_den, P, d_updates, dk, dv, accumulate, dq, B, HW, N, D, scale, eps, ws, ws_bytes,
+                 stream, SAB_NMAX);
+}
+
+// The same backward for 1 <= N <= 16 slots (N <= 8: the kernel of sf_slot_attn_iter_bwd_f32, same bits; 9 .. 16: the two-launch form).
+size_t sf_slot_attn_iter_bwd16_workspace_bytes(int B, int HW, int N, int D) { return sab_workspace_bytes(B, HW, N, D); }
+
+int sf_slot_attn_iter_bwd16_f32(const float* k, const float* v, int ld, long long batch_stride, const float* q,
+                                const float* part_num, const float* part_den, int P, const float* d_updates, float* dk, float* dv,
+                                int accumulate, float* dq, int B, int HW, int N, int D, float scale, float eps, void* ws,
+                                size_t ws_bytes, void* stream) {
+  return sab_run(k, v, ld, batch_stride, q, part_num, part_den, P, d_updates, dk, dv, accumulate, dq, B, HW, N, D, scale, eps, ws, ws_bytes,
+                 stream, SAB_NMAX16);
 }
 
 }  // extern "C"

@@ -106,7 +106,7 @@ SaWs carve(const SaDims& d, float* base) {
   w.dh = take(R * D); w.dupd = take(R * D); w.dsp = take(R * D); w.dhp = take(R * D);
   w.w2t = take(H * D); w.w1t = take(H * D); w.wiht = take(3 * D * D); w.whht = take(3 * D * D); w.wqt = take(D * D);
   w.wkvt = take(2 * D * C); w.dwkv = take(2 * D * C);
-  w.iter_ws_bytes = sf_slot_attn_iter_bwd_workspace_bytes(d.B, d.HW, d.N, d.D);
+  w.iter_ws_bytes = sf_slot_attn_iter_bwd16_workspace_bytes(d.B, d.HW, d.N, d.D);   // (the same count as the 8-slot query for N <= 8)
   w.iter_ws = take(w.iter_ws_bytes / 4 + 64);
   size_t pf = sf_grad_partial_floats(d.M, 2 * d.D, d.Cin);
   const size_t alt[] = {sf_grad_partial_floats(I * R, 3 * d.D, d.D), sf_grad_partial_floats(I * R, d.H, d.D),
@@ -123,7 +123,7 @@ int check(const sf_slot_attention* m, SaDims& d, int B, int HW, int iters) {
   d.B = B; d.HW = HW; d.N = m->num_slots; d.D = m->slot_size; d.Cin = m->in_features; d.H = m->mlp_hidden; d.I = iters;
   SF_REQUIRE(d.D == 64 || d.D == 128 || d.D == 192 || d.D == 256, "slot_size must be 64 / 128 / 192 / 256");
   SF_REQUIRE(d.Cin % 64 == 0 && d.H % 64 == 0 && d.Cin <= 1024, "in_features and mlp_hidden must be multiples of 64");
-  SF_REQUIRE(d.N >= 1 && d.N <= 8, "1..8 slots");
+  SF_REQUIRE(d.N >= 1 && d.N <= 16, "1..16 slots");
   d.P = sf_slot_attn_num_partials(HW);
   SF_REQUIRE((HW % d.P) == 0 && ((HW / d.P) % 16) == 0, "HW must be a multiple of 16");
   d.M = (long long)B * HW;
@@ -226,7 +226,8 @@ int sf_slot_attention_train_bwd_f32(const sf_slot_attention* m, const float* inp
     SF_TRY(gemm(w.dgi + o * 3 * D, w.wiht, nullptr, nullptr, w.dupd, R, D, 3 * D, 0, st));
     SF_TRY(gemm(w.dgh + o * 3 * D, w.whht, nullptr, w.dhp, w.dsp, R, D, 3 * D, 0, st));
     // attention half: dk|dv accumulate over the iterations
-    SF_TRY(sf_slot_attn_iter_bwd_f32(w.kv, w.kv + D, 2 * D, (long long)HW * 2 * D, w.q + o * D, w.pn + (size_t)it * B * d.P * N * D,
+    // (N <= 8: the kernel of sf_slot_attn_iter_bwd_f32; 9 .. 16 slots: the two-launch form)
+    SF_TRY(sf_slot_attn_iter_bwd16_f32(w.kv, w.kv + D, 2 * D, (long long)HW * 2 * D, w.q + o * D, w.pn + (size_t)it * B * d.P * N * D,
                                      w.pd + (size_t)it * B * d.P * N, d.P, w.dupd, w.dkv, w.dkv + D, it != I - 1, w.dq + o * D, B, HW,
                                      N, D, scale, m->eps, w.iter_ws, w.iter_ws_bytes, st));
     // q = LN_q(slots) Wq^T

@@ -188,10 +188,13 @@ def slot_attn_iter_bwd(k, v, q, pn, pd, d_updates, dk=None, dv=None, eps=1e-6):
     if not acc:
         dk, dv = torch.empty_like(k), torch.empty_like(v)
     dq = torch.empty_like(q)
-    nb = lib().sf_slot_attn_iter_bwd_workspace_bytes(B, HW, N, D)
+    # N <= 8: the 8-slot entry point; 9 .. 16 slots: the two-launch form behind its own entry point
+    ws_bytes, bwd = ((lib().sf_slot_attn_iter_bwd_workspace_bytes, lib().sf_slot_attn_iter_bwd_f32) if N <= 8 else
+                     (lib().sf_slot_attn_iter_bwd16_workspace_bytes, lib().sf_slot_attn_iter_bwd16_f32))
+    nb = ws_bytes(B, HW, N, D)
     ws = torch.empty(nb, dtype=torch.uint8, device=k.device)
-    check(lib().sf_slot_attn_iter_bwd_f32(_p(k), _p(v), D, HW * D, _p(q), _p(pn), _p(pd), P, _p(d_updates), _p(dk), _p(dv),
-                                          int(acc), _p(dq), B, HW, N, D, float(D)**-0.5, eps, ws.data_ptr(), nb, _stream()))
+    check(bwd(_p(k), _p(v), D, HW * D, _p(q), _p(pn), _p(pd), P, _p(d_updates), _p(dk), _p(dv),
+              int(acc), _p(dq), B, HW, N, D, float(D)**-0.5, eps, ws.data_ptr(), nb, _stream()))
     return dq, dk, dv
 
 
