@@ -447,6 +447,33 @@ size_t sf_slate_generate_workspace_bytes(const sf_slate_decoder* m, int B, int s
 int sf_slate_generate_f32(const sf_slate_decoder* m, const float* slots, int B, int steps, long long* tokens_out,
                           float* logits_out, void* ws, size_t ws_bytes, void* stream);
 
+/* The same generation with one launch per token (slate_step.hip): a workgroup owns frames_per_wg consecutive frames for a whole
+ * token step -- embedding, every block, final LayerNorm, vocabulary head, argmax -- and talks to no other workgroup; the K/V
+ * cache and the token array are the only state between launches.  Exact fp32 FMA.
+ * sf_slate_step_ok reads shapes only (never a weight) and returns 1 where the fused step applies.  It refuses:
+ *   d_model <= 0, d_model > 512 or d_model % 32 != 0;  num_heads < 1, > 16 or not dividing d_model;
+ *   a head size other than 16, 32, 48 or 64;  num_layers < 1 or > 8;  vocab_size < 1;  num_slots < 1;  max_len < 0. */
+int sf_slate_step_ok(const sf_slate_decoder* m);
+/* enough for either form (0 for a NULL model, B <= 0 or steps <= 0) */
+size_t sf_slate_generate_tok_workspace_bytes(const sf_slate_decoder* m, int B, int steps);
+/* slots [B,N,d] -> tokens_out int64 [B,steps]; logits_out [B,steps,V] on the device, or NULL (then no logits are written).
+ * frames_per_wg: 1, 2 or 4 asks for the fused step with that many frames per workgroup; 0 is the library's choice.
+ * Where sf_slate_step_ok is 0 -- whatever frames_per_wg says -- or the library's choice for this B is the launch chain,
+ * sf_slate_generate_f32 runs.  *frames_per_wg_ran (may be NULL) receives the form that ran: 0 = the launch chain, else the
+ * frames per workgroup of the fused step.
+ * The library's choice (profiles/steve_render.md; the fused step is chosen only where it beat the chain by more than the 6 %
+ * box-to-box spread; measured at the Physion decoder, 1024 steps, on one MI355X): up to 192 frames the fused step
+ * with one frame per workgroup (0.88 / 0.82 / 0.77 / 0.70 of the chain's time at 1 / 12 / 64 / 192 frames; two frames per
+ * workgroup never beat one by more than the spread, four lost to the chain from 12 frames on); beyond 192 frames, where nothing
+ * is measured, the launch chain. */
+int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int B, int steps, long long* tokens_out,
+                              float* logits_out, int frames_per_wg, void* ws, size_t ws_bytes, void* stream,
+                              int* frames_per_wg_ran);
+/* out[r, :] = table[ids[r], :], ids int64 [R], table [table_rows, d], d % 4 == 0 (the first 1x1 convolution of the dVAE decoder
+ * on a one-hot token map).  An id outside the table is clamped to its ends, so a wrong id never reads out of bounds. */
+int sf_gather_rows_f32(const float* table, const long long* ids, float* out, long long R, int d, long long table_rows,
+                       void* stream);
+
 /* ---- whole-path engines ------------------------------------------------------------------ */
 
 /* One nn.TransformerEncoderLayer (relu, batch_first); all pointers device, torch layouts. */

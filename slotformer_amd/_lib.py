@@ -273,6 +273,10 @@ SIGNATURES = {
     'sf_gumbel_softmax_rows_f32': (I, [FP, C.c_ulonglong, F32, FP, LL, I, VP]),
     'sf_slate_generate_workspace_bytes': (SZ, [C.POINTER(sf_slate_decoder), I, I]),
     'sf_slate_generate_f32': (I, [C.POINTER(sf_slate_decoder), FP, I, I, VP, FP, VP, SZ, VP]),
+    'sf_slate_step_ok': (I, [C.POINTER(sf_slate_decoder)]),
+    'sf_slate_generate_tok_workspace_bytes': (SZ, [C.POINTER(sf_slate_decoder), I, I]),
+    'sf_slate_generate_tok_f32': (I, [C.POINTER(sf_slate_decoder), FP, I, I, VP, FP, I, VP, SZ, VP, C.POINTER(I)]),
+    'sf_gather_rows_f32': (I, [FP, VP, FP, LL, I, LL, VP]),
     'sf_packed_linear_bytes': (SZ, [I, I]),
     'sf_pack_linear_weights': (I, [FP, VP, I, I, VP]),
     'sf_attn_packed_bytes': (SZ, [I, I]),

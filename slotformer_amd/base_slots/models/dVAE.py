@@ -112,9 +112,12 @@ class dVAE(BaseModel):
         if torch.is_grad_enabled():   # under autograd: the same arithmetic as a chain of differentiable nodes
             recon = self.decode_nhwc(z.permute(0, 2, 3, 1).float()).permute(0, 3, 1, 2)
             return recon.unflatten(0, (B, -1)) if unflatten else recon
+        recon = self._decoder_tail(self._block(z.permute(0, 2, 3, 1).contiguous().float(), self.decoder[0]))
+        return recon.unflatten(0, (B, -1)) if unflatten else recon
+
+    def _decoder_tail(self, x):
+        """The decoder stack after its first block: x NHWC [F,h,w,64] -> image [F,3,4h,4w]."""
         d = self.decoder
-        x = z.permute(0, 2, 3, 1).contiguous().float()
-        x = self._block(x, d[0])
         x = self._block(x, d[1])
         x = self._block(x, d[2])
         x = self._block(x, d[3])
@@ -125,8 +128,31 @@ class dVAE(BaseModel):
         x = self._block(x, d[9], pixel_shuffle=2)
         last = d[11]
         x = ops.linear(x, last.weight.detach().reshape(self.img_channels, 64).contiguous(), last.bias.detach())
-        recon = x.permute(0, 3, 1, 2).contiguous()
-        return recon.unflatten(0, (B, -1)) if unflatten else recon
+        return x.permute(0, 3, 1, 2).contiguous()
+
+    def detokenize_nhwc(self, z):
+        """`detokenize` of a channels-last map z [F,h,w,V] (no transpose on the way in) -> image [F,3,4h,4w]."""
+        assert z.dim() == 4 and z.shape[-1] == self.vocab_size
+        if torch.is_grad_enabled():
+            raise RuntimeError('slotformer_amd dVAE.detokenize_nhwc is inference-only: call it under torch.no_grad()')
+        return self._decoder_tail(self._block(z.contiguous().float(), self.decoder[0]))
+
+    def detokenize_ids(self, ids):
+        """Token ids [F,h,w] int64 on the device -> image [F,3,4h,4w]: `detokenize` of their one-hot map without building it.  The first
+        decoder block's bias-free 1x1 convolution on a one-hot vector is one column of its weight, so it runs as a row gather of the
+        transposed weight (`sf_gather_rows_f32`); the rest of the stack runs as in `detokenize`."""
+        if torch.is_grad_enabled():
+            raise RuntimeError('slotformer_amd dVAE.detokenize_ids is inference-only: call it under torch.no_grad()')
+        if not (torch.is_tensor(ids) and ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 3):
+            raise RuntimeError('detokenize_ids needs int64 token ids [F,h,w] on a HIP device; there is no CPU fallback')
+        blk = self.decoder[0]
+        w = blk.m.weight
+        key = ('ids', w.data_ptr(), w._version)
+        if key not in self._packed:
+            self._packed = {} if len(self._packed) > 8 else self._packed
+            self._packed[key] = w.detach().reshape(w.shape[0], w.shape[1]).t().float().contiguous()   # [V, 64]
+        y = ops.gather_rows(self._packed[key], ids.contiguous())                                   # [F,h,w,64]
+        return self._decoder_tail(ops.groupnorm1_nhwc(y, blk.weight.detach(), blk.bias.detach(), relu=True))
 
     # ---- training forward (dVAE.py:113-139) ---------------------------------------------------------------
     def _block_t(self, x, blk, pixel_shuffle=1):

@@ -166,6 +166,13 @@ class STEVE(StoSAVi):
             loss_dict['img_recon_loss'] = losses.image_recon_loss(out_dict['recon_img'], out_dict['gt_img'])
         return loss_dict
 
+    def render(self, slots, soft=False, gumbel=None, seed=None, frames_per_wg=0):
+        """Slots [F,N,D] -> frames on the device, the reconstruction of base_slots/method.py:353-378 (`trans_decoder` generates the
+        token grid, `dvae` detokenises it): {'tokens' [F,h,w], 'hard' [F,3,H,W]} (+ 'soft' with soft=True); see
+        `steve_render.render_slots`."""
+        from ...steve_render import render_slots
+        return render_slots(self.trans_decoder, self.dvae, slots, soft=soft, gumbel=gumbel, seed=seed, frames_per_wg=frames_per_wg)
+
     def train(self, mode=True):
         """steve.py: the dVAE stays in eval mode."""
         super().train(mode)

@@ -213,6 +213,35 @@ class STEVETransformerDecoder(nn.Module):
                                           ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream))
         return tokens, logits.cpu()
 
+    def generate_tokens(self, slots, steps, return_logits=False, frames_per_wg=0):
+        """Greedy generation that stays on the device (`sf_slate_generate_tok_f32`): one launch per token where the fused step
+        applies (`sf_slate_step_ok`), a workgroup owning `frames_per_wg` frames (1, 2 or 4; 0 = the library's choice, which may
+        be the launch chain of `generate_cached`).  Returns (tokens [B,steps] int64, logits [B,steps,V] or None), both on the
+        device; the logits are only written with return_logits=True.  `self.last_generate_form` is the form that ran: 0 for the
+        launch chain, else the frames per workgroup of the fused step."""
+        import ctypes as C
+        from ..._lib import check, lib
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError('slotformer_amd STEVETransformerDecoder is inference-only: .eval() + torch.no_grad()')
+        if not (torch.is_tensor(slots) and slots.is_cuda and slots.dtype == torch.float32):
+            raise RuntimeError('generate_tokens needs float32 slots on a HIP device; there is no CPU fallback')
+        if frames_per_wg not in (0, 1, 2, 4):
+            raise ValueError(f'generate_tokens: frames_per_wg is 0 (the library\'s choice), 1, 2 or 4, got {frames_per_wg!r}')
+        assert slots.shape[1] == self.num_slots and steps - 1 <= self.max_len
+        slots = slots.contiguous()
+        B = slots.shape[0]
+        m, _ = self._slate_plan()
+        tokens = torch.empty(B, steps, dtype=torch.int64, device=slots.device)
+        logits = torch.empty(B, steps, self.vocab_size, dtype=torch.float32, device=slots.device) if return_logits else None
+        nb = lib().sf_slate_generate_tok_workspace_bytes(C.byref(m), B, steps)
+        ws = torch.empty(nb, dtype=torch.uint8, device=slots.device)
+        ran = C.c_int(-1)
+        check(lib().sf_slate_generate_tok_f32(C.byref(m), slots.data_ptr(), B, steps, tokens.data_ptr(),
+                                              None if logits is None else logits.data_ptr(), int(frames_per_wg), ws.data_ptr(), nb,
+                                              torch.cuda.current_stream().cuda_stream, C.byref(ran)))
+        self.last_generate_form = ran.value
+        return tokens, logits
+
     def generate(self, slots, steps, sample=False, temperature=1.0):
         """Autoregressive generation (steve_transformer.py:305-333): the whole prefix is re-run every step, as in the reference;
         greedy (sample=False: argmax) or sampled (sample=True: one draw per step from softmax(logits / temperature) -- the softmax a HIP

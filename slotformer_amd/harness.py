@@ -55,6 +55,51 @@ def rollout_video_slots(model, ori_slots, frame_offset, history_len=None, obs_fr
     return out
 
 
+def render_chunks(num_frames, frames_per_call=64):
+    """[(start, stop), ...] covering range(num_frames) once, `frames_per_call` frames per chunk (the last one may be shorter)."""
+    if int(frames_per_call) < 1:
+        raise ValueError(f'slotformer_amd.harness: frames_per_call >= 1, got {frames_per_call!r}')
+    return [(s, min(s + int(frames_per_call), num_frames)) for s in range(0, num_frames, int(frames_per_call))]
+
+
+@torch.no_grad()
+def render_video_slots(model, slots, frames_per_call=64, soft=False, to_host=False):
+    """The device form of STEVE's `_slots2video` (video_prediction/method.py:207-219): slots [V,T,N,D] or [T,N,D] -> the frames
+    `model.render` draws from them (the hard image; with soft=True the Gumbel-softmax one), float32 [V,T,3,H,W] / [T,3,H,W] on the
+    device.  `model` is a STEVESlotFormer or STEVE in eval mode.  The frames go through `render` in chunks of `frames_per_call`
+    (at 64 frames of the 4096-word vocabulary the optional logits take 1 GB).  to_host=True: uint8 [..., H, W, 3] in pinned host
+    memory instead (`egress.frames_to_uint8` per chunk), each chunk downloaded on a side stream behind the next chunk's generation."""
+    from . import egress
+    lead = tuple(slots.shape[:-2])
+    assert slots.dim() in (3, 4), 'slots are [V, T, N, D] or [T, N, D]'
+    flat = slots.reshape((-1, ) + tuple(slots.shape[-2:])).float().to(model.device).contiguous()
+    key = 'soft' if soft else 'hard'
+    F_ = flat.shape[0]
+    out, copies, keep = None, None, []
+    for a, b in render_chunks(F_, frames_per_call):
+        frames = model.render(flat[a:b], soft=soft)[key]
+        if not to_host:
+            if out is None:
+                out = torch.empty((F_, ) + tuple(frames.shape[1:]), dtype=torch.float32, device=frames.device)
+            out[a:b] = frames
+            continue
+        u8 = egress.frames_to_uint8(frames)
+        if out is None:
+            out = torch.empty((F_, ) + tuple(u8.shape[1:]), dtype=torch.uint8, pin_memory=True)
+            copies = torch.cuda.Stream(device=frames.device)
+        ready = torch.cuda.Event()
+        ready.record()
+        copies.wait_event(ready)
+        with torch.cuda.stream(copies):
+            out[a:b].copy_(u8, non_blocking=True)
+        keep.append(u8)   # alive until its copy has run
+    if out is None:
+        raise ValueError('slotformer_amd.harness: render_video_slots needs at least one frame')
+    if to_host:
+        copies.synchronize()
+    return out.reshape(lead + tuple(out.shape[1:]))
+
+
 @torch.no_grad()
 def encode_then_rollout(savi, slotformer, img0, vid_len, noise=None):
     """H3 -- test_phyre_planning.py:159-174: SAVi on the first frame(s), zero-pad to `vid_len`,

@@ -344,6 +344,17 @@ def argmax_rows(x):
     return out
 
 
+def gather_rows(table, ids):
+    """table[ids]: table [rows, d] float32, ids int64 [...] on the device -> [..., d] (`sf_gather_rows_f32`)."""
+    _chk(table)
+    if ids.dtype != torch.int64 or not ids.is_cuda or not ids.is_contiguous():
+        raise TypeError('gather_rows: ids must be a contiguous int64 device tensor')
+    rows, d = table.shape
+    out = torch.empty(tuple(ids.shape) + (d, ), device=table.device, dtype=torch.float32)
+    check(lib().sf_gather_rows_f32(_p(table), ids.data_ptr(), _p(out), ids.numel(), d, rows, _stream()))
+    return out
+
+
 def cross_entropy(logits, target):
     """F.cross_entropy(logits [R,V], target int64 [R]) with mean reduction -> 0-dim tensor."""
     _chk(logits)

@@ -66,6 +66,12 @@ class STEVESlotFormer(SlotFormer):
         hard = self.dvae.detokenize(self._token_map(one_hot))
         return soft, hard
 
+    def render(self, slots, soft=False, gumbel=None, seed=None, frames_per_wg=0):
+        """`decode` that stays on the device (`steve_render.render_slots`): slots [F,N,D] -> {'tokens' [F,h,w], 'hard' [F,3,H,W]}
+        (+ 'soft' with soft=True; its noise is `gumbel` [F,V,h,w] or generated in the kernel from `seed`)."""
+        from ...steve_render import render_slots
+        return render_slots(self.decoder, self.dvae, slots, soft=soft, gumbel=gumbel, seed=seed, frames_per_wg=frames_per_wg)
+
     def rollout(self, past_slots, pred_len, decode=False, with_gt=True):
         """Slots only: this model never renders inside rollout (steve_slotformer.py:105-109)."""
         return self.rollouter(past_slots[:, -self.history_len:], pred_len)

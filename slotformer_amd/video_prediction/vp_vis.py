@@ -2,7 +2,8 @@
 on the egress kernels (slotformer_amd/egress.py, csrc/egress.hip): device tensors are composed, quantised and drawn on on the device and downloaded
 once; CPU tensors take egress's plain-torch home.  torchvision is not needed.
 
-Beside them the forms that stay on the device and return uint8 in a video writer's layout -- make_video_u8, batch_draw_bbox_u8 -- and
+Beside them the forms that stay on the device and return uint8 in a video writer's layout -- make_video_u8, batch_draw_bbox_u8 --, STEVE's three-tile
+video (make_steve_video, make_steve_video_u8: base_slots/method.py:293-310) and
 slot_decomposition_grid, the grid of the trainers' sample videos (base_slots/method.py:102-131), for anyone porting a trainer off its make_grid loops.
 
 One difference from the reference: a box with a side thinner than 2 * bbox_width is outlined inside the box only (PIL, which torchvision draws with,
@@ -46,6 +47,23 @@ def make_video_u8(video, pred_video, history_len=6, layout='hwc'):
     """make_video as uint8 ((video * 255.) cast toward zero, what _save_video writes) [T, 2 (H + 4), W + 4, 3] ('hwc') or [T, 3, 2 (H + 4), W + 4]
     ('chw'), left on the inputs' device."""
     return egress.video_grid(_video_tiles(video, pred_video, history_len), nrow=1, padding=0, dtype=torch.uint8, layout=layout)
+
+
+def _steve_tiles(video, soft_video, hard_video):
+    return [egress.Img(_f32(video)), egress.Img(_f32(soft_video)), egress.Img(_f32(hard_video))]
+
+
+def make_steve_video(video, soft_video, hard_video):
+    """STEVEMethod._make_video (base_slots/method.py:293-310): videos [T, 3, H, W] in [-1, 1] -> float32 [T, 3, H + 4, 3 (W + 2) + 2] in [0, 1]: per
+    frame the original, the Gumbel-softmax reconstruction and the argmax-token reconstruction in one row (make_grid, nrow 3, padding 2); left on the
+    inputs' device (the reference's is on the CPU: `.cpu()` it where that matters)."""
+    return egress.video_grid(_steve_tiles(video, soft_video, hard_video), nrow=3, padding=2)
+
+
+def make_steve_video_u8(video, soft_video, hard_video, layout='hwc'):
+    """make_steve_video as uint8 ((video * 255.) cast toward zero) [T, H + 4, 3 (W + 2) + 2, 3] ('hwc') or [T, 3, H + 4, 3 (W + 2) + 2] ('chw'), left on
+    the inputs' device."""
+    return egress.video_grid(_steve_tiles(video, soft_video, hard_video), nrow=3, padding=2, dtype=torch.uint8, layout=layout)
 
 
 def batch_draw_bbox_u8(imgs, bboxes, pres_masks=None, bbox_width=2):
