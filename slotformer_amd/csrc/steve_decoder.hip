@@ -577,15 +577,17 @@ __global__ void embed_kernel(const long long* __restrict__ idx, long long idx_bs
   *(f32x4*)(out + row * d + 4 * c4) = e + p;
 }
 
-// first index of the row maximum (torch.argmax / topk(k=1) tie rule); one workgroup of 256 threads per row
+// first index of the row maximum (torch.argmax / topk(k=1) tie rule); one workgroup of 256 threads per row.  A thread starts from
+// its own first element, so a row whose maximum is -inf (fully masked logits) yields its first index like any other tie; a thread
+// that owns no element (t >= V) carries (-inf, INT_MAX), which loses every tie.  Rows that hold a NaN are unspecified.
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, long long ld, long long* __restrict__ out,
                                                           long long out_stride, int V) {
   const long long r = blockIdx.x;
   const float* xr = x + r * ld;
   const int t = threadIdx.x;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int j = t; j < V; j += 256) {
+  float best = t < V ? xr[t] : -INFINITY;
+  int bi = t < V ? t : 0x7fffffff;
+  for (int j = t + 256; j < V; j += 256) {
     const float v = xr[j];
     if (v > best) {
       best = v;
