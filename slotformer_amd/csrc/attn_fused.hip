@@ -10,11 +10,6 @@
 // predictor.py:33-44).
 #include "sf_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 constexpr int FA_NT = 512;   // 8 waves: the projection is fill-rate bound, more loads in flight per CU
 // padded sequence length: template parameter ROWS = 64 (two 32-row MFMA blocks) or 128 (four: the 15-frame Physion window, 90 tokens)

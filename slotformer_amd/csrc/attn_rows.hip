@@ -23,13 +23,8 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 #include "layer_fused.h"
+#include "qkv_heads.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int NT = 512;
@@ -42,17 +37,6 @@ constexpr size_t K1_PLANES = (size_t)2 * TRMAX * AP * 2;          // hi | lo pla
 constexpr size_t K1_LDS = K1_PLANES + 2 * D * 4;                  // + gamma | beta
 constexpr size_t K2_LDS = (size_t)2 * 64 * AP * 2;                // O planes [hi, lo][64][AP]
 static_assert(K1_LDS <= 160 * 1024 && K2_LDS <= 160 * 1024, "LDS budget");
-
-__device__ __forceinline__ void split4(__bf16* hp, __bf16* lp, int off, f32x4 v) {
-  const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-  const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
-  *(bf16x4*)(hp + off) = hi;
-  *(bf16x4*)(lp + off) = lo;
-}
-
-// position of key t inside its video's v^T rows: the score accumulators of a 32x32 MFMA hold keys (r & 3) + 8 (r >> 2) + 4 (lane >> 5),
-// and eight consecutive registers are one B fragment of the PV product -- bits 2 and 3 of the key index trade places
-__device__ __forceinline__ int vpos(int t) { return (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1); }
 
 struct RowsArgs {
   const float* xin;
@@ -68,14 +52,6 @@ struct RowsArgs {
   int B, L, Lq, nt, ng, main_blocks;
   int dbg;
 };
-
-// m / L for 0 <= m < 2^22 (one float multiply and two corrections instead of a 32-bit integer division)
-__device__ __forceinline__ int div_rows(int m, int L, float invL) {
-  int q = (int)((float)m * invL);
-  q -= (q * L > m);
-  q += ((q + 1) * L <= m);
-  return q;
-}
 }  // namespace
 
 __device__ long long ar_ts[32];   // phase timestamps of workgroup 0 (SF_DBG=lf=16)
@@ -162,22 +138,14 @@ __device__ __forceinline__ void qkv_rows_body(const RowsArgs& A, const int tile)
     for (int kc = 0; kc < NK; ++kc) {
       const int k = kc * KC + 4 * c4;
       const f32x4 gm = *(const f32x4*)(GB + k), be = *(const f32x4*)(GB + D + k);
-      split4(Ah, Al, r * AP + k, ok ? (vv[kc] - mu) * rs * gm + be : zero4);
+      sf_split4(Ah, Al, r * AP + k, ok ? (vv[kc] - mu) * rs * gm + be : zero4);
     }
   };
   // ---- weight ring: slot = chunk & 3, chunk gc = group index * 8 + (k-step / 2); buffer loads with scalar fragment offsets ----
   bf16x8 ring[4][2][2];
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(A.wqkv_p), 0, 0x7fffffff, 0x00020000);
   const unsigned hpb = (unsigned)(((wave >> 1) * 6 + 3 * (wave & 1)) * 16 * 2048);   // + g * 16 * 2048
-  auto load_chunk = [&](int gc) {
-    const int g = G0 + gc / 8, ks0 = (gc % 8) * 2;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl)
-        ring[gc & 3][k][pl] = __builtin_bit_cast(
-            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (unsigned)(lane * 16), hpb + (unsigned)((g * 16 + ks0 + k) * 2048 + pl * 1024), 0));
-  };
+  auto load_chunk = [&](int gc) { qh_load_chunk(ring, wrs, hpb, G0, gc, lane); };
   const float scale = 1.0f / sqrtf((float)HD);
   const int kg = lane >> 5;
   const int ao = (lane & 31) * AP + 8 * (lane >> 5);
@@ -270,9 +238,9 @@ __device__ __forceinline__ void qkv_rows_body(const RowsArgs& A, const int tile)
 #pragma unroll
           for (int gq = 0; gq < 4; ++gq) {
             const f32x4 bv = bv4[gq];
-            split4(ph, ph + PL, 8 * gq,
-                   f32x4{(acc[rb][4 * gq] + bv[0]) * mul, (acc[rb][4 * gq + 1] + bv[1]) * mul, (acc[rb][4 * gq + 2] + bv[2]) * mul,
-                         (acc[rb][4 * gq + 3] + bv[3]) * mul});
+            sf_split4(ph, ph + PL, 8 * gq,
+                      f32x4{(acc[rb][4 * gq] + bv[0]) * mul, (acc[rb][4 * gq + 1] + bv[1]) * mul, (acc[rb][4 * gq + 2] + bv[2]) * mul,
+                            (acc[rb][4 * gq + 3] + bv[3]) * mul});
           }
         }
       } else {
@@ -443,7 +411,7 @@ __global__ __launch_bounds__(NT) void attn_core_kernel(CoreArgs A) {
     for (int g = 0; g < 4; ++g) {
       f32x4 v = f32x4{oacc[0][4 * g] * f0, oacc[0][4 * g + 1] * f0, oacc[0][4 * g + 2] * f0, oacc[0][4 * g + 3] * f0};
       if (nrb == 2) v += f32x4{oacc[1][4 * g] * f1, oacc[1][4 * g + 1] * f1, oacc[1][4 * g + 2] * f1, oacc[1][4 * g + 3] * f1};
-      split4(Oh, Ol, row * AP + wave * HD + 8 * g + 4 * (lane >> 5), inq ? v : zero4);
+      sf_split4(Oh, Ol, row * AP + wave * HD + 8 * g + 4 * (lane >> 5), inq ? v : zero4);
     }
   }
   __builtin_amdgcn_sched_barrier(0);

@@ -7,28 +7,18 @@
 //     consecutive rows; the second read starts `second` rows further down: 4 for the natural k order 8 kk .. 8 kk + 7).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "split_bf16.h"
 
-typedef __bf16 pl_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 pl_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 pl_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pl_f32x2 __attribute__((ext_vector_type(2)));
-typedef float pl_f32x16 __attribute__((ext_vector_type(16)));
 #define PL_LDS(T, p) ((T __attribute__((address_space(3)))*)(p))
 
 struct PlFrag {
-  pl_bf16x8 h, l;
+  bf16x8 h, l;
 };
-// two f32 -> packed bf16 hi pair and lo pair
-__device__ __forceinline__ void pl_split2(float a, float b, unsigned& hi, unsigned& lo) {
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector((pl_f32x2{a, b}), pl_bf16x2));
-  const float fa = __builtin_bit_cast(float, hi << 16), fb = __builtin_bit_cast(float, hi & 0xffff0000u);
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector((pl_f32x2{a - fa, b - fb}), pl_bf16x2));
-}
 __device__ __forceinline__ PlFrag pl_rd(const char* lds, int hoff, int loff, int pitch, int row0, int k0, int lane) {
   const int o = (row0 + (lane & 31)) * pitch + (k0 + 8 * (lane >> 5)) * 2;
   PlFrag f;
-  f.h = *(const pl_bf16x8*)(lds + hoff + o);
-  f.l = *(const pl_bf16x8*)(lds + loff + o);
+  f.h = *(const bf16x8*)(lds + hoff + o);
+  f.l = *(const bf16x8*)(lds + loff + o);
   return f;
 }
 // kstep: rows per kk half (8 for the natural order: lane half kk holds rows k0 + 8 kk ..; 4 for the accumulator order of a 32x32 block, where half kk
@@ -37,16 +27,16 @@ __device__ __forceinline__ PlFrag pl_rd_tr(const char* lds, int hoff, int loff, 
   const int j = lane & 15, g = lane >> 4, kk = lane >> 5;
   const int o = (k0 + kstep * kk + (j >> 2)) * pitch + (col0 + 16 * (g & 1) + 4 * (j & 3)) * 2;
   PlFrag f;
-  const pl_bf16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(pl_bf16x4, lds + hoff + o));
-  const pl_bf16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(pl_bf16x4, lds + hoff + o + second * pitch));
-  const pl_bf16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(pl_bf16x4, lds + loff + o));
-  const pl_bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(pl_bf16x4, lds + loff + o + second * pitch));
+  const bf16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(bf16x4, lds + hoff + o));
+  const bf16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(bf16x4, lds + hoff + o + second * pitch));
+  const bf16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(bf16x4, lds + loff + o));
+  const bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(PL_LDS(bf16x4, lds + loff + o + second * pitch));
   f.h = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
   f.l = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
   return f;
 }
 // acc += a . b in split-bf16: hi.lo + lo.hi + hi.hi
-__device__ __forceinline__ void pl_mma(pl_f32x16& acc, const PlFrag& a, const PlFrag& b) {
+__device__ __forceinline__ void pl_mma(f32x16& acc, const PlFrag& a, const PlFrag& b) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);

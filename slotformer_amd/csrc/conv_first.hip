@@ -8,11 +8,6 @@
 // produces the 128 x 64 outputs (K = 75 padded to 80: 5 k16-steps x 3 MFMAs).
 #include "sf_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 constexpr int CF_NT = 512, CF_CO = 64, CF_CI = 3, CF_KS = 5, CF_K = CF_CI * CF_KS * CF_KS, CF_KP = 80;   // 75 -> 80
 constexpr int CF_TW = 64, CF_TR = 2;
@@ -26,12 +21,6 @@ struct CfGeo {
   static constexpr size_t lds = (size_t)(CF_CI * HR * HCP + 4) * 4 + (size_t)2 * (CF_TR * CF_TW + CF_CO) * CF_PP * 2;   // (+ four zero floats behind the halo: the padding entries of the patch matrix)
 };
 
-__device__ __forceinline__ void put4(__bf16* hp, __bf16* lp, int off, f32x4 v) {
-  const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-  const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
-  *(bf16x4*)(hp + off) = hi;
-  *(bf16x4*)(lp + off) = lo;
-}
 }  // namespace
 
 // PERSISTENT form (round 6): a workgroup walks tiles (2 output rows of a frame) blockIdx.x, + gridDim.x, ...: the weights are split into their planes ONCE,
@@ -69,7 +58,7 @@ __global__ __launch_bounds__(CF_NT, CF_WPS) void conv_first_kernel(const float* 
       const int k = 4 * k4 + e;
       v[e] = k < CF_K ? w[co * CF_K + k] : 0.f;
     }
-    put4(Wh, Wl, co * CF_PP + 4 * k4, v);
+    sf_split4(Wh, Wl, co * CF_PP + 4 * k4, v);
   }
   // ---- the 20 patch entries of this thread: entry (p, k) = In[c][STRIDE*row + ky][STRIDE*x + kx], k = c*25 + ky*5 + kx ----
   const int p = t & 127, kg = t >> 7;          // pixel, group of 20 k values
@@ -137,7 +126,7 @@ __global__ __launch_bounds__(CF_NT, CF_WPS) void conv_first_kernel(const float* 
       f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = In[(poff[2 * q + (e >> 1)] >> (16 * (e & 1))) & 0xffffu];
-      put4(Ah, Al, p * CF_PP + kg * 20 + 4 * q, v);
+      sf_split4(Ah, Al, p * CF_PP + kg * 20 + 4 * q, v);
     }
     __syncthreads();   // patch planes complete
     // ---- [128 x 80] . [80 x 64]: wave = (row, 32-pixel block, 32-cout block) ----

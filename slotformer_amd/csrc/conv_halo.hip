@@ -14,11 +14,6 @@
 // Reference call site: the encoder convs i > 0, savi.py:231-239 (+ SoftPositionEmbed add, utils.py:60-63).
 #include "sf_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 constexpr int CH = 64, KS = 5, PAD = 2, TW = 64, TR = 2;     // channels, taps, tile width / rows
 constexpr int HR = TR + KS - 1, HWD = TW + KS - 1;           // halo 6 x 68 pixels
@@ -49,13 +44,6 @@ __global__ __launch_bounds__(NT) void conv5x5_halo_kernel(const float* __restric
   const int f = bid / tiles_per_frame, y0 = (bid - f * tiles_per_frame) * TR;
   const float* inf = in + (long long)f * H * TW * CH;
 
-  auto split_store = [&](__bf16* hp, __bf16* lp, int off, f32x4 v) {
-    const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-    const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
-    *(bf16x4*)(hp + off) = hi;
-    *(bf16x4*)(lp + off) = lo;
-  };
-
   // ---- weights of tap 0 (prefetch) -------------------------------------------------------------
   // per tap: 64 cout rows x 64 cin f32 = 1024 float4 -> 2 per thread; w layout [cout][tap][cin]
   const int wc4 = t & 15, wr0 = t >> 4;  // float4 column, cout row (and +32)
@@ -68,7 +56,7 @@ __global__ __launch_bounds__(NT) void conv5x5_halo_kernel(const float* __restric
   };
   auto store_w = [&](int buf, const f32x4(&r)[2]) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) split_store(Wh + buf * WBUF, Wl + buf * WBUF, (wr0 + 32 * i) * PS + 4 * wc4, r[i]);
+    for (int i = 0; i < 2; ++i) sf_split4(Wh + buf * WBUF, Wl + buf * WBUF, (wr0 + 32 * i) * PS + 4 * wc4, r[i]);
   };
 #pragma unroll
   for (int q = 0; q < KS; ++q) load_w(q, wreg[q]);
@@ -92,7 +80,7 @@ __global__ __launch_bounds__(NT) void conv5x5_halo_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int idx = t + NT * i;
-      if (idx < TOTAL) split_store(Hh, Hl, (idx >> 4) * PS + 4 * (idx & 15), hv[i]);
+      if (idx < TOTAL) sf_split4(Hh, Hl, (idx >> 4) * PS + 4 * (idx & 15), hv[i]);
     }
   }
   store_w(0, wreg[0]);

@@ -16,10 +16,6 @@
 #include "sf_internal.h"
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -145,10 +141,7 @@ __device__ __forceinline__ void conv5x5_rows4_body(const float* __restrict__ in,
           *(f16x4*)(Hh + off) = hi;
           *(f16x4*)(Hl + off) = lo;
         } else {
-          const bf16x4 hi = __builtin_convertvector(hv[i], bf16x4);
-          const bf16x4 lo = __builtin_convertvector(hv[i] - __builtin_convertvector(hi, f32x4), bf16x4);
-          *(bf16x4*)(Hh + off) = hi;
-          *(bf16x4*)(Hl + off) = lo;
+          sf_split4(Hh, Hl, off, hv[i]);
         }
       }
     }

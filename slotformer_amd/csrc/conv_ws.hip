@@ -18,11 +18,6 @@
 #include "sf_internal.h"
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 extern "C" int sf_get_conv_fp16x2(void);
 namespace {
 constexpr int CH = 64, KS = 5, TW = 64, NTAP = KS * KS;

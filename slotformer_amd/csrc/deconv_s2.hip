@@ -22,11 +22,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 constexpr int CH = 64, KS = 5, NT = 512;
 constexpr int PS = CH + 8;                                   // bf16 elements per halo pixel (144 B = 9 16-B slots: conflict-free b128)
@@ -163,10 +158,7 @@ __global__ __launch_bounds__(NT) void deconv5x5s2_kernel(const float* __restrict
       const int idx = t + NT * i;
       if (idx < TOTAL) {
         const int off = (idx >> 4) * PS + 4 * (idx & 15);
-        const bf16x4 hi = __builtin_convertvector(hv[i], bf16x4);
-        const bf16x4 lo = __builtin_convertvector(hv[i] - __builtin_convertvector(hi, f32x4), bf16x4);
-        *(bf16x4*)(Hh + off) = hi;
-        *(bf16x4*)(Hl + off) = lo;
+        sf_split4(Hh, Hl, off, hv[i]);
       }
     }
   }

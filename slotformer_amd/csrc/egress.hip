@@ -22,8 +22,6 @@ constexpr int kMaxBoxes = 256;
 constexpr size_t kLdsMax = 64 * 1024;
 
 
-__device__ __forceinline__ float to_rgb(float x) { return fminf(fmaxf(fmaf(x, 0.5f, 0.5f), 0.f), 1.f); }
-
 // v * 255 (one rounding), clamped to [0, 255], cast toward zero or rounded half to even
 __device__ __forceinline__ unsigned quant(float v, int nearest) {
   float s = fminf(fmaxf(__fmul_rn(v, 255.f), 0.f), 255.f);
@@ -31,7 +29,7 @@ __device__ __forceinline__ unsigned quant(float v, int nearest) {
   return (unsigned)(int)s;
 }
 
-__device__ __forceinline__ unsigned frame_byte(float x, int rgb, int nearest) { return quant(rgb ? to_rgb(x) : x, nearest); }
+__device__ __forceinline__ unsigned frame_byte(float x, int rgb, int nearest) { return quant(rgb ? sf_to_rgb(x) : x, nearest); }
 
 // n bytes S[head ..] -> g[0 ..], head = g & 15: aligned 16-byte stores, the ragged ends byte by byte
 __device__ __forceinline__ void lds_to_global(const unsigned char* S, unsigned char* g, int n, int tid) {
@@ -239,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void grid_kernel(GridArgs p) {
             float v[VW];
             load_f32<VW>(a + c * HW, v);
 #pragma unroll
-            for (int j = 0; j < VW; ++j) put(c, x + j, to_rgb(v[j]));
+            for (int j = 0; j < VW; ++j) put(c, x + j, sf_to_rgb(v[j]));
           }
         } else if (tl.kind == SF_EGRESS_SLOTS) {
           const long long tn = (long long)t * tl.N + tl.n;
@@ -253,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void grid_kernel(GridArgs p) {
             float v[VW];
             load_f32<VW>(a + c * HW, v);
 #pragma unroll
-            for (int j = 0; j < VW; ++j) put(c, x + j, to_rgb(__fadd_rn(__fmul_rn(v[j], m[j]), om[j])));
+            for (int j = 0; j < VW; ++j) put(c, x + j, sf_to_rgb(__fadd_rn(__fmul_rn(v[j], m[j]), om[j])));
           }
         } else {
           int id[VW];
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(kThreads) void grid_kernel(GridArgs p) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
               const float col01 = __fdiv_rn((float)pal[id[j] * 3 + c], 255.f);
-              put(c, x + j, to_rgb(__fsub_rn(__fmul_rn(col01, 2.f), 1.f)));
+              put(c, x + j, sf_to_rgb(__fsub_rn(__fmul_rn(col01, 2.f), 1.f)));
             }
           }
         }

@@ -4,8 +4,6 @@
 // mask resize.  gfx950 only.
 #include "sf_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---------------------------------------------------------------------------------------
 // LayerNorm over the last dim, one wave per row (nn.LayerNorm, biased variance).
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, SfRowMap xmap,

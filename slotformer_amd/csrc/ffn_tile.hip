@@ -11,12 +11,8 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 #include "layer_fused.h"
+#include "qkv_heads.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int NT = 512, D = 256, HC = 256, NCH = 4;
@@ -26,13 +22,6 @@ constexpr size_t PLANES = (size_t)2 * ROWS * AP * 2;   // hi | lo planes of 64 r
 constexpr size_t FT_LDS = 2 * PLANES;                  // LN2 planes + hidden planes
 static_assert(FT_LDS <= 160 * 1024, "LDS budget");
 constexpr int RD = 4;                              // weight ring depth in two-k-step chunks: RD - 1 in flight
-
-__device__ __forceinline__ void split4(__bf16* hp, __bf16* lp, int off, f32x4 v) {
-  const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-  const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
-  *(bf16x4*)(hp + off) = hi;
-  *(bf16x4*)(lp + off) = lo;
-}
 
 struct TileArgs {
   const float* x2;          // [M][256] finished rows of the attention block
@@ -97,7 +86,7 @@ __device__ __forceinline__ void ffn_tile_body(const TileArgs& A, f32x4 (&ysum)[2
       rstd[i] = 1.0f / sqrtf(sf_sum64((dv[0] * dv[0] + dv[1] * dv[1]) + (dv[2] * dv[2] + dv[3] * dv[3])) * (1.0f / D) + A.ln_eps);
     }
 #pragma unroll
-    for (int i = 0; i < 8; ++i) split4(Xh, Xl, (wave + 8 * i) * AP + 4 * lane, (xr[i] - mean[i]) * rstd[i] * lng + lnb);
+    for (int i = 0; i < 8; ++i) sf_split4(Xh, Xl, (wave + 8 * i) * AP + 4 * lane, (xr[i] - mean[i]) * rstd[i] * lng + lnb);
   }
   const int tok = lane & 31, kg = lane >> 5, nb = wave * 32 + 4 * kg;
   __syncthreads();   // LN2 planes
@@ -154,8 +143,8 @@ __device__ __forceinline__ void ffn_tile_body(const TileArgs& A, f32x4 (&ysum)[2
         h0[q] = fmaxf(a0[4 * g + q] + bv[q], 0.f);
         h1[q] = fmaxf(a1[4 * g + q] + bv[q], 0.f);
       }
-      split4(Hh, Hl, tok * AP + nb + 8 * g, h0);
-      split4(Hh, Hl, (32 + tok) * AP + nb + 8 * g, h1);
+      sf_split4(Hh, Hl, tok * AP + nb + 8 * g, h0);
+      sf_split4(Hh, Hl, (32 + tok) * AP + nb + 8 * g, h1);
     }
     __syncthreads();   // hidden planes of chunk c
     if (c == 0) FTS(2);
@@ -242,13 +231,6 @@ struct NextArgs {
   float* xpark;                 // [B * Lq][256]: residual rows of the next attention block
   int B, L, Lq;                 // videos, rows per video, query rows per video of the NEXT attention block
 };
-__device__ __forceinline__ int vpos(int t) { return (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1); }
-__device__ __forceinline__ int div_rows(int m, int L, float invL) {
-  int q = (int)((float)m * invL);
-  q -= (q * L > m);
-  q += ((q + 1) * L <= m);
-  return q;
-}
 }  // namespace
 
 __global__ __launch_bounds__(NT) void ffn_qkv_tile_kernel(TileArgs A, NextArgs N) {
@@ -267,15 +249,7 @@ __global__ __launch_bounds__(NT) void ffn_qkv_tile_kernel(TileArgs A, NextArgs N
   bf16x8 ring[4][2][2];
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(N.wqkv_p), 0, 0x7fffffff, 0x00020000);
   const unsigned hpb = (unsigned)(((wave >> 1) * 6 + 3 * (wave & 1)) * 16 * 2048);
-  auto load_chunk = [&](int gc) {
-    const int g = gc / 8, ks0 = (gc % 8) * 2;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl)
-        ring[gc & 3][k][pl] = __builtin_bit_cast(
-            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (unsigned)(lane * 16), hpb + (unsigned)((g * 16 + ks0 + k) * 2048 + pl * 1024), 0));
-  };
+  auto load_chunk = [&](int gc) { qh_load_chunk(ring, wrs, hpb, 0, gc, lane); };
   load_chunk(0);
   load_chunk(1);
   load_chunk(2);
@@ -326,7 +300,7 @@ __global__ __launch_bounds__(NT) void ffn_qkv_tile_kernel(TileArgs A, NextArgs N
       for (int kc = 0; kc < 4; ++kc) {
         const int k = kc * 64 + 4 * c4;
         const f32x4 gm = *(const f32x4*)(GB + k), be = *(const f32x4*)(GB + D + k);
-        split4(Ah, Al, r * AP + k, ok ? (vv[kc] - mu) * rs * gm + be : zero4);
+        sf_split4(Ah, Al, r * AP + k, ok ? (vv[kc] - mu) * rs * gm + be : zero4);
       }
     }
   }
@@ -389,9 +363,9 @@ __global__ __launch_bounds__(NT) void ffn_qkv_tile_kernel(TileArgs A, NextArgs N
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           const f32x4 bv = bv4[gq];
-          split4(ph, ph + PL, 8 * gq,
-                 f32x4{(acc[rb][4 * gq] + bv[0]) * mul, (acc[rb][4 * gq + 1] + bv[1]) * mul, (acc[rb][4 * gq + 2] + bv[2]) * mul,
-                       (acc[rb][4 * gq + 3] + bv[3]) * mul});
+          sf_split4(ph, ph + PL, 8 * gq,
+                    f32x4{(acc[rb][4 * gq] + bv[0]) * mul, (acc[rb][4 * gq + 1] + bv[1]) * mul, (acc[rb][4 * gq + 2] + bv[2]) * mul,
+                          (acc[rb][4 * gq + 3] + bv[3]) * mul});
         }
       } else {
         __bf16* pv = N.planes + ((long long)(b * NH + wave) * 6 + 4) * PL + vpos(tk);

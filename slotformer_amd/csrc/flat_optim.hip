@@ -16,7 +16,6 @@ constexpr int GN_NT = 256;         // threads per workgroup
 constexpr int GN_MAX_GRID = 1024;  // 4 workgroups on each of the 256 CUs; beyond it the threads stride over the bucket
 constexpr size_t GN_HEAD = 16;     // bytes in front of the partials: the arrival counter
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 inline int gn_grid(long long n) {
@@ -25,13 +24,6 @@ inline int gn_grid(long long n) {
 }
 
 __device__ __forceinline__ unsigned gn_bad(float x) { return (__builtin_bit_cast(unsigned, x) & 0x7f800000u) == 0x7f800000u; }   // NaN or +-Inf
-
-// xor butterfly over the wave: every lane ends with the same bits, whatever the lane
-__device__ __forceinline__ double gn_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ws: [0] arrival counter (zero between calls), [GN_HEAD ...) grid x {double sum of squares, u64 non-finite flag}
 __global__ __launch_bounds__(GN_NT) void grad_clip_coef_kernel(const float* __restrict__ g, long long n, float max_norm,
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(GN_NT) void grad_clip_coef_kernel(const float* __re
       bad |= gn_bad(x);
     }
   }
-  sum = gn_wave_sum(sum);
+  sum = sf_wave_sum(sum);
   const bool wbad = __ballot(bad != 0) != 0;
   if (lane == 0) {
     s_sum[wave] = sum;
@@ -96,7 +88,7 @@ __global__ __launch_bounds__(GN_NT) void grad_clip_coef_kernel(const float* __re
       anybad |= __hip_atomic_load(parts + 2 * b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  tot = gn_wave_sum(tot);
+  tot = sf_wave_sum(tot);
   const bool wbad2 = __ballot(anybad != 0) != 0;
   __syncthreads();   // (s_sum / s_bad of the first round have been read)
   if (lane == 0) {

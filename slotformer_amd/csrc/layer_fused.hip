@@ -26,12 +26,6 @@
 #include <type_traits>
 #include <string.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 constexpr int LF_NT = 512;
 constexpr int LF_D = 256, LF_HD = 32, LF_NH = 8;   // model width, head width, heads
@@ -51,12 +45,6 @@ constexpr int FB_AP = LF_D + 8;     // bf16 pitch of the A / H planes (528 B = 3
 constexpr int FB_XP = LF_D + 4;     // f32 pitch of the x2 stash
 constexpr size_t FB_LDS = (size_t)4 * FB_ROWS * FB_AP * 2 + (size_t)FB_ROWS * FB_XP * 4;   // A + H planes, x2 stash
 
-__device__ __forceinline__ void split4(__bf16* hp, __bf16* lp, int off, f32x4 v) {
-  const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-  const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
-  *(bf16x4*)(hp + off) = hi;
-  *(bf16x4*)(lp + off) = lo;
-}
 }  // namespace
 
 __device__ unsigned lf_seam_timeouts;   // seam hand-offs that gave up waiting (sf_seam_timeouts): must stay 0
@@ -315,7 +303,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& A, const int hp, const
     for (int kc = 0; kc < NK; ++kc) {
       const int k = kc * FA_KC + 4 * c4;
       const f32x4 g = *(const f32x4*)(GB + k), be = *(const f32x4*)(GB + LF_D + k);
-      split4(Ah, Al, r * A2_AP + k, ok ? (vv[kc] - mu) * rs * g + be : zero4);
+      sf_split4(Ah, Al, r * A2_AP + k, ok ? (vv[kc] - mu) * rs * g + be : zero4);
     }
   };
   // q|k|v^T = W . LN(x)^T (weights as the MFMA A operand) for token block 0 (SEL 0), token block 1 (SEL 1) or both with the
@@ -482,9 +470,9 @@ __device__ __forceinline__ void attn_body(const AttnArgs& A, const int hp, const
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const f32x4 bv = *(const f32x4*)(GB + 2 * LF_D + wave * 32 + 8 * g + 4 * kg);
-            split4(ph, ph + AT_QPL, tokn * AT_QP + 8 * g + 4 * kg,
-                   f32x4{(acc[rbk][4 * g] + bv[0]) * mul, (acc[rbk][4 * g + 1] + bv[1]) * mul, (acc[rbk][4 * g + 2] + bv[2]) * mul,
-                         (acc[rbk][4 * g + 3] + bv[3]) * mul});
+            sf_split4(ph, ph + AT_QPL, tokn * AT_QP + 8 * g + 4 * kg,
+                      f32x4{(acc[rbk][4 * g] + bv[0]) * mul, (acc[rbk][4 * g + 1] + bv[1]) * mul, (acc[rbk][4 * g + 2] + bv[2]) * mul,
+                            (acc[rbk][4 * g + 3] + bv[3]) * mul});
           }
         } else {
           // v: TRANSPOSED split-bf16 planes [channel][key position].  The swapped-operand projection left token
@@ -567,11 +555,8 @@ __device__ __forceinline__ void attn_body(const AttnArgs& A, const int hp, const
     for (int ks = 0; ks < 2; ++ks) {
       const f32x4 p0 = {sacc[8 * ks], sacc[8 * ks + 1], sacc[8 * ks + 2], sacc[8 * ks + 3]};
       const f32x4 p1 = {sacc[8 * ks + 4], sacc[8 * ks + 5], sacc[8 * ks + 6], sacc[8 * ks + 7]};
-      const bf16x4 h0 = __builtin_convertvector(p0, bf16x4), h1 = __builtin_convertvector(p1, bf16x4);
-      const bf16x4 l0 = __builtin_convertvector(p0 - __builtin_convertvector(h0, f32x4), bf16x4);
-      const bf16x4 l1 = __builtin_convertvector(p1 - __builtin_convertvector(h1, f32x4), bf16x4);
-      const bf16x8 ph = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-      const bf16x8 pl = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+      bf16x8 ph, pl;
+      sf_split8(p0, p1, ph, pl);
       const bf16x8 vh = *(const bf16x8*)(Vh + vo + 16 * ks), vl = *(const bf16x8*)(Vh + AT_VPL + vo + 16 * ks);
       oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, oacc, 0, 0, 0);
       oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, oacc, 0, 0, 0);
@@ -610,7 +595,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& A, const int hp, const
         v = *(const f32x4*)(OT + (w0 * 32 + qq) * QSTR + 4 * q4);
         if (nrb == 2) v += *(const f32x4*)(OT + ((w0 + 1) * 32 + qq) * QSTR + 4 * q4);
       }
-      split4(Oh, Ol, row * A2_OP + h2 * 32 + 4 * q4, v);
+      sf_split4(Oh, Ol, row * A2_OP + h2 * 32 + 4 * q4, v);
     }
   }
   __syncthreads();
@@ -826,7 +811,7 @@ __global__ __launch_bounds__(LF_NT) void attn_all_kernel(AttnArgs A) {
     for (int kc = 0; kc < NK; ++kc) {
       const int k = kc * FA_KC + 4 * c4;
       const f32x4 g = *(const f32x4*)(GB + k), be = *(const f32x4*)(GB + LF_D + k);
-      split4(Ah, Al, r * A2_AP + k, ok ? (vv[kc] - mu) * rs * g + be : zero4);
+      sf_split4(Ah, Al, r * A2_AP + k, ok ? (vv[kc] - mu) * rs * g + be : zero4);
     }
   };
   ln_row(ra[0][0], ra[1][0], ra[2][0], ra[3][0], r0, aok[0]);
@@ -944,9 +929,9 @@ __global__ __launch_bounds__(LF_NT) void attn_all_kernel(AttnArgs A) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
               const f32x4 bv = *(const f32x4*)(bq + 8 * g + 4 * kg);
-              split4(ph, ph + AT_QPL, tokn * AT_QP + 8 * g + 4 * kg,
-                     f32x4{(acc[rbk][4 * g] + bv[0]) * mul, (acc[rbk][4 * g + 1] + bv[1]) * mul, (acc[rbk][4 * g + 2] + bv[2]) * mul,
-                           (acc[rbk][4 * g + 3] + bv[3]) * mul});
+              sf_split4(ph, ph + AT_QPL, tokn * AT_QP + 8 * g + 4 * kg,
+                        f32x4{(acc[rbk][4 * g] + bv[0]) * mul, (acc[rbk][4 * g + 1] + bv[1]) * mul, (acc[rbk][4 * g + 2] + bv[2]) * mul,
+                              (acc[rbk][4 * g + 3] + bv[3]) * mul});
             }
           } else {
             __bf16* vh = Vtp + (hh * 2) * AT_VPL;
@@ -1018,11 +1003,8 @@ __global__ __launch_bounds__(LF_NT) void attn_all_kernel(AttnArgs A) {
       for (int ks = 0; ks < 2; ++ks) {
         const f32x4 p0 = {sacc[8 * ks], sacc[8 * ks + 1], sacc[8 * ks + 2], sacc[8 * ks + 3]};
         const f32x4 p1 = {sacc[8 * ks + 4], sacc[8 * ks + 5], sacc[8 * ks + 6], sacc[8 * ks + 7]};
-        const bf16x4 h0 = __builtin_convertvector(p0, bf16x4), h1 = __builtin_convertvector(p1, bf16x4);
-        const bf16x4 l0 = __builtin_convertvector(p0 - __builtin_convertvector(h0, f32x4), bf16x4);
-        const bf16x4 l1 = __builtin_convertvector(p1 - __builtin_convertvector(h1, f32x4), bf16x4);
-        const bf16x8 ph = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-        const bf16x8 pl = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+        bf16x8 ph, pl;
+        sf_split8(p0, p1, ph, pl);
         const bf16x8 vh = *(const bf16x8*)(Vh + vo + 16 * ks), vl = *(const bf16x8*)(Vh + AT_VPL + vo + 16 * ks);
         oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, oacc, 0, 0, 0);
         oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, oacc, 0, 0, 0);
@@ -1059,7 +1041,7 @@ __global__ __launch_bounds__(LF_NT) void attn_all_kernel(AttnArgs A) {
           v = *(const f32x4*)(OT + (w0 * 32 + qq) * QSTR + 4 * q4);
           if (nrb == 2) v += *(const f32x4*)(OT + ((w0 + 1) * 32 + qq) * QSTR + 4 * q4);
         }
-        split4(Oh, Ol, row * A2_OP + h2 * 32 + 4 * q4, v);
+        sf_split4(Oh, Ol, row * A2_OP + h2 * 32 + 4 * q4, v);
       }
     }
     __syncthreads();
@@ -1219,7 +1201,7 @@ __device__ __forceinline__ void sb_compute(const SbArgs& a, const SbFrags& f, co
       f32x4 v;
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = acc[4 * g + q] + R[(nb1 * 16 + 4 * g + q) * 64 + lane] + f.bo4[g][q];
-      split4(Ph, Pl, tok * SB_PP + c1 + 8 * g, v);
+      sf_split4(Ph, Pl, tok * SB_PP + c1 + 8 * g, v);
       if (m < M) *(f32x4*)(a.slots + mb * a.slots_bs + a.slots_off + (long long)mn * SB_C + c1 + 8 * g) = v;
     }
   }
@@ -1377,7 +1359,7 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& F, const int blk) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = wave + 8 * i;
-      split4(Ah, Al, r * FB_AP + 4 * lane, (x2[i] - mean[i]) * rstd[i] * g + be);
+      sf_split4(Ah, Al, r * FB_AP + 4 * lane, (x2[i] - mean[i]) * rstd[i] * g + be);
       if (carry) *(f32x4*)(X2 + r * FB_XP + 4 * lane) = x2[i];
     }
   }
@@ -1413,7 +1395,7 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& F, const int blk) {
     f32x4 hv;
 #pragma unroll
     for (int q = 0; q < 4; ++q) hv[q] = fmaxf(acc[4 * g + q] + bv[q], 0.f);
-    split4(Hh, Hl, tok * FB_AP + nb + 8 * g, hv);
+    sf_split4(Hh, Hl, tok * FB_AP + nb + 8 * g, hv);
   }
   __syncthreads();
   LF_TS(4);
@@ -1499,7 +1481,7 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& F, const int blk) {
       // out-proj -> slots and in-proj -> ring, by this workgroup alone (s_last is uniform: barriers are safe)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        split4(Ah, Al, (wave + 8 * i) * FB_AP + 4 * lane, ((oth[0][i] + oth[1][i]) + oth[2][i]) + oth[3][i]);
+        sf_split4(Ah, Al, (wave + 8 * i) * FB_AP + 4 * lane, ((oth[0][i] + oth[1][i]) + oth[2][i]) + oth[3][i]);
       __syncthreads();
       sb_compute(sb, sbf, Ah, Al, (float*)Hh, Hh + 4 * 16 * 64 * 2, Hh + 4 * 16 * 64 * 2 + 32 * SB_PP, row0, M, lane, wave);
       if (sb.seam_flags) {
@@ -1587,7 +1569,7 @@ __global__ __launch_bounds__(LF_NT) void step_boundary_kernel(const float* __res
       const int idx = t + LF_NT * i, r = idx >> 5, q4 = idx & 31;
       const int gm = min(row0 + r, M - 1), gb = gm / sb.nslots, gn = gm - gb * sb.nslots;
       const f32x4 v = *(const f32x4*)(sb.slots + gb * sb.slots_bs + sb.slots_off + (long long)gn * SB_C + 4 * q4);
-      split4(Ph, Pl, r * SB_PP + 4 * q4, v);
+      sf_split4(Ph, Pl, r * SB_PP + 4 * q4, v);
     }
     __syncthreads();
     const int tok = lane & 31, c2 = wave * 32 + 4 * (lane >> 5);
@@ -1618,7 +1600,7 @@ __global__ __launch_bounds__(LF_NT) void step_boundary_kernel(const float* __res
   for (int i = 0; i < 4; ++i) {
     const int r = wave + 8 * i;
     const f32x4 v = *(const f32x4*)(y + (long long)min(row0 + r, M - 1) * LF_D + 4 * lane);
-    split4(Yh, Yl, r * SB_YP + 4 * lane, v);
+    sf_split4(Yh, Yl, r * SB_YP + 4 * lane, v);
   }
   __syncthreads();
   sb_compute(sb, f, Yh, Yl, R, Ph, Pl, row0, M, lane, wave);
@@ -1719,7 +1701,7 @@ __global__ __launch_bounds__(LF_NT) void ffn_wide_parts_kernel(FfnArgs F) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = 32 * (q & 1) + wave + 8 * i;
-      split4(Ph, Ph + F6_ROWS * FB_AP, r * FB_AP + 4 * lane, (x2[i] - mean[i]) * rstd[i] * lng + lnb);
+      sf_split4(Ph, Ph + F6_ROWS * FB_AP, r * FB_AP + 4 * lane, (x2[i] - mean[i]) * rstd[i] * lng + lnb);
       // chunk 0 carries the residual and the bias (ffn_body's rule): parked in this thread's own output float4
       if (c == 0 && row0 + 32 * q + wave + 8 * i < M)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x2[i] + b2v), xpr, rowoff(32 * q + wave + 8 * i), xps, 0);
@@ -1772,8 +1754,8 @@ __global__ __launch_bounds__(LF_NT) void ffn_wide_parts_kernel(FfnArgs F) {
         h0[q] = fmaxf(a0[4 * g + q] + bv[q], 0.f);
         h1[q] = fmaxf(a1[4 * g + q] + bv[q], 0.f);
       }
-      split4(Hh, Hh + F6_ROWS * FB_AP, tok * FB_AP + nb + 8 * g, h0);
-      split4(Hh, Hh + F6_ROWS * FB_AP, (32 + tok) * FB_AP + nb + 8 * g, h1);
+      sf_split4(Hh, Hh + F6_ROWS * FB_AP, tok * FB_AP + nb + 8 * g, h0);
+      sf_split4(Hh, Hh + F6_ROWS * FB_AP, (32 + tok) * FB_AP + nb + 8 * g, h1);
     }
   };
   f32x16 acc0, acc1;

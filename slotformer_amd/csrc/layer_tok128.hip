@@ -192,28 +192,28 @@ __global__ __launch_bounds__(LS_NT) void layer_tok128_kernel(LsArgs A) {
       sm[s] += s0 + s1;
     };
     auto psplit_chunk = [&](int s, int c) {
-      split8(quad(S[s][c >> 1], 2 * (c & 1)), quad(S[s][c >> 1], 2 * (c & 1) + 1), ph[s][c >> 1][c & 1], pl[s][c >> 1][c & 1]);
+      sf_split8(quad(S[s][c >> 1], 2 * (c & 1)), quad(S[s][c >> 1], 2 * (c & 1) + 1), ph[s][c >> 1][c & 1], pl[s][c >> 1][c & 1]);
     };
     auto kconv = [&](int s) {
       const float* bk = (const float*)pb + Q_BQKV + LS_D + 32 * hp;
       bf16x8 fh, fl;
-      split8(quad(ka, 2 * s) + *(const f32x4*)(bk + 16 * s), quad(ka, 2 * s + 1) + *(const f32x4*)(bk + 16 * s + 8), fh, fl);
+      sf_split8(quad(ka, 2 * s) + *(const f32x4*)(bk + 16 * s), quad(ka, 2 * s + 1) + *(const f32x4*)(bk + 16 * s + 8), fh, fl);
       *(bf16x8*)(kwr + (s * 2) * 4096) = fh;
       *(bf16x8*)(kwr + (s * 2 + 1) * 4096) = fl;
     };
     auto qconv = [&](int s) {
       const float* bq = (const float*)pb + Q_BQKV + 32 * hp;
-      split8((quad(qa, 2 * s) + *(const f32x4*)(bq + 16 * s)) * qscale, (quad(qa, 2 * s + 1) + *(const f32x4*)(bq + 16 * s + 8)) * qscale, qh[s], ql[s]);
+      sf_split8((quad(qa, 2 * s) + *(const f32x4*)(bq + 16 * s)) * qscale, (quad(qa, 2 * s + 1) + *(const f32x4*)(bq + 16 * s + 8)) * qscale, qh[s], ql[s]);
     };
     auto vconv = [&](int s) {   // lane = dim of the pair, registers 8 s .. 8 s + 7 = keys of the block's k-step s
       const float bv = P[Q_BQKV + 2 * LS_D + 32 * hp + n];
       bf16x8 fh, fl;
-      split8(quad(va, 2 * s) + bv, quad(va, 2 * s + 1) + bv, fh, fl);
+      sf_split8(quad(va, 2 * s) + bv, quad(va, 2 * s + 1) + bv, fh, fl);
       *(bf16x8*)(vwr + (s * 2) * 1024) = fh;
       *(bf16x8*)(vwr + (s * 2 + 1) * 1024) = fl;
     };
     // registers 8 s .. 8 s + 7 of O = dims of head s, from the product with head s's probabilities
-    auto oconv = [&](int s) { split8(quad(O, 2 * s) * rinv[s], quad(O, 2 * s + 1) * rinv[s], oh[s], ol[s]); };
+    auto oconv = [&](int s) { sf_split8(quad(O, 2 * s) * rinv[s], quad(O, 2 * s + 1) * rinv[s], oh[s], ol[s]); };
     // scores of the previous pair: S^T[key][query] = K Q^T per head (ONE k-step: fragment s of K and of q) for the wave's three key blocks
     auto scores = [&]() {
 #pragma unroll
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(LS_NT) void layer_tok128_kernel(LsArgs A) {
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
       const f32x4 u0 = __builtin_elementwise_max(quad(Hx, 2 * s) + b1q[2 * s], z4);
       const f32x4 u1 = __builtin_elementwise_max(quad(Hx, 2 * s + 1) + b1q[2 * s + 1], z4);
-      split8(u0, u1, hh[s], hl[s]);
+      sf_split8(u0, u1, hh[s], hl[s]);
     };
     // one step = [W1_j: first product of block j into Hn | bias / ReLU / split of block j - 1 (Hp)] + [W2_{j-1}: second product of block j - 1]
     auto ffn_step = [&](f32x16& Hn, const f32x16& Hp, int j) {

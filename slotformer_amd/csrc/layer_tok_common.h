@@ -5,21 +5,8 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 __device__ __forceinline__ bf16x8 cat8(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
-// eight f32 -> hi | lo bf16 fragments
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, bf16x8& hi, bf16x8& lo) {
-  const bf16x4 h0 = __builtin_convertvector(a, bf16x4), h1 = __builtin_convertvector(b, bf16x4);
-  const bf16x4 l0 = __builtin_convertvector(a - __builtin_convertvector(h0, f32x4), bf16x4);
-  const bf16x4 l1 = __builtin_convertvector(b - __builtin_convertvector(h1, f32x4), bf16x4);
-  hi = cat8(h0, h1);
-  lo = cat8(l0, l1);
-}
 __device__ __forceinline__ f32x4 quad(const f32x16& a, int g) { return f32x4{a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]}; }
 // the value of the lane that holds the other half of this token's features / keys (lane ^ 32): one v_permlane32_swap, no LDS.  (The instruction swaps the
 // upper half of its first operand with the lower half of its second; whether the compiler gives the two copies of `v` one register or two, the partner's
@@ -265,7 +252,7 @@ __device__ __forceinline__ void lt_layernorm(const f32x16 (&X)[NOB], const char*
         const int g = 2 * s2i + gg, c = 32 * ob + 8 * g;
         v[gg] = (quad(X[ob], g) - mu) * rs * *(const f32x4*)(pb + (GOFF + c) * 4) + *(const f32x4*)(pb + (BOFF + c) * 4);
       }
-      split8(v[0], v[1], xh[2 * ob + s2i], xl[2 * ob + s2i]);
+      sf_split8(v[0], v[1], xh[2 * ob + s2i], xl[2 * ob + s2i]);
       __builtin_amdgcn_sched_barrier(0);   // (left alone the scheduler requests all 64 gamma / beta vectors first: 200 spilled registers)
     }
 }

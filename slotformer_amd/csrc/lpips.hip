@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     py[s] = rem / W;
     px[s] = rem - py[s] * W;
   }
-  pl_f32x16 acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -198,14 +198,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
           a = in_hi[off[s] + (long long)(2 * cc) * P];
           b = in_lo[off[s] + (long long)(2 * cc) * P];
         }
-        xf[s].h = __builtin_bit_cast(pl_bf16x8, a);
-        xf[s].l = __builtin_bit_cast(pl_bf16x8, b);
+        xf[s].h = __builtin_bit_cast(bf16x8, a);
+        xf[s].l = __builtin_bit_cast(bf16x8, b);
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const long long wi = wbase + ((long long)t * KS + cc) * 64;
-        wf[t].h = __builtin_bit_cast(pl_bf16x8, w_hi[wi]);
-        wf[t].l = __builtin_bit_cast(pl_bf16x8, w_lo[wi]);
+        wf[t].h = __builtin_bit_cast(bf16x8, w_hi[wi]);
+        wf[t].l = __builtin_bit_cast(bf16x8, w_lo[wi]);
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t)

@@ -13,11 +13,6 @@
 #include "slot_chain.h"
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // the per-pixel chain in its pixel-stationary form (pixel_feat_tok_kernel below): process default; sf_set_pixel_tok(0): the tile kernels
 static int g_pixel_tok = 1;
 extern "C" int sf_get_pixel_tok(void) { return g_pixel_tok; }
@@ -320,7 +315,7 @@ __global__ __launch_bounds__(PW_NT) void pixel_mlp_feat192_kernel(const float* _
   f32x4 xr[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) xr[i] = *(const f32x4*)(x + (long long)min(m0 + r0 + 32 * i, M - 1) * PW_C0 + 4 * c4);
-  PsBuf s;
+  PsRing<3> s;
   constexpr int KS1 = PW_C0 / 16, KS2 = PW_C1 / 16;
   if (wave < PW_NB) ps_prime<PsChunk<KS1>::CH>(s, w1p, PW_NB, wave, 0, lane);
 #pragma unroll
@@ -333,7 +328,7 @@ __global__ __launch_bounds__(PW_NT) void pixel_mlp_feat192_kernel(const float* _
     const f32x4 dv = xr[i] - mean;
     const float vs = sf_sum16((dv[0] * dv[0] + dv[1] * dv[1]) + (dv[2] * dv[2] + dv[3] * dv[3]));
     const float rstd = 1.0f / sqrtf(vs * (1.0f / PW_C0) + eps);
-    ps_split4(Ph, Pl, (r0 + 32 * i) * PW_KP + 4 * c4, dv * rstd * g0 + be0);
+    sf_split4(Ph, Pl, (r0 + 32 * i) * PW_KP + 4 * c4, dv * rstd * g0 + be0);
   }
   __syncthreads();
   f32x16 acc[4];
@@ -353,7 +348,7 @@ __global__ __launch_bounds__(PW_NT) void pixel_mlp_feat192_kernel(const float* _
       for (int g = 0; g < 4; ++g) {
         const int n = 32 * wave + 8 * g + 4 * kg;
         const f32x4 bv = *(const f32x4*)(PV + n);
-        ps_split4(Ph, Pl, (32 * rb + tok) * PW_KP + n,
+        sf_split4(Ph, Pl, (32 * rb + tok) * PW_KP + n,
                   f32x4{fmaxf(acc[rb][4 * g] + bv[0], 0.f), fmaxf(acc[rb][4 * g + 1] + bv[1], 0.f), fmaxf(acc[rb][4 * g + 2] + bv[2], 0.f),
                         fmaxf(acc[rb][4 * g + 3] + bv[3], 0.f)});
       }
@@ -755,13 +750,6 @@ __global__ __launch_bounds__(PT_NT) void pixel_feat_tok_kernel(const float* __re
     const float o = other(v);
     return h ? o + v : v + o;   // (lower half first in both lanes: the two halves of a pixel get the same bits)
   };
-  auto split8 = [](const f32x4 a, const f32x4 b, bf16x8& hi, bf16x8& lo) {
-    const bf16x4 h0 = __builtin_convertvector(a, bf16x4), h1 = __builtin_convertvector(b, bf16x4);
-    const bf16x4 l0 = __builtin_convertvector(a - __builtin_convertvector(h0, f32x4), bf16x4);
-    const bf16x4 l1 = __builtin_convertvector(b - __builtin_convertvector(h1, f32x4), bf16x4);
-    hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-    lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
   const char* wl = pt_lds + lane * 16;
   // tile = 32 pixels; consecutive tiles go to consecutive WAVES (a workgroup covers 256 consecutive pixels per round: its stores fill whole rows together)
   const long long ntile = ((long long)M + 31) / 32, tstep = (long long)gridDim.x * (PT_NT / 64);
@@ -805,8 +793,8 @@ __global__ __launch_bounds__(PT_NT) void pixel_feat_tok_kernel(const float* __re
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int c = 32 * h + 8 * ks;
-      split8(xv[2 * ks] * rstd * *(const f32x4*)(PV + PV_G0 + c) + *(const f32x4*)(PV + PV_B0 + c),
-             xv[2 * ks + 1] * rstd * *(const f32x4*)(PV + PV_G0 + c + 4) + *(const f32x4*)(PV + PV_B0 + c + 4), xh[ks], xl[ks]);
+      sf_split8(xv[2 * ks] * rstd * *(const f32x4*)(PV + PV_G0 + c) + *(const f32x4*)(PV + PV_B0 + c),
+                xv[2 * ks + 1] * rstd * *(const f32x4*)(PV + PV_G0 + c + 4) + *(const f32x4*)(PV + PV_B0 + c + 4), xh[ks], xl[ks]);
     }
     // ---- fc1 + b1 + ReLU: hidden block blk -> the two virtual k-steps (blk, s) of fc2 ----
     bf16x8 hh[8], hl[8];
@@ -845,7 +833,7 @@ __global__ __launch_bounds__(PT_NT) void pixel_feat_tok_kernel(const float* __re
 #pragma unroll
             for (int q = 0; q < 4; ++q) u[gg][q] = fmaxf(acc[e][4 * g + q] + bb[q], 0.f);
           }
-          split8(u[0], u[1], hh[2 * blk + sx], hl[2 * blk + sx]);
+          sf_split8(u[0], u[1], hh[2 * blk + sx], hl[2 * blk + sx]);
         }
       }
     }
@@ -912,7 +900,7 @@ __global__ __launch_bounds__(PT_NT) void pixel_feat_tok_kernel(const float* __re
         if (live) {
           if constexpr (PLANES) {
             bf16x8 yh, yl;
-            split8(y[0], y[1], yh, yl);
+            sf_split8(y[0], y[1], yh, yl);
             __bf16* pr = (__bf16*)out + pix * (2 * PM_C1);
             *(bf16x8*)(pr + c0) = yh;
             *(bf16x8*)(pr + PM_C1 + c0) = yl;

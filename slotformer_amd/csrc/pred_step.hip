@@ -77,7 +77,7 @@ __global__ __launch_bounds__(PS_NT) void pred_step_kernel(PsArgs a) {
   const int nrows = min(RW, R - row0);                  // real rows of this workgroup
   const int ur = t >> 4, c4 = t & 15;                   // thread = (row, 16 threads per row)
   const int urc = min(ur, nrows - 1);
-  PsBuf s;
+  PsRing<3> s;
   const bool lstm = a.wih != nullptr;
 
   // first fragments of the first product, then the rows
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(PS_NT) void pred_step_kernel(PsArgs a) {
     }
     const float rs = 1.0f / sqrtf(sf_sum16(vs) / (float)D + a.eps);
 #pragma unroll
-    for (int i = 0; i < NQ; ++i) ps_split4(Ph, Pl, ur * KP + 4 * (c4 + 16 * i), v[i] * rs * gg[i] + bb[i]);
+    for (int i = 0; i < NQ; ++i) sf_split4(Ph, Pl, ur * KP + 4 * (c4 + 16 * i), v[i] * rs * gg[i] + bb[i]);
   };
 
   ln_fetch(a.layer[0].n1g, a.layer[0].n1b);
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(PS_NT) void pred_step_kernel(PsArgs a) {
         for (int i = 0; i < CPT / 4; ++i) o[i] += sc[j] * *(const f32x4*)(QKV + jr * QP + 2 * D + co + 4 * i);
       }
 #pragma unroll
-      for (int i = 0; i < CPT / 4; ++i) ps_split4(Ph, Pl, ur * KP + co + 4 * i, o[i] * inv);
+      for (int i = 0; i < CPT / 4; ++i) sf_split4(Ph, Pl, ur * KP + co + 4 * i, o[i] * inv);
     }
     __syncthreads();
     // ---- x += Wo O + bo (waves < D / 32: one column block each); the others request their first lin1 fragments ----
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(PS_NT) void pred_step_kernel(PsArgs a) {
                                                KP, lane);
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            ps_split4(Hh, Hl, tok * HP + 32 * j + 8 * g + 4 * kg,
+            sf_split4(Hh, Hl, tok * HP + 32 * j + 8 * g + 4 * kg,
                       f32x4{fmaxf(acc[4 * g] + bv[g][0], 0.f), fmaxf(acc[4 * g + 1] + bv[g][1], 0.f), fmaxf(acc[4 * g + 2] + bv[g][2], 0.f),
                             fmaxf(acc[4 * g + 3] + bv[g][3], 0.f)});
         }
@@ -294,10 +294,10 @@ __global__ __launch_bounds__(PS_NT) void pred_step_kernel(PsArgs a) {
 
   // ---- LSTM step: the predictor output and the previous state as planes ----
 #pragma unroll
-  for (int i = 0; i < NQ; ++i) ps_split4(Ph, Pl, ur * KP + 4 * (c4 + 16 * i), *(const f32x4*)(XF + ur * XP + 4 * (c4 + 16 * i)));
+  for (int i = 0; i < NQ; ++i) sf_split4(Ph, Pl, ur * KP + 4 * (c4 + 16 * i), *(const f32x4*)(XF + ur * XP + 4 * (c4 + 16 * i)));
   {
     const float* hs = a.h + (long long)(row0 + urc) * H;
-    for (int i = c4; i < H / 4; i += 16) ps_split4(Sh, Sl, ur * SP + 4 * i, *(const f32x4*)(hs + 4 * i));
+    for (int i = c4; i < H / 4; i += 16) sf_split4(Sh, Sl, ur * SP + 4 * i, *(const f32x4*)(hs + 4 * i));
   }
   __syncthreads();
   // wave = hidden block jb: the four gate blocks (i, f, g, o: rows jb, H/32 + jb, ...) of W_ih (K = D) and W_hh (K = H)
@@ -353,25 +353,25 @@ __global__ __launch_bounds__(PS_NT) void pred_step_kernel(PsArgs a) {
         const int cc = 32 * jb + 8 * g + 4 * kg;
         if (q == 0) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) ig[4 * g + e] = ps_sigmoid(acc[4 * g + e] + bq[g][e]);
+          for (int e = 0; e < 4; ++e) ig[4 * g + e] = sf_sigmoid_fast(acc[4 * g + e] + bq[g][e]);
         } else if (q == 2) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) ig[4 * g + e] *= ps_tanh(acc[4 * g + e] + bq[g][e]);
+          for (int e = 0; e < 4; ++e) ig[4 * g + e] *= sf_tanh_fast(acc[4 * g + e] + bq[g][e]);
         } else if (q == 1) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) cn[4 * g + e] = ps_sigmoid(acc[4 * g + e] + bq[g][e]) * cp[g][e] + ig[4 * g + e];
+          for (int e = 0; e < 4; ++e) cn[4 * g + e] = sf_sigmoid_fast(acc[4 * g + e] + bq[g][e]) * cp[g][e] + ig[4 * g + e];
         } else {
           f32x4 hn, cv;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             cv[e] = cn[4 * g + e];
-            hn[e] = ps_sigmoid(acc[4 * g + e] + bq[g][e]) * ps_tanh(cv[e]);
+            hn[e] = sf_sigmoid_fast(acc[4 * g + e] + bq[g][e]) * sf_tanh_fast(cv[e]);
           }
           if (tok < nrows) {
             *(f32x4*)(a.c + (long long)grow * H + cc) = cv;
             *(f32x4*)(a.h + (long long)grow * H + cc) = hn;
           }
-          ps_split4(Nh, Nl, tok * SP + cc, hn);
+          sf_split4(Nh, Nl, tok * SP + cc, hn);
         }
       }
     }

@@ -23,10 +23,6 @@
 #include "sf_internal.h"
 #include "bf16_planes.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // ---------------------------------------------------------------------------------------------------------------------
 // dropout mask
 // ---------------------------------------------------------------------------------------------------------------------
@@ -270,16 +266,6 @@ __global__ __launch_bounds__(256) void attn_train_bwd_kernel(const float* __rest
 // 96 tokens: every product (q k^T, P v, g v^T, Pd^T g, dS k, dS^T q) is a set of 32x32 output tiles whose operands are
 // read from zero-padded LDS tiles through (row, k) -> address functors, one tile per wave at a time.
 // ---------------------------------------------------------------------------------------------------------------------
-template <class FA, class FB>
-__device__ __forceinline__ f32x16 mm32(FA a, FB b, int K, int lane) {
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  const int i0 = lane & 31, kk = lane >> 5;
-  for (int k = 0; k < K; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a(i0, k + kk), b(k + kk, i0), acc, 0, 0, 0);
-  return acc;
-}
-#define MM_ROW(r, lane) (((r) & 3) + 8 * ((r) >> 2) + 4 * ((lane) >> 5))
 
 // load q (scaled), k, v [L, HD] of (video b, head h) into zero-padded [Lp][HD + 1] tiles
 template <int HD>
@@ -314,7 +300,7 @@ __device__ __forceinline__ void attn_probs_mfma(const float* q, const float* k, 
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int t = wave; t < nt * nt; t += 4) {
     const int ti = (t / nt) * 32, tj = (t % nt) * 32;
-    const f32x16 acc = mm32([&](int i, int kk) { return q[(ti + i) * HP + kk]; },
+    const f32x16 acc = sf_mm32<false>([&](int i, int kk) { return q[(ti + i) * HP + kk]; },
                             [&](int kk, int j) { return k[(tj + j) * HP + kk]; }, HD, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r) P[(ti + MM_ROW(r, lane)) * lp + tj + (lane & 31)] = acc[r];
@@ -368,7 +354,7 @@ __global__ __launch_bounds__(256) void attn_train_fwd_mfma_kernel(const float* _
   const int Le = (L + 1) & ~1;
   for (int t = wave; t < nt * (HD / 32); t += 4) {
     const int ti = (t / (HD / 32)) * 32, tj = (t % (HD / 32)) * 32;
-    const f32x16 acc = mm32([&](int i, int kk) { return P[(ti + i) * lp + kk]; },
+    const f32x16 acc = sf_mm32<false>([&](int i, int kk) { return P[(ti + i) * lp + kk]; },
                             [&](int kk, int j) { return v[kk * HP + tj + j]; }, Le, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -412,14 +398,14 @@ __global__ __launch_bounds__(256) void attn_train_bwd_mfma_kernel(const float* _
     const int t = wave + 4 * n;
     if (t < nt * nt) {
       const int ti = (t / nt) * 32, tj = (t % nt) * 32;
-      dp[n] = mm32([&](int i, int kk) { return g[(ti + i) * HP + kk]; }, [&](int kk, int j) { return v[(tj + j) * HP + kk]; }, HD,
+      dp[n] = sf_mm32<false>([&](int i, int kk) { return g[(ti + i) * HP + kk]; }, [&](int kk, int j) { return v[(tj + j) * HP + kk]; }, HD,
                    lane);
     }
   }
   // dV = Pd^T g
   for (int t = wave; t < nt * HT; t += 4) {
     const int ti = (t / HT) * 32, tj = (t % HT) * 32;
-    const f32x16 acc = mm32([&](int i, int kk) { return dS[kk * lp + ti + i]; },
+    const f32x16 acc = sf_mm32<false>([&](int i, int kk) { return dS[kk * lp + ti + i]; },
                             [&](int kk, int j) { return g[kk * HP + tj + j]; }, Le, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -458,10 +444,10 @@ __global__ __launch_bounds__(256) void attn_train_bwd_mfma_kernel(const float* _
     const int ti = (tt / HT) * 32, tj = (tt % HT) * 32;
     f32x16 acc;
     if (!isk)
-      acc = mm32([&](int i, int kk) { return dS[(ti + i) * lp + kk]; }, [&](int kk, int j) { return k[kk * HP + tj + j]; }, Le,
+      acc = sf_mm32<false>([&](int i, int kk) { return dS[(ti + i) * lp + kk]; }, [&](int kk, int j) { return k[kk * HP + tj + j]; }, Le,
                  lane);
     else
-      acc = mm32([&](int i, int kk) { return dS[kk * lp + ti + i]; }, [&](int kk, int j) { return q[kk * HP + tj + j]; }, Le,
+      acc = sf_mm32<false>([&](int i, int kk) { return dS[kk * lp + ti + i]; }, [&](int kk, int j) { return q[kk * HP + tj + j]; }, Le,
                  lane);
     const float sc = isk ? 1.f : scale;
 #pragma unroll
@@ -751,11 +737,6 @@ inline void launch_reduce_partials(const float* partial, float* out, int G, long
 // grid (N/64 * K/64, splits): split z handles rows [z*rps, (z+1)*rps) and writes partial[z][N][K].
 // ---------------------------------------------------------------------------------------------------------------------
 #define TN_P 68
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void tn_split8(const f32x8 v, bf16x8& hi, bf16x8& lo) {
-  hi = __builtin_convertvector(v, bf16x8);
-  lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x8), bf16x8);
-}
 // The 32-row chunk of both operands lives in LDS as bf16 hi / lo PLANES (bf16_planes.h; every element split once, where it is staged, instead of once per
 // wave that reads it): the contraction index is the tile's ROW index, so the operand fragments come out through ds_read_b64_tr_b16 -- two transposing
 // reads per plane and k16 step instead of eight scalar reads + a conversion chain.  Row pitch 192 bytes: the four rows x two 16-column groups a
@@ -791,13 +772,12 @@ __global__ __launch_bounds__(256) void grad_gemm_tn_kernel(const float* __restri
     py1 = *reinterpret_cast<const float4*>(Yb + (long long)(lr + 16) * N);
     px1 = *reinterpret_cast<const float4*>(Xb + (long long)(lr + 16) * K);
   }
-  typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
   auto stage = [&](const float4 v, int hoff, int loff, int row) {
     unsigned h0, l0, h1, l1;
     pl_split2(v.x, v.y, h0, l0);
     pl_split2(v.z, v.w, h1, l1);
-    *(u32x2_*)(tsm + hoff + row * TN_PB + lc * 2) = u32x2_{h0, h1};
-    if (MODE != 2) *(u32x2_*)(tsm + loff + row * TN_PB + lc * 2) = u32x2_{l0, l1};
+    *(u32x2*)(tsm + hoff + row * TN_PB + lc * 2) = u32x2{h0, h1};
+    if (MODE != 2) *(u32x2*)(tsm + loff + row * TN_PB + lc * 2) = u32x2{l0, l1};
   };
   for (int rb = 0; rb < nrows; rb += 32) {
     __syncthreads();

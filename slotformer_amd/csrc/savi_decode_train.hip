@@ -10,8 +10,6 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // d_dec [F*N, HW, 4] from d_recon [F, 3, HW]:  d_rgb_n = m_n d_recon;  d_alpha_n = m_n (rgb_n.d_recon - sum_k m_k rgb_k.d_recon)
 __global__ __launch_bounds__(256) void decode_combine_bwd_kernel(const float* __restrict__ dec, const float* __restrict__ d_recon,
                                                                  float* __restrict__ d_dec, int F, int N, int HW) {

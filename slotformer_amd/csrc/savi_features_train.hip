@@ -12,16 +12,7 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define CW_P 68
-__device__ __forceinline__ void cw_split8(const f32x8 v, bf16x8& hi, bf16x8& lo) {
-  hi = __builtin_convertvector(v, bf16x8);
-  lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x8), bf16x8);
-}
 
 // dW[n][tap][k] = sum over pixels (f, y, x) of A[f, y, x, n] * X[f, y*s + dy, x*s + dx, k]:  A [rows, CA] lives on an H x W
 // grid, X [*, 64] on an Hx x Wx grid, (dy, dx) = tap - ks/2, zero outside the image.
@@ -92,14 +83,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
 #pragma unroll
       for (int j = 0; j < 8; ++j) a[j] = Ys[ro + j * CW_P + wn + (lane & 31)];
       bf16x8 ah, al;
-      cw_split8(a, ah, al);
+      sf_split8(a, ah, al);
 #pragma unroll
       for (int t = 0; t < KS; ++t) {
         f32x8 b;
 #pragma unroll
         for (int j = 0; j < 8; ++j) b[j] = Xs[t][ro + j * CW_P + wk + (lane & 31)];
         bf16x8 bh, bl;
-        cw_split8(b, bh, bl);
+        sf_split8(b, bh, bl);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
         if (MODE != 2) {
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[t], 0, 0, 0);
@@ -183,14 +174,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_win_kernel(const float* __rest
 #pragma unroll
       for (int j = 0; j < 8; ++j) a[j] = Ys[(m0 + j) * CW_P + wn + (lane & 31)];
       bf16x8 ah, al;
-      cw_split8(a, ah, al);
+      sf_split8(a, ah, al);
 #pragma unroll
       for (int t = 0; t < KS; ++t) {
         f32x8 b;
 #pragma unroll
         for (int j = 0; j < 8; ++j) b[j] = Xw[((m0 + j) * S + t) * CW_P + wk + (lane & 31)];
         bf16x8 bh, bl;
-        cw_split8(b, bh, bl);
+        sf_split8(b, bh, bl);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
         if (MODE != 2) {
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[t], 0, 0, 0);

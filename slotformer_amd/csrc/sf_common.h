@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include "split_bf16.h"
 
 #define SF_WAVE 64
 
@@ -120,4 +121,13 @@ __device__ __forceinline__ float sf_wave_max(float v) {
                fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48))));
 }
 
+// the same in double, as an xor butterfly: every lane ends with the same bits, whatever the lane
+__device__ __forceinline__ double sf_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 __device__ __forceinline__ float sf_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+// [-1, 1] -> [0, 1], clamped (one fma whatever the file's contraction setting)
+__device__ __forceinline__ float sf_to_rgb(float x) { return fminf(fmaxf(fmaf(x, 0.5f, 0.5f), 0.f), 1.f); }

@@ -13,47 +13,12 @@
 #include "sf_internal.h"
 #include "bf16_planes.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// one 32x32 output tile, C[i][j] = sum_k a(i, k) b(k, j), operands read from LDS through the functors.
-// BF3 = false: exact-f32 MFMA (32x32x2, 64 cycles per 2 k).  BF3 = true (library precision modes 1 / 2): the operands are
-// split into bf16 hi + lo on the fly and contracted as hi*hi + hi*lo + lo*hi on the 32x32x16 bf16 MFMA -- 5x less
-// matrix-pipe time per k, which is what bounds these kernels (K must then be a multiple of 16).
-template <bool BF3, class FA, class FB>
-__device__ __forceinline__ f32x16 sab_mm32(FA a, FB b, int K, int lane) {
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  const int i0 = lane & 31, kk = lane >> 5;
-  if constexpr (BF3) {
-    for (int k = 0; k < K; k += 16) {
-      f32x8 av, bv;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        av[j] = a(i0, k + 8 * kk + j);
-        bv[j] = b(k + 8 * kk + j, i0);
-      }
-      const bf16x8 ah = __builtin_convertvector(av, bf16x8), bh = __builtin_convertvector(bv, bf16x8);
-      const bf16x8 al = __builtin_convertvector(av - __builtin_convertvector(ah, f32x8), bf16x8);
-      const bf16x8 bl = __builtin_convertvector(bv - __builtin_convertvector(bh, f32x8), bf16x8);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-    }
-  } else {
-    for (int k = 0; k < K; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a(i0, k + kk), b(k + kk, i0), acc, 0, 0, 0);
-  }
-  return acc;
-}
 // both operands k-contiguous in LDS (rows 16-byte aligned): A[i][k] at arow + i * pa, B[j][k] at brow + j * pb -- two ds_read_b128
 // per operand per k16 step instead of eight scalar reads
 template <bool BF3>
 __device__ __forceinline__ f32x16 sab_mm32_kk(const float* A, int pa, const float* Bm, int pb, int K, int lane) {
   if constexpr (!BF3) {
-    return sab_mm32<false>([&](int i, int k) { return A[i * pa + k]; }, [&](int k, int j) { return Bm[j * pb + k]; }, K, lane);
+    return sf_mm32<false>([&](int i, int k) { return A[i * pa + k]; }, [&](int k, int j) { return Bm[j * pb + k]; }, K, lane);
   } else {
     f32x16 acc;
 #pragma unroll
@@ -259,9 +224,9 @@ __global__ __launch_bounds__(256) void slate_attn_bwd_kernel(SabArgs p, int hd) 
     // dV_j += P^T dO_i ; dK_j += dS^T (Q_i * scale)   (contraction over the 64 queries)
     if (at < 2 * CT) {
       // tiles 0 .. 2*CT-1 cover [64 keys][HDP]; ati = key offset, atj = channel offset
-      const f32x16 a1 = sab_mm32<BF3>([&](int i, int kk) { return Ps[kk * 68 + ati + i]; }, [&](int kk, int j) { return Gs[kk * P + atj + j]; }, 64,
+      const f32x16 a1 = sf_mm32<BF3>([&](int i, int kk) { return Ps[kk * 68 + ati + i]; }, [&](int kk, int j) { return Gs[kk * P + atj + j]; }, 64,
                                  lane);
-      const f32x16 a2 = sab_mm32<BF3>([&](int i, int kk) { return Ds[kk * 68 + ati + i]; }, [&](int kk, int j) { return Qs[kk * P + atj + j]; }, 64,
+      const f32x16 a2 = sf_mm32<BF3>([&](int i, int kk) { return Ds[kk * 68 + ati + i]; }, [&](int kk, int j) { return Qs[kk * P + atj + j]; }, 64,
                                  lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -272,7 +237,7 @@ __global__ __launch_bounds__(256) void slate_attn_bwd_kernel(SabArgs p, int hd) 
     // dQ_i += scale * dS K_j  (tiles over [64 queries][HDP]; atomics: several key blocks add into the same rows)
     for (int t = wave; t < 2 * CT; t += 4) {
       const int qi0 = (t / CT) * 32, c0 = (t % CT) * 32;
-      const f32x16 a3 = sab_mm32<BF3>([&](int i, int kk) { return Ds[(qi0 + i) * 68 + kk]; }, [&](int kk, int j) { return Ks[kk * P + c0 + j]; }, 64,
+      const f32x16 a3 = sf_mm32<BF3>([&](int i, int kk) { return Ds[(qi0 + i) * 68 + kk]; }, [&](int kk, int j) { return Ks[kk * P + c0 + j]; }, 64,
                                  lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -314,15 +279,13 @@ __device__ __forceinline__ void sab_frag_load(const float* base, int ld, int row
     a = (rok && c < hd) ? a : z;
     b = (rok && c + 4 < hd) ? b : z;
     const f32x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    f.h[s] = __builtin_convertvector(v, bf16x8);
-    f.l[s] = __builtin_convertvector(v - __builtin_convertvector(f.h[s], f32x8), bf16x8);
+    sf_split8(v, f.h[s], f.l[s]);
   }
 }
 // Every LDS tile of this kernel holds its elements ALREADY split: one 32-bit word = bf16 hi (upper half) | bf16 lo (lower half),
 // produced once where the element is written.  An operand fragment is then 8 words -> two v_perm_b32 per word pair instead of
 // the ~24 conversion instructions per fragment that the f32 tiles cost every time a wave read them (30 fragments per block
 // pair and wave: the conversions were the largest share of this kernel's issue slots).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned sab_pack1(float v) {
   const __bf16 h = (__bf16)v;
   const __bf16 l = (__bf16)(v - (float)h);
@@ -487,7 +450,6 @@ __global__ __launch_bounds__(256, 2) void slate_attn_bwd48_kernel(SabArgs p, int
 //  * K_j's fragments for S (B operand, contraction over channels) and for dQ (B operand, contraction over keys) and V_j's for dP live in registers.
 // No conversion, no v_perm and no scalar LDS read in the loop: ~650 instructions per query block and wave instead of ~1650 (54 MFMAs either way).
 // exp runs in base 2 (Q' = Q scale log2(e), LSE' = LSE log2(e); dK is multiplied by ln 2 at the end).  65.5 KB of LDS: two workgroups per CU.
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 namespace {
 constexpr int V2_QP = 112, V2_TP = 144;          // row pitches in BYTES: query-major tiles [64][56 bf16], key-major tiles [64][72 bf16]
 constexpr int V2_QT = 64 * V2_QP, V2_TT = 64 * V2_TP;
@@ -731,7 +693,7 @@ __global__ __launch_bounds__(256) void slate_attn_fwd_train_kernel(SabArgs p, fl
     }
     __syncthreads();
     if (at < 2 * CT) {
-      const f32x16 a = sab_mm32<BF3>([&](int i, int kk) { return Ss[(ati + i) * 68 + kk]; }, [&](int kk, int j) { return Vs[kk * P + atj + j]; }, 64,
+      const f32x16 a = sf_mm32<BF3>([&](int i, int kk) { return Ss[(ati + i) * 68 + kk]; }, [&](int kk, int j) { return Vs[kk * P + atj + j]; }, 64,
                                 lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) oacc[r] = oacc[r] * rs[ati + SAB_ROW(r, lane)] + a[r];

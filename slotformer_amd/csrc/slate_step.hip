@@ -10,8 +10,6 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 constexpr int ST_NT = 1024;          // threads per workgroup
 constexpr int ST_NW = ST_NT / 64;    // waves

@@ -20,22 +20,6 @@
 #define SA_HMAX 512
 
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-
-// full 64-lane sum, result in every lane
-__device__ __forceinline__ float wave_allsum(float v) {
-  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);  // row_half_mirror
-  v += dpp_mov<0x140>(v);  // row_mirror
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
 template <int VPT, int NS = SA_NMAX>
 __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
     const float* __restrict__ k, const float* __restrict__ v, int ld, long long batch_stride,
@@ -88,7 +72,7 @@ __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
       }
 #pragma unroll
       for (int n = 0; n < NS; ++n)
-        if (n < N) s[n] = wave_allsum(s[n]);
+        if (n < N) s[n] = sf_group_sum<64>(s[n]);
       float mx = s[0];
 #pragma unroll
       for (int n = 1; n < NS; ++n)
@@ -150,17 +134,15 @@ __global__ __launch_bounds__(256) void sa_attn_partial_kernel(
 //            product per wave: v_mfma_f32_16x16x4_f32 with V loaded straight into A-operand
 //            layout (lane i owns the DB = D/16 consecutive channels DB*i .. DB*i+DB-1, so a
 //            wave reads whole 512/768-B rows) and the attention tile as B operand from LDS.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // KT = float: f32 K/V rows (the product path).  KT = __bf16 (sf_slot_attn_iter_bf16): K/V STORED as bf16 -- half the HBM
 // bytes of this HBM-bound kernel -- widened to f32 when loaded; all arithmetic stays f32.
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 template <typename KT>
-__device__ __forceinline__ f32x4v sa_load4(const KT* p) {
+__device__ __forceinline__ f32x4 sa_load4(const KT* p) {
   if constexpr (sizeof(KT) == 4) {
-    return *(const f32x4v*)p;
+    return *(const f32x4*)p;
   } else {
-    return __builtin_convertvector(*(const bf16x4v*)p, f32x4v);
+    return __builtin_convertvector(*(const bf16x4*)p, f32x4);
   }
 }
 
@@ -202,7 +184,7 @@ __global__ __launch_bounds__(256, (NS > SA_NMAX && D <= 128 ? 2 : 1)) void sa_at
   // per SIMD leave 256) -- instead of one slab ahead: the four dependent round trips of phase 1 (~2 us each from HBM) were most of a
   // workgroup's ~19 us, and a workgroup's latency IS the launch time (one round of workgroups on the whole chip, two on a 128-CU mask)
   constexpr int NSL = D / 32, PF = D <= 128 ? NSL : 1;   // (wider slots: one slab ahead as before -- the tile would not fit the registers)
-  f32x4v nx[PF][8];
+  f32x4 nx[PF][8];
 #pragma unroll
   for (int c = 0; c < PF; ++c)
 #pragma unroll
@@ -211,21 +193,21 @@ __global__ __launch_bounds__(256, (NS > SA_NMAX && D <= 128 ? 2 : 1)) void sa_at
   for (int sl = 0; sl < NSL; ++sl) {
     const int d0 = 32 * sl;
 #pragma unroll
-    for (int u = 0; u < 8; ++u) *(f32x4v*)&s_k[wave][(lane >> 3) + 8 * u][4 * (lane & 7)] = nx[sl % PF][u];
+    for (int u = 0; u < 8; ++u) *(f32x4*)&s_k[wave][(lane >> 3) + 8 * u][4 * (lane & 7)] = nx[sl % PF][u];
     if (sl + PF < NSL) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) nx[sl % PF][u] = sa_load4<KT>(kslab + (long long)(8 * u) * ld + d0 + 32 * PF);
     }
     __builtin_amdgcn_wave_barrier();
-    f32x4v kx[8];
+    f32x4 kx[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) kx[u] = *(const f32x4v*)&s_k[wave][lane][4 * u];
+    for (int u = 0; u < 8; ++u) kx[u] = *(const f32x4*)&s_k[wave][lane][4 * u];
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
 #pragma unroll
       for (int n = 0; n < NS; ++n) {
-        const f32x4v qq = *(const f32x4v*)(&s_q[n][d0 + 4 * u]);
+        const f32x4 qq = *(const f32x4*)(&s_q[n][d0 + 4 * u]);
         s[n] = fmaf(kx[u][0], qq[0], s[n]);
         s[n] = fmaf(kx[u][1], qq[1], s[n]);
         s[n] = fmaf(kx[u][2], qq[2], s[n]);
@@ -256,10 +238,9 @@ __global__ __launch_bounds__(256, (NS > SA_NMAX && D <= 128 ? 2 : 1)) void sa_at
   __builtin_amdgcn_wave_barrier();
 
   // ---- phase 2: num^T[d, n] += V^T . A on the f32 MFMA ------------------------------------------
-  typedef float f32x4a __attribute__((ext_vector_type(4)));
-  f32x4a acc[DB];
+  f32x4 acc[DB];
 #pragma unroll
-  for (int j = 0; j < DB; ++j) acc[j] = f32x4a{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < DB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int li = lane & 15, lk = lane >> 4;  // A: row i = li (channels DB*li..), k = lk (pixel in group of 4)
   const KT* vbase = v + (long long)b * batch_stride + (long long)(pix0 + lk) * ld + DB * li;
   // (round 4) the 16 k-steps fully unrolled: every V row of the wave is requested before the first MFMA needs one (DB / 4 16-byte loads
@@ -268,7 +249,7 @@ __global__ __launch_bounds__(256, (NS > SA_NMAX && D <= 128 ? 2 : 1)) void sa_at
   constexpr int PFV = D <= 128 ? 16 : 4;
 #pragma unroll
   for (int k0 = 0; k0 < 16; k0 += PFV) {
-    f32x4v vq[PFV][DB / 4];
+    f32x4 vq[PFV][DB / 4];
 #pragma unroll
     for (int ks = 0; ks < PFV; ++ks)
 #pragma unroll
@@ -380,7 +361,7 @@ __device__ __forceinline__ void su_col_dot(const float* __restrict__ w, int ldw,
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
-      const f32x4v x0 = *(const f32x4v*)(x + (k + u) * SU_R), x1 = *(const f32x4v*)(x + (k + u) * SU_R + 4);
+      const f32x4 x0 = *(const f32x4*)(x + (k + u) * SU_R), x1 = *(const f32x4*)(x + (k + u) * SU_R + 4);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         acc[r] = fmaf(wv[u], x0[r], acc[r]);
@@ -814,43 +795,42 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int pix0 = chunk * (NW * NT4 * TP) + wave * NT4 * TP;
   const int li = lane & 15, lg = lane >> 4;
-  typedef float f32x4a __attribute__((ext_vector_type(4)));
   static_assert(D == 128, "sa_attn_tile_kernel: D = 128 (two whole rows per load instruction)");
   // ---- rows: instruction u of a tile brings rows 2 u and 2 u + 1 whole (lane & 31 = the 16-byte column); two tiles requested at once ----
   const float* xs = x + (long long)b * batch_stride + (long long)(pix0 + (lane >> 5)) * ld + 4 * (lane & 31);
   float* tile = s_x + wave * TP * XP;
-  f32x4v stage[8];   // (one tile ahead: with two stages in flight the kernel spilled at 128 registers -- four waves per SIMD are what two workgroups per CU need)
+  f32x4 stage[8];   // (one tile ahead: with two stages in flight the kernel spilled at 128 registers -- four waves per SIMD are what two workgroups per CU need)
 #pragma unroll
-  for (int u = 0; u < 8; ++u) stage[u] = *(const f32x4v*)(xs + (long long)(2 * u) * ld);
+  for (int u = 0; u < 8; ++u) stage[u] = *(const f32x4*)(xs + (long long)(2 * u) * ld);
   for (int idx = threadIdx.x; idx < NS * D; idx += 512) {
     const int n = idx / D, d = idx - n * D;
     s_q[idx] = n < N ? q[((long long)b * N + n) * D + d] * scale : 0.f;
   }
   __syncthreads();
   SATS(1);
-  f32x4a nacc[NH][4];
+  f32x4 nacc[NH][4];
 #pragma unroll
   for (int h = 0; h < NH; ++h)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) nacc[h][e] = f32x4a{0.f, 0.f, 0.f, 0.f};
+    for (int e = 0; e < 4; ++e) nacc[h][e] = f32x4{0.f, 0.f, 0.f, 0.f};
   float den = 0.f;
   float* at = s_a + wave * TP * 17;
 #pragma unroll 1
   for (int ti = 0; ti < NT4; ++ti) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) *(f32x4v*)(tile + (2 * u + (lane >> 5)) * XP + 4 * (lane & 31)) = stage[u];
+    for (int u = 0; u < 8; ++u) *(f32x4*)(tile + (2 * u + (lane >> 5)) * XP + 4 * (lane & 31)) = stage[u];
     if (ti + 1 < NT4) {   // the stage is free: the rows of the next tile, in flight while this one is multiplied
 #pragma unroll
-      for (int u = 0; u < 8; ++u) stage[u] = *(const f32x4v*)(xs + (long long)(TP * (ti + 1) + 2 * u) * ld);
+      for (int u = 0; u < 8; ++u) stage[u] = *(const f32x4*)(xs + (long long)(TP * (ti + 1) + 2 * u) * ld);
     }
     __builtin_amdgcn_wave_barrier();
     // ---- logits[pixel][slot]: A = tile rows (i = li: pixel, k = lg), B (k = lg, j = li: slot) = the scaled queries from LDS (zero beyond NS) ----
-    f32x4a acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int sl = 0; sl < NSLAB; ++sl) {
-      const f32x4v xa = *(const f32x4v*)(tile + li * XP + 16 * sl + 4 * lg);
-      f32x4v qb = *(const f32x4v*)(s_q + (li & (NS - 1)) * D + 16 * sl + 4 * lg);
-      if (li >= NS) qb = f32x4v{0.f, 0.f, 0.f, 0.f};
+      const f32x4 xa = *(const f32x4*)(tile + li * XP + 16 * sl + 4 * lg);
+      f32x4 qb = *(const f32x4*)(s_q + (li & (NS - 1)) * D + 16 * sl + 4 * lg);
+      if (li >= NS) qb = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], qb[e], acc, 0, 0, 0);
     }
@@ -878,7 +858,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       const float aop = at[(4 * ks + lg) * 17 + li];
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
-        const f32x4v xb = *(const f32x4v*)(tile + (4 * ks + lg) * XP + 64 * h + 4 * li);
+        const f32x4 xb = *(const f32x4*)(tile + (4 * ks + lg) * XP + 64 * h + 4 * li);
 #pragma unroll
         for (int e = 0; e < 4; ++e) nacc[h][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(aop, xb[e], nacc[h][e], 0, 0, 0);
       }
@@ -896,10 +876,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
-        f32x4v o;
+        f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = nacc[h][e][r];
-        *(f32x4v*)(s_red + (wave * NS + 4 * lg + r) * XP + 64 * h + 4 * li) = o;
+        *(f32x4*)(s_red + (wave * NS + 4 * lg + r) * XP + 64 * h + 4 * li) = o;
       }
   }
   if (lg == 0 && li < NS) s_red[(wave * NS + li) * XP + D] = den;

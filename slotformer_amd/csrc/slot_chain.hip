@@ -18,8 +18,6 @@
 #include "slot_update_body.h"
 #include "slot_chain.h"
 
-typedef unsigned int u32x4c __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int SC_D = 128, SC_NT = 512, SC_NW = 8, SC_TP = 32;          // slot size, threads, waves, pixels per tile
@@ -39,13 +37,6 @@ static_assert(SC_LDS <= 160 * 1024, "slot chain: LDS budget");
 // 16-byte chunk position of (row, chunk) inside a 256-byte plane row
 __device__ __forceinline__ int sc_swz(int row) { return 2 * ((row & 3) | (((row >> 3) & 1) << 2)); }
 
-__device__ __forceinline__ void sc_split8(const f32x4 a, const f32x4 b, bf16x8& hi, bf16x8& lo) {
-  const bf16x4 h0 = __builtin_convertvector(a, bf16x4), h1 = __builtin_convertvector(b, bf16x4);
-  const bf16x4 l0 = __builtin_convertvector(a - __builtin_convertvector(h0, f32x4), bf16x4);
-  const bf16x4 l1 = __builtin_convertvector(b - __builtin_convertvector(h1, f32x4), bf16x4);
-  hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-  lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 #define SC_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 
 #ifdef SC_STAMPS
@@ -77,7 +68,7 @@ __device__ __forceinline__ void sc_attend_core(const __bf16* __restrict__ frame,
   //      starts with the rows the first one read last (the ones still in this XCD's L2) ----
   // (explicit address spaces: inside a non-inlined function the pointers are generic, and FLAT loads count on lgkmcnt as well -- every LDS wait of the
   //  tile loop then waited for the rows in flight: 2.2 us per tile whatever the prefetch depth)
-  typedef const u32x4c __attribute__((address_space(1))) * gvec;
+  typedef const u32x4 __attribute__((address_space(1))) * gvec;
   typedef float __attribute__((address_space(3))) * lflt;
   typedef f32x4 __attribute__((address_space(3))) * lvec;
   // (a non-inlined function receives even uniform arguments in vector registers: the frame base back into scalar registers, so that a load is
@@ -89,7 +80,7 @@ __device__ __forceinline__ void sc_attend_core(const __bf16* __restrict__ frame,
   const lflt qL = (lflt)qg, pnL = (lflt)pnum, pdL = (lflt)pden;
   auto tile_at = [&](int k) { return rev ? ntiles - 1 - k : k; };
   const char __attribute__((address_space(1)))* src = (const char __attribute__((address_space(1)))*)fb;
-  u32x4c stage[16];
+  u32x4 stage[16];
 #pragma unroll
   for (int u = 0; u < 16; ++u) stage[u] = *(gvec)(src + (long long)tile_at(0) * (SC_TP * 512) + (voff + u * 1024));
   typedef char __attribute__((address_space(3))) * lchr;
@@ -119,7 +110,7 @@ __device__ __forceinline__ void sc_attend_core(const __bf16* __restrict__ frame,
           b = *(lvec)(qL + qo + 4) * s2;
         }
       }
-      sc_split8(a, b, qh[ks], ql[ks]);
+      sf_split8(a, b, qh[ks], ql[ks]);
     }
   }
   // per-lane LDS offsets.  Tile write: lane = (row within the pair l >> 5, 16-byte chunk c = l & 31 of the 512-byte row: plane c >> 4, chunk c & 15)
@@ -158,7 +149,7 @@ __device__ __forceinline__ void sc_attend_core(const __bf16* __restrict__ frame,
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int row = 2 * u + wrow;
-      *(u32x4c __attribute__((address_space(3)))*)(tileL + wplane * 8192 + row * 256 + ((wchunk ^ sc_swz(row)) << 4)) = stage[u];
+      *(u32x4 __attribute__((address_space(3)))*)(tileL + wplane * 8192 + row * 256 + ((wchunk ^ sc_swz(row)) << 4)) = stage[u];
     }
 #ifndef SC_NOLOAD
     if (k + 1 < ntiles) {
@@ -214,7 +205,7 @@ __device__ __forceinline__ void sc_attend_core(const __bf16* __restrict__ frame,
         a0[e2] = atL[(8 * kb + e2) * SC_ATP + i16];
         a1[e2] = atL[(8 * kb + 4 + e2) * SC_ATP + i16];
       }
-      sc_split8(a0, a1, ath, atl);
+      sf_split8(a0, a1, ath, atl);
     }
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) {

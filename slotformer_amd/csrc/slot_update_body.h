@@ -3,12 +3,6 @@
 #pragma once
 #include "sf_internal.h"
 
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #ifdef UM_STAMPS
 __device__ long long um_ts[16];
 #define UMTS(i) do { if (block == 0 && threadIdx.x == 0) um_ts[i] = wall_clock64(); } while (0)
@@ -30,26 +24,6 @@ constexpr int UV_BIH = 0, UV_BHH = 3 * UM_D, UV_LNG = 6 * UM_D, UV_LNB = 7 * UM_
 constexpr int UV_PG = UM_NV, UV_PBT = UV_PG + UM_D, UV_PB0 = UV_PBT + UM_D, UV_PB2 = UV_PB0 + UM_H, UV_KB = UV_PB2 + UM_D, UM_NV_NEXT = UV_KB + 2 * UM_D;
 constexpr int UM_KP = 2 * UM_D + 8;   // f32 pitch of the kernel-distribution rows (they take the place of the hidden planes)
 static_assert(UM_H == 2 * UM_D && UM_NV == 1664 && UM_NV_NEXT == 5 * 512, "parameter-vector staging");
-
-__device__ __forceinline__ void um_split4(__bf16* hp, __bf16* lp, int off, f32x4 v) {
-  const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-  const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
-  *(bf16x4*)(hp + off) = hi;
-  *(bf16x4*)(lp + off) = lo;
-}
-
-// sigmoid / tanh on the hardware exponential (v_exp_f32, ~1 ulp): the gate arithmetic of 32 x 128 elements runs on four waves, and
-// the libm forms took 5.6 us of a 20 us kernel; their error is far below the split-bf16 products feeding them
-__device__ __forceinline__ float um_sigmoid(float x) { return __frcp_rn(1.0f + __expf(-x)); }
-__device__ __forceinline__ float um_tanh(float x) { return 1.0f - 2.0f * __frcp_rn(__expf(2.0f * x) + 1.0f); }
-
-// fragment (ks, nb, plane) of a packed [N][K] matrix (pack_linear_kernel, layer_fused.hip): 64 lanes x 16 B
-// (an explicitly GLOBAL load: where the body runs inside a non-inlined function -- slot_chain.hip -- the pointer is generic, and a flat load counts on
-//  lgkmcnt as well: every LDS wait of the update would wait for the weight stream)
-__device__ __forceinline__ bf16x8 um_frag(const uint4* p, int nblocks, int nb, int ks, int pl, int lane) {
-  typedef const uint4 __attribute__((address_space(1))) * gptr;
-  return __builtin_bit_cast(bf16x8, ((gptr)p)[((long long)(ks * nblocks + nb) * 2 + pl) * 64 + lane]);
-}
 
 template <int NKS>
 struct UmFrags {
@@ -259,10 +233,10 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
     float den = 0.f;
     for (int p = 0; p < rv.P; ++p) den += DN[ur * 64 + p];
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    um_split4(Uh, Ul, ur * UM_DP + uc, rok ? n0 / den : zero4);
-    um_split4(Uh, Ul, ur * UM_DP + uc + 4, rok ? n1 / den : zero4);
-    um_split4(Xh, Xl, ur * UM_DP + uc, rok ? h0 : zero4);
-    um_split4(Xh, Xl, ur * UM_DP + uc + 4, rok ? h1 : zero4);
+    sf_split4(Uh, Ul, ur * UM_DP + uc, rok ? n0 / den : zero4);
+    sf_split4(Uh, Ul, ur * UM_DP + uc + 4, rok ? n1 / den : zero4);
+    sf_split4(Xh, Xl, ur * UM_DP + uc, rok ? h0 : zero4);
+    sf_split4(Xh, Xl, ur * UM_DP + uc + 4, rok ? h1 : zero4);
     *(f32x4*)(Fp + ur * UM_FP + uc) = rok ? h0 : zero4;
     *(f32x4*)(Fp + ur * UM_FP + uc + 4) = rok ? h1 : zero4;
   }
@@ -289,7 +263,7 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
       const f32x4 bz = *(const f32x4*)(PV + UV_BIH + UM_D + c) + *(const f32x4*)(PV + UV_BHH + UM_D + c), bn = *(const f32x4*)(PV + UV_BHH + 2 * UM_D + c);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        EX[((cb * 2 + 0) * 16 + 4 * g + q) * 64 + lane] = um_sigmoid(g1[4 * g + q] + bz[q]);
+        EX[((cb * 2 + 0) * 16 + 4 * g + q) * 64 + lane] = sf_sigmoid_fast(g1[4 * g + q] + bz[q]);
         EX[((cb * 2 + 1) * 16 + 4 * g + q) * 64 + lane] = g2[4 * g + q] + bn[q];
       }
     }
@@ -301,7 +275,7 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
       const int c = 32 * cb + 8 * g + 4 * kg;
       const f32x4 br = *(const f32x4*)(PV + UV_BIH + c) + *(const f32x4*)(PV + UV_BHH + c);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) g1[4 * g + q] = um_sigmoid(g1[4 * g + q] + br[q]);
+      for (int q = 0; q < 4; ++q) g1[4 * g + q] = sf_sigmoid_fast(g1[4 * g + q] + br[q]);
     }
   }
   __syncthreads();
@@ -316,7 +290,7 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
       for (int q = 0; q < 4; ++q) {
         const float rr = g1[4 * g + q];
         const float z = EX[((cb * 2 + 0) * 16 + 4 * g + q) * 64 + lane], ghn = EX[((cb * 2 + 1) * 16 + 4 * g + q) * 64 + lane];
-        const float nn = um_tanh(g2[4 * g + q] + bn[q] + rr * ghn);
+        const float nn = sf_tanh_fast(g2[4 * g + q] + bn[q] + rr * ghn);
         hn[q] = (1.f - z) * nn + z * hp[q];
       }
       *(f32x4*)(Fn + tok * UM_FP + c) = hn;
@@ -336,8 +310,8 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
     const float var = sf_sum16(((d0[0] * d0[0] + d0[1] * d0[1]) + (d0[2] * d0[2] + d0[3] * d0[3])) +
                                ((d1[0] * d1[0] + d1[1] * d1[1]) + (d1[2] * d1[2] + d1[3] * d1[3]))) / (float)UM_D;
     const float rs = 1.0f / sqrtf(var + a.ln_eps);
-    um_split4(Xh, Xl, ur * UM_DP + uc, d0 * rs * *(const f32x4*)(PV + UV_LNG + uc) + *(const f32x4*)(PV + UV_LNB + uc));
-    um_split4(Xh, Xl, ur * UM_DP + uc + 4, d1 * rs * *(const f32x4*)(PV + UV_LNG + uc + 4) + *(const f32x4*)(PV + UV_LNB + uc + 4));
+    sf_split4(Xh, Xl, ur * UM_DP + uc, d0 * rs * *(const f32x4*)(PV + UV_LNG + uc) + *(const f32x4*)(PV + UV_LNB + uc));
+    sf_split4(Xh, Xl, ur * UM_DP + uc + 4, d1 * rs * *(const f32x4*)(PV + UV_LNG + uc + 4) + *(const f32x4*)(PV + UV_LNB + uc + 4));
   }
   __syncthreads();
 
@@ -352,7 +326,7 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
     const f32x4 bb = *(const f32x4*)(PV + UV_B1 + c);
     const f32x4 hv = {fmaxf(g1[4 * g] + bb[0], 0.f), fmaxf(g1[4 * g + 1] + bb[1], 0.f), fmaxf(g1[4 * g + 2] + bb[2], 0.f),
                       fmaxf(g1[4 * g + 3] + bb[3], 0.f)};
-    um_split4(Hh, Hl, tok * UM_HP + c, hv);
+    sf_split4(Hh, Hl, tok * UM_HP + c, hv);
   }
   __syncthreads();
 
@@ -410,8 +384,8 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
       const float rs = 1.0f / sqrtf(var + a.ln_eps);
       const f32x4 y0 = d0 * rs * *(const f32x4*)(PV + UV_PG + uc) + *(const f32x4*)(PV + UV_PBT + uc);
       const f32x4 y1 = d1 * rs * *(const f32x4*)(PV + UV_PG + uc + 4) + *(const f32x4*)(PV + UV_PBT + uc + 4);
-      um_split4(Xh, Xl, ur * UM_DP + uc, y0);
-      um_split4(Xh, Xl, ur * UM_DP + uc + 4, y1);
+      sf_split4(Xh, Xl, ur * UM_DP + uc, y0);
+      sf_split4(Xh, Xl, ur * UM_DP + uc + 4, y1);
       *(f32x4*)(Fn + ur * UM_FP + uc) = a.pm_norm_first ? y0 : v0;
       *(f32x4*)(Fn + ur * UM_FP + uc + 4) = a.pm_norm_first ? y1 : v1;
     }
@@ -427,7 +401,7 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
       const f32x4 bb = *(const f32x4*)(PV + UV_PB0 + c);
       const f32x4 hv = {fmaxf(g1[4 * g] + bb[0], 0.f), fmaxf(g1[4 * g + 1] + bb[1], 0.f), fmaxf(g1[4 * g + 2] + bb[2], 0.f),
                         fmaxf(g1[4 * g + 3] + bb[3], 0.f)};
-      um_split4(Hh, Hl, tok * UM_HP + c, hv);
+      sf_split4(Hh, Hl, tok * UM_HP + c, hv);
     }
     __syncthreads();
     // ---- lat = residual + W2 hidden + b2: wave = (block, K half), halves meet in LDS; lat -> X planes ----
@@ -447,7 +421,7 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
         f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = (g2[4 * g + q] + EX[(cb * 2 * 16 + 4 * g + q) * 64 + lane]) + bb[q] + res[q];
-        um_split4(Xh, Xl, tok * UM_DP + c, v);
+        sf_split4(Xh, Xl, tok * UM_DP + c, v);
       }
     }
     __syncthreads();
@@ -499,8 +473,8 @@ __device__ __forceinline__ void um_rows(const ArgsT& a, const VarT& rv, float* u
     const float var = sf_sum16(((d0[0] * d0[0] + d0[1] * d0[1]) + (d0[2] * d0[2] + d0[3] * d0[3])) +
                                ((d1[0] * d1[0] + d1[1] * d1[1]) + (d1[2] * d1[2] + d1[3] * d1[3]))) / (float)UM_D;
     const float rs = 1.0f / sqrtf(var + a.ln_eps);
-    um_split4(Xh, Xl, ur * UM_DP + uc, d0 * rs * *(const f32x4*)(PV + UV_QG + uc) + *(const f32x4*)(PV + UV_QB + uc));
-    um_split4(Xh, Xl, ur * UM_DP + uc + 4, d1 * rs * *(const f32x4*)(PV + UV_QG + uc + 4) + *(const f32x4*)(PV + UV_QB + uc + 4));
+    sf_split4(Xh, Xl, ur * UM_DP + uc, d0 * rs * *(const f32x4*)(PV + UV_QG + uc) + *(const f32x4*)(PV + UV_QB + uc));
+    sf_split4(Xh, Xl, ur * UM_DP + uc + 4, d1 * rs * *(const f32x4*)(PV + UV_QG + uc + 4) + *(const f32x4*)(PV + UV_QB + uc + 4));
   }
   __syncthreads();
 #pragma unroll

@@ -79,46 +79,17 @@ __device__ __forceinline__ void uw_layernorm(const float* F, __bf16* Xh, __bf16*
   const float rs = 1.0f / sqrtf(sf_sum16(q) / (float)UW_D + eps);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
-    ps_split4(Xh, Xl, r * UW_DP + c + 4 * i, d[i] * rs * *(const f32x4*)(g + c + 4 * i) + *(const f32x4*)(b + c + 4 * i));
+    sf_split4(Xh, Xl, r * UW_DP + c + 4 * i, d[i] * rs * *(const f32x4*)(g + c + 4 * i) + *(const f32x4*)(b + c + 4 * i));
 }
 
-// The fragment ring of a wave: four slots of TWO k-steps, three chunks (12 KB) in flight while one is consumed (the four-slot ring of three
-// k-steps of stream_mfma.h is 96 registers: with two accumulators it spills at the 168 registers a lane has with twelve waves per CU).
+// The fragment ring of a wave (stream_mfma.h) with slots of TWO k-steps, three chunks (12 KB) in flight while one is consumed (with slots of three
+// k-steps and two accumulators the kernel spills at the 168 registers a lane has with twelve waves per CU).
 // A product over 12 k-steps is six chunks, so consecutive products start at slot 0, 2, 0, ... (S0).
 constexpr int UW_CH = 2, UW_NC = UW_KS / UW_CH;
-struct UwRing {
-  bf16x8 w[4][UW_CH][2];
-};
-__device__ __forceinline__ void uw_load(UwRing& s, int slot, const uint4* p, int nblocks, int nb, int ks0, int lane) {
-#pragma unroll
-  for (int k = 0; k < UW_CH; ++k) {
-    s.w[slot][k][0] = ps_frag(p, nblocks, nb, ks0 + k, 0, lane);
-    s.w[slot][k][1] = ps_frag(p, nblocks, nb, ks0 + k, 1, lane);
-  }
-}
-// acc[4 g + q] += out[token = lane & 31][column 32 nb + 8 g + 4 (lane >> 5) + q] over k-steps ks0 .. ks0 + 11 of column block nb of the packed
-// matrix p (X planes: k-step 0 at the pointer).  Chunks 0..2 are already in slots S0 .. S0 + 2; every iteration requests the chunk three ahead --
-// behind the end of this product chunks 0..2 of the NEXT one (pn NULL: none), which starts at slot (S0 + 6) & 3.
 template <int S0>
-__device__ __forceinline__ void uw_block(f32x16& acc, UwRing& s, const uint4* p, int nblocks, int nb, int ks0, const uint4* pn, int nblocksn, int nbn,
-                                         int ksn, const __bf16* Xh, const __bf16* Xl, int stride, int lane) {
-  const int ao = (lane & 31) * stride + 8 * (lane >> 5);
-#pragma unroll
-  for (int c = 0; c < UW_NC; ++c) {
-    if (c + 3 < UW_NC)
-      uw_load(s, (S0 + c + 3) & 3, p, nblocks, nb, ks0 + (c + 3) * UW_CH, lane);
-    else if (pn)
-      uw_load(s, (S0 + c + 3) & 3, pn, nblocksn, nbn, ksn + (c + 3 - UW_NC) * UW_CH, lane);
-#pragma unroll
-    for (int k = 0; k < UW_CH; ++k) {
-      const int ks = c * UW_CH + k;
-      const bf16x8 xh = *(const bf16x8*)(Xh + ao + ks * 16), xl = *(const bf16x8*)(Xl + ao + ks * 16);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s.w[(S0 + c) & 3][k][0], xl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s.w[(S0 + c) & 3][k][1], xh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s.w[(S0 + c) & 3][k][0], xh, acc, 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);   // the requests stay one ring slot per chunk
-  }
+__device__ __forceinline__ void uw_block(f32x16& acc, PsRing<UW_CH>& s, const uint4* p, int nblocks, int nb, int ks0, const uint4* pn, int nblocksn,
+                                         int nbn, int ksn, const __bf16* Xh, const __bf16* Xl, int stride, int lane) {
+  ps_ring_block<UW_NC, UW_CH, UW_CH, S0, 1>(&acc, s, p, nblocks, nb, ks0, pn, nblocksn, nbn, ksn, Xh, Xl, stride, lane);
 }
 
 __global__ __launch_bounds__(UW_NT) void sa_slot_update_wide_kernel(UwArgs a) {
@@ -182,9 +153,9 @@ __global__ __launch_bounds__(UW_NT) void sa_slot_update_wide_kernel(UwArgs a) {
   // the GRU products of this wave: half 0 = gate r (W_ir u + W_hr h) then W_in u; half 1 = gate z then W_hn h  (row blocks r 0-5, z 6-11, n 12-17)
   const int nb1 = half * UW_NB + cb, nb3 = 2 * UW_NB + cb;
   const uint4* p3 = half == 0 ? a.w_ih_p : a.w_hh_p;
-  UwRing ring;
+  PsRing<UW_CH> ring;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) uw_load(ring, c, a.w_ih_p, 3 * UW_NB, nb1, c * UW_CH, lane);
+  for (int c = 0; c < 3; ++c) ps_load<UW_CH>(ring, c, a.w_ih_p, 3 * UW_NB, nb1, c * UW_CH, lane);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
     if (t + UW_NT * i < UW_ROWS * 64) DN[t + UW_NT * i] = dnv[i];
@@ -214,10 +185,10 @@ __global__ __launch_bounds__(UW_NT) void sa_slot_update_wide_kernel(UwArgs a) {
     float den = 0.f;
     for (int p = 0; p < a.P; ++p) den += DN[ur * 64 + p];
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    ps_split4(Uh, Ul, ur * UW_DP + uc, rok ? n0 / den : zero4);
-    ps_split4(Uh, Ul, ur * UW_DP + uc + 4, rok ? n1 / den : zero4);
-    ps_split4(Xh, Xl, ur * UW_DP + uc, rok ? h0 : zero4);
-    ps_split4(Xh, Xl, ur * UW_DP + uc + 4, rok ? h1 : zero4);
+    sf_split4(Uh, Ul, ur * UW_DP + uc, rok ? n0 / den : zero4);
+    sf_split4(Uh, Ul, ur * UW_DP + uc + 4, rok ? n1 / den : zero4);
+    sf_split4(Xh, Xl, ur * UW_DP + uc, rok ? h0 : zero4);
+    sf_split4(Xh, Xl, ur * UW_DP + uc + 4, rok ? h1 : zero4);
     *(f32x4*)(Fp + ur * UW_FP + uc) = rok ? h0 : zero4;
     *(f32x4*)(Fp + ur * UW_FP + uc + 4) = rok ? h1 : zero4;
   }
@@ -239,7 +210,7 @@ __global__ __launch_bounds__(UW_NT) void sa_slot_update_wide_kernel(UwArgs a) {
       const f32x4 bz = *(const f32x4*)(PV + WV_BIH + UW_D + c) + *(const f32x4*)(PV + WV_BHH + UW_D + c), bn = *(const f32x4*)(PV + WV_BHH + 2 * UW_D + c);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        EX[((cb * 2 + 0) * 16 + 4 * g + q) * 64 + lane] = ps_sigmoid(g1[4 * g + q] + bz[q]);
+        EX[((cb * 2 + 0) * 16 + 4 * g + q) * 64 + lane] = sf_sigmoid_fast(g1[4 * g + q] + bz[q]);
         EX[((cb * 2 + 1) * 16 + 4 * g + q) * 64 + lane] = g2[4 * g + q] + bn[q];
       }
     }
@@ -254,9 +225,9 @@ __global__ __launch_bounds__(UW_NT) void sa_slot_update_wide_kernel(UwArgs a) {
       f32x4 hn;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float rr = ps_sigmoid(g1[4 * g + q] + br[q]);
+        const float rr = sf_sigmoid_fast(g1[4 * g + q] + br[q]);
         const float z = EX[((cb * 2 + 0) * 16 + 4 * g + q) * 64 + lane], ghn = EX[((cb * 2 + 1) * 16 + 4 * g + q) * 64 + lane];
-        const float nn = ps_tanh(g2[4 * g + q] + bn[q] + rr * ghn);
+        const float nn = sf_tanh_fast(g2[4 * g + q] + bn[q] + rr * ghn);
         hn[q] = (1.f - z) * nn + z * hp[q];
       }
       *(f32x4*)(Fn + tok * UW_FP + c) = hn;
@@ -278,7 +249,7 @@ __global__ __launch_bounds__(UW_NT) void sa_slot_update_wide_kernel(UwArgs a) {
     const f32x4 bb = *(const f32x4*)(PV + WV_B1 + c);
     const f32x4 hv = {fmaxf(g1[4 * g] + bb[0], 0.f), fmaxf(g1[4 * g + 1] + bb[1], 0.f), fmaxf(g1[4 * g + 2] + bb[2], 0.f),
                       fmaxf(g1[4 * g + 3] + bb[3], 0.f)};
-    ps_split4(Hh, Hl, tok * UW_HP + c, hv);
+    sf_split4(Hh, Hl, tok * UW_HP + c, hv);
   }
   __syncthreads();
 

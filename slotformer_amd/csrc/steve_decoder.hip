@@ -6,9 +6,6 @@
 #include "sf_internal.h"
 #include "bf16_planes.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 constexpr int GN_P = 64;   // partial records per sample
 
@@ -344,9 +341,8 @@ __global__ __launch_bounds__(256, SLATE_BF3_WPS) void slate_flash_bf3_kernel(con
       pl_split2(a[2], a[3], h1, l1);
       pl_split2(c[0], c[1], h2, l2);
       pl_split2(c[2], c[3], h3, l3);
-      typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-      qf[s].h = __builtin_bit_cast(pl_bf16x8, (u32x4_{h0, h1, h2, h3}));
-      qf[s].l = __builtin_bit_cast(pl_bf16x8, (u32x4_{l0, l1, l2, l3}));
+      qf[s].h = __builtin_bit_cast(bf16x8, (u32x4{h0, h1, h2, h3}));
+      qf[s].l = __builtin_bit_cast(bf16x8, (u32x4{l0, l1, l2, l3}));
     }
   }
   // columns HD .. HD + 7 of the planes (+ the slack) feed only output channels >= HD: finite values
@@ -376,9 +372,8 @@ __global__ __launch_bounds__(256, SLATE_BF3_WPS) void slate_flash_bf3_kernel(con
       unsigned h0, l0, h1, l1;
       pl_split2(tt[n][0], tt[n][1], h0, l0);
       pl_split2(tt[n][2], tt[n][3], h1, l1);
-      typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-      *(u32x2_*)(bsm + hoff + r * PB + c * 2) = u32x2_{h0, h1};
-      *(u32x2_*)(bsm + loff + r * PB + c * 2) = u32x2_{l0, l1};
+      *(u32x2*)(bsm + hoff + r * PB + c * 2) = u32x2{h0, h1};
+      *(u32x2*)(bsm + loff + r * PB + c * 2) = u32x2{l0, l1};
     }
   };
   fetch(0);
@@ -439,9 +434,8 @@ __global__ __launch_bounds__(256, SLATE_BF3_WPS) void slate_flash_bf3_kernel(con
       pl_split2(sacc[8 * s + 2], sacc[8 * s + 3], h1, l1);
       pl_split2(sacc[8 * s + 4], sacc[8 * s + 5], h2, l2);
       pl_split2(sacc[8 * s + 6], sacc[8 * s + 7], h3, l3);
-      typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-      pf[s].h = __builtin_bit_cast(pl_bf16x8, (u32x4_{h0, h1, h2, h3}));
-      pf[s].l = __builtin_bit_cast(pl_bf16x8, (u32x4_{l0, l1, l2, l3}));
+      pf[s].h = __builtin_bit_cast(bf16x8, (u32x4{h0, h1, h2, h3}));
+      pf[s].l = __builtin_bit_cast(bf16x8, (u32x4{l0, l1, l2, l3}));
     }
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {

@@ -30,14 +30,6 @@ struct VpTaps {
   float w[VP_R + 1];   // w[k] = weight at distance k from the centre
 };
 
-__device__ __forceinline__ float vp_to_rgb(float v) { return fminf(fmaxf(fmaf(v, 0.5f, 0.5f), 0.f), 1.f); }
-
-__device__ __forceinline__ double vp_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // The SSIM map is cropped by the filter radius on every side (structural_similarity: crop(S, (win_size - 1) // 2)), so a kept map pixel (oy, ox)
 // -- crop coordinates -- reads image rows oy .. oy + 10 and columns ox .. ox + 10 only: no tap of a kept pixel crosses the image edge and scipy's
 // `reflect` rows never enter the mean.  A tile therefore loads plain image pixels; what lies outside the image (ragged tiles) is loaded as 0 and
@@ -64,7 +56,7 @@ __global__ __launch_bounds__(256) void vp_image_tile_kernel(const float* __restr
     if (c < VP_IW && iy < H && ix < W) {
       a = g[(long long)iy * W + ix];
       b = p[(long long)iy * W + ix];
-      if (to_rgb) a = vp_to_rgb(a), b = vp_to_rgb(b);
+      if (to_rgb) a = sf_to_rgb(a), b = sf_to_rgb(b);
       if (iy >= own_y0 && iy < own_y1 && ix >= own_x0 && ix < own_x1) {
         const float d = a - b;
         sse += (double)(d * d);
@@ -133,8 +125,8 @@ __global__ __launch_bounds__(256) void vp_image_tile_kernel(const float* __restr
     const float s = (a1 * a2) / (b1 * b2);
     if (ox0 + col < mw && oy0 + r0 + j < mh) ssum += (double)s;
   }
-  sse = vp_wave_sum(sse);
-  ssum = vp_wave_sum(ssum);
+  sse = sf_wave_sum(sse);
+  ssum = sf_wave_sum(ssum);
   if ((tid & 63) == 0) red[0][tid >> 6] = sse, red[1][tid >> 6] = ssum;
   __syncthreads();
   if (tid < 2) partial[(plane * gridDim.x + blockIdx.x) * 2 + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
@@ -149,8 +141,8 @@ __global__ __launch_bounds__(64) void vp_image_finish_kernel(const double* __res
     a += partial[(f * n + i) * 2];
     b += partial[(f * n + i) * 2 + 1];
   }
-  a = vp_wave_sum(a);
-  b = vp_wave_sum(b);
+  a = sf_wave_sum(a);
+  b = sf_wave_sum(b);
   if (threadIdx.x == 0) {
     mse[f] = a / 3.;                                        // summed over H and W, averaged over the channels
     psnr[f] = 10. * log10(1. / (a / (3. * H * W)));         // data range 1; +inf for equal frames
