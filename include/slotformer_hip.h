@@ -474,6 +474,33 @@ int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int
 int sf_gather_rows_f32(const float* table, const long long* ids, float* out, long long R, int d, long long table_rows,
                        void* stream);
 
+/* ---- dVAE token ids without the logits (base_slots/tokenize_images.py, dVAE.py:24-35, 52-77; csrc/dvae_tokens.hip) --------------------------------
+ * The two ends of the dVAE encoder as kernels of their own: the 4x4 / stride-4 patch embedding read straight from NCHW frames, and the vocabulary
+ * head with the argmax inside (the logits live in MFMA accumulators only).  Between them the six 1x1 blocks run on sf_linear_f32 /
+ * sf_groupnorm1_nhwc_f32 as before.  Arithmetic of both: split-bf16 (every f32 operand = bf16 hi + bf16 lo, three products, f32 accumulation)
+ * WHATEVER sf_set_precision says -- token targets have one definition -- every sum in a fixed order, no atomics: a pixel's id does not depend on
+ * its place in the batch.  No workspace.
+ *
+ * sf_dvae_tokens_ok reads shapes only: 1 exactly when K == 64 (features of the head), C == 3, H >= 4 and W >= 4 are multiples of 4, and V is a
+ * multiple of 32 (the MFMA block) with 32 <= V <= 2^20; 0 otherwise. */
+int sf_dvae_tokens_ok(int V, int K, int C, int H, int W);
+/* Bytes of the packed head weight: V * K * 4 (a bf16 hi plane of V * K elements and the lo plane behind it); 0 unless K == 64 and V as above. */
+size_t sf_dvae_head_packed_bytes(int V, int K);
+/* w [V,K] f32 (the head's 1x1 convolution, torch's layout) -> packed, in fragment order: for every block vb of 32 words and every k-step ks of 16
+ * features, 64 lanes x 8 bf16, lane l holding W[32 vb + (l & 31)][16 ks + 8 (l >> 5) + 0..7] -- element ((vb * 4 + ks) * 64 + l) * 8 + j of the hi
+ * plane (bf16 of the value, round to nearest even), the lo plane (bf16 of the remainder) behind it.  The _host twin takes and fills HOST memory with
+ * the same bytes. */
+int sf_dvae_pack_head_weights(const float* w, void* packed, int V, int K, void* stream);
+int sf_dvae_pack_head_weights_host(const float* w, void* packed, int V, int K);
+/* img [F,C,H,W] f32 (NCHW, C == 3, H and W multiples of 4), w [64,C,4,4] -> y [F,H/4,W/4,64] (NHWC): the bias-free 4x4 / stride-4 convolution of
+ * the first encoder block, before its GroupNorm.  img and w 16-byte aligned. */
+int sf_dvae_patch_embed_f32(const float* img, const float* w, float* y, int F, int C, int H, int W, void* stream);
+/* ids[r] = the FIRST index of the maximum over v of (W[v] . x[r] + bias[v]); x [R,K] f32 with row stride ld >= K (a multiple of 4), w_packed from
+ * sf_dvae_pack_head_weights, bias [V] or NULL.  ids_i64 [R] and ids_i16 [R]: either may be NULL, not both; int16 (the dtype of the token files)
+ * is refused when V > 32768.  A row holding a NaN gives an unspecified (valid) id.  x, w_packed and bias 16-byte aligned. */
+int sf_dvae_head_argmax_f32(const float* x, long long ld, const void* w_packed, const float* bias, long long* ids_i64, short* ids_i16, long long R,
+                            int V, int K, void* stream);
+
 /* ---- whole-path engines ------------------------------------------------------------------ */
 
 /* One nn.TransformerEncoderLayer (relu, batch_first); all pointers device, torch layouts. */

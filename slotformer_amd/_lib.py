@@ -277,6 +277,12 @@ SIGNATURES = {
     'sf_slate_generate_tok_workspace_bytes': (SZ, [C.POINTER(sf_slate_decoder), I, I]),
     'sf_slate_generate_tok_f32': (I, [C.POINTER(sf_slate_decoder), FP, I, I, VP, FP, I, VP, SZ, VP, C.POINTER(I)]),
     'sf_gather_rows_f32': (I, [FP, VP, FP, LL, I, LL, VP]),
+    'sf_dvae_tokens_ok': (I, [I, I, I, I, I]),
+    'sf_dvae_head_packed_bytes': (SZ, [I, I]),
+    'sf_dvae_pack_head_weights': (I, [FP, VP, I, I, VP]),
+    'sf_dvae_pack_head_weights_host': (I, [VP, VP, I, I]),
+    'sf_dvae_patch_embed_f32': (I, [FP, FP, FP, I, I, I, I, VP]),
+    'sf_dvae_head_argmax_f32': (I, [FP, LL, VP, FP, VP, VP, LL, I, I, VP]),
     'sf_packed_linear_bytes': (SZ, [I, I]),
     'sf_pack_linear_weights': (I, [FP, VP, I, I, VP]),
     'sf_attn_packed_bytes': (SZ, [I, I]),

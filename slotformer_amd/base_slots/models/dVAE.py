@@ -4,7 +4,8 @@ The modules below only hold parameters under the reference's state-dict names (`
 `encoder.{i}.weight/bias`, `decoder.…`); `tokenize` / `detokenize` run on the HIP library: 1x1 convolutions and the
 4x4/stride-4 patch embedding as GEMMs over channels-last pixels (`sf_linear_f32`), the 3x3 convolutions on the
 implicit-GEMM conv (`sf_conv2d_nhwc_f32`), GroupNorm(1)+ReLU(+PixelShuffle) in `sf_groupnorm1_nhwc_f32`, the token
-pick in `sf_argmax_rows_f32`.  In training (`forward` outside `testing`, row N1) the same kernels run as autograd nodes of
+pick in `sf_argmax_rows_f32`.  `tokenize_ids` is the dataset tokeniser: the patch embedding straight from NCHW frames and the vocabulary head with
+the argmax inside (`sf_dvae_patch_embed_f32`, `sf_dvae_head_argmax_f32`), no logits in memory.  In training (`forward` outside `testing`, row N1) the same kernels run as autograd nodes of
 `slotformer_amd.train` (`sf_linear_bwd_f32`, `sf_groupnorm1_nhwc_bwd_f32`, `sf_softmax_rows_bwd_f32`)."""
 import torch
 from torch import nn
@@ -101,6 +102,52 @@ class dVAE(BaseModel):
         else:
             z = idx
         return z.unflatten(0, (B, -1)) if unflatten else z
+
+    def _head_packed(self):
+        """The vocabulary head in the fragment order `ops.linear_argmax` streams; rebuilt when the parameter changes (as `_w3x3`)."""
+        w = self.encoder[7].weight
+        key = ('head', w.data_ptr(), w._version)
+        if key not in self._packed:
+            self._packed = {} if len(self._packed) > 8 else self._packed
+            self._packed[key] = ops.pack_head_weight(w.detach().reshape(self.vocab_size, 64).float().contiguous())
+        return self._packed[key]
+
+    @torch.no_grad()
+    def tokenize_ids(self, imgs, out=None, dtype=torch.int64):
+        """Token ids of frames for tokenising a dataset (base_slots/tokenize_images.py): imgs [B,(T,)3,H,W] device float32 -> ids [B,(T,)h,w]
+        int64 or int16 (`dtype`; int16 is what the token files hold), written into `out` when given (contiguous, that dtype, that many
+        elements).  What `tokenize(one_hot=False)` computes, without the patchify copy in front and without the logits [F,h,w,V] behind: the 4x4
+        convolution reads the frames as they lie (`ops.patch_embed`) and the head picks the id from its accumulators (`ops.linear_argmax`), both in
+        split-bf16 whatever the precision mode, so ids may differ from `tokenize` where the two best logits are closer than that arithmetic resolves.
+        Asynchronous on the current stream; never syncs with the host.  Shapes `sf_dvae_tokens_ok` refuses go through `tokenize`."""
+        if not (torch.is_tensor(imgs) and imgs.is_cuda and imgs.dtype == torch.float32 and imgs.dim() in (4, 5)):
+            raise RuntimeError('slotformer_amd dVAE.tokenize_ids needs float32 frames [B,(T,)3,H,W] on a HIP device; there is no CPU fallback')
+        if dtype not in (torch.int64, torch.int16):
+            raise TypeError(f'dVAE.tokenize_ids: dtype is torch.int64 or torch.int16, got {dtype}')
+        if dtype == torch.int16 and self.vocab_size > 32768:
+            raise ValueError(f'dVAE.tokenize_ids: int16 ids cannot hold a vocabulary of {self.vocab_size}')
+        lead = tuple(imgs.shape[:-3])
+        flat = imgs.reshape((-1, ) + tuple(imgs.shape[-3:])).contiguous()
+        F_, C_, H, W = flat.shape
+        shape = lead + (H // 4, W // 4)
+        if out is not None and not (out.is_cuda and out.dtype == dtype and out.is_contiguous() and out.numel() == F_ * (H // 4) * (W // 4)):
+            raise TypeError(f'dVAE.tokenize_ids: out must be a contiguous {dtype} device tensor of {shape}')
+        if not ops.dvae_tokens_ok(self.vocab_size, 64, C_, H, W):
+            ids = self.tokenize(flat, one_hot=False).to(dtype).reshape(shape)   # the slower path, never an error
+            if out is None:
+                return ids
+            out.view(shape).copy_(ids)
+            return out.view(shape)
+        e = self.encoder
+        x = ops.patch_embed(flat, e[0].m.weight.detach().contiguous())
+        x = ops.groupnorm1_nhwc(x, e[0].weight.detach(), e[0].bias.detach(), relu=True)
+        for i in range(1, 7):
+            x = self._block(x, e[i])
+        if out is None:
+            out = torch.empty(shape, device=flat.device, dtype=dtype)
+        kw = {'out': out} if dtype == torch.int64 else {'out_i16': out}
+        ops.linear_argmax(x, self._head_packed(), e[7].bias.detach(), self.vocab_size, **kw)
+        return out.view(shape)
 
     def detokenize(self, z):
         """dVAE.py:79-100: z [B,(T,)V,h,w] (probabilities over the vocabulary) -> image [B,(T,)3,4h,4w]."""

@@ -55,6 +55,52 @@ def rollout_video_slots(model, ori_slots, frame_offset, history_len=None, obs_fr
     return out
 
 
+@torch.no_grad()
+def extract_video_tokens(dvae, videos, batch_size=64, ingest=None, to_host=True):
+    """base_slots/tokenize_images.py:15-40 -- the dVAE token ids of whole clips, as the token files hold them.  videos [N, T, 3, H, W] float
+    frames (anything `.float()` takes), on the device or on the host -> int16 [N, T, h*w], in pinned host memory with to_host=True (what
+    `slot_io.save_video_tokens` writes), on the device otherwise.  The frames go through `dvae.tokenize_ids` in chunks of `batch_size` FRAMES (a clip
+    may span chunks; the last chunk may be shorter): no logits buffer anywhere, and only a chunk of a host-resident set is on the device at a
+    time.  Each chunk's ids are written straight into the result; the download of a chunk runs on a side stream behind the next chunk's kernels.
+    ingest: an `ingest.FrameIngest` -- `videos` is then the decoder's RAW uint8 clips [N, T, H0, W0, 3] ([N, T, H0, W0] with a palette), normalised
+    and resized on the device chunk by chunk, as `extract_and_rollout` takes them."""
+    if int(batch_size) < 1:
+        raise ValueError(f'slotformer_amd.harness: batch_size >= 1, got {batch_size!r}')
+    if dvae.vocab_size > 32768:
+        raise ValueError(f'slotformer_amd.harness: int16 token files cannot hold a vocabulary of {dvae.vocab_size}')
+    dev = dvae.device
+    if ingest is None:
+        if videos.dim() != 5:
+            raise ValueError(f'slotformer_amd.harness: clips are [N, T, 3, H, W], got {tuple(videos.shape)}')
+        N, T, _, H, W = videos.shape
+    else:
+        shape = ingest.output_shape(videos)   # (raises for anything but contiguous uint8 frames)
+        if videos.dim() != (4 if ingest.palette is not None else 5):
+            raise ValueError(f'slotformer_amd: ingest= takes clips [N, T, H0, W0, 3] ([N, T, H0, W0] with a palette), got {tuple(videos.shape)}')
+        N, T, H, W = shape[0], shape[1], shape[-2], shape[-1]
+    flat = videos.reshape((N * T, ) + tuple(videos.shape[2:]))
+    hw = (H // 4) * (W // 4)
+    F_ = N * T
+    out = torch.empty(F_, hw, dtype=torch.int16, pin_memory=True) if to_host else torch.empty(F_, hw, dtype=torch.int16, device=dev)
+    copies, keep = (torch.cuda.Stream(device=dev), []) if to_host else (None, None)
+    for a, b in render_chunks(F_, batch_size):
+        chunk = flat[a:b].to(dev, non_blocking=True)
+        chunk = ingest(chunk) if ingest is not None else chunk.float()
+        if not to_host:
+            dvae.tokenize_ids(chunk, out=out[a:b], dtype=torch.int16)
+            continue
+        ids = dvae.tokenize_ids(chunk, dtype=torch.int16)
+        ready = torch.cuda.Event()
+        ready.record()
+        copies.wait_event(ready)
+        with torch.cuda.stream(copies):
+            out[a:b].copy_(ids.view(b - a, hw), non_blocking=True)
+        keep.append(ids)   # alive until its copy has run
+    if to_host:
+        copies.synchronize()
+    return out.view(N, T, hw)
+
+
 def render_chunks(num_frames, frames_per_call=64):
     """[(start, stop), ...] covering range(num_frames) once, `frames_per_call` frames per chunk (the last one may be shorter)."""
     if int(frames_per_call) < 1:

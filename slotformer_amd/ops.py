@@ -344,6 +344,55 @@ def argmax_rows(x):
     return out
 
 
+def dvae_tokens_ok(V, K, C, H, W):
+    """Whether patch_embed / linear_argmax take these shapes (`sf_dvae_tokens_ok`; shapes only, no device needed)."""
+    return bool(lib().sf_dvae_tokens_ok(int(V), int(K), int(C), int(H), int(W)))
+
+
+def patch_embed(imgs, weight):
+    """imgs [F,3,H,W] NCHW, weight [64,3,4,4] -> [F,H/4,W/4,64] NHWC: the bias-free 4x4 / stride-4 convolution of the dVAE's first block, read
+    straight from the frames (`sf_dvae_patch_embed_f32`, split-bf16 whatever the library's precision mode)."""
+    _chk(imgs, weight)
+    F_, C_, H, W = imgs.shape
+    out = torch.empty(F_, H // 4, W // 4, 64, device=imgs.device, dtype=torch.float32)
+    check(lib().sf_dvae_patch_embed_f32(_p(imgs), _p(weight), _p(out), F_, C_, H, W, _stream()))
+    return out
+
+
+def pack_head_weight(w):
+    """[V,64] -> the split-bf16 fragment-order copy `linear_argmax` streams (uint8 buffer, `sf_dvae_pack_head_weights`)."""
+    _chk(w)
+    V, K = w.shape
+    nb = lib().sf_dvae_head_packed_bytes(V, K)
+    if nb == 0:
+        raise RuntimeError(f'slotformer_amd pack_head_weight: K must be 64 and V a multiple of 32, got [{V}, {K}]')
+    out = torch.empty(nb, device=w.device, dtype=torch.uint8)
+    check(lib().sf_dvae_pack_head_weights(_p(w), out.data_ptr(), V, K, _stream()))
+    return out
+
+
+def linear_argmax(x, w_packed, bias, V, out=None, out_i16=None):
+    """First index of the maximum of each row of x @ W.T + bias WITHOUT the product in memory (`sf_dvae_head_argmax_f32`).  x [..., 64] (rows may
+    be strided: a 2-D x with stride(1) == 1), w_packed = pack_head_weight(W [V,64]), bias [V] or None.  Returns int64 ids [...] by default; out
+    (int64) / out_i16 (int16) are contiguous device tensors of x's leading shape to write into -- give either or both, and what was given is
+    returned (a tuple for both)."""
+    strided = torch.is_tensor(x) and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) > x.shape[1]
+    _chk(x[:1] if strided else x, bias)
+    if not (torch.is_tensor(w_packed) and w_packed.is_cuda and w_packed.dtype == torch.uint8 and w_packed.is_contiguous()):
+        raise RuntimeError('linear_argmax: w_packed is the uint8 device buffer of pack_head_weight; there is no CPU fallback')
+    K = x.shape[-1]
+    ld = x.stride(0) if strided else K
+    lead = tuple(x.shape[:-1])
+    R = x.numel() // K
+    if out is None and out_i16 is None:
+        out = torch.empty(lead, device=x.device, dtype=torch.int64)
+    for t, dt in ((out, torch.int64), (out_i16, torch.int16)):
+        if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == R):
+            raise TypeError(f'linear_argmax: outputs must be contiguous {dt} device tensors of {R} elements')
+    check(lib().sf_dvae_head_argmax_f32(x.data_ptr(), ld, w_packed.data_ptr(), _p(bias), _p(out), _p(out_i16), R, int(V), K, _stream()))
+    return out if out_i16 is None else out_i16 if out is None else (out, out_i16)
+
+
 def gather_rows(table, ids):
     """table[ids]: table [rows, d] float32, ids int64 [...] on the device -> [..., d] (`sf_gather_rows_f32`)."""
     _chk(table)

@@ -6,6 +6,8 @@
 * PHYRE: one ``{data_idx:06d}.npy`` per sample holding ``slots[:vid_len]`` (extract_phyre_slots.py:69-76);
   extraction is restartable -- files already present are skipped, the newest one is redone in case it
   was truncated (extract_phyre_slots.py:45-53).
+* Physion dVAE tokens: one int16 ``[T, h*w]`` ``.npy`` per video beside the videos (tokenize_images.py:55-66), read back as strided int32 clips
+  (datasets/physion.py:81-93); files already present are skipped.
 """
 import os
 import pickle
@@ -50,6 +52,47 @@ def read_clip(video_slots, video_path, start_idx, n_sample_frames, frame_offset)
     except KeyError:
         raise ValueError(f'no slots for {video_path}')
     return np.stack([slots[start_idx + n * frame_offset] for n in range(n_sample_frames)], 0).astype(np.float32)
+
+
+def token_path(video_path, dvae_name):
+    """Where the dVAE tokens of a Physion video live (tokenize_images.py:57-63, datasets/physion.py:81-85): the video's path with
+    `TrainMP4s/` -> `TrainNpys-<dvae_name>/`, `TestMP4s/` -> `TestNpys-<dvae_name>/` and `.mp4` -> `.npy`.  The dataset names a video by its
+    frame folder (no extension): `.npy` is then appended, which gives the same file."""
+    p = video_path.replace('TrainMP4s/', f'TrainNpys-{dvae_name}/').replace('TestMP4s/', f'TestNpys-{dvae_name}/')
+    return p.replace('.mp4', '.npy') if '.mp4' in p else p + '.npy'
+
+
+def save_video_tokens(files, tokens, dvae_name, overwrite=False):
+    """One `[T, h*w]` int16 file per video (tokenize_images.py:55-66) at `token_path(file, dvae_name)`; tokens: array-like [N, T, h*w] (what
+    `harness.extract_video_tokens` returns).  A file that already exists is left alone unless `overwrite`, so an interrupted run resumes
+    where it stopped; each file is written under a temporary name and renamed, so a crash never leaves a truncated one behind.  Returns the
+    paths it wrote."""
+    assert len(files) == len(tokens)
+    written = []
+    for f, t in zip(files, tokens):
+        path = token_path(f, dvae_name)
+        if os.path.exists(path) and not overwrite:
+            continue
+        t = np.asarray(t)
+        if t.ndim != 2:
+            raise ValueError(f'tokens of a video are [T, h*w], got {t.shape}')
+        if t.dtype != np.int16 and (t.min() < 0 or t.max() > 32767):
+            raise ValueError('token ids do not fit the int16 of the token files')
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        tmp = path + '.tmp.npy'
+        np.save(tmp, t.astype(np.int16))
+        os.replace(tmp, path)
+        written.append(path)
+    return written
+
+
+def read_token_clip(path, start_idx, n_sample_frames, frame_offset):
+    """datasets/physion.py:81-93: the strided clip [n_sample_frames, h*w] int32 of one video's token file, or None when the file is missing
+    (the dataset then leaves `token_id` out and the model tokenises the frames itself)."""
+    if not os.path.exists(path):
+        return None
+    tokens = np.load(path)   # [T, h*w]
+    return np.stack([tokens[start_idx + n * frame_offset] for n in range(n_sample_frames)], 0).astype(np.int32)
 
 
 def phyre_path(save_root, data_idx):
