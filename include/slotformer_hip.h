@@ -80,7 +80,9 @@ int sf_conv2d_nhwc_f32(const float* in, const float* w_packed, const float* bias
 int sf_pack_conv_weight_f32(const float* w_oihw, float* w_ohwi, int Cout, int Cin, int ks, void* stream);
 /* 64 -> 64 channel 5 x 5 convolutions on a 64-pixel-wide grid: w_ohwi (above) -> split-bf16 copy in MFMA-fragment order,
  * sf_conv_frag_bytes(64, 64, 5) bytes; sf_conv5x5_frag_f32 is sf_conv2d_nhwc_f32 for that shape on the fragment copy (H % 4 == 0,
- * split-bf16 mode; csrc/conv_rows4.hip).  relu / add as sf_conv2d_nhwc_f32. */
+ * split-bf16 mode; csrc/conv_rows4.hip).  relu / add as sf_conv2d_nhwc_f32.  The first 409,600 bytes are the A operands of v_mfma_f32_16x16x32_bf16:
+ * 16-byte piece ((((tap * 2 + kh) * 2 + cb) * 2 + a) * 2 + plane) * 64 + lane = w[cb * 32 + 16 a + (lane & 15)][tap][kh * 32 + 8 (lane >> 4) + 0 .. 7],
+ * plane 0 bf16(w), plane 1 bf16(w - plane 0); behind them the single-fp16 copy of the opt-in arithmetic below. */
 /* Per-pixel chain of the SAVi encoder up to the normalised Slot-Attention inputs (64 -> 128 -> 128 channels; savi.py:245-250, 66-70):
  * feat [M][128] = LN(fc2(relu(fc1(LN(x))))), x [M][64]; torch-layout weights w1 [128][64], w2 [128][128].  form 0: one 128-pixel tile per
  * workgroup, weights through LDS; form 1: weights resident in registers, four tiles per workgroup; form 2 (the one the encode uses): the same on

@@ -7,8 +7,10 @@
 // per-tap staging of activations at all.  Only the weights (16 KB per tap) stream through a double
 // buffer.  Fill bytes per tile: 104 KB halo + 400 KB weights instead of 1.2 MB.
 //
-//   8 waves: (row 0/1) x (pixel block 0/1) x (cin half 0/1), two 32x32 accumulators (both cout blocks) each;
-//   per tap and wave: 2 k16-steps x 2 cout blocks x (hi*hi + hi*lo + lo*hi) v_mfma_f32_32x32x16_bf16.
+//   8 waves: (row 0/1) x (pixel block 0/1) x (cin half 0/1), two 32x32 accumulators (both cout blocks) each, as four 16x16 tiles;
+//   per tap and wave: one K = 32 step x 2 cout blocks x 4 tiles x (lo*hi + hi*lo + hi*hi) v_mfma_f32_16x16x32_bf16 -- the product and the
+//   order of sf_conv_tile16 (split_bf16.h), shared with conv_rows4.hip and conv_ws.hip bit for bit.  A tile takes the pixels (couts) of one
+//   parity of its 32-block: conflict-free ds_read_b128 at the 144-byte pitch.
 //   LDS: halo planes 2 x 6*68*72 bf16 (pixel stride 144 B = 9 16-B slots: conflict-free b128)
 //        + weight planes 2 buffers x 2 x 64*72 bf16  = 154 KB.
 // Reference call site: the encoder convs i > 0, savi.py:231-239 (+ SoftPositionEmbed add, utils.py:60-63).
@@ -93,12 +95,12 @@ __global__ __launch_bounds__(NT) void conv5x5_halo_kernel(const float* __restric
   // acc[0] = the cout block this wave finishes (block kh), acc[1] = the one it hands to its partner: the runtime
   // choice sits in the weight ADDRESS, never in a register index (that turns every MFMA into select + hazard nops).
   const int row = wave >> 2, pxb = ((wave >> 1) & 1) * 32, kh = wave & 1;
-  f32x16 acc[2];
+  f32x4 acc[2][2][2];   // [cout block][cout parity ta][pixel parity tp]; register e of a lane = pixel 2 (4 (lane >> 4) + e) + tp, cout 2 (lane & 15) + ta
 #pragma unroll
   for (int q = 0; q < 2; ++q)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-  const int a_lane = (lane & 31) * PS + 8 * (lane >> 5) + 32 * kh;   // pixel (or cout) row + k half, + this wave's cin half
+    for (int j = 0; j < 4; ++j) acc[q][j >> 1][j & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int a_lane = 2 * (lane & 15) * PS + 8 * (lane >> 4) + 32 * kh;   // pixel (or cout) row of parity 0 + k quarter, + this wave's cin half
   for (int ky = 0; ky < KS; ++ky) {
 #pragma unroll
     for (int kx = 0; kx < KS; ++kx) {
@@ -111,24 +113,25 @@ __global__ __launch_bounds__(NT) void conv5x5_halo_kernel(const float* __restric
       const __bf16* bh = Wh + buf * WBUF + a_lane;
       const __bf16* bl = Wl + buf * WBUF + a_lane;
       const int cq[2] = {kh * 32 * PS, (1 - kh) * 32 * PS};
+      bf16x8 xh[2], xl[2];
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 xh = *(const bf16x8*)(ah + ks * 16);
+      for (int tp = 0; tp < 2; ++tp) {
+        xh[tp] = *(const bf16x8*)(ah + tp * PS);
+        if constexpr (!BF1) xl[tp] = *(const bf16x8*)(al + tp * PS);
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        bf16x8 y[2][2];   // [cout parity][hi, lo]
+#pragma unroll
+        for (int ta = 0; ta < 2; ++ta) {
+          y[ta][0] = *(const bf16x8*)(bh + cq[q] + ta * PS);
+          if constexpr (!BF1) y[ta][1] = *(const bf16x8*)(bl + cq[q] + ta * PS);
+        }
         if constexpr (BF1) {
 #pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const bf16x8 yh = *(const bf16x8*)(bh + cq[q] + ks * 16);
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, yh, acc[q], 0, 0, 0);
-          }
+          for (int j = 0; j < 4; ++j) acc[q][j >> 1][j & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[j & 1], y[j >> 1][0], acc[q][j >> 1][j & 1], 0, 0, 0);
         } else {
-          const bf16x8 xl = *(const bf16x8*)(al + ks * 16);
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const bf16x8 yh = *(const bf16x8*)(bh + cq[q] + ks * 16), yl = *(const bf16x8*)(bl + cq[q] + ks * 16);
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, yh, acc[q], 0, 0, 0);
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, yl, acc[q], 0, 0, 0);
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, yh, acc[q], 0, 0, 0);
-          }
+          sf_conv_block32<false>(y, xh, xl, acc[q]);
         }
       }
       // weights of tap+1 (slot (kx+1)%5, requested four taps ago) -> the buffer last read one barrier ago
@@ -140,15 +143,15 @@ __global__ __launch_bounds__(NT) void conv5x5_halo_kernel(const float* __restric
   // ---- combine the two k-halves: wave kh keeps cout block kh and receives that block from its partner ----------
   float* X = (float*)lds;   // [8 waves][16][64] f32 = 32 KB over the (now dead) halo
 #pragma unroll
-  for (int r = 0; r < 16; ++r) X[(wave * 16 + r) * 64 + lane] = acc[1][r];
+  for (int r = 0; r < 16; ++r) X[(wave * 16 + r) * 64 + lane] = acc[1][(r >> 2) & 1][r >> 3][r & 3];   // r = 4 (2 tp + ta) + e
   __syncthreads();
-  f32x16 fin = acc[0];
+  float fin[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) fin[r] += X[((wave ^ 1) * 16 + r) * 64 + lane];
+  for (int r = 0; r < 16; ++r) fin[r] = acc[0][(r >> 2) & 1][r >> 3][r & 3] + X[((wave ^ 1) * 16 + r) * 64 + lane];
 
   // ---- epilogue: bias, ReLU, optional per-position table, NHWC store ------------------------------------
-  const int co = kh * 32 + (lane & 31);
-  const float bv = bias ? bias[co] : 0.f;
+  // (register r = 4 (2 tp + ta) + e of a lane)
+  const float bv2[2] = {bias ? bias[kh * 32 + 2 * (lane & 15)] : 0.f, bias ? bias[kh * 32 + 2 * (lane & 15) + 1] : 0.f};
   // relu == 2 (training, backward-data pass): `add` is the forward activation of the layer below, laid out like `out`, and
   // acts as its ReLU mask -- out = add > 0 ? conv : 0
   const bool mask = relu == 2;
@@ -157,13 +160,13 @@ __global__ __launch_bounds__(NT) void conv5x5_halo_kernel(const float* __restric
   float av[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int px = pxb + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int px = pxb + 2 * (4 * (lane >> 4) + (r & 3)) + (r >> 3), co = kh * 32 + 2 * (lane & 15) + ((r >> 2) & 1);
     av[r] = add ? add[((long long)(mask ? f * H + y : y) * TW + px) * CH + co] : 0.f;
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int px = pxb + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    const float t = fmaxf(fin[r] + bv, lo);
+    const int px = pxb + 2 * (4 * (lane >> 4) + (r & 3)) + (r >> 3), co = kh * 32 + 2 * (lane & 15) + ((r >> 2) & 1);
+    const float t = fmaxf(fin[r] + bv2[(r >> 2) & 1], lo);
     out[(((long long)f * H + y) * TW + px) * CH + co] = mask ? (av[r] > 0.f ? t : 0.f) : t + av[r];
   }
 }

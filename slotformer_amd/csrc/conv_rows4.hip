@@ -7,11 +7,12 @@
 //     split into bf16 hi / lo) and each wave pulls ITS fragments -- the A operand -- straight from memory into a ring of four
 //     taps' registers, three taps in flight.  No barrier inside the 25 taps: the eight waves run free;
 //   * a workgroup owns 4 output rows (256 pixels x 64 channels); the 8 x 68 halo is split into bf16 planes in LDS once (153 KB);
-//   * wave = (cout block, row pair, half of the input channels): one weight fragment feeds FOUR 32-pixel blocks -- 16 LDS
-//     fragment reads per 24 MFMAs;
+//   * wave = (cout block, row pair, half of the input channels): one tap's weight fragments feed FOUR 32-pixel blocks -- 16 LDS
+//     fragment reads per 48 MFMAs (16x16x32: a tile is the pixels of one parity of a block, see sf_conv_tile16);
 //   * the two cin halves meet in LDS after the last tap (each wave finishes two of its four pixel blocks).
 // Per workgroup 800 KB of weight fragments + 139 KB of halo for 600 MFMAs per SIMD (19.2 k cycles).
-// Same products, same order per cin half as conv_halo.hip (taps ascending, k-steps ascending, x_lo w_hi + x_hi w_lo + x_hi w_hi).
+// Same products, same order per cin half as conv_halo.hip (taps ascending, one K = 32 step per tap, x_lo w_hi + x_hi w_lo + x_hi w_hi:
+// sf_conv_tile16, split_bf16.h).  The opt-in fp16 x 2 form keeps the 32x32x16 shape and its own fragment copy.
 // Reference call site: the encoder convs i > 0, savi.py:231-239 (+ SoftPositionEmbed add, utils.py:60-63).
 #include "sf_internal.h"
 #include <stdlib.h>
@@ -26,20 +27,20 @@ constexpr int PS = CH + 8;                                   // bf16 elements pe
 constexpr int HALO = HR * HWD * PS;                          // elements per halo plane
 constexpr int NT = 512;
 constexpr int NTAP = KS * KS;
-constexpr int FRAG_BYTES = NTAP * 4 * 2 * 2 * 64 * 16;      // 409,600: one uint4 per (tap, k-step, cout block, plane, lane)
+constexpr int FRAG_BYTES = NTAP * 2 * 2 * 2 * 2 * 64 * 16;  // 409,600: one uint4 per (tap, cin half, cout block, cout half, plane, lane)
 constexpr int FRAG16_BYTES = FRAG_BYTES / 2;                // + the single-fp16 copy (one plane)
 constexpr size_t LDS_BYTES = (size_t)2 * HALO * sizeof(__bf16);   // 156,672
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert((size_t)8 * 32 * 64 * 4 <= LDS_BYTES, "the exchange of the cin halves fits over the dead halo");
 }  // namespace
 
-// w_ohwi [64][25][64] f32 -> fragment order, split-bf16:
-//   uint4 index = ((((tap * 4 + ks) * 2 + cb) * 2 + plane) * 64 + lane),  element j = w[cb*32 + (lane & 31)][tap][ks*16 + 8 (lane >> 5) + j]
+// w_ohwi [64][25][64] f32 -> fragment order, split-bf16: the A operand of v_mfma_f32_16x16x32_bf16 (16 couts x 32 cin per fragment)
+//   uint4 index = ((((tap * 2 + kh) * 2 + cb) * 2 + a) * 2 + plane) * 64 + lane,  element j = w[cb*32 + 16 a + (lane & 15)][tap][kh*32 + 8 (lane >> 4) + j]
 __global__ void pack_conv_frag_kernel(const float* __restrict__ w, uint4* __restrict__ out) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= NTAP * 4 * 2 * 2 * 64) return;
-  const int lane = idx & 63, plane = (idx >> 6) & 1, cb = (idx >> 7) & 1, ks = (idx >> 8) & 3, tap = idx >> 10;
-  const float* src = w + ((long long)(cb * 32 + (lane & 31)) * NTAP + tap) * CH + ks * 16 + 8 * (lane >> 5);
+  const int lane = idx & 63, plane = (idx >> 6) & 1, a = (idx >> 7) & 1, cb = (idx >> 8) & 1, kh = (idx >> 9) & 1, tap = idx >> 10;
+  const float* src = w + ((long long)(cb * 32 + 16 * a + (lane & 15)) * NTAP + tap) * CH + kh * 32 + 8 * (lane >> 4);
   union {
     __bf16 h[8];
     uint4 u;
@@ -51,14 +52,17 @@ __global__ void pack_conv_frag_kernel(const float* __restrict__ w, uint4* __rest
     o.h[j] = plane ? (__bf16)(a - (float)ah) : ah;
   }
   out[idx] = o.u;
-  // the single-fp16 copy of the same fragments (F16X2 form of the kernel) behind the split-bf16 planes: uint4 index FRAG_BYTES / 16 + (((tap * 4 + ks) * 2 + cb) * 64 + lane)
+  // the single-fp16 copy (F16X2 form of the kernel, 32x32x16 fragments) behind the split-bf16 planes: uint4 index FRAG_BYTES / 16 +
+  // (((tap * 4 + ks) * 2 + cb) * 64 + lane), element j = w[cb*32 + (lane & 31)][tap][ks*16 + 8 (lane >> 5) + j] -- by the threads of plane 0, relabelled
   if (plane == 0) {
+    const int ks = 2 * kh + a;
+    const float* s16 = w + ((long long)(cb * 32 + (lane & 31)) * NTAP + tap) * CH + ks * 16 + 8 * (lane >> 5);
     union {
       _Float16 h[8];
       uint4 u;
     } q;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) q.h[j] = (_Float16)src[j];
+    for (int j = 0; j < 8; ++j) q.h[j] = (_Float16)s16[j];
     out[FRAG_BYTES / 16 + (((tap * 4 + ks) * 2 + cb) * 64 + lane)] = q.u;
   }
 }
@@ -88,14 +92,14 @@ __device__ __forceinline__ void conv5x5_rows4_body(const float* __restrict__ in,
   const float* inf = in + (long long)f * H * TW * CH;
   const int cb = wave & 1, rp = (wave >> 1) & 1, kh = wave >> 2;   // cout block, row pair, cin half
 
-  // ---- weight ring: slot = tap & 3 holds the tap's 2 k-steps x (hi, lo) of this wave's (cout block, cin half) ----
-  constexpr int RD = 6;   // ring depth in taps: RD - 1 in flight
-  bf16x8 ring[RD][2][2];   // (F16X2: [.][k][0] only, holding 8 fp16)
+  // ---- weight ring: slot = tap % RD holds the tap's 2 cout halves x (hi, lo) of this wave's (cout block, cin half) ----
+  constexpr int RD = F16X2 ? 6 : 5;   // ring depth in taps: RD - 1 in flight (3,000 cycles of MFMAs; a sixth slot of the 16x16x32 form spills a fragment)
+  bf16x8 ring[RD][2][2];   // (F16X2: [.][k-step][0] only, holding 8 fp16)
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wf), 0, 0x7fffffff, 0x00020000);
   // (every workgroup walks the taps in step -- all CUs of an XCD want the same 16 KB at the same time; four copies of the fragments read by
   //  alternate waves / workgroups, i.e. other L2 channels, changed nothing: profiles/r03_probes.txt section 12)
   const unsigned wbase = F16X2 ? (unsigned)(FRAG_BYTES + ((2 * kh) * 2 + cb) * 1024)            // + tap * 8 KB + ks2 * 2 KB
-                               : (unsigned)((((2 * kh) * 2 + cb) * 2) * 1024);                  // + tap * 16 KB + ks2 * 4 KB + plane * 1 KB
+                               : (unsigned)(((kh * 2 + cb) * 4) * 1024);                        // + tap * 16 KB + a * 2 KB + plane * 1 KB
   auto load_tap = [&](int tap) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -106,7 +110,7 @@ __device__ __forceinline__ void conv5x5_rows4_body(const float* __restrict__ in,
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
           ring[tap % RD][k][pl] = __builtin_bit_cast(
-              bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (unsigned)(lane * 16), wbase + (unsigned)(tap * 16384 + k * 4096 + pl * 1024), 0));
+              bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (unsigned)(lane * 16), wbase + (unsigned)(tap * 16384 + k * 2048 + pl * 1024), 0));
       }
     }
   };
@@ -150,22 +154,28 @@ __device__ __forceinline__ void conv5x5_rows4_body(const float* __restrict__ in,
   __syncthreads();
   CTS(2);
 
-  // ---- 25 taps, no barrier: acc[i] = (row 2 rp + (i >> 1), pixel block i & 1) x cout block cb over this wave's cin half ----
-  f32x16 acc[4];
+  // ---- 25 taps, no barrier: block i = (row 2 rp + (i >> 1), pixel block i & 1) x cout block cb over this wave's cin half; the accumulators of a
+  //      block are four 16 x 16 tiles [2 a + p] (cout half a, pixel parity p), or one 32 x 32 tile in the F16X2 form ----
+  f32x4 acc[4][4];
+  f32x16 acc16[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 4; ++i) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-  // the activation fragments of half-tap s + 1 are requested BEFORE the 12 MFMAs of half-tap s (two register buffers): the LDS
-  // latency sits under the matrix pipe instead of in front of every MFMA pair
-  const int x_lane = (lane & 31) * PS + 8 * (lane >> 5) + 32 * kh + 2 * rp * HWD * PS;
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc16[i][r] = 0.f;
+  }
+  // the activation fragments of half-tap s + 1 are requested BEFORE the MFMAs of half-tap s (two register buffers): the LDS
+  // latency sits under the matrix pipe instead of in front of every MFMA pair.  A half-tap is one pixel parity of a tap (the k-step s & 1 of it
+  // in the F16X2 form)
+  const int x_lane = (F16X2 ? (lane & 31) * PS + 8 * (lane >> 5) : 2 * (lane & 15) * PS + 8 * (lane >> 4)) + 32 * kh + 2 * rp * HWD * PS;
   bf16x8 xf[2][4][2];
   auto read_x = [&](int s, int buf) {
     const int tap = s >> 1, k = s & 1;
     const int ky = tap / KS, kx = tap - ky * KS;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int off = (((i >> 1) + ky) * HWD + (i & 1) * 32 + kx) * PS + k * 16;
+      const int off = (((i >> 1) + ky) * HWD + (i & 1) * 32 + kx) * PS + (F16X2 ? k * 16 : k * PS);
       xf[buf][i][0] = *(const bf16x8*)(Hh + x_lane + off);
       xf[buf][i][1] = *(const bf16x8*)(Hl + x_lane + off);
     }
@@ -180,24 +190,19 @@ __device__ __forceinline__ void conv5x5_rows4_body(const float* __restrict__ in,
       const f16x8 w = __builtin_bit_cast(f16x8, ring[tap % RD][k][0]);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, __builtin_bit_cast(f16x8, xf[s & 1][i][1]), acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, __builtin_bit_cast(f16x8, xf[s & 1][i][0]), acc[i], 0, 0, 0);
+        acc16[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, __builtin_bit_cast(f16x8, xf[s & 1][i][1]), acc16[i], 0, 0, 0);
+        acc16[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, __builtin_bit_cast(f16x8, xf[s & 1][i][0]), acc16[i], 0, 0, 0);
       }
       if (k == 0 && tap + RD - 1 < NTAP) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
       if (s + 1 < 2 * NTAP) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
     } else {
-      const bf16x8 wh = ring[tap % RD][k][0], wl = ring[tap % RD][k][1];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xf[s & 1][i][1], acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xf[s & 1][i][0], acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xf[s & 1][i][0], acc[i], 0, 0, 0);
-      }
-      // issue order inside the half-tap: the weight requests, the 8 fragment reads of the NEXT half-tap, then the 12 MFMAs
+      for (int i = 0; i < 4; ++i) sf_conv_half32(ring[tap % RD], xf[s & 1][i][0], xf[s & 1][i][1], acc[i][k], acc[i][2 + k]);
+      // issue order inside the half-tap: the weight requests, the 8 fragment reads of the NEXT half-tap, then the 24 MFMAs
       if (k == 0 && tap + RD - 1 < NTAP) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
       if (s + 1 < 2 * NTAP) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);
     }
     __builtin_amdgcn_sched_barrier(0);   // requests stay in their half-tap
     if (s == 9) CTS(3);
@@ -216,8 +221,9 @@ __device__ __forceinline__ void conv5x5_rows4_body(const float* __restrict__ in,
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      X[((wave * 2 + i) * 16 + r) * 64 + lane] = kh ? acc[i][r] : acc[2 + i][r];
-      fin[i][r] = kh ? acc[2 + i][r] : acc[i][r];
+      const float lo2 = F16X2 ? acc16[i][r] : acc[i][r >> 2][r & 3], hi2 = F16X2 ? acc16[2 + i][r] : acc[2 + i][r >> 2][r & 3];
+      X[((wave * 2 + i) * 16 + r) * 64 + lane] = kh ? lo2 : hi2;
+      fin[i][r] = kh ? hi2 : lo2;
     }
   __syncthreads();
   const int pw = wave ^ 4;   // the partner: same cout block and row pair, the other cin half
@@ -227,65 +233,73 @@ __device__ __forceinline__ void conv5x5_rows4_body(const float* __restrict__ in,
     for (int r = 0; r < 16; ++r) fin[i][r] += X[((pw * 2 + i) * 16 + r) * 64 + lane];
 
   if constexpr (HEAD) {
-    // ---- epilogue with the 1x1 head: s[j] = sum_c head_w[j][c] relu(y[c] + b[c]) over the lane's 16 channels, the other half wave's
-    //      (lane ^ 32), then the other cout block's (wave ^ 1) through LDS; cout block 0 adds head_b and stores 16 bytes per pixel ----
+    // ---- epilogue with the 1x1 head: s[j] = sum_c head_w[j][c] relu(y[c] + b[c]) over the lane's 8 channels of a pixel (two tiles of 4), the
+    //      other three quarter waves' (lane ^ 16, lane ^ 32), then the other cout block's (wave ^ 1) through LDS; cout block 0 adds head_b and
+    //      stores 16 bytes per pixel ----
     float* XH = (float*)lds + 16 * 1024;   // behind the 64 KB exchange of the cin halves: [rp * 2 + kh][i][32 pixels][4]
-    const int c0h = cb * 32 + 4 * (lane >> 5);
+    const int c0h = cb * 32 + 4 * (lane >> 4);
     const int yh = y0 + 2 * rp + kh;
-    f32x4 sums[2];
+    f32x4 sums[2][2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      f32x4 sj = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 bv = bias ? *(const f32x4*)(bias + c0h + 8 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int p = 0; p < 2; ++p) {
+        f32x4 sj = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float yv = fmaxf(fin[i][4 * g + q] + bv[q], 0.f);
+        for (int a = 0; a < 2; ++a) {
+          const f32x4 bv = bias ? *(const f32x4*)(bias + c0h + 16 * a) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int j = 0; j < 4; ++j) sj[j] = fmaf(yv, add[j * CH + c0h + 8 * g + q], sj[j]);
+          for (int q = 0; q < 4; ++q) {
+            const float yv = fmaxf(fin[i][4 * (2 * a + p) + q] + bv[q], 0.f);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sj[j] = fmaf(yv, add[j * CH + c0h + 16 * a + q], sj[j]);
+          }
         }
-      }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sj[j] += __shfl_xor(sj[j], 32, 64);
-      sums[i] = sj;
-      if (cb == 1 && lane < 32) *(f32x4*)(XH + (((rp * 2 + kh) * 2 + i) * 32 + lane) * 4) = sj;
-    }
+        for (int j = 0; j < 4; ++j) sj[j] += __shfl_xor(sj[j], 16, 64);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sj[j] += __shfl_xor(sj[j], 32, 64);
+        sums[i][p] = sj;
+        if (cb == 1 && lane < 16) *(f32x4*)(XH + (((rp * 2 + kh) * 2 + i) * 32 + 2 * lane + p) * 4) = sj;
+      }
     __syncthreads();
-    if (cb == 0 && lane < 32) {
+    if (cb == 0 && lane < 16) {
       const f32x4 hb = *(const f32x4*)head_b;
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const f32x4 oth = *(const f32x4*)(XH + (((rp * 2 + kh) * 2 + i) * 32 + lane) * 4);
-        *(f32x4*)(out + (((long long)f * H + yh) * TW + i * 32 + lane) * 4) = (sums[i] + oth) + hb;
-      }
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const f32x4 oth = *(const f32x4*)(XH + (((rp * 2 + kh) * 2 + i) * 32 + 2 * lane + p) * 4);
+          *(f32x4*)(out + (((long long)f * H + yh) * TW + i * 32 + 2 * lane + p) * 4) = (sums[i][p] + oth) + hb;
+        }
     }
     CTS(7);
     return;
   }
-  // ---- epilogue: bias, ReLU, optional per-position table, NHWC store (a lane holds 4 x 4 consecutive channels of one pixel) ----
+  // ---- epilogue: bias, ReLU, optional per-position table, NHWC store (piece g of a lane: 4 consecutive channels of one pixel -- tile (a, p) =
+  //      (g >> 1, g & 1): pixel 2 (lane & 15) + p, channels 16 a + 4 (lane >> 4) ..; F16X2: pixel lane & 31, channels 8 g + 4 (lane >> 5) ..) ----
   // relu == 2 (training, backward-data pass): `add` is the forward activation of the layer below, laid out like `out`, and
   // acts as its ReLU mask -- out = add > 0 ? conv : 0
   const bool mask = relu == 2;
   const float lo = relu == 1 ? 0.f : -INFINITY;
   const int y = y0 + 2 * rp + kh;
-  const int c0 = cb * 32 + 4 * (lane >> 5);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int px = i * 32 + (lane & 31);
-    const long long o = (((long long)f * H + y) * TW + px) * CH + c0;
-    const long long ao = ((long long)(mask ? f * H + y : y) * TW + px) * CH + c0;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const f32x4 bv = bias ? *(const f32x4*)(bias + c0 + 8 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
-      const f32x4 av = add ? *(const f32x4*)(add + ao + 8 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
+      const int px = i * 32 + (F16X2 ? (lane & 31) : 2 * (lane & 15) + (g & 1));
+      const int c0 = cb * 32 + (F16X2 ? 4 * (lane >> 5) + 8 * g : 4 * (lane >> 4) + 16 * (g >> 1));
+      const long long o = (((long long)f * H + y) * TW + px) * CH + c0;
+      const long long ao = ((long long)(mask ? f * H + y : y) * TW + px) * CH + c0;
+      const f32x4 bv = bias ? *(const f32x4*)(bias + c0) : f32x4{0.f, 0.f, 0.f, 0.f};
+      const f32x4 av = add ? *(const f32x4*)(add + ao) : f32x4{0.f, 0.f, 0.f, 0.f};
       f32x4 v;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float tv = fmaxf(fin[i][4 * g + q] + bv[q], lo);
         v[q] = mask ? (av[q] > 0.f ? tv : 0.f) : tv + av[q];
       }
-      *(f32x4*)(out + o + 8 * g) = v;
+      *(f32x4*)(out + o) = v;
     }
   }
   CTS(7);

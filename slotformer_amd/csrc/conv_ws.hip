@@ -7,16 +7,19 @@
 //   * a workgroup is four waves, one per SIMD, 512 registers each; wave = (cout block cb, cin half kh) keeps ITS 100 weight fragments (400 registers)
 //     for the whole launch: no weight traffic inside the loop at all;
 //   * a workgroup owns a contiguous range of output rows of the launch (frames x rows, any count) and walks it row by row: LDS holds a ring of six
-//     halo rows (two bf16 planes, 117 KB); while the 300 MFMAs of a row run, the row after the next window is loaded, split and written to the ring and
+//     halo rows (two bf16 planes, 117 KB); while the 600 MFMAs of a row run, the row after the next window is loaded, split and written to the ring and
 //     the previous row's results leave -- fill, exchange and epilogue ride under the matrix pipe instead of in front of it;
 //   * the two rows of zeros between two frames of the stream are shared by the frame above and the frame below (a frame change costs two exposed fills);
-//   * per row and wave 2 x 50 x (2 ds_read_b128 + 3 MFMA); the two cin halves of a pixel block meet through a double-buffered 16 KB exchange: a wave
-//     computes the block its partner finishes first, hands it over, keeps the accumulators of its own block and stores them one row later.
-// Same arithmetic as conv_rows4.hip bit for bit: per cin half taps ascending, k-steps ascending, x_lo w_hi + x_hi w_lo + x_hi w_hi, then half 0 + half 1,
-// bias, ReLU, per-position table.  Reads the fragment copy of sf_pack_conv_frag_weights unchanged.
+//   * per row and wave 2 x 50 steps of 6 MFMAs (16x16x32: one tap, one 16-pixel tile, both 16-cout halves, three passes).  A tile is the pixels of one
+//     parity of the block, so the odd tile of tap kx IS the even tile of tap kx + 1: 30 fragment pairs (60 ds_read_b128) per block feed the 50 steps;
+//   * the two cin halves of a pixel block meet through a double-buffered 16 KB exchange: a wave computes the block its partner finishes first, hands
+//     it over, keeps the accumulators of its own block and stores them one row later.
+// Same arithmetic as conv_rows4.hip bit for bit (sf_conv_tile16, split_bf16.h): per cin half taps ascending, one K = 32 step per tap,
+// x_lo w_hi + x_hi w_lo + x_hi w_hi, then half 0 + half 1, bias, ReLU, per-position table.  Reads the fragment copy of sf_pack_conv_frag_weights unchanged.
 // Reference call site: the encoder convs i > 0, savi.py:231-239 (+ SoftPositionEmbed add, utils.py:60-63).
 #include "sf_internal.h"
 #include <stdlib.h>
+#include <type_traits>
 
 extern "C" int sf_get_conv_fp16x2(void);
 namespace {
@@ -30,13 +33,19 @@ constexpr int PLANE_B = NR * ROWE * 2;            // 58,752 B
 constexpr int X_B = 4 * 16 * 64 * 4;              // one exchange buffer: [wave][16][64] f32 = 16 KB
 constexpr int LDS_B = 2 * PLANE_B + 2 * X_B + 256;      // 150,272 B (ring + the partner exchange + the wave's own parked block)
 static_assert(LDS_B <= 160 * 1024, "LDS budget");
-static_assert(PLANE_B + (32 + 4) * PS * 2 + 64 < 65536, "lo-plane reads stay inside the ds immediate offset");
+static_assert(PLANE_B + (KS + 1) * PS * 2 + 64 < 65536, "lo-plane reads stay inside the ds immediate offset");
 }  // namespace
+
+template <int I, int N, class F>
+__device__ __forceinline__ void ws_static_for(F&& f) {   // f(integral_constant I), ..., f(integral_constant N - 1)
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    ws_static_for<I + 1, N>(f);
+  }
+}
 
 __device__ long long cw_ts[16];   // phase time stamps of workgroup 0 (SF_DBG=conv; sf_debug_read_ts_conv_ws)
 #define WTS(i) do { if (dbg && blockIdx.x == 0 && threadIdx.x == 0) cw_ts[i] = wall_clock64(); } while (0)
-
-#define WS_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 
 struct CwArgs {
   const float* in;
@@ -83,15 +92,22 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) hv[i] = *(const f32x4*)(src + 4 * (t + NT * (2 * half + i)));
   };
-  auto fill_write = [&](int slot, bool zero, int half, const f32x4 (&hv)[2]) __attribute__((always_inline)) {
-    __bf16* rh = Hh + slot * ROWE + fill_off + 32 * half * PS;
+  // ... written in two stages per float4 (the hi plane, then the lo plane: hv[i] becomes the residual in between) so that the row loop can place
+  // them in separate steps: an MFMA of 16 cycles hides two VALU instructions, not a clump of thirty
+  auto fill_write_hi = [&](int slot, bool zero, int half, int i, f32x4 (&hv)[2]) __attribute__((always_inline)) {
+    const f32x4 x = zero ? f32x4{0.f, 0.f, 0.f, 0.f} : hv[i];
+    const bf16x4 hi = __builtin_convertvector(x, bf16x4);
+    *(bf16x4*)(Hh + slot * ROWE + fill_off + (32 * half + 16 * i) * PS) = hi;
+    hv[i] = x - __builtin_convertvector(hi, f32x4);
+  };
+  auto fill_write_lo = [&](int slot, int half, int i, const f32x4 (&hv)[2]) __attribute__((always_inline)) {
+    *(bf16x4*)(Hh + slot * ROWE + fill_off + (32 * half + 16 * i) * PS + NR * ROWE) = __builtin_convertvector(hv[i], bf16x4);
+  };
+  auto fill_write = [&](int slot, bool zero, int half, f32x4 (&hv)[2]) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const f32x4 x = zero ? f32x4{0.f, 0.f, 0.f, 0.f} : hv[i];
-      const bf16x4 hi = __builtin_convertvector(x, bf16x4);
-      const bf16x4 lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x4), bf16x4);
-      *(bf16x4*)(rh + 16 * i * PS) = hi;
-      *(bf16x4*)(rh + 16 * i * PS + NR * ROWE) = lo;
+      fill_write_hi(slot, zero, half, i, hv);
+      fill_write_lo(slot, half, i, hv);
     }
   };
   auto fill_sync = [&](int f, int r, int slot) __attribute__((always_inline)) {
@@ -106,15 +122,15 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
   };
   auto wrap = [&](int slot) __attribute__((always_inline)) -> int { return slot >= NR ? slot - NR : slot; };
 
-  // B-operand address of a lane inside a ring row (bytes): pixel (lane & 31) [+ 32 pb + kx], cin 32 kh + 8 (lane >> 5) [+ 16 k]
-  const unsigned lane_b = (unsigned)(((lane & 31) * PS + 32 * kh + 8 * (lane >> 5)) * 2);
+  // B-operand address of a lane inside a ring row (bytes): pixel 2 (lane & 15) [+ 32 pb + kx + p], cin 32 kh + 8 (lane >> 4)
+  const unsigned lane_b = (unsigned)((2 * (lane & 15) * PS + 32 * kh + 8 * (lane >> 4)) * 2);
   const int ob = kh;                      // the pixel block this wave finishes (its partner, wave ^ 2, finishes the other one)
-  // exchange [which][wave][r4][lane][4] f32, 16-byte accesses, lane-contiguous.  which 0: the accumulators of the block the partner finishes (read by
+  // exchange [which][wave][tile 2 a + p][lane][4] f32, 16-byte accesses, lane-contiguous.  which 0: the accumulators of the block the partner finishes (read by
   // the partner), which 1: those of the wave's own block (read back by itself one row later: no accumulators live across rows)
   float* Xw = X + wave * 1024 + lane * 4;
   const float* Xp = X + (wave ^ 2) * 1024 + lane * 4;
   float* Xo = X + 4096 + wave * 1024 + lane * 4;
-  const int c0 = cb * 32 + 4 * (lane >> 5);
+  const int c0 = cb * 32 + 4 * (lane >> 4);   // + 16 a: accumulator tile (a, p) of a lane = couts c0 + 16 a .. + 3 of pixel 2 (lane & 15) + p
   const float lo_clip = A.relu == 1 ? 0.f : -INFINITY;
 
   // the first window
@@ -122,7 +138,7 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
   int slot0 = 0;   // ring slot of stream row s0 (the stream is renumbered from this workgroup's first row)
   {
     // (all five rows requested before the first is converted: one memory latency, not five)
-    f32x4 hw[5][2][2];
+    f32x4 hw[5][2][2];   // (not const: fill_write leaves the residuals in it)
     bool zw[5];
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
@@ -142,59 +158,64 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
   }
   __syncthreads();
   WTS(1);
-  // ---- the wave's weights: 25 taps x 2 k-steps x (hi, lo) of (cout block cb, cin half kh); requested behind the first window so that the fill's
+  // ---- the wave's weights: 25 taps x 2 cout halves x (hi, lo) of (cout block cb, cin half kh); requested behind the first window so that the fill's
   //      registers are free again (the compiler spilled half of the fragments around it otherwise) ----
   bf16x8 wt[NTAP][2][2];
   {
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(A.wf), 0, 0x7fffffff, 0x00020000);
-    const unsigned wbase = (unsigned)((((2 * kh) * 2 + cb) * 2) * 1024);   // + tap * 16 KB + k * 4 KB + plane * 1 KB
+    const unsigned wbase = (unsigned)(((kh * 2 + cb) * 4) * 1024);   // + tap * 16 KB + a * 2 KB + plane * 1 KB
 #pragma unroll
     for (int tap = 0; tap < NTAP; ++tap)
 #pragma unroll
-      for (int k = 0; k < 2; ++k)
+      for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
-          wt[tap][k][pl] = __builtin_bit_cast(
-              bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (unsigned)(lane * 16), wbase + (unsigned)(tap * 16384 + k * 4096 + pl * 1024), 0));
+          wt[tap][a][pl] = __builtin_bit_cast(
+              bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (unsigned)(lane * 16), wbase + (unsigned)(tap * 16384 + a * 2048 + pl * 1024), 0));
   }
 
   // (the "previous row" of the first row is that row itself: its epilogue stores garbage where the row's own epilogue, one row later, stores the
   //  results -- same lanes, same addresses, program order; no branch in the loop)
   int fp = f, yp = y;
 
-  // one pixel block of one output row: 50 steps of (2 fragment reads, 3 MFMAs); side(s) is issued in front of step s's MFMAs
+  // one pixel block of one output row: 50 steps (tap, pixel parity p) of 6 MFMAs; side(s) is issued in front of step s's MFMAs.  Step (ky, kx, p)
+  // takes fragment pair 6 ky + kx + p (the tile at pixel offset kx + p of ring row ky): each pair is read once and serves two consecutive steps.
 #ifndef WS_PF
 #define WS_PF 2
 #endif
-  auto block = [&](const unsigned (&ra)[5], int pb, f32x16& acc, auto&& side) __attribute__((always_inline)) {
+  auto block = [&](const unsigned (&ra)[5], int pb, f32x4 (&acc)[2][2], auto&& side) __attribute__((always_inline)) {
     const unsigned pbo = (unsigned)(pb * 32 * PS * 2);
-    constexpr int PF = WS_PF, NB = PF + 1;   // fragment reads issued PF steps ahead
+    constexpr int PF = WS_PF, NB = PF + 1;   // the pair of step s + PF is requested in front of step s: at most NB pairs are live
+    constexpr int NFR = KS * (KS + 1);
     bf16x8 xh[NB], xl[NB];
-    auto rd = [&](int s, int buf) __attribute__((always_inline)) {
-      const int tap = s >> 1, k = s & 1, ky = tap / KS, kx = tap - ky * KS;
+    auto frag_of = [](int s) constexpr -> int { const int tap = s >> 1, ky = tap / KS; return ky * (KS + 1) + (tap - ky * KS) + (s & 1); };
+    auto rd = [&](int fr) __attribute__((always_inline)) {
+      const int ky = fr / (KS + 1), off = fr - ky * (KS + 1);
       const char* p = lds_raw + (ra[ky] + pbo);
-      xl[buf] = *(const bf16x8*)(p + (kx * PS + 16 * k) * 2 + PLANE_B);
-      xh[buf] = *(const bf16x8*)(p + (kx * PS + 16 * k) * 2);
+      xl[fr % NB] = *(const bf16x8*)(p + off * PS * 2 + PLANE_B);
+      xh[fr % NB] = *(const bf16x8*)(p + off * PS * 2);
     };
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int s = 0; s < PF; ++s) rd(s, s % NB);
-#pragma unroll
-    for (int s = 0; s < 2 * NTAP; ++s) {
-      const int tap = s >> 1, k = s & 1;
-      if (s + PF < 2 * NTAP) rd(s + PF, (s + PF) % NB);
+      for (int p = 0; p < 2; ++p) acc[a][p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // (compile-time steps, not an unrolled loop: every register index below is a constant by construction -- a loop the unroller gives up on,
+    //  its body is large, would put the 400 weight registers into scratch)
+    auto want = [=](int s) constexpr -> int { return s < 0 ? -1 : s + PF < 2 * NTAP ? frag_of(s + PF) : NFR - 1; };
+    ws_static_for<0, frag_of(PF - 1) + 1>([&](auto FR) __attribute__((always_inline)) { rd(FR); });
+    ws_static_for<0, 2 * NTAP>([&](auto S) __attribute__((always_inline)) {
+      constexpr int s = S, tap = s >> 1, p = s & 1, fr = frag_of(s);
+      constexpr int first = s == 0 ? frag_of(PF - 1) + 1 : want(s - 1) + 1;
+      ws_static_for<first, want(s) + 1>([&](auto FR) __attribute__((always_inline)) { rd(FR); });
 #ifndef WS_NOSB
       __builtin_amdgcn_sched_barrier(0);
 #endif
       side(s);
-      acc = WS_MFMA(wt[tap][k][0], xl[s % NB], acc);
-      acc = WS_MFMA(wt[tap][k][1], xh[s % NB], acc);
-      acc = WS_MFMA(wt[tap][k][0], xh[s % NB], acc);
+      sf_conv_half32(wt[tap], xh[fr % NB], xl[fr % NB], acc[0][p], acc[1][p]);
 #ifndef WS_NOSB
       __builtin_amdgcn_sched_barrier(0);
 #endif
-    }
+    });
   };
 
   // the epilogue of the previous row's own block: own half + the partner's, bias, ReLU, per-position table, NHWC store -- four pieces of four channels,
@@ -202,23 +223,25 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
   // of the steps in between (a wave that waits for them at once drains its LDS queue in front of every piece: 1400-3300 cycles per row)
   f32x4 e_oth, e_own, e_bv, e_av = {0.f, 0.f, 0.f, 0.f};
   auto epilogue_request = [&](int g, int yq) __attribute__((always_inline)) {
-    const int px = ob * 32 + (lane & 31);
+    const int px = ob * 32 + 2 * (lane & 15) + (g & 1);   // piece g = accumulator tile (a, p) = (g >> 1, g & 1)
     e_oth = *(const f32x4*)(Xp + g * 256);
     e_own = *(const f32x4*)(Xo + g * 256);
-    e_bv = *(const f32x4*)(Bs + c0 + 8 * g);
-    if constexpr (ADD) e_av = *(const f32x4*)(A.add + ((long long)yq * TW + px) * CH + c0 + 8 * g);
+    e_bv = *(const f32x4*)(Bs + c0 + 16 * (g >> 1));
+    if constexpr (ADD) e_av = *(const f32x4*)(A.add + ((long long)yq * TW + px) * CH + c0 + 16 * (g >> 1));
   };
-  auto epilogue_store = [&](int g, int fq, int yq) __attribute__((always_inline)) {
-    const int px = ob * 32 + (lane & 31);
-    f32x4 v;
+  auto epilogue_sum = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int q = 0; q < 4; ++q)   // (half 0 + half 1; float addition commutes, so both waves of a pair produce the bits of conv_rows4.hip)
-      v[q] = fmaxf((e_own[q] + e_oth[q]) + e_bv[q], lo_clip) + e_av[q];
-    *(f32x4*)(A.out + (((long long)(fq * H + yq) * TW) + px) * CH + c0 + 8 * g) = v;
+      e_own[q] = fmaxf((e_own[q] + e_oth[q]) + e_bv[q], lo_clip) + e_av[q];
   };
-  auto put_acc = [&](float* dst, const f32x16& acc) __attribute__((always_inline)) {
+  auto epilogue_store = [&](int g, int fq, int yq) __attribute__((always_inline)) {
+    const int px = ob * 32 + 2 * (lane & 15) + (g & 1);
+    const f32x4 v = e_own;
+    *(f32x4*)(A.out + (((long long)(fq * H + yq) * TW) + px) * CH + c0 + 16 * (g >> 1)) = v;
+  };
+  auto put_acc = [&](float* dst, const f32x4 (&acc)[2][2]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) *(f32x4*)(dst + r4 * 256) = f32x4{acc[4 * r4], acc[4 * r4 + 1], acc[4 * r4 + 2], acc[4 * r4 + 3]};
+    for (int g = 0; g < 4; ++g) *(f32x4*)(dst + g * 256) = acc[g >> 1][g & 1];
   };
 
   const int nrows = (int)(g1 - g0);
@@ -253,7 +276,7 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
     const int fslot = wrap(slot0 + 5);
     const int fq = fp, yq = yp;
     f32x4 hv[2];
-    f32x16 acc;
+    f32x4 acc[2][2];
     // ---- the block the partner finishes; beside it the previous row leaves and the first half of the fill arrives ----
     block(ra, 1 - ob, acc, [&](int s) __attribute__((always_inline)) {
 #ifdef WS_NOSIDE
@@ -261,8 +284,10 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
 #endif
       if (s == 0) fill_load(fsrc, 0, hv);
       if (s >= 2 && s < 42 && (s - 2) % 10 == 0) epilogue_request((s - 2) / 10, yq);
+      if (s >= 9 && s < 49 && s % 10 == 9) epilogue_sum();
       if (s >= 10 && s < 50 && s % 10 == 0) epilogue_store(s / 10 - 1, fq, yq);
-      if (s == 44) fill_write(fslot, fzero, 0, hv);
+      if (s == 41 || s == 45) fill_write_hi(fslot, fzero, 0, (s - 41) >> 2, hv);
+      if (s == 43 || s == 47) fill_write_lo(fslot, 0, (s - 43) >> 2, hv);
     });
 #ifdef WS_STAMPS
     const long long k1 = WS_CLK();
@@ -280,7 +305,8 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
       return;
 #endif
       if (s == 0) fill_load(fsrc, 1, hv);
-      if (s == 40) fill_write(fslot, fzero, 1, hv);
+      if (s == 37 || s == 41) fill_write_hi(fslot, fzero, 1, (s - 37) >> 2, hv);
+      if (s == 39 || s == 43) fill_write_lo(fslot, 1, (s - 39) >> 2, hv);
     });
     put_acc(Xo, acc);
     fp = f;
@@ -310,6 +336,7 @@ __global__ __launch_bounds__(NT) void conv5x5_ws_kernel(CwArgs A) {
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     epilogue_request(g, yp);
+    epilogue_sum();
     epilogue_store(g, fp, yp);
   }
   WTS(3);

@@ -50,6 +50,38 @@ __device__ __forceinline__ bf16x8 ps_frag(const uint4* p, int nblocks, int nb, i
   return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 16, ((ks * nblocks + nb) * 2 + pl) * 1024, 0));
 }
 
+// ---- the product of the 5 x 5 / 64 -> 64 convolutions (conv_ws.hip, conv_rows4.hip, conv_halo.hip): THE definition of its order ----
+// One tap over one 32-channel half of the input channels is ONE K = 32 step of v_mfma_f32_16x16x32_bf16 per 16 x 16 tile (16 couts x 16 pixels),
+// three passes in this order: x_lo w_hi, x_hi w_lo, x_hi w_hi.  Around it every kernel walks the taps ascending per cin half and adds half 0 + half 1
+// last.  The chip holds a higher clock on this shape than on 32x32x16 at equal cycles per FLOP (profiles/conv_mfma_shape.md).
+// Operand of a lane: row-or-column (lane & 15) of the tile, channels 8 (lane >> 4) .. + 7 of the half.  Which 16 pixels (couts) make a tile is the
+// caller's: all three kernels take the pixels of one parity of a 32-pixel block, 2 (lane & 15) + p, which keeps ds_read_b128 at the 144-byte pixel
+// pitch conflict-free (consecutive pixels put lanes 0-3 / 12-15 and 20-27 of a 16-lane read group on the same banks).
+// W_IS_A: the weights are the A operand -- accumulator register q of a lane = cout 4 (lane >> 4) + q, pixel lane & 15; else the transpose.
+template <bool W_IS_A = true>
+__device__ __forceinline__ void sf_conv_tile16(const bf16x8 wh, const bf16x8 wl, const bf16x8 xh, const bf16x8 xl, f32x4& acc) {
+  if constexpr (W_IS_A) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh, acc, 0, 0, 0);
+  } else {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wh, acc, 0, 0, 0);
+  }
+}
+// 32 couts (two tiles a; w[a][0] hi, w[a][1] lo) x one 16-pixel tile, and the whole 32-cout x 32-pixel block of a tap (pixel tiles p; acc[a][p])
+template <bool W_IS_A = true>
+__device__ __forceinline__ void sf_conv_half32(const bf16x8 (&w)[2][2], const bf16x8 xh, const bf16x8 xl, f32x4& acc0, f32x4& acc1) {
+  sf_conv_tile16<W_IS_A>(w[0][0], w[0][1], xh, xl, acc0);
+  sf_conv_tile16<W_IS_A>(w[1][0], w[1][1], xh, xl, acc1);
+}
+template <bool W_IS_A = true>
+__device__ __forceinline__ void sf_conv_block32(const bf16x8 (&w)[2][2], const bf16x8 (&xh)[2], const bf16x8 (&xl)[2], f32x4 (&acc)[2][2]) {
+#pragma unroll
+  for (int p = 0; p < 2; ++p) sf_conv_half32<W_IS_A>(w, xh[p], xl[p], acc[0][p], acc[1][p]);
+}
+
 // one 32x32 output tile, C[i][j] = sum_k a(i, k) b(k, j), operands read from LDS through the (row, k) -> value functors; the accumulator's
 // register r holds row MM_ROW(r, lane), column lane & 31.
 // BF3 = false: exact-f32 MFMA (32x32x2, 64 cycles per 2 k).  BF3 = true (library precision modes 1 / 2): the operands are
