@@ -71,6 +71,13 @@ int sf_layernorm_f32(const float* x, const float* gamma, const float* beta, floa
 int sf_conv2d_nchw_in_f32(const float* img, long long frame_stride, const float* weight, const float* bias,
                           const float* add, float* out, int F, int Cin, int Hin, int Win, int Cout, int ks,
                           int stride, int relu, void* stream);
+/* The same convolution with the frames in groups, as the batched encode launches it for all time steps of a [B][T] clip at once: output frame i reads
+ * the image at img + (i % fgroup) * frame_stride + (i / fgroup) * group_stride floats.  Only the shapes of the persistent kernel (csrc/conv_first.hip:
+ * 3 -> 64 channels, 5 x 5, 64 x 64 at stride 1 or 128 x 128 at stride 2; split-bf16 mode); anything else is an error, there is no generic grouped
+ * path.  The kernel walks its tiles on 2 * sf_stream_cus(stream) workgroups. */
+int sf_conv2d_nchw_in_grouped_f32(const float* img, long long frame_stride, int fgroup, long long group_stride, const float* weight,
+                                  const float* bias, const float* add, float* out, int F, int Cin, int Hin, int Win, int Cout, int ks,
+                                  int stride, int relu, void* stream);
 
 /* Encoder convs i > 0 (savi.py:231-239): stride 1, padding ks/2, NHWC in -> NHWC out,
  * w_packed [Cout,ks,ks,Cin] (sf_pack_conv_weight_f32); `add` as above (used for the soft
@@ -86,7 +93,10 @@ int sf_pack_conv_weight_f32(const float* w_oihw, float* w_ohwi, int Cout, int Ci
 /* Per-pixel chain of the SAVi encoder up to the normalised Slot-Attention inputs (64 -> 128 -> 128 channels; savi.py:245-250, 66-70):
  * feat [M][128] = LN(fc2(relu(fc1(LN(x))))), x [M][64]; torch-layout weights w1 [128][64], w2 [128][128].  form 0: one 128-pixel tile per
  * workgroup, weights through LDS; form 1: weights resident in registers, four tiles per workgroup; form 2 (the one the encode uses): the same on
- * 64-pixel tiles with 256 threads, two workgroups per CU (csrc/pixel_mlp.hip).  Same bits. */
+ * 64-pixel tiles with 256 threads, two workgroups per CU (csrc/pixel_mlp.hip).  Same bits.  form 3: the pixel-stationary kernel (sf_set_pixel_tok
+ * below; another summation order), on at most sf_stream_cus(stream) workgroups.  form 4: `feat` is M rows of 512 bytes instead, bf16 hi | bf16 lo of
+ * the 128 channels (hi = bf16(y), lo = bf16(y - hi), round to nearest even), written by the launch the encode uses for them: form 3's kernel under
+ * sf_set_pixel_tok(1), form 2's under sf_set_pixel_tok(0). */
 int sf_pixel_feat_f32(const float* x, const float* ln0_g, const float* ln0_b, const float* w1, const float* b1, const float* w2,
                       const float* b2, const float* ln1_g, const float* ln1_b, float* feat, int M, float eps, int form, void* stream);
 size_t sf_conv_frag_bytes(int Cout, int Cin, int ks);
@@ -288,6 +298,21 @@ int sf_slot_attn_num_partials(int HW);
 int sf_slot_attn_iter_f32(const float* k, const float* v, int ld, long long batch_stride, const float* q,
                           float* part_num, float* part_den, float* attn_out, int B, int HW, int N, int D,
                           float scale, float eps, void* stream);
+/* The same iteration on keys == values kept as rows of 512 bytes (bf16 hi | lo of 128 channels: sf_pixel_feat_f32 form 4), the default of the encode
+ * (sa_attn_planes_kernel, csrc/slot_chain.hip; sf_set_slot_attn_planes below).  Frame b starts batch_stride_rows rows behind frame b - 1; slot size 128,
+ * HW a multiple of 512, 1 <= N <= 8.  P = HW / 256 records per frame: record 2c holds the sums over pixels 512 c .. 512 c + 511, the odd records are
+ * zero.  attn_out NULL or [B][N][HW] with attn_batch_stride floats between frames. */
+int sf_slot_attn_iter_planes_f32(const void* planes, long long batch_stride_rows, const float* q, float* part_num, float* part_den,
+                                 float* attn_out, long long attn_batch_stride, int B, int HW, int N, float scale, float eps, void* stream);
+/* The slots of a time step before its first iteration, as one launch (sa_slot_prologue_kernel, csrc/slot_attn.hip; savi.py:393-402, predictor.py:65-73,
+ * project_q): lat = prev NULL ? init[row % N] : ResidualMLPPredictor(prev); kernel_dist = Linear(lat) [2D]; slots = mu (+ noise * exp(logvar / 2));
+ * q = project_q(slots).  Exact f32.  Matrices TRANSPOSED ([in][out]): pm_w0_t [D][2D], pm_w2_t [2D][D], kd_w_t [D][2D], q_w_t [D][D].  noise row (b, n)
+ * at noise + b * noise_bs + n * D, kdist_out row (b, n) at kdist_out + b * kdist_bs + n * 2D (either may be NULL).  D a multiple of 64, at most 384. */
+int sf_slot_prologue_f32(const float* prev, const float* init, const float* pm_ln_g, const float* pm_ln_b, const float* pm_w0_t,
+                         const float* pm_b0, const float* pm_w2_t, const float* pm_b2, int norm_first, const float* kd_w_t,
+                         const float* kd_b, const float* noise, long long noise_bs, float* kdist_out, long long kdist_bs,
+                         const float* q_ln_g, const float* q_ln_b, const float* q_w_t, float* slots_out, float* q_out, int B, int N,
+                         int D, float ln_eps, void* stream);
 
 /* bf16-STORAGE variant (SURVEY.md 8(b2) `sf_slot_attn_iter_bf16`): k, v are bf16 rows (ld / batch_stride in elements), half the
  * bytes of this HBM-bound kernel; logits, softmax, the weighted sums and every output stay f32.  Rounding K/V to bf16 costs
@@ -339,6 +364,21 @@ int sf_slot_update_packed_f32(const float* part_num, const float* part_den, int 
                               const float* mlp_b1, const void* mlp_w2_packed, const float* mlp_b2, float* slots_out,
                               const float* q_ln_g, const float* q_ln_b, const void* q_w_packed, float* q_out, int B, int N,
                               int D, int H, float ln_eps, void* stream);
+/* The same (D = 128, H = 256 only) the way the encode launches a time step's last iteration: out2 NULL or a second copy of the rows, row (b, n) at
+ * out2 + b * out2_bs + n * D; p_step 1 or 2: only every p_step-th partial record is read (2: the even ones, what sf_slot_attn_iter_planes_f32 fills);
+ * and, next_slots not NULL, the NEXT form: behind the update the same workgroups run the slot prologue of the following step on the updated rows --
+ * ResidualMLPPredictor (pm_*, norm_first), kernel_dist Linear (kd_*), sampling with noise (row (b, n) at noise + b * noise_bs + n * D, or NULL) -> next_slots
+ * [B * N][D] (not slots_out), kdist_out (row (b, n) at kdist_out + b * kdist_bs + n * 2D, or NULL), and q_out = project_q(next_slots) instead of
+ * project_q(slots_out).  pm_w0_packed / pm_w2_packed / kd_w_packed: sf_pack_linear_weights copies of the torch-layout [2D][D], [D][2D], [2D][D]. */
+int sf_slot_update_packed_next_f32(const float* part_num, const float* part_den, int P, const float* slots_prev,
+                                   const void* gru_ih_packed, const void* gru_hh_packed, const float* gru_b_ih,
+                                   const float* gru_b_hh, const float* ln_g, const float* ln_b, const void* mlp_w1_packed,
+                                   const float* mlp_b1, const void* mlp_w2_packed, const float* mlp_b2, float* slots_out,
+                                   const float* q_ln_g, const float* q_ln_b, const void* q_w_packed, float* q_out, int B, int N,
+                                   int D, int H, float ln_eps, float* out2, long long out2_bs, int p_step, const float* pm_ln_g,
+                                   const float* pm_ln_b, const void* pm_w0_packed, const float* pm_b0, const void* pm_w2_packed,
+                                   const float* pm_b2, int norm_first, const void* kd_w_packed, const float* kd_b, const float* noise,
+                                   long long noise_bs, float* kdist_out, long long kdist_bs, float* next_slots, void* stream);
 
 /* nn.MultiheadAttention core for short sequences: qkv [B*L,3d] (q|k|v), out [B*Lq,d]; queries
  * are the last Lq rows of each sequence (Lq == L: all). */
@@ -904,7 +944,9 @@ int sf_set_slot_chain(int on);
 int sf_get_slot_chain(void);
 /* The Slot-Attention iterations of sf_savi_encode_* (folded form, slot size 128, 4096 pixels) on feature rows kept as bf16 hi | lo: logits and weighted sums as
  * split-bf16 v_mfma_f32_16x16x32_bf16 products (sa_attn_planes_kernel, csrc/slot_chain.hip) instead of exact-f32 16x16x4 MFMAs on f32 rows
- * (sa_attn_tile_kernel) -- a third of the matrix-pipe time, the same records, split-bf16 rounding apart (~5e-6).  Process default 1; 0: the f32 rows. */
+ * (sa_attn_tile_kernel) -- a third of the matrix-pipe time, the same records, split-bf16 rounding apart.  That rounding grows with the logit scale: measured against float64 on N(0, 1)
+ * rows, the attention is ~5e-6 off at logits of std 1, 4e-5 at std 8 and 1.5e-4 at std 32 (near one-hot softmax; the f32 rows: 5e-7 / 3e-6 / 8e-6), the
+ * updates within 8e-6 at every scale (tests/test_encode_kernels_gpu.py, profiles/encode_kernel_tests.md).  Process default 1; 0: the f32 rows. */
 int sf_set_slot_attn_planes(int on);
 int sf_get_slot_attn_planes(void);
 /* The per-pixel chain of the encoder (encoder_out_layer + SlotAttention.norm_inputs, savi.py:245-250, 66; 64 -> 128 -> 128 channels) in its pixel-stationary

@@ -144,6 +144,7 @@ SIGNATURES = {
     'sf_linear_f32': (I, [FP, I, FP, FP, FP, FP, F32, FP, I, FP, I, I, I, I, I, VP]),
     'sf_layernorm_f32': (I, [FP, FP, FP, FP, I, I, F32, VP]),
     'sf_conv2d_nchw_in_f32': (I, [FP, LL, FP, FP, FP, FP, I, I, I, I, I, I, I, I, VP]),
+    'sf_conv2d_nchw_in_grouped_f32': (I, [FP, LL, I, LL, FP, FP, FP, FP, I, I, I, I, I, I, I, I, VP]),
     'sf_conv2d_nhwc_f32': (I, [FP, FP, FP, FP, FP, I, I, I, I, I, I, I, VP]),
     'sf_pack_conv_weight_f32': (I, [FP, FP, I, I, I, VP]),
     'sf_pixel_feat_f32': (I, [FP] * 10 + [I, F32, I, VP]),
@@ -191,6 +192,10 @@ SIGNATURES = {
     'sf_slot_attn_iter_f32': (I, [FP, FP, I, LL, FP, FP, FP, FP, I, I, I, I, F32, F32, VP]),
     'sf_slot_update_f32': (I, [FP, FP, I, FP] + [FP] * 10 + [FP, I, I, I, I, F32, VP]),
     'sf_slot_update_packed_f32': (I, [FP, FP, I, FP, VP, VP, FP, FP, FP, FP, VP, FP, VP, FP, FP, FP, FP, VP, FP, I, I, I, I, F32, VP]),
+    'sf_slot_attn_iter_planes_f32': (I, [VP, LL, FP, FP, FP, FP, LL, I, I, I, F32, F32, VP]),
+    'sf_slot_prologue_f32': (I, [FP] * 8 + [I, FP, FP, FP, LL, FP, LL, FP, FP, FP, FP, FP, I, I, I, F32, VP]),
+    'sf_slot_update_packed_next_f32': (I, [FP, FP, I, FP, VP, VP, FP, FP, FP, FP, VP, FP, VP, FP, FP, FP, FP, VP, FP, I, I, I, I, F32,
+                                           FP, LL, I, FP, FP, VP, FP, VP, FP, I, VP, FP, FP, LL, FP, LL, FP, VP]),
     'sf_mha_f32': (I, [FP, FP, I, I, I, I, I, VP]),
     'sf_qkv_attention_f32': (I, [FP, FP, FP, F32, FP, FP, FP, I, I, I, I, I, VP]),
     'sf_lstm_pointwise_f32': (I, [FP, FP, FP, FP, I, I, VP]),

@@ -184,3 +184,15 @@ int sf_conv_first_grouped_ex(const float* img, long long frame_stride, int fgrou
   if (stride == 1 && Hin == 64 && Win == 64) return launch_cf<1>(img, frame_stride, w, bias, add, out, F, 64, Hin, Win, relu, fgroup, group_stride, st);
   return 1;
 }
+
+// C ABI (include/slotformer_hip.h): the grouped launch by itself.  There is no generic grouped path: a shape the kernel does not take is an error.
+extern "C" int sf_conv2d_nchw_in_grouped_f32(const float* img, long long frame_stride, int fgroup, long long group_stride, const float* weight,
+                                             const float* bias, const float* add, float* out, int F, int Cin, int Hin, int Win, int Cout, int ks,
+                                             int stride, int relu, void* stream) {
+  SF_REQUIRE(img && weight && out, "sf_conv2d_nchw_in_grouped_f32: null pointer");
+  SF_REQUIRE(sf_get_precision() >= 1, "sf_conv2d_nchw_in_grouped_f32: split-bf16 mode only");
+  const int rc = sf_conv_first_grouped_ex(img, frame_stride, fgroup, group_stride, weight, bias, add, out, F, Cin, Hin, Win, Cout, ks, stride, relu,
+                                          (hipStream_t)stream);
+  SF_REQUIRE(rc != 1, "sf_conv2d_nchw_in_grouped_f32: 3 -> 64 channels, 5 x 5, 64 x 64 at stride 1 or 128 x 128 at stride 2, F >= 1, fgroup >= 1");
+  return rc;
+}

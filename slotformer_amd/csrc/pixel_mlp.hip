@@ -942,13 +942,15 @@ int sf_pixel_mlp_feat_planes_ex(const float* x, const float* ln0_g, const float*
 // Kernel-level entry point (include/slotformer_hip.h): feat [M][128] = LN(128)(fc2(relu(fc1(LN(64)(x))))) -- encoder_out_layer followed by
 // SlotAttention.norm_inputs (savi.py:245-250, 66-70).  form 0: one 128-pixel tile per workgroup, weights through LDS; 1: weights resident in
 // registers, four tiles per workgroup; 2: the same on 64-pixel tiles, 256 threads, two workgroups per CU (0-2: the same bits); 3: pixel-stationary
-// (pixel_feat_tok_kernel: another summation order, split-bf16 rounding apart).
+// (pixel_feat_tok_kernel: another summation order, split-bf16 rounding apart); 4: feat is M rows of 512 B, bf16 hi | lo of the 128 channels, written the way
+// the encode writes them (sf_pixel_mlp_feat_planes_ex: form 3's kernel under sf_set_pixel_tok(1), form 2's under 0).
 extern "C" int sf_pixel_feat_f32(const float* x, const float* ln0_g, const float* ln0_b, const float* w1, const float* b1, const float* w2,
                                  const float* b2, const float* ln1_g, const float* ln1_b, float* feat, int M, float eps, int form, void* stream) {
   SF_REQUIRE(x && ln0_g && ln0_b && w1 && b1 && w2 && b2 && ln1_g && ln1_b && feat && M > 0, "sf_pixel_feat_f32: null pointer / empty problem");
-  SF_REQUIRE(form >= 0 && form <= 3, "sf_pixel_feat_f32: form must be 0 .. 3");
+  SF_REQUIRE(form >= 0 && form <= 4, "sf_pixel_feat_f32: form must be 0 .. 4");
   SF_REQUIRE(sf_get_precision() == 1, "sf_pixel_feat_f32: split-bf16 mode only");
   hipStream_t st = (hipStream_t)stream;
+  if (form == 4) return sf_pixel_mlp_feat_planes_ex(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, feat, M, eps, st);
   if (form == 3) return sf_pixel_feat_tok_launch<false>(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, feat, M, eps, st);   // pixel-stationary
   if (form >= 1) return sf_pixel_feat_stream_launch(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, feat, M, eps, st, form == 1 ? 128 : 64);
   SF_TRY(sf_ensure_dyn_lds((const void*)pixel_mlp_kv_kernel<true>, (size_t)(PM_LDS)));

@@ -712,6 +712,19 @@ int sf_slot_attn_iter_f32(const float* k, const float* v, int ld, long long batc
   return sf_slot_attn_iter_ex(k, v, ld, batch_stride, q, part_num, part_den, attn_out, (long long)N * HW, B, HW,
                               N, D, scale, eps, (hipStream_t)stream);
 }
+
+// The one-launch slot prologue by itself (sf_slot_prologue_ex; matrices transposed: [in][out])
+int sf_slot_prologue_f32(const float* prev, const float* init, const float* pm_ln_g, const float* pm_ln_b, const float* pm_w0_t,
+                         const float* pm_b0, const float* pm_w2_t, const float* pm_b2, int norm_first, const float* kd_w_t,
+                         const float* kd_b, const float* noise, long long noise_bs, float* kdist_out, long long kdist_bs,
+                         const float* q_ln_g, const float* q_ln_b, const float* q_w_t, float* slots_out, float* q_out, int B, int N,
+                         int D, float ln_eps, void* stream) {
+  SF_REQUIRE(B >= 0 && N >= 1 && D >= 1, "sf_slot_prologue_f32: bad shape");
+  const int rc = sf_slot_prologue_ex(prev, init, pm_ln_g, pm_ln_b, pm_w0_t, pm_b0, pm_w2_t, pm_b2, norm_first, kd_w_t, kd_b, noise, noise_bs,
+                                     kdist_out, kdist_bs, q_ln_g, q_ln_b, q_w_t, slots_out, q_out, B, N, D, ln_eps, (hipStream_t)stream);
+  SF_REQUIRE(rc != 1, "sf_slot_prologue_f32: slot size 64, 128, 192, ... 384; init, the kernel-distribution and q operands, and with prev the predictor's");
+  return rc;
+}
 }  // extern "C"
 
 // bf16-storage variant of the iteration (SURVEY.md 8(b2) `sf_slot_attn_iter_bf16`): k, v point to bf16 rows (ld, batch_stride in

@@ -432,6 +432,12 @@ int sf_slot_attn_planes_ex(const void* planes, long long batch_stride_rows, cons
   return 0;
 }
 
+// C ABI (include/slotformer_hip.h): the iteration by itself
+extern "C" int sf_slot_attn_iter_planes_f32(const void* planes, long long batch_stride_rows, const float* q, float* part_num, float* part_den,
+                                            float* attn_out, long long attn_batch_stride, int B, int HW, int N, float scale, float eps, void* stream) {
+  return sf_slot_attn_planes_ex(planes, batch_stride_rows, q, part_num, part_den, attn_out, attn_batch_stride, B, HW, N, scale, eps, (hipStream_t)stream);
+}
+
 bool sf_slot_chain_ok(int D, int H, int HW, int N) { return D == SC_D && H == UM_H && HW >= 256 && HW % (SC_NW * SC_TP) == 0 && N >= 1 && N <= 8; }
 
 int sf_slot_chain_ex(const void* feat_planes, int NB, int B, int T, int HW, int N, int iters, float scale, float eps, float ln_eps, float* slotsA, float* slotsB,

@@ -88,6 +88,27 @@ extern "C" int sf_slot_update_packed_f32(const float* part_num, const float* par
                                 (hipStream_t)stream);
 }
 
+// The same with a second strided copy of the rows (out2: row (b, n) at out2 + b * out2_bs + n * D, or NULL), every p_step-th partial record read, and --
+// next_slots not NULL -- the NEXT form: the slot prologue of the following time step behind the update (SfNextStep).  Slot size 128 / slot MLP 256.
+extern "C" int sf_slot_update_packed_next_f32(const float* part_num, const float* part_den, int P, const float* slots_prev, const void* gru_ih_packed,
+                                              const void* gru_hh_packed, const float* gru_b_ih, const float* gru_b_hh, const float* ln_g,
+                                              const float* ln_b, const void* mlp_w1_packed, const float* mlp_b1, const void* mlp_w2_packed,
+                                              const float* mlp_b2, float* slots_out, const float* q_ln_g, const float* q_ln_b,
+                                              const void* q_w_packed, float* q_out, int B, int N, int D, int H, float ln_eps, float* out2,
+                                              long long out2_bs, int p_step, const float* pm_ln_g, const float* pm_ln_b, const void* pm_w0_packed,
+                                              const float* pm_b0, const void* pm_w2_packed, const float* pm_b2, int norm_first,
+                                              const void* kd_w_packed, const float* kd_b, const float* noise, long long noise_bs, float* kdist_out,
+                                              long long kdist_bs, float* next_slots, void* stream) {
+  SF_REQUIRE(sf_slot_update_mfma_ok(D, H, P), "sf_slot_update_packed_next_f32: slot size 128 with slot MLP size 256, and at most 64 partial records");
+  SfNextStep nx;
+  nx.pm_ln_g = pm_ln_g; nx.pm_ln_b = pm_ln_b; nx.pm_w0_p = pm_w0_packed; nx.pm_b0 = pm_b0; nx.pm_w2_p = pm_w2_packed; nx.pm_b2 = pm_b2;
+  nx.norm_first = norm_first; nx.kd_w_p = kd_w_packed; nx.kd_b = kd_b; nx.noise = noise; nx.noise_bs = noise_bs; nx.kdist_out = kdist_out;
+  nx.kdist_bs = kdist_bs; nx.slots = next_slots;
+  return sf_slot_update_mfma_ex(part_num, part_den, P, slots_prev, gru_ih_packed, gru_hh_packed, gru_b_ih, gru_b_hh, ln_g, ln_b, mlp_w1_packed,
+                                mlp_b1, mlp_w2_packed, mlp_b2, slots_out, out2, out2_bs, q_ln_g, q_ln_b, q_w_packed, q_out, B, N, ln_eps,
+                                (hipStream_t)stream, next_slots ? &nx : nullptr, p_step);
+}
+
 #ifdef UM_STAMPS
 extern "C" int sf_debug_read_ts_um(long long* out16) {
   hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(um_ts), sizeof(long long) * 16);

@@ -153,6 +153,30 @@ def conv2d_first(img, weight, bias, stride, relu=True, add=None):
     return out
 
 
+def conv2d_first_clip(clip, weight, bias, stride, relu=True, add=None):
+    """clip [B,T,3,H,W] -> [T*B,Ho,Wo,64] NHWC, time-major (frame t * B + b = clip[b, t]): the grouped launch of the batched encode."""
+    _chk(clip, weight, bias, add)
+    B, T, Cin, H, W = clip.shape
+    Cout, ks = weight.shape[0], weight.shape[2]
+    Ho = (H + 2 * (ks // 2) - ks) // stride + 1
+    Wo = (W + 2 * (ks // 2) - ks) // stride + 1
+    out = torch.empty(T * B, Ho, Wo, Cout, device=clip.device, dtype=torch.float32)
+    check(lib().sf_conv2d_nchw_in_grouped_f32(_p(clip), T * Cin * H * W, B, Cin * H * W, _p(weight), _p(bias), _p(add), _p(out), T * B, Cin,
+                                              H, W, Cout, ks, stride, int(relu), _stream()))
+    return out
+
+
+def pixel_feat(x, ln0, fc1, fc2, ln1, form=3, eps=1e-5):
+    """x [M,64] -> LN(fc2(relu(fc1(LN(x))))): [M,128] float32 (form 0 .. 3), or [M,256] bfloat16 rows hi | lo (form 4).  ln = (gamma, beta),
+    fc = (weight, bias) in torch layout."""
+    _chk(x, *ln0, *fc1, *fc2, *ln1)
+    M = x.shape[0]
+    out = torch.empty(M, 256, device=x.device, dtype=torch.bfloat16) if form == 4 else torch.empty(M, 128, device=x.device, dtype=torch.float32)
+    check(lib().sf_pixel_feat_f32(_p(x), _p(ln0[0]), _p(ln0[1]), _p(fc1[0]), _p(fc1[1]), _p(fc2[0]), _p(fc2[1]), _p(ln1[0]), _p(ln1[1]),
+                                  out.data_ptr(), M, eps, form, _stream()))
+    return out
+
+
 def conv2d_nhwc(x, w_packed, bias, relu=True, add=None):
     """x [F,H,W,Cin] NHWC, w_packed [Cout,k,k,Cin] -> [F,H,W,Cout]."""
     _chk(x, w_packed, bias, add)
@@ -176,6 +200,39 @@ def slot_attn_iter(k, v, q, eps=1e-6, want_attn=False):
     check(lib().sf_slot_attn_iter_f32(_p(k), _p(v), D, HW * D, _p(q), _p(pn), _p(pd), _p(attn), B, HW, N, D,
                                       float(D)**-0.5, eps, _stream()))
     return pn, pd, attn
+
+
+def slot_attn_iter_planes(planes, q, eps=1e-6, want_attn=False):
+    """slot_attn_iter for keys == values kept as planes [B,HW,256] bfloat16 (hi | lo of 128 channels; pixel_feat form 4); q [B,N,128]."""
+    _chk(q)
+    if not (planes.is_cuda and planes.dtype == torch.bfloat16 and planes.is_contiguous() and planes.shape[-1] == 256):
+        raise RuntimeError('slot_attn_iter_planes needs contiguous bfloat16 rows [B, HW, 256] on a HIP device')
+    B, HW, _ = planes.shape
+    N, P = q.shape[1], HW // 256
+    pn = torch.empty(B, P, N, 128, device=q.device, dtype=torch.float32)
+    pd = torch.empty(B, P, N, device=q.device, dtype=torch.float32)
+    attn = torch.empty(B, N, HW, device=q.device, dtype=torch.float32) if want_attn else None
+    check(lib().sf_slot_attn_iter_planes_f32(planes.data_ptr(), HW, _p(q), _p(pn), _p(pd), _p(attn), N * HW, B, HW, N, 128.0**-0.5, eps,
+                                             _stream()))
+    return pn, pd, attn
+
+
+def slot_prologue(prev, init, pm, kd, q, noise=None, norm_first=True, want_kdist=False, B=None, ln_eps=1e-5):
+    """The slots of a time step before its first iteration.  prev [B,N,D] or None (then B videos start from init [N,D]); pm = (ln_g, ln_b, w0, b0, w2,
+    b2) of the residual-MLP predictor or None, kd = (w, b) of the kernel-distribution Linear, q = (ln_g, ln_b, w) of project_q, all in torch layout
+    (transposed here); noise [B,N,D] or None -> (slots [B,N,D], q [B,N,D], kernel_dist [B,N,2D] | None)."""
+    pm = pm or (None, ) * 6
+    _chk(prev, init, *pm, *kd, *q, noise)
+    N, D = init.shape
+    B = prev.shape[0] if prev is not None else B
+    t = lambda w: None if w is None else w.t().contiguous()   # noqa: E731
+    w0_t, w2_t, kd_t, q_t = t(pm[2]), t(pm[4]), t(kd[0]), t(q[2])
+    slots, q_out = torch.empty(B, N, D, device=init.device), torch.empty(B, N, D, device=init.device)
+    kdist = torch.empty(B, N, 2 * D, device=init.device) if want_kdist else None
+    check(lib().sf_slot_prologue_f32(_p(prev), _p(init), _p(pm[0]), _p(pm[1]), _p(w0_t), _p(pm[3]), _p(w2_t), _p(pm[5]), int(norm_first), _p(kd_t),
+                                     _p(kd[1]), _p(noise), N * D, _p(kdist), N * 2 * D, _p(q[0]), _p(q[1]), _p(q_t), _p(slots), _p(q_out), B, N, D,
+                                     ln_eps, _stream()))
+    return slots, q_out, kdist
 
 
 def slot_attn_iter_bwd(k, v, q, pn, pd, d_updates, dk=None, dv=None, eps=1e-6):
@@ -232,6 +289,23 @@ def slot_update_packed(pn, pd, slots_prev, gru, ln_g, ln_b, w1, b1, w2, b2, q=No
                                           _p(out), _p(q[0]) if q is not None else None, _p(q[1]) if q is not None else None,
                                           qp.data_ptr() if qp is not None else None, _p(q_out), B, N, D, w1.shape[0], ln_eps, _stream()))
     return (out, q_out) if q is not None else out
+
+
+def slot_update_packed_next(pn, pd, slots_prev, gru, ln_g, ln_b, w1, b1, w2, b2, q, pm, kd, noise=None, norm_first=True, want_kdist=False,
+                            p_step=1, ln_eps=1e-5):
+    """slot_update_packed followed, in the same launch, by the slot prologue of the next time step (slot_prologue's pm / kd in torch layout, packed
+    here) -> (slots_out, next_slots, q of next_slots, kernel_dist | None); only every p_step-th partial record is read."""
+    _chk(pn, pd, slots_prev, *gru, ln_g, ln_b, w1, b1, w2, b2, *q, *pm, *kd, noise)
+    B, P, N, D = pn.shape
+    out, nxt, q_out = torch.empty_like(slots_prev), torch.empty_like(slots_prev), torch.empty_like(slots_prev)
+    kdist = torch.empty(B, N, 2 * D, device=pn.device) if want_kdist else None
+    pk = [pack_linear(w) for w in (gru[0], gru[1], w1, w2, q[2], pm[2], pm[4], kd[0])]
+    check(lib().sf_slot_update_packed_next_f32(_p(pn), _p(pd), P, _p(slots_prev), pk[0].data_ptr(), pk[1].data_ptr(), _p(gru[2]), _p(gru[3]), _p(ln_g),
+                                               _p(ln_b), pk[2].data_ptr(), _p(b1), pk[3].data_ptr(), _p(b2), _p(out), _p(q[0]), _p(q[1]),
+                                               pk[4].data_ptr(), _p(q_out), B, N, D, w1.shape[0], ln_eps, None, 0, p_step, _p(pm[0]), _p(pm[1]),
+                                               pk[5].data_ptr(), _p(pm[3]), pk[6].data_ptr(), _p(pm[5]), int(norm_first), pk[7].data_ptr(),
+                                               _p(kd[1]), _p(noise), N * D, _p(kdist), N * 2 * D, _p(nxt), _stream()))
+    return out, nxt, q_out, kdist
 
 
 def mha(qkv, B, L, d_model, num_heads, Lq=None):
