@@ -543,6 +543,39 @@ int sf_dvae_patch_embed_f32(const float* img, const float* w, float* y, int F, i
 int sf_dvae_head_argmax_f32(const float* x, long long ld, const void* w_packed, const float* bias, long long* ids_i64, short* ids_i16, long long R,
                             int V, int K, void* stream);
 
+/* ---- Physion VQA readout on rolled-out slots (physion_vqa/models/readout.py; csrc/physion_readout.hip) -------------------------------------------
+ * logit[k][b] = max_t ( w2_k . agg_{i<j} ( W1_k cat(s_ti, s_tj) + b1_k ) + b2_k ) for a stack of K heads, agg = 0 max / 1 sum / 2 mean over the
+ * N (N - 1) / 2 slot pairs in itertools.combinations order.  linear1 of a pair is U_i + V_j (U = S W1[:, :C]^T + b1, V = S W1[:, C:]^T): one product
+ * per slot, no gathered pair tensor.  U | V are split-bf16 products (every f32 operand = bf16 hi + bf16 lo, three products, f32 accumulation) WHATEVER
+ * sf_set_precision says; every sum has a fixed order and no floating-point atomic is used: equal inputs give equal bits, and a video's results do not
+ * depend on its place in the batch.  Ties: the FIRST timestep / pair of the maximum.
+ *
+ * slots: video v, frame t, slot n at slots + v * stride_v + t * stride_t + n * C (strides in elements, multiples of 4; stride_t >= N * C), V videos;
+ * batch entry b reads video video_index[b] (int32, any order, repeats allowed) or video b when video_index is NULL.  Only frames [0, T) of the
+ * named videos are read; an index outside [0, V) gives NaN results, never an access.  slots and W1 16-byte aligned.
+ * Shapes (sf_physion_readout_ok, shapes only): 2 <= N <= 16, C and F multiples of 32 in [32, 256]; T >= 1, B >= 1, 1 <= K <= 65535. */
+int sf_physion_readout_ok(int N, int C, int F);
+/* W1 [K,F,2C], b1 [K,F], w2 [K,F], b2 [K] -> logits [K,B], t_star [K,B] (int32), and when not NULL step_logits [K,B,T] and pair_star [K,B,F]
+ * (uint8: per feature the winning pair at t_star for agg = max; zeros for sum / mean). */
+int sf_physion_readout_fwd_f32(const float* slots, long long stride_v, long long stride_t, int V, const int* video_index, const float* W1,
+                               const float* b1, const float* w2, const float* b2, float* logits, int* t_star, float* step_logits,
+                               unsigned char* pair_star, int K, int B, int T, int N, int C, int F, int agg, void* stream);
+/* Backward of ONE head: g [B] = dL/dlogit, t_star [B] from the forward, pair_star [B,F] from the forward or NULL (max: the winning pairs are then
+ * found again) -> dW1 [F,2C], db1 [F], dw2 [F], db2 [1], overwritten.  The gradient reaches frame t_star of each video only (max: the one pair of each
+ * feature); the slots are frozen inputs.  Two launches: the relation at t_star per video, then per feature a sum over the videos in ascending order.
+ * A t_star outside [0, T) or a recorded pair >= N (N - 1) / 2 gives NaN gradients, never an access.  workspace: 16-byte aligned,
+ * sf_physion_readout_bwd_workspace_bytes(B, N, F) bytes (0 for unsupported arguments). */
+size_t sf_physion_readout_bwd_workspace_bytes(int B, int N, int F);
+int sf_physion_readout_bwd_f32(const float* slots, long long stride_v, long long stride_t, int V, const int* video_index, const float* W1,
+                               const float* b1, const float* w2, const float* g, const int* t_star, const unsigned char* pair_star, float* dW1,
+                               float* db1, float* dw2, float* db2, int B, int T, int N, int C, int F, int agg, void* workspace,
+                               size_t workspace_bytes, void* stream);
+/* One launch: logits [K,B], labels [B] (f32, 0 / 1), task_idx [B] (int32) or NULL, thresholds: n_thresh <= 16 floats in HOST memory ->
+ * loss [K] = mean_b BCE-with-logits, g [K,B] = dloss/dlogit, and counts [K,n_thresh], task_counts [K,n_tasks,n_thresh] (int32; n_tasks <= 64) of
+ * (sigmoid(logit) > thresh) == label, ADDED to what the buffers hold, so that batches accumulate.  Every output may be NULL. */
+int sf_physion_readout_score_f32(const float* logits, const float* labels, const int* task_idx, const float* thresholds, int n_thresh, int n_tasks,
+                                 float* loss, float* g, int* counts, int* task_counts, int K, int B, void* stream);
+
 /* ---- whole-path engines ------------------------------------------------------------------ */
 
 /* One nn.TransformerEncoderLayer (relu, batch_first); all pointers device, torch layouts. */

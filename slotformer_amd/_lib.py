@@ -288,6 +288,11 @@ SIGNATURES = {
     'sf_dvae_pack_head_weights_host': (I, [VP, VP, I, I]),
     'sf_dvae_patch_embed_f32': (I, [FP, FP, FP, I, I, I, I, VP]),
     'sf_dvae_head_argmax_f32': (I, [FP, LL, VP, FP, VP, VP, LL, I, I, VP]),
+    'sf_physion_readout_ok': (I, [I, I, I]),
+    'sf_physion_readout_fwd_f32': (I, [FP, LL, LL, I, VP, FP, FP, FP, FP, FP, VP, FP, VP, I, I, I, I, I, I, I, VP]),
+    'sf_physion_readout_bwd_workspace_bytes': (SZ, [I, I, I]),
+    'sf_physion_readout_bwd_f32': (I, [FP, LL, LL, I, VP, FP, FP, FP, FP, VP, VP, FP, FP, FP, FP, I, I, I, I, I, I, VP, SZ, VP]),
+    'sf_physion_readout_score_f32': (I, [FP, FP, VP, C.POINTER(F32), I, I, FP, FP, VP, VP, I, I, VP]),
     'sf_packed_linear_bytes': (SZ, [I, I]),
     'sf_pack_linear_weights': (I, [FP, VP, I, I, VP]),
     'sf_attn_packed_bytes': (SZ, [I, I]),

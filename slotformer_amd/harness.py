@@ -289,3 +289,27 @@ def extract_and_rollout(savi, rollouter, videos, pred_len, batch_size=32, noises
     if to_host:
         torch.cuda.synchronize(dev)
     return out if dec is None else (out, dec)
+
+
+@torch.no_grad()
+def readout_video_slots(readout, slots, batch_size, video_len=75, to_host=True):
+    """The contact probability of every video of slots [V, T, N, C] as `rollout_video_slots` returns them (on the device or on the host):
+    sigmoid of the `PhysionReadout` logit over the first `video_len` frames, float32 [V] -- in pinned host memory with to_host=True, on the device
+    otherwise.  The videos go through in chunks of `batch_size` (the last one may be ragged); a device-resident tensor is read in place through
+    its strides, of a host-resident one only a chunk is on the device at a time."""
+    if int(batch_size) < 1:
+        raise ValueError(f'slotformer_amd.harness: batch_size >= 1, got {batch_size!r}')
+    if slots.dim() != 4:
+        raise ValueError(f'slotformer_amd.harness: slots are [V, T, N, C], got {tuple(slots.shape)}')
+    readout.eval()
+    dev = readout.device
+    V = slots.shape[0]
+    probs = torch.empty(V, dtype=torch.float32, device=dev)
+    for a, b in render_chunks(V, int(batch_size)):
+        chunk = slots[a:b, :video_len].float().to(dev, non_blocking=True)
+        torch.sigmoid(readout({'slots': chunk})['logits'], out=probs[a:b])
+    if not to_host:
+        return probs
+    out = torch.empty(V, dtype=torch.float32, pin_memory=True)
+    out.copy_(probs)
+    return out

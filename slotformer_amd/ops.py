@@ -529,3 +529,124 @@ def slate_attention_cached(q, kv_cache, Lk, num_heads, d_model, k_off, v_off):
                                                _p(out), ldq, ld, ld, d_model, Lq * ldq, Lmax * ld, Lmax * ld, Lq * d_model, B, Lq,
                                                Lk, num_heads, d_model // num_heads, 0, _stream()))
     return out
+
+
+# ---- Physion VQA readout (csrc/physion_readout.hip) ------------------------------------------------------------------------------------------
+READOUT_AGG = {'max': 0, 'sum': 1, 'mean': 2}
+READOUT_LIMITS = '2 <= num_slots <= 16, slot_size and feats_dim multiples of 32 in [32, 256]'
+READOUT_MAX_THRESH = 16
+
+
+def physion_readout_ok(N, C, F):
+    """Whether the readout kernels take these shapes (`sf_physion_readout_ok`; shapes only, no device needed)."""
+    return bool(lib().sf_physion_readout_ok(int(N), int(C), int(F)))
+
+
+def _readout_slots(slots, video_len):
+    """slots [V, T_all, N, C] as the kernels read them -- any video / frame stride, [N, C] contiguous inside a frame, so a `[:, :video_len]` view
+    costs no copy -> (slots, T)."""
+    if not (torch.is_tensor(slots) and slots.is_cuda):
+        raise RuntimeError('slotformer_amd: the readout needs its slots on a HIP device; there is no CPU fallback')
+    if slots.dim() != 4:
+        raise ValueError(f'slotformer_amd: readout slots are [V, T, N, C], got {tuple(slots.shape)}')
+    if slots.dtype != torch.float32:
+        slots = slots.float()
+    N, C = slots.shape[2:]
+    if slots.stride(3) != 1 or slots.stride(2) != C or slots.stride(1) < N * C or slots.stride(1) % 4 or slots.stride(0) % 4 or slots.data_ptr() % 16:
+        slots = slots.contiguous()
+    T = slots.shape[1] if video_len is None else min(int(video_len), slots.shape[1])
+    return slots, T
+
+
+def _readout_heads(W1, b1, w2, b2):
+    """A head or a stack of K heads -> ([K,F,2C], [K,F], [K,F], [K]) contiguous float32."""
+    W1 = W1.detach()
+    W1 = W1.unsqueeze(0) if W1.dim() == 2 else W1
+    K, F = W1.shape[:2]
+    out = (W1.float().contiguous(), b1.detach().float().reshape(K, F).contiguous(), w2.detach().float().reshape(K, F).contiguous(),
+           b2.detach().float().reshape(K).contiguous())
+    _chk(*out)
+    return out
+
+
+def _index32(idx, dev):
+    return None if idx is None else torch.as_tensor(idx, device=dev).to(torch.int32).contiguous()
+
+
+def physion_readout_fwd(slots, W1, b1, w2, b2, agg, video_index=None, video_len=None, want_steps=False, want_pairs=False):
+    """logits [K,B] = max over the first `video_len` frames of the readout of each of K heads (`sf_physion_readout_fwd_f32`; split-bf16 whatever the
+    library's precision mode).  slots [V,T_all,N,C] (see `_readout_slots`); batch entry b is video `video_index[b]` (any order, repeats allowed),
+    or the V videos in order.  Returns (logits [K,B], t_star [K,B] int32, step_logits [K,B,T] or None, pair_star [K,B,F] uint8 or None)."""
+    slots, T = _readout_slots(slots, video_len)
+    W1, b1, w2, b2 = _readout_heads(W1, b1, w2, b2)
+    V, _, N, C = slots.shape
+    K, F = W1.shape[:2]
+    if W1.shape[2] != 2 * C:
+        raise ValueError(f'slotformer_amd: linear1 takes {W1.shape[2]} inputs, a slot pair has {2 * C}')
+    video_index = _index32(video_index, slots.device)
+    B = V if video_index is None else video_index.numel()
+    dev = slots.device
+    logits = torch.empty(K, B, dtype=torch.float32, device=dev)
+    t_star = torch.empty(K, B, dtype=torch.int32, device=dev)
+    steps = torch.empty(K, B, T, dtype=torch.float32, device=dev) if want_steps else None
+    pairs = torch.empty(K, B, F, dtype=torch.uint8, device=dev) if want_pairs else None
+    check(lib().sf_physion_readout_fwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, _p(video_index), _p(W1), _p(b1), _p(w2), _p(b2),
+                                           _p(logits), _p(t_star), _p(steps), _p(pairs), K, B, T, N, C, F, READOUT_AGG[agg], _stream()))
+    return logits, t_star, steps, pairs
+
+
+def physion_readout_bwd(slots, W1, b1, w2, g, t_star, agg, pair_star=None, video_index=None, video_len=None, out=None):
+    """Gradients of ONE head from g [B] = dL/dlogit and the forward's routing (`sf_physion_readout_bwd_f32`): (dW1 [F,2C], db1 [F], dw2 [F],
+    db2 [1]); `out`: a flat float32 buffer of F * 2C + 2F + 1 elements to write them into, in that order (the views are returned)."""
+    slots, T = _readout_slots(slots, video_len)
+    W1, b1, w2, _ = _readout_heads(W1, b1, w2, torch.zeros(1, device=slots.device))
+    if W1.shape[0] != 1:
+        raise ValueError('slotformer_amd: the readout backward takes one head')
+    V, _, N, C = slots.shape
+    F = W1.shape[1]
+    video_index = _index32(video_index, slots.device)
+    B = V if video_index is None else video_index.numel()
+    g = g.detach().float().reshape(B).contiguous()
+    t_star = t_star.reshape(B).to(torch.int32).contiguous()
+    if pair_star is not None:
+        pair_star = pair_star.reshape(B, F).to(torch.uint8).contiguous()
+    n = F * 2 * C + 2 * F + 1
+    flat = torch.empty(n, dtype=torch.float32, device=slots.device) if out is None else out
+    if flat.numel() != n or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError(f'slotformer_amd: the readout gradient buffer holds {n} contiguous float32 elements')
+    dW1, db1, dw2, db2 = flat[:F * 2 * C].view(F, 2 * C), flat[F * 2 * C:F * 2 * C + F], flat[F * 2 * C + F:F * 2 * C + 2 * F], flat[n - 1:]
+    nbytes = int(lib().sf_physion_readout_bwd_workspace_bytes(B, N, F))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=slots.device)
+    check(lib().sf_physion_readout_bwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, _p(video_index), _p(W1), _p(b1), _p(w2), _p(g),
+                                           _p(t_star), _p(pair_star), _p(dW1), _p(db1), _p(dw2), _p(db2), B, T, N, C, F, READOUT_AGG[agg],
+                                           ws.data_ptr(), ws.numel(), _stream()))
+    return dW1, db1, dw2, db2
+
+
+def physion_readout_score(logits, labels, threshs=(), task_idx=None, n_tasks=0, want_loss=True, want_grad=True, counts=None, task_counts=None):
+    """One launch over logits [K,B] (`sf_physion_readout_score_f32`): the mean BCE-with-logits loss [K], g [K,B] = dloss/dlogit, and the int32 counts
+    [K,thresholds] (and [K,n_tasks,thresholds]) of (sigmoid(logit) > thresh) == label, ADDED to `counts` / `task_counts` when those are passed, so
+    that batches accumulate.  Returns (loss, g, counts, task_counts); what was not asked for is None."""
+    import ctypes as C
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        raise RuntimeError('slotformer_amd: the readout score needs its logits on a HIP device; there is no CPU fallback')
+    logits = logits.detach().float()
+    logits = (logits.unsqueeze(0) if logits.dim() == 1 else logits).contiguous()
+    K, B = logits.shape
+    dev = logits.device
+    labels = torch.as_tensor(labels, device=dev).float().reshape(B).contiguous()
+    threshs = [float(t) for t in threshs]
+    if len(threshs) > READOUT_MAX_THRESH:
+        raise ValueError(f'slotformer_amd: at most {READOUT_MAX_THRESH} thresholds per score launch, got {len(threshs)}')
+    task_idx = _index32(task_idx, dev)
+    n_tasks = int(n_tasks) if task_idx is not None else 0
+    loss = torch.empty(K, dtype=torch.float32, device=dev) if want_loss else None
+    g = torch.empty(K, B, dtype=torch.float32, device=dev) if want_grad else None
+    if threshs and counts is None:
+        counts = torch.zeros(K, len(threshs), dtype=torch.int32, device=dev)
+    if threshs and n_tasks and task_counts is None:
+        task_counts = torch.zeros(K, n_tasks, len(threshs), dtype=torch.int32, device=dev)
+    th = (C.c_float * max(len(threshs), 1))(*threshs)
+    check(lib().sf_physion_readout_score_f32(_p(logits), _p(labels), _p(task_idx), th, len(threshs), n_tasks, _p(loss), _p(g), _p(counts),
+                                             _p(task_counts), K, B, _stream()))
+    return loss, g, counts, task_counts

@@ -1019,3 +1019,60 @@ def dropout_keep_mask(seed, step, layer, site, numel, p):
         idx = np.arange(numel, dtype=np.uint32)
         u = mix(idx ^ sseed) >> np.uint32(8)
     return u >= np.uint32(int(float(np.float32(p)) * 16777216.0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Physion VQA readout (physion_vqa/models/readout.py) under autograd: two nodes over the kernels of csrc/physion_readout.hip
+# ---------------------------------------------------------------------------------------------------------------------
+class _Readout(torch.autograd.Function):
+    """logits [B] (and the per-step logits [B,T], not differentiable) of one head; the slots are frozen inputs, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, slots, video_index, video_len, agg, want_steps, W1, b1, w2, b2):
+        from . import ops
+        logits, t_star, steps, pairs = ops.physion_readout_fwd(slots, W1, b1, w2, b2, agg, video_index=video_index, video_len=video_len,
+                                                               want_steps=want_steps, want_pairs=agg == 'max')
+        ctx.keep = (slots, video_index, video_len, agg, t_star, pairs)
+        ctx.save_for_backward(W1, b1, w2, b2)
+        steps = steps[0] if want_steps else logits.new_empty(0)
+        ctx.mark_non_differentiable(steps)
+        return logits[0], steps
+
+    @staticmethod
+    def backward(ctx, g, _d_steps):
+        from . import ops
+        slots, video_index, video_len, agg, t_star, pairs = ctx.keep
+        W1, b1, w2, b2 = ctx.saved_tensors
+        dW1, db1, dw2, db2 = ops.physion_readout_bwd(slots, W1, b1, w2, g, t_star, agg, pair_star=pairs, video_index=video_index,
+                                                     video_len=video_len)
+        return None, None, None, None, None, dW1.view_as(W1), db1.view_as(b1), dw2.view_as(w2), db2.view_as(b2)
+
+
+class _ReadoutLoss(torch.autograd.Function):
+    """Mean BCE-with-logits of logits [B] against labels: one score launch; its backward is the g that launch wrote."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        from . import ops
+        loss, g, _, _ = ops.physion_readout_score(logits, labels)
+        ctx.save_for_backward(g)
+        ctx.shape = logits.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        g, = ctx.saved_tensors
+        return (g[0] * d_loss).view(ctx.shape), None
+
+
+def readout_with_grad(readout, slots, video_index=None, video_len=None, return_steps=False):
+    """PhysionReadout.forward under autograd (readout.py:56-79): slots [V,T,N,C] -> logits [B] (with return_steps also the per-step logits [B,T]).
+    Forward and backward are `sf_physion_readout_fwd_f32` / `sf_physion_readout_bwd_f32`; the gradient reaches each video's winning frame only."""
+    logits, steps = _Readout.apply(slots, video_index, video_len, readout.agg_func, bool(return_steps), readout.linear1.weight, readout.linear1.bias,
+                                   readout.linear2.weight, readout.linear2.bias)
+    return (logits, steps) if return_steps else logits
+
+
+def readout_loss(logits, labels):
+    """F.binary_cross_entropy_with_logits(logits, labels) (readout.py:81-87) on the score kernel, differentiable in `logits`."""
+    return _ReadoutLoss.apply(logits, labels)
