@@ -648,6 +648,35 @@ int sf_debug_read_ts_layer_tok(long long* out16);   /* wall-clock stamps (10 ns)
 size_t sf_attn_rows_planes_bytes(int B);
 int sf_attn_block_rows_f32(const sf_tfm_layer* w, const float* x, float* out, void* planes, int B, int L, int Lq, void* stream);
 
+/* ---- PHYRE task-success readout and AUCCESS ranks (phyre_planning/models/readout.py, test_phyre_planning.py; csrc/phyre_readout.hip) -------------
+ * Inference only.  logit[b] = cls_mlp( TransformerEncoder( [CLS ; in_proj(slots[b, sel[t], n]) + enc_t_pe[t]] )[0] ): three launches -- the token
+ * rows x [B][1 + T N][128] (t-major, slot-minor; split-bf16 product on MFMA, f32 accumulation), the num_layers pre-LN layers as ONE token-stationary
+ * launch (layers[l].tok_packed: sf_pack_layer_tok_weights copies for (128, 8, 512); eps 1e-5), and the head Linear(128,128) - ReLU - Linear(128,1)
+ * on row 0 in plain f32.  Fixed summation orders, no floating-point atomics: equal inputs give equal bits.
+ *
+ * slots: video v, frame f, slot n at slots + v * stride_v + f * stride_t + n * C (strides in elements, multiples of 4; stride_t >= N * C), V videos
+ * of T_all frames, read in place; batch entry b reads video video_index[b] (int32, device; any order, repeats allowed) or video b when NULL; an index
+ * outside [0, V) gives NaN logits, never an access.  sel: T int32 in HOST memory, sel[t] in [-1, T_all): the frame of token group t; -1 is a frame of
+ * zeros (tokens = bias + enc_t_pe[t], nothing is read).  The position row is chosen by t, the place in sel.  in_proj_w [128][C], in_proj_b [128],
+ * enc_t_pe [T][128], cls [128], layers: HOST array [num_layers], mlp_w1 [128][128], mlp_b1 [128], mlp_w2 [128], mlp_b2 [1] -> logits [B];
+ * conf [B] = sigmoid(logit) when not NULL; scatter_table[scatter_index[b]] = conf[b] when scatter_table is not NULL (scatter_index [B] int32, device;
+ * an index outside [0, scatter_len) is skipped).  workspace: 16-byte aligned, sf_phyre_readout_workspace_bytes(B, N, T) bytes (0 for unsupported
+ * arguments).  Limits (sf_phyre_readout_ok, shapes only): 1 <= N <= 16, C a multiple of 32 in [32, 256], T >= 1, 1 + T N <= 96,
+ * (d_model, heads, ffn) = (128, 8, 512), 1 <= num_layers <= 8.  Every violation -- and a process precision other than split-bf16, which the layers
+ * need -- is a negative return code before any launch. */
+int sf_phyre_readout_ok(int num_slots, int slot_size, int T, int d_model, int num_heads, int ffn, int num_layers);
+size_t sf_phyre_readout_workspace_bytes(int B, int num_slots, int T);
+int sf_phyre_readout_fwd_f32(const float* slots, long long stride_v, long long stride_t, int V, int T_all, const int* video_index, const int* sel,
+                             const float* in_proj_w, const float* in_proj_b, const float* enc_t_pe, const float* cls, const sf_tfm_layer* layers,
+                             int num_layers, int d_model, int num_heads, int ffn, const float* mlp_w1, const float* mlp_b1, const float* mlp_w2,
+                             const float* mlp_b2, float* logits, float* conf, const int* scatter_index, float* scatter_table, long long scatter_len,
+                             int B, int T, int N, int C, void* workspace, size_t workspace_bytes, void* stream);
+/* conf [tasks][actions] f32, status [tasks][actions] int32 (phyre's SimulationStatus: 0 invalid input, -1 not solved, > 0 solved) ->
+ * first_rank [tasks] int32 = #{status != 0 and conf > c*}, c* = max conf over {status > 0}: the 0-based place of the first solved action when the
+ * valid actions are ranked by falling confidence and a solved action wins ties; `actions` when the task has no solved action.  One workgroup per
+ * task, two passes over its row. */
+int sf_phyre_auccess_f32(const float* conf, const int* status, int* first_rank, int tasks, int actions, void* stream);
+
 /* SlotRollouter / SingleStepSlotRollouter (slotformer.py:48-134, single_step_slotformer.py:6-90). */
 typedef struct {
   int num_slots, slot_size, d_model, num_layers, num_heads, ffn_dim, norm_first;

@@ -293,6 +293,11 @@ SIGNATURES = {
     'sf_physion_readout_bwd_workspace_bytes': (SZ, [I, I, I]),
     'sf_physion_readout_bwd_f32': (I, [FP, LL, LL, I, VP, FP, FP, FP, FP, VP, VP, FP, FP, FP, FP, I, I, I, I, I, I, VP, SZ, VP]),
     'sf_physion_readout_score_f32': (I, [FP, FP, VP, C.POINTER(F32), I, I, FP, FP, VP, VP, I, I, VP]),
+    'sf_phyre_readout_ok': (I, [I, I, I, I, I, I, I]),
+    'sf_phyre_readout_workspace_bytes': (SZ, [I, I, I]),
+    'sf_phyre_readout_fwd_f32': (I, [FP, LL, LL, I, I, VP, C.POINTER(C.c_int), FP, FP, FP, FP, C.POINTER(sf_tfm_layer), I, I, I, I, FP, FP, FP, FP, FP,
+                                     FP, VP, FP, LL, I, I, I, I, VP, SZ, VP]),
+    'sf_phyre_auccess_f32': (I, [FP, VP, VP, I, I, VP]),
     'sf_packed_linear_bytes': (SZ, [I, I]),
     'sf_pack_linear_weights': (I, [FP, VP, I, I, VP]),
     'sf_attn_packed_bytes': (SZ, [I, I]),

@@ -184,6 +184,20 @@ def rollouter_plan(r, packed=True):
     return plan
 
 
+def phyre_readout_plan(m):
+    """m: phyre_planning.models.PHYREReadout on the device -> the host array of its layers with their token-stationary fragment copies
+    (`plan.layers`), cached on the module and rebuilt when a parameter changes, as `rollouter_plan`."""
+    sig = _signature(m)
+    plan = getattr(m, '_sf_plan', None)
+    if plan is not None and plan.sig == sig:
+        return plan
+    plan = _Plan()
+    plan.layers = C.cast(_tfm_layers(plan, m.transformer_encoder, pack_ffn=True), C.POINTER(sf_tfm_layer))
+    plan.struct, plan.sig = plan.layers, sig
+    m._sf_plan = plan
+    return plan
+
+
 def rollout_opts(opts):
     """dict / None -> ctypes sf_rollout_opts (None).  Keys: precision ('f32' | 'bf16x3' | 'bf16' | 'fp16' (probe) | 0..3), seam (bool),
     ffn_rows (32 | 64 | 128), attn_heads (2 | 8: heads per attention workgroup), attn_rows (0 | 128: q|k|v projection on row tiles of

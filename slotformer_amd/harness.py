@@ -313,3 +313,53 @@ def readout_video_slots(readout, slots, batch_size, video_len=75, to_host=True):
     out = torch.empty(V, dtype=torch.float32, pin_memory=True)
     out.copy_(probs)
     return out
+
+
+@torch.no_grad()
+def phyre_plan(savi, slotformer, readout, frames, statuses=None, batch_size=128, ingest=None, reference_indexing=True, to_host=True):
+    """The inference loop of test_phyre_planning.py for V candidate actions: first frame -> SAVi slots -> single-step rollout -> task-success
+    classifier -> sigmoid.  frames [V, 1, 3, H, W] (with ingest=, an `ingest.FrameIngest`: the raw uint8 first frames [V, 1, H0, W0, 3], or PHYRE's
+    colour indices [V, 1, H0, W0] with a palette), on the device or on the host; statuses [V] (phyre's SimulationStatus, optional): actions with
+    INVALID_INPUT (0) are neither encoded nor rolled out and get the confidence -1, as the reference pads them.  Returns conf [V] float32 -- in
+    pinned host memory with to_host=True, on the device otherwise.
+
+    The valid actions go through `extract_and_rollout` (`batch_size` actions per encode / rollout batch) with pred_len = max(sel_slots); the
+    rolled-out slots stay on the device and go through `readout` (a PHYREReadout) in chunks of `batch_size`, read in place; the head kernel
+    writes every confidence straight to its place in conf.
+
+    reference_indexing=True reproduces what test_phyre_planning.py really feeds the classifier: SingleStepSlotFormer.forward classifies
+    cat(gt_slots, pred_slots), and in planning gt_slots are the zero frames the first frame was padded with -- so with vid_len = max(sel_slots) + 1
+    an index s < vid_len - 1 reads a frame of ZEROS and an index s >= vid_len - 1 reads prediction s - (vid_len - 1); sel_slots [0, 3] reads
+    [zeros, the first prediction].  Nothing is concatenated: the kernel takes a frame table with -1 for a zero frame
+    (`phyre_planning.frame_table`).  reference_indexing=False indexes [slot0, predictions] instead -- frame 0 is the encoded first frame, frame s
+    the prediction s - 1 --, which is what the classifier was trained on (rollout_phyre_slots.py)."""
+    from . import phyre_planning as pp
+    if int(batch_size) < 1:
+        raise ValueError(f'slotformer_amd.harness: batch_size >= 1, got {batch_size!r}')
+    if frames.dim() < 2 or frames.shape[1] != 1:
+        raise ValueError(f'slotformer_amd.harness: phyre_plan takes the FIRST frame of every action, [V, 1, ...], got {tuple(frames.shape)}')
+    readout.eval()
+    dev = readout.device
+    if dev.type != 'cuda':
+        raise RuntimeError('slotformer_amd: phyre_plan runs on a HIP device only; there is no CPU fallback')
+    V = frames.shape[0]
+    table = pp.frame_table(readout.sel_slots, reference_indexing)
+    conf = torch.full((V, ), pp.INVALID_CONF, dtype=torch.float32, device=dev)
+    if statuses is None:
+        index = torch.arange(V)
+    else:
+        statuses = torch.as_tensor(statuses).flatten().cpu()
+        if statuses.numel() != V:
+            raise ValueError(f'slotformer_amd.harness: {V} first frames, {statuses.numel()} statuses')
+        index = torch.nonzero(statuses != pp.INVALID_INPUT).flatten()
+    if index.numel():
+        valid = frames if index.numel() == V else frames[index.to(frames.device)]
+        slots = extract_and_rollout(savi, slotformer.rollouter, valid, max(readout.sel_slots), batch_size=int(batch_size), ingest=ingest)
+        index = index.to(dev, torch.int32)
+        for a, b in render_chunks(index.numel(), int(batch_size)):
+            readout.logits_of(slots[a:b], sel=table, scatter_index=index[a:b], scatter_table=conf)
+    if not to_host:
+        return conf
+    out = torch.empty(V, dtype=torch.float32, pin_memory=True)
+    out.copy_(conf)
+    return out

@@ -650,3 +650,60 @@ def physion_readout_score(logits, labels, threshs=(), task_idx=None, n_tasks=0, 
     check(lib().sf_physion_readout_score_f32(_p(logits), _p(labels), _p(task_idx), th, len(threshs), n_tasks, _p(loss), _p(g), _p(counts),
                                              _p(task_counts), K, B, _stream()))
     return loss, g, counts, task_counts
+
+
+# ---- PHYRE task-success readout and AUCCESS ranks (csrc/phyre_readout.hip) ---------------------------------------------------------------------
+PHYRE_LIMITS = ('1 <= num_slots <= 16, slot_size a multiple of 32 in [32, 256], 1 + len(sel_slots) * num_slots <= 96 tokens, '
+                '(d_model, num_heads, ffn_dim) = (128, 8, 512), norm_first, 1 <= num_layers <= 8')
+
+
+def phyre_readout_ok(num_slots, slot_size, T, d_model=128, num_heads=8, ffn=512, num_layers=4):
+    """Whether the PHYRE readout kernels take these shapes (`sf_phyre_readout_ok`; shapes only, no device needed)."""
+    return bool(lib().sf_phyre_readout_ok(int(num_slots), int(slot_size), int(T), int(d_model), int(num_heads), int(ffn), int(num_layers)))
+
+
+def phyre_readout_fwd(slots, sel, in_proj_w, in_proj_b, enc_t_pe, cls, layers, num_layers, mlp_w1, mlp_b1, mlp_w2, mlp_b2, video_index=None,
+                      want_conf=False, scatter_index=None, scatter_table=None, d_model=128, num_heads=8, ffn=512):
+    """logits [B] of the PHYRE readout (`sf_phyre_readout_fwd_f32`: embed, the layers as one launch, head).  slots [V,T_all,N,C] (see
+    `_readout_slots`: read in place through their strides); sel: the frame of every token group as host integers, -1 = a frame of zeros; batch
+    entry b is video `video_index[b]`, or the V videos in order.  layers: a host array of `sf_tfm_layer` whose `tok_packed` copies exist
+    (engine.phyre_readout_plan).  want_conf: also sigmoid(logit) [B]; scatter_table (float32, contiguous) with scatter_index [B]: the
+    confidences are written to scatter_table[scatter_index[b]] by the head kernel.  Returns (logits, conf or None)."""
+    import ctypes as C
+    slots, T_all = _readout_slots(slots, None)
+    V, _, N, Cs = slots.shape
+    dev = slots.device
+    sel = [int(s) for s in sel]
+    T = len(sel)
+    video_index = _index32(video_index, dev)
+    B = V if video_index is None else video_index.numel()
+    _chk(in_proj_w, in_proj_b, enc_t_pe, cls, mlp_w1, mlp_b1, mlp_w2, mlp_b2, scatter_table)
+    scatter_index = _index32(scatter_index, dev)
+    if scatter_table is not None and (scatter_index is None or scatter_index.numel() != B):
+        raise ValueError(f'slotformer_amd: a scatter table needs one scatter_index entry per batch entry ({B})')
+    logits = torch.empty(B, dtype=torch.float32, device=dev)
+    conf = torch.empty(B, dtype=torch.float32, device=dev) if want_conf else None
+    nbytes = int(lib().sf_phyre_readout_workspace_bytes(B, N, T))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    check(lib().sf_phyre_readout_fwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), (C.c_int * max(T, 1))(*sel),
+                                         _p(in_proj_w), _p(in_proj_b), _p(enc_t_pe), _p(cls), layers, int(num_layers), int(d_model), int(num_heads),
+                                         int(ffn), _p(mlp_w1), _p(mlp_b1), _p(mlp_w2), _p(mlp_b2), _p(logits), _p(conf), _p(scatter_index),
+                                         _p(scatter_table), 0 if scatter_table is None else scatter_table.numel(), B, T, N, Cs, ws.data_ptr(),
+                                         ws.numel(), _stream()))
+    return logits, conf
+
+
+def phyre_auccess_ranks(conf, status):
+    """first_rank [tasks] int32 (`sf_phyre_auccess_f32`): for every task the number of valid actions (status != 0) whose confidence lies strictly
+    above the best solved action's (status > 0) -- `actions` when no action of the task is solved.  conf [tasks, actions] float32 and status
+    [tasks, actions] (any integer dtype) on the device."""
+    if not (torch.is_tensor(conf) and conf.is_cuda and torch.is_tensor(status) and status.is_cuda):
+        raise RuntimeError('slotformer_amd: AUCCESS ranks need conf and status on a HIP device; there is no CPU fallback')
+    if conf.dim() != 2 or tuple(status.shape) != tuple(conf.shape) or conf.numel() == 0:
+        raise ValueError(f'slotformer_amd: conf and status are [tasks, actions], got {tuple(conf.shape)} and {tuple(status.shape)}')
+    conf = conf.detach().float().contiguous()
+    status = status.to(torch.int32).contiguous()
+    tasks, actions = conf.shape
+    ranks = torch.empty(tasks, dtype=torch.int32, device=conf.device)
+    check(lib().sf_phyre_auccess_f32(_p(conf), _p(status), _p(ranks), tasks, actions, _stream()))
+    return ranks
