@@ -677,6 +677,56 @@ int sf_phyre_readout_fwd_f32(const float* slots, long long stride_v, long long s
  * task, two passes over its row. */
 int sf_phyre_auccess_f32(const float* conf, const int* status, int* first_rank, int tasks, int actions, void* stream);
 
+/* ---- CLEVRER VQA: the Aloe reasoner (clevrer_vqa/models/transformer.py, aloe.py; csrc/aloe.hip) ---------------------------------------------------
+ * Inference only.  tokens[b] = [CLS ; vision_in_proj([slot | 0 1]) for (t, n) t-major ; q_in_proj([q_embedding[token] | type pair | 1 0])] + pos,
+ * L = 1 + T N + text_len rows of d_model; num_layers pre-LN nn.TransformerEncoderLayer (relu, eps 1e-5) with the padded text positions masked out as
+ * keys; logits[b] = W2 relu(W1 x[b, 0] + b1) + b2.  Launches: the token rows (split-bf16 on MFMA), per layer LN1 + q|k|v, the masked attention
+ * (split-bf16 on MFMA, f32 softmax), out_proj + residual, LN2 + linear1 + ReLU, linear2 + residual (the library's GEMM), and a plain-f32 head.  The
+ * last layer computes k | v for every row and everything else for the CLS rows only.  Fixed summation orders, no floating-point atomics: equal inputs
+ * give equal bits.
+ * Limits (sf_aloe_ok, shapes only): 1 <= N <= 16 slots, C a multiple of 32 in [32, 256], T >= 1, text_len >= 1, 1 + T N + text_len <= 256,
+ * d_model = heads * head_dim <= 256 and a multiple of 4 (the GEMM's K), head_dim even in [4, 32], ffn a multiple of 64 in [64, 1024],
+ * 1 <= layers <= 32; pre-LN only.  Every violation -- and a process precision other than split-bf16 -- is a negative return code with a message before
+ * any launch. */
+typedef struct {
+  int num_slots, slot_size, T, text_len;   /* N, C, frames per question, text positions (question + choice) */
+  int question_len;                        /* multiple choice: text positions < question_len carry the question id pair [1 0], the others [0 1] */
+  int d_model, num_heads, ffn_dim, num_layers;
+  int vocab, emb_dim;                      /* rows of text_table; E = width of q_embedding (q_in_proj takes E + 4 inputs: E | type pair | text id pair) */
+  const float* cls;                        /* [d_model] */
+  const float* pos;                        /* [L][d_model]: added to every row, CLS included */
+  const float *vision_w, *vision_b;        /* vision_in_proj [d_model][C + 2] (column C + 1 is the vision id [0 1]), [d_model]; 16-byte aligned */
+  const float* q_in_proj_w;                /* [d_model][E + 4]: only its type columns E and E + 1 are read */
+  const float* text_table;                 /* [vocab][d_model] from sf_aloe_text_table_f32 */
+  const sf_tfm_layer* layers;              /* HOST array [num_layers]; the torch-layout pointers only */
+} sf_aloe;
+int sf_aloe_ok(int num_slots, int slot_size, int T, int text_len, int d_model, int num_heads, int ffn, int num_layers);
+/* bytes of the forward's workspace (token rows twice, attention rows, q|k|v, hidden rows); 0 for unsupported arguments or B outside [1, 65535] */
+size_t sf_aloe_workspace_bytes(int B, int num_slots, int T, int text_len, int d_model, int ffn);
+/* Once per weight version: q_embedding [vocab][E], q_in_proj_w [d_model][E + 4], q_in_proj_b [d_model] ->
+ * table[w] = q_in_proj_w[:, :E] q_embedding[w] + q_in_proj_w[:, E + 2] + q_in_proj_b  ([vocab][d_model]; text_token = [1 0] selects column E + 2). */
+int sf_aloe_text_table_f32(const float* q_embedding, const float* q_in_proj_w, const float* q_in_proj_b, float* table, int vocab, int emb_dim, int d_model,
+                           void* stream);
+/* slots: video v, frame f, slot n at slots + v * stride_v + f * stride_t + n * C (strides in elements, multiples of 4; stride_t >= N * C), V videos of
+ * T_all frames, read in place.  Batch entry b reads video video_index[b] (int32, device; any order, repeats allowed; NULL: video b) at frames
+ * start[b] + t * frame_offset, t < T (start: int32, device; NULL: 0).  tokens [B][text_len] int32 and pad_mask [B][text_len] bytes (1 = padded, never a
+ * key) on the device.  multiple_choice: 0 = every text position carries the id pair [0 1]; 1 = see question_len.  head_w1 [mlp_hidden][d_model],
+ * head_b1 [mlp_hidden], head_w2 [num_outputs][mlp_hidden], head_b2 [num_outputs] (both <= 1024) -> logits [B][num_outputs]; answers [B] int32 when not
+ * NULL: the argmax (first index on ties), for num_outputs == 1 logit > 0.  A video, a frame or the token of an unpadded position outside its table
+ * gives NaN logits (answer -1) for that entry, never an access.  workspace: 16-byte aligned, sf_aloe_workspace_bytes(...) bytes. */
+int sf_aloe_fwd_f32(const sf_aloe* m, const float* slots, long long stride_v, long long stride_t, int V, int T_all, const int* video_index, const int* start,
+                    int frame_offset, const int* tokens, const unsigned char* pad_mask, int multiple_choice, const float* head_w1, const float* head_b1,
+                    const float* head_w2, const float* head_b2, int mlp_hidden, int num_outputs, float* logits, int* answers, int B, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* One launch of one workgroup.  cls_logits [B1][num_answers] with cls_labels [B1] (int32); mc_logits [Bn] with mc_labels [Bn] (f32, 0 / 1), mc_flag [Bn]
+ * (int32: the question of every choice, non-decreasing runs) and mc_subtype [Q] (int32; explanatory 1, predictive 2, counterfactual 3; NULL: none).
+ * Either kind may be empty (B1 = 0 / Bn = 0, its pointers NULL).  -> losses [2] = mean cross-entropy, mean BCE-with-logits (0 for an empty kind);
+ * ques_correct [Q] int32 = every choice of the question has (logit > 0) == label; counts [10] int32, ADDED to what the buffer holds so that batches
+ * accumulate: descriptive (right, questions), multiple choice (right, questions), then the same for subtypes 1, 2, 3.  losses and counts may be NULL.
+ * A label outside [0, num_answers) gives a NaN loss, an mc_flag outside [0, Q) is skipped: never an access. */
+int sf_aloe_score_f32(const float* cls_logits, const int* cls_labels, int B1, int num_answers, const float* mc_logits, const float* mc_labels,
+                      const int* mc_flag, int Bn, const int* mc_subtype, int Q, float* losses, int* ques_correct, int* counts, void* stream);
+
 /* SlotRollouter / SingleStepSlotRollouter (slotformer.py:48-134, single_step_slotformer.py:6-90). */
 typedef struct {
   int num_slots, slot_size, d_model, num_layers, num_heads, ffn_dim, norm_first;

@@ -26,6 +26,12 @@ class sf_rollouter(C.Structure):
                 ('layers', C.POINTER(sf_tfm_layer)), ('in_proj_packed', C.c_void_p), ('out_proj_packed', C.c_void_p)]
 
 
+class sf_aloe(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('num_slots', 'slot_size', 'T', 'text_len', 'question_len', 'd_model', 'num_heads', 'ffn_dim', 'num_layers',
+                                       'vocab', 'emb_dim')] + [(n, FP) for n in ('cls', 'pos', 'vision_w', 'vision_b', 'q_in_proj_w', 'text_table')] + [
+                                           ('layers', C.POINTER(sf_tfm_layer))]
+
+
 class sf_rollout_opts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ('precision', 'seam_fused', 'ffn_rows', 'attn_heads_per_wg', 'attn_qkv_rows', 'ffn_tile', 'cus_available', 'layer_tok')]
 
@@ -298,6 +304,11 @@ SIGNATURES = {
     'sf_phyre_readout_fwd_f32': (I, [FP, LL, LL, I, I, VP, C.POINTER(C.c_int), FP, FP, FP, FP, C.POINTER(sf_tfm_layer), I, I, I, I, FP, FP, FP, FP, FP,
                                      FP, VP, FP, LL, I, I, I, I, VP, SZ, VP]),
     'sf_phyre_auccess_f32': (I, [FP, VP, VP, I, I, VP]),
+    'sf_aloe_ok': (I, [I, I, I, I, I, I, I, I]),
+    'sf_aloe_workspace_bytes': (SZ, [I, I, I, I, I, I]),
+    'sf_aloe_text_table_f32': (I, [FP, FP, FP, FP, I, I, I, VP]),
+    'sf_aloe_fwd_f32': (I, [C.POINTER(sf_aloe), FP, LL, LL, I, I, VP, VP, I, VP, VP, I, FP, FP, FP, FP, I, I, FP, VP, I, VP, SZ, VP]),
+    'sf_aloe_score_f32': (I, [FP, VP, I, I, FP, FP, VP, I, VP, I, FP, VP, VP, VP]),
     'sf_packed_linear_bytes': (SZ, [I, I]),
     'sf_pack_linear_weights': (I, [FP, VP, I, I, VP]),
     'sf_attn_packed_bytes': (SZ, [I, I]),

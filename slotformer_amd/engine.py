@@ -198,6 +198,34 @@ def phyre_readout_plan(m):
     return plan
 
 
+def aloe_plan(tm):
+    """tm: clevrer_vqa.models.CLEVRERTransformerModel on the device -> plan.struct, the `sf_aloe` descriptor: its layers as a host array, the
+    text table P[w] = q_in_proj([q_embedding[w] | . . | 1 0]) computed once (`ops.aloe_text_table`), the position rows.  Cached on the module and
+    rebuilt when a parameter changes ((data_ptr, _version) of every parameter), as `phyre_readout_plan`."""
+    sig = _signature(tm)
+    plan = getattr(tm, '_sf_plan', None)
+    if plan is not None and plan.sig == sig:
+        return plan
+    plan = _Plan()
+    s = _lib.sf_aloe()
+    enc = tm.transformer_encoder
+    l0 = enc.layers[0]
+    # (num_slots, T and text_len are the call's: the model reads them off its inputs and fills a copy of the descriptor)
+    s.slot_size, s.question_len = tm.vision_in_proj.in_features - 2, tm.question_len
+    s.d_model, s.num_heads, s.ffn_dim, s.num_layers = tm.d_model, l0.self_attn.num_heads, l0.linear1.out_features, len(enc.layers)
+    s.vocab, s.emb_dim = tm.q_embedding.num_embeddings, tm.q_embedding.embedding_dim
+    s.cls, s.pos = plan.dp(tm.CLS.reshape(-1)), plan.dp(enc.pos_enc.reshape(-1, tm.d_model))
+    s.vision_w, s.vision_b = plan.dp(tm.vision_in_proj.weight), plan.dp(tm.vision_in_proj.bias)
+    s.q_in_proj_w = plan.dp(tm.q_in_proj.weight)
+    plan.text_table = ops.aloe_text_table(tm.q_embedding.weight.detach().float().contiguous(), tm.q_in_proj.weight.detach().float().contiguous(),
+                                          tm.q_in_proj.bias.detach().float().contiguous())
+    s.text_table = plan.dp(plan.text_table)
+    s.layers = C.cast(_tfm_layers(plan, enc), C.POINTER(sf_tfm_layer))
+    plan.struct, plan.sig = s, sig
+    tm._sf_plan = plan
+    return plan
+
+
 def rollout_opts(opts):
     """dict / None -> ctypes sf_rollout_opts (None).  Keys: precision ('f32' | 'bf16x3' | 'bf16' | 'fp16' (probe) | 0..3), seam (bool),
     ffn_rows (32 | 64 | 128), attn_heads (2 | 8: heads per attention workgroup), attn_rows (0 | 128: q|k|v projection on row tiles of

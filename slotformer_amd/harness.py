@@ -363,3 +363,48 @@ def phyre_plan(savi, slotformer, readout, frames, statuses=None, batch_size=128,
     out = torch.empty(V, dtype=torch.float32, pin_memory=True)
     out.copy_(conf)
     return out
+
+
+@torch.no_grad()
+def clevrer_answers(model, slots, questions, batch_size=256, to_host=True):
+    """The inference loop of test_clevrer_vqa.py without its file I/O: slots [V, T_all, N, C] on the device (the rolled-out CLEVRER slots, read in
+    place), questions: the collated arrays -- `cls_q_tokens`, `cls_q_pad_mask` [B1, L], `cls_video_index`, `cls_start` [B1]; `mc_q_tokens`,
+    `mc_q_pad_mask` [Bn, L], `mc_flag` [Bn] (the question of every choice, non-decreasing), `mc_video_index`, `mc_start` [B2] (per QUESTION: the
+    video of a choice is video_index[mc_flag], an index composition); `frame_offset` and `num_frames` (datasets/clevrer.py: _get_slots reads
+    frames start + t * frame_offset; the caller applies the predictive-question shift to the start frames).  A kind may be absent or empty.
+    Returns (descriptive answer ids [B1] int32, per-choice booleans [Bn]) -- in pinned host memory with to_host=True, on the device otherwise;
+    `clevrer_vqa.result_records` assembles the reference's records from them.  `batch_size` sequences per forward, the last batch ragged."""
+    if int(batch_size) < 1:
+        raise ValueError(f'slotformer_amd.harness: batch_size >= 1, got {batch_size!r}')
+    model.eval()
+    dev = model.device
+    if dev.type != 'cuda' or not (torch.is_tensor(slots) and slots.is_cuda):
+        raise RuntimeError('slotformer_amd: clevrer_answers runs on a HIP device only; there is no CPU fallback')
+    tm = model.transformer_model
+    offset, frames = int(questions.get('frame_offset', 1)), questions.get('num_frames')
+
+    def on_dev(key, dtype):
+        v = questions.get(key)
+        return None if v is None else torch.as_tensor(v).to(dev, dtype)
+
+    out = []
+    for kind in ('cls', 'mc'):
+        tokens, pad = on_dev(f'{kind}_q_tokens', torch.int32), on_dev(f'{kind}_q_pad_mask', torch.uint8)
+        n = 0 if tokens is None else tokens.shape[0]
+        ans = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            vidx, start = on_dev(f'{kind}_video_index', torch.int64), on_dev(f'{kind}_start', torch.int64)
+            if kind == 'mc':
+                flag = on_dev('mc_flag', torch.int64)
+                vidx, start = vidx[flag], None if start is None else start[flag]
+            for a, b in render_chunks(n, int(batch_size)):
+                _, got = tm.answer(slots, tokens[a:b], pad[a:b], kind == 'mc', video_index=vidx[a:b], start=None if start is None else start[a:b],
+                                   frame_offset=offset, num_frames=frames, want_answers=True)
+                ans[a:b] = got
+        out.append(ans if kind == 'cls' else ans > 0)
+    if not to_host:
+        return tuple(out)
+    host = tuple(torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in out)
+    for h, t in zip(host, out):
+        h.copy_(t)
+    return host

@@ -707,3 +707,93 @@ def phyre_auccess_ranks(conf, status):
     ranks = torch.empty(tasks, dtype=torch.int32, device=conf.device)
     check(lib().sf_phyre_auccess_f32(_p(conf), _p(status), _p(ranks), tasks, actions, _stream()))
     return ranks
+
+
+# ---- CLEVRER VQA: the Aloe reasoner (csrc/aloe.hip) --------------------------------------------------------------------------------------------
+ALOE_LIMITS = ('1 <= num_slots <= 16, slot_size a multiple of 32 in [32, 256], 1 + frames * num_slots + text positions <= 256 tokens, '
+               'd_model = heads * head_dim <= 256 and a multiple of 4, head_dim even in [4, 32], ffn_dim a multiple of 64 in [64, 1024], '
+               'norm_first, 1 <= num_layers <= 32')
+ALOE_COUNT_KEYS = ('descriptive', 'multiple-choice', 'explanatory', 'predictive', 'counterfactual')   # (right, questions) pairs of the counts
+
+
+def aloe_ok(num_slots, slot_size, T, text_len, d_model, num_heads, ffn, num_layers):
+    """Whether the Aloe kernels take these shapes (`sf_aloe_ok`; shapes only, no device needed)."""
+    return bool(lib().sf_aloe_ok(int(num_slots), int(slot_size), int(T), int(text_len), int(d_model), int(num_heads), int(ffn), int(num_layers)))
+
+
+def aloe_text_table(q_embedding, q_in_proj_w, q_in_proj_b):
+    """table [vocab, d_model] = q_in_proj over [q_embedding[w] | . . | 1 0] without the type pair (`sf_aloe_text_table_f32`)."""
+    _chk(q_embedding, q_in_proj_w, q_in_proj_b)
+    vocab, E = q_embedding.shape
+    d = q_in_proj_w.shape[0]
+    if q_in_proj_w.shape[1] != E + 4:
+        raise ValueError(f'slotformer_amd: q_in_proj takes {q_in_proj_w.shape[1]} inputs, an embedding with its two id pairs has {E + 4}')
+    table = torch.empty(vocab, d, dtype=torch.float32, device=q_embedding.device)
+    check(lib().sf_aloe_text_table_f32(_p(q_embedding), _p(q_in_proj_w), _p(q_in_proj_b), _p(table), vocab, E, d, _stream()))
+    return table
+
+
+def aloe_fwd(model_struct, slots, tokens, pad_mask, head, multiple_choice, video_index=None, start=None, frame_offset=1, want_answers=False):
+    """logits [B, A] of the Aloe reasoner (`sf_aloe_fwd_f32`).  model_struct: the `sf_aloe` of engine.aloe_plan; slots [V,T_all,N,C] read in place
+    (see `_readout_slots`) at video `video_index[b]` (default b), frames `start[b] + t * frame_offset` (default from 0); tokens / pad_mask
+    [B, text_len] (pad_mask True = padded); head: (W1, b1, W2, b2) of the answer MLP.  Returns (logits, answers [B] int32 or None)."""
+    import ctypes as C
+    slots, T_all = _readout_slots(slots, None)
+    V = slots.shape[0]
+    dev = slots.device
+    tokens = torch.as_tensor(tokens, device=dev).to(torch.int32).contiguous()
+    pad_mask = torch.as_tensor(pad_mask, device=dev).to(torch.uint8).contiguous()
+    m = model_struct
+    if tokens.dim() != 2 or tokens.shape[1] != m.text_len or tuple(pad_mask.shape) != tuple(tokens.shape):
+        raise ValueError(f'slotformer_amd: tokens and pad mask are [B, {m.text_len}], got {tuple(tokens.shape)} and {tuple(pad_mask.shape)}')
+    if tuple(slots.shape[2:]) != (m.num_slots, m.slot_size):
+        raise ValueError(f'slotformer_amd: slots are [V, T, {m.num_slots}, {m.slot_size}], got {tuple(slots.shape)}')
+    B = tokens.shape[0]
+    video_index, start = _index32(video_index, dev), _index32(start, dev)
+    for name, t in (('video_index', video_index), ('start', start)):
+        if t is not None and t.numel() != B:
+            raise ValueError(f'slotformer_amd: {name} holds one entry per batch entry ({B}), got {t.numel()}')
+    W1, b1, W2, b2 = head
+    _chk(W1, b1, W2, b2)
+    H, A = W1.shape[0], W2.shape[0]
+    logits = torch.empty(B, A, dtype=torch.float32, device=dev)
+    answers = torch.empty(B, dtype=torch.int32, device=dev) if want_answers else None
+    nbytes = int(lib().sf_aloe_workspace_bytes(B, m.num_slots, m.T, m.text_len, m.d_model, m.ffn_dim))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    check(lib().sf_aloe_fwd_f32(C.byref(m), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), _p(start), int(frame_offset),
+                                _p(tokens), _p(pad_mask), int(bool(multiple_choice)), _p(W1), _p(b1), _p(W2), _p(b2), H, A, _p(logits), _p(answers), B,
+                                ws.data_ptr(), ws.numel(), _stream()))
+    return logits, answers
+
+
+def aloe_score(cls_logits=None, cls_labels=None, mc_logits=None, mc_labels=None, mc_flag=None, mc_subtype=None, counts=None, device=None):
+    """One launch (`sf_aloe_score_f32`): losses [2] = (mean cross-entropy of the descriptive logits [B1, A], mean BCE-with-logits of the
+    multiple-choice logits [Bn]; 0 for an absent kind), ques_correct [Q] int32 (Q = len(mc_subtype): every choice of the question right) and the
+    int32 counts [10] -- (right, questions) for ALOE_COUNT_KEYS -- ADDED to `counts` when it is passed, so that batches accumulate."""
+    have_cls, have_mc = cls_logits is not None and cls_logits.numel() > 0, mc_logits is not None and mc_logits.numel() > 0
+    dev = cls_logits.device if have_cls else (mc_logits.device if have_mc else device)
+    if dev is None or torch.device(dev).type != 'cuda':
+        raise RuntimeError('slotformer_amd: the answer score needs its logits on a HIP device; there is no CPU fallback')
+    B1 = A = Bn = Q = 0
+    if have_cls:
+        cls_logits = cls_logits.detach().float().contiguous()
+        B1, A = cls_logits.shape
+        cls_labels = torch.as_tensor(cls_labels, device=dev).reshape(B1).to(torch.int32).contiguous()
+    else:
+        cls_logits = cls_labels = None
+    if have_mc:
+        mc_logits = mc_logits.detach().float().reshape(-1).contiguous()
+        Bn = mc_logits.numel()
+        mc_labels = torch.as_tensor(mc_labels, device=dev).reshape(Bn).float().contiguous()
+        mc_flag = torch.as_tensor(mc_flag, device=dev).reshape(Bn).to(torch.int32).contiguous()
+        mc_subtype = _index32(mc_subtype, dev)
+        Q = 0 if mc_subtype is None else mc_subtype.numel()
+    else:
+        mc_logits = mc_labels = mc_flag = mc_subtype = None
+    losses = torch.empty(2, dtype=torch.float32, device=dev)
+    ques = torch.empty(Q, dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.zeros(10, dtype=torch.int32, device=dev)
+    check(lib().sf_aloe_score_f32(_p(cls_logits), _p(cls_labels), B1, A, _p(mc_logits), _p(mc_labels), _p(mc_flag), Bn, _p(mc_subtype), Q, _p(losses),
+                                  ques.data_ptr() if Q else None, _p(counts), _stream()))
+    return losses, ques, counts
