@@ -243,6 +243,26 @@ int sf_ingest_frames_u8(const unsigned char* src, const unsigned char* palette, 
 int sf_resize_masks_nearest(const void* src, int src_is_u8, const void* tables, long long* out_i64, unsigned char* out_u8, int F, int H0,
                             int W0, int H, int W, void* stream);
 
+/* ---- annotation masks -> ground truth (base_slots/datasets/clevrer.py:101-125 _read_masks, datasets/utils.py:46-77; csrc/rle_masks.hip) ---------
+ * The run-length masks of F frames, parsed and packed on the host (slotformer_amd/annotations.py): run_ends [num_runs] uint32, the CUMULATIVE run
+ * ends of every object one after the other -- run j of an object covers the column-major source indices [end[j-1], end[j]) (index x * h + y), odd j
+ * is covered --; object_offsets [num_objects + 1], the first run of every object; frame_offsets [F + 1], the first object of every frame (a
+ * pointer INTO a longer array selects a range of frames: the offsets are absolute).  A frame's objects beyond the 15th are ignored.  tables: the
+ * DEVICE copy of the mode-2 (nearest) table of (h, w) -> (H, W), the one sf_resize_masks_nearest takes.
+ * labels [F,H,W] as int64 and / or uint8 (either may be NULL): 1 + the first object of the frame, in order, that covers the pixel's source pixel, 0
+ * where none does = argmax(0) over [not any(objects), objects...].  extents [F,15,5] int32: {min x, min y, max x, max y, pixels} of every object's
+ * OWN resized mask (an object hidden behind an earlier one has no label pixel but keeps its extents); {-1,-1,-1,-1,0} without a pixel.  Integer
+ * results, equal bits on every run.  Every offset read is clamped to num_objects / num_runs and every table entry to the source size:
+ * unvalidated arrays give wrong labels, never an access outside the arrays.  One launch, nothing to zero beforehand. */
+int sf_rle_label_maps(const unsigned* run_ends, const int* object_offsets, const int* frame_offsets, const void* tables, long long* labels_i64,
+                      unsigned char* labels_u8, int* extents, int F, int num_objects, int num_runs, int h, int w, int H, int W, void* stream);
+/* masks_to_boxes_pad (datasets/utils.py:59-77) on the extents of sf_rle_label_maps: bbox [F,num,4] float32 [min x, min y, max x, max y] and
+ * pres_mask [F,num] bytes (torch.bool): the objects with a pixel AFTER the resize, compacted in order, padded with zeros; pres_mask is 1 for the
+ * first k.  (The label ids of sf_rle_label_maps are not compacted: the asymmetry is the reference's.)  num <= 64.  flag: one device word, zeroed by
+ * the call, set to 1 when a frame has more objects with a pixel than num (the reference fails with a shape error there); such a frame keeps its
+ * first num boxes. */
+int sf_rle_boxes_pad(const int* extents, float* bbox, unsigned char* pres_mask, unsigned* flag, int F, int num, void* stream);
+
 /* ---- egress: decoded frames, slot decompositions, segment ids and boxes -> the videos a writer takes (video_prediction/vp_vis.py make_video /
  * draw_bbox, base_slots/method.py _make_video_grid, the `(video * 255.).astype(np.uint8)` of _save_video; csrc/egress.hip) -----------------------
  * The float work is the reference's float32 operations in their order, each rounded once (nothing is contracted into an fma except x * 0.5 + 0.5,

@@ -189,6 +189,8 @@ SIGNATURES = {
     'sf_ingest_tables_host': (I, [VP, SZ, I, I, I, I, I]),
     'sf_ingest_frames_u8': (I, [VP, VP, I, VP, FP, FP, FP, I, I, I, I, I, I, I, VP]),
     'sf_resize_masks_nearest': (I, [VP, I, VP, VP, VP, I, I, I, I, I, VP]),
+    'sf_rle_label_maps': (I, [VP, VP, VP, VP, VP, VP, VP, I, I, I, I, I, I, I, VP]),
+    'sf_rle_boxes_pad': (I, [VP, FP, VP, VP, I, I, VP]),
     'sf_egress_frames_u8': (I, [FP, VP, LL, I, I, I, I, I, VP]),
     'sf_egress_grid_shape': (I, [I, I, I, I, I, I, C.POINTER(I), C.POINTER(I)]),
     'sf_egress_grid': (I, [C.POINTER(sf_egress_tile), I, VP, I, I, I, I, I, I, F32, I, VP]),

@@ -408,3 +408,120 @@ def clevrer_answers(model, slots, questions, batch_size=256, to_host=True):
     for h, t in zip(host, out):
         h.copy_(t)
     return host
+
+
+VP_METRICS = ('mse', 'psnr', 'ssim', 'percept_dist', 'ari', 'fari', 'miou', 'ap', 'ar')   # the arrays test_vp.py saves, plus 'ap'
+
+
+@torch.no_grad()
+def evaluate_video_prediction(model, slots, frames, rollout_len=None, batch_size=8, ingest=None, annotations=None, gt=None, lpips=None,
+                              eval_traj=None, max_n_objects=6):
+    """The loop of video_prediction/test_vp.py:139-163, 211-219 without its file I/O: per batch of `batch_size` videos (the last one may be ragged)
+    the burn-in slots are rolled out, the predicted slots decoded to frames and a uint8 segmentation, the predicted boxes taken from it, and the
+    batch scored by `vp_utils.pred_eval_step_device`; the per-step means are accumulated over the batches weighted by the batch size
+    (AverageMeter.update(val, B): sum += val * B) in float64 ON THE DEVICE.  No host synchronisation and no download inside the loop; one download
+    at the end.
+
+    model: a SlotFormer in eval mode (its rollouter and its StoSAVi decoder).  slots [V, T_total, N, C], the stored slots, on the host or on the
+    device: only the first `history_len` frames are read.  frames [V, T_total, 3, R, R] float32 in [-1, 1], or with ingest= (an
+    `ingest.FrameIngest`) the raw uint8 clips [V, T_total, H0, W0, 3]; only frames [history_len, history_len + rollout_len) are read.
+    rollout_len: default T_total - history_len.  The ground truth of the trajectory scores, over the same T_total frames: annotations= the
+    nested list [V][T_total] of per-frame run-length masks of `annotations.pack_frames`, packed once, uploaded ahead of the loop and expanded
+    per batch by `annotations.ground_truth` at the resolution of `ingest` (without ingest=: at R x R); or gt= {'mask' [V, T_total, R, R] int64,
+    'pres_mask' [V, T_total, M] bool, 'bbox' [V, T_total, M, 4] float32}, ready tensors.  eval_traj: default 'a ground truth was given'; without
+    (OBJ3D) the five trajectory scores are zeros, as in the reference.  lpips: a `slotformer_amd.lpips.LPIPS`, or None: 'percept_dist' is then
+    0.0, as `pred_eval_step` has it.
+
+    Returns {'mse', 'psnr', 'ssim', 'percept_dist', 'ari', 'fari', 'miou', 'ap', 'ar': np.float64 [rollout_len], 'num_videos': V}.  A step mean
+    that is NaN ('ap' / 'ar' of a batch with a frame without boxes) makes that entry NaN for good, as the reference's AverageMeter does.
+    RuntimeError when a mask id lay outside [0, 16), as `pred_eval_step` raises -- read from the one download, after the loop."""
+    from . import engine
+    from . import annotations as ann
+    from .video_prediction import vp_utils
+    if int(batch_size) < 1:
+        raise ValueError(f'slotformer_amd.harness: batch_size >= 1, got {batch_size!r}')
+    if annotations is not None and gt is not None:
+        raise ValueError('slotformer_amd.harness: annotations= or gt=, not both')
+    model.eval()
+    dev = model.device
+    if dev.type != 'cuda':
+        raise RuntimeError('slotformer_amd: evaluate_video_prediction runs on a HIP device only; there is no CPU fallback')
+    if slots.dim() != 4:
+        raise ValueError(f'slotformer_amd.harness: slots are [V, T_total, N, C], got {tuple(slots.shape)}')
+    V, T_total, N, C_ = slots.shape
+    hist = model.history_len
+    L_ = T_total - hist if rollout_len is None else int(rollout_len)
+    if V < 1 or L_ < 1 or hist + L_ > T_total:
+        raise ValueError(f'slotformer_amd.harness: {V} videos of {T_total} frames, burn-in {hist}, rollout {L_}')
+    if ingest is None:
+        if frames.dim() != 5 or tuple(frames.shape[:3]) != (V, T_total, 3):
+            raise ValueError(f'slotformer_amd.harness: frames are [{V}, {T_total}, 3, R, R], got {tuple(frames.shape)}')
+        from . import ingest as ingest_mod
+        mask_ingest = ingest_mod.FrameIngest(tuple(frames.shape[-2:]))   # (only its nearest table is used)
+    else:
+        shape = ingest.output_shape(frames)   # (raises for anything but contiguous uint8 frames)
+        if frames.dim() != (4 if ingest.palette is not None else 5) or tuple(shape[:2]) != (V, T_total):
+            raise ValueError(f'slotformer_amd: ingest= takes clips [{V}, {T_total}, H0, W0, 3] ([.., H0, W0] with a palette), got {tuple(frames.shape)}')
+        mask_ingest = ingest
+    if eval_traj is None:
+        eval_traj = annotations is not None or gt is not None
+    if eval_traj and annotations is None and gt is None:
+        raise ValueError('slotformer_amd.harness: eval_traj needs annotations= or gt=')
+    packed = None
+    if eval_traj and annotations is not None:
+        if len(annotations) != V or any(len(v) != T_total for v in annotations):
+            raise ValueError(f'slotformer_amd.harness: annotations are a nested list [{V}][{T_total}] of per-frame object lists')
+        packed = ann.pack_frames([list(v[hist:hist + L_]) for v in annotations])   # the frames that are scored, [V][L]
+        packed.on(dev)                                                             # uploaded once, ahead of the loop
+    elif eval_traj:
+        for k, nd in (('mask', 4), ('pres_mask', 3), ('bbox', 4)):
+            if k not in gt or gt[k].dim() != nd or tuple(gt[k].shape[:2]) != (V, T_total):
+                raise ValueError(f'slotformer_amd.harness: gt= holds mask [V, T_total, R, R], pres_mask [V, T_total, M] and bbox [V, T_total, M, 4]')
+    K = len(vp_utils.METRICS)
+    acc = torch.zeros((K + 1) * L_ + 2, dtype=torch.float64, device=dev)   # the sums and, behind them, the two flag words: one download
+    total = acc[:(K + 1) * L_].view(K + 1, L_)                             # rows of vp_utils.METRICS, then percept_dist
+    flags = torch.zeros(2, dtype=torch.int32, device=dev)                  # a mask id outside [0, 16); more non-empty objects than boxes
+    for a, b in render_chunks(V, int(batch_size)):
+        B = b - a
+        clip = torch.empty(B, hist + L_, N, C_, dtype=torch.float32, device=dev)
+        clip[:, :hist].copy_(slots[a:b, :hist], non_blocking=True)
+        engine.rollout(model.rollouter, clip, hist, L_)
+        recon, _, _, seg = engine.savi_decode(model, clip[:, hist:].reshape(B * L_, N, C_), want=('seg', ), seg_dtype=torch.uint8)
+        R = recon.shape[-1]
+        recon, seg = recon.view(B, L_, 3, R, R), seg.view(B, L_, R, R)
+        want = frames[a:b, hist:hist + L_]
+        if ingest is None:
+            want = want.to(dev, torch.float32, non_blocking=True).contiguous()
+        else:
+            want = ingest(want.contiguous().to(dev, non_blocking=True))
+        if tuple(want.shape) != tuple(recon.shape):
+            raise ValueError(f'slotformer_amd.harness: ground-truth frames {tuple(want.shape[-2:])}, decoded frames {R} x {R}')
+        kw = {}
+        if eval_traj:
+            if packed is not None:
+                g, over = ann.device_ground_truth(packed.frames(a * L_, b * L_, lead=(B, L_)), mask_ingest, max_n_objects, dev)
+                flags[1:] |= over
+            else:
+                g = {k: gt[k][a:b, hist:hist + L_].to(dev, non_blocking=True) for k in ('mask', 'pres_mask', 'bbox')}
+            kw = dict(gt_mask=g['mask'].long(), pred_mask=seg, gt_pres_mask=g['pres_mask'].bool(), gt_bbox=g['bbox'].float(),
+                      pred_bbox=vp_utils.masks_to_boxes(seg, model.num_slots))
+        out = vp_utils.pred_eval_step_device(want, recon, eval_traj=bool(eval_traj), lpips=lpips, **kw)
+        # (the step's result buffers are reused by the next call of this shape: accumulate now)
+        total[:K] += torch.stack([out[m] for m in vp_utils.METRICS]) * B
+        if lpips is not None:
+            total[K] += out['percept_dist'] * B
+        flags[:1] |= out['id_out_of_range']
+    acc[(K + 1) * L_:] = flags
+    host = torch.empty(acc.shape, dtype=torch.float64, pin_memory=True)
+    host.copy_(acc, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    if host[-1].item() != 0:
+        raise ValueError(f'evaluate_video_prediction: a frame has more than {int(max_n_objects) + 1} non-empty objects (max_n_objects + 1)')
+    if host[-2].item() != 0:
+        raise RuntimeError('evaluate_video_prediction: a mask id outside [0, 16)')
+    avg = host[:(K + 1) * L_].view(K + 1, L_).numpy() / float(V)
+    res = {m: avg[i].copy() for i, m in enumerate(vp_utils.METRICS)}
+    res['percept_dist'] = avg[K].copy()
+    res = {m: res[m] for m in VP_METRICS}
+    res['num_videos'] = V
+    return res
