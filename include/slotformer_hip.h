@@ -811,6 +811,22 @@ int sf_set_layer_tok(int on);   /* process default of sf_rollout_opts.layer_tok 
 int sf_get_layer_tok(void);
 int sf_rollout_opts_f32(const sf_rollouter* m, float* slots, int B, int T_total, int pred_len, void* ws, size_t ws_bytes,
                         void* stream, const sf_rollout_opts* opts); /* opts == NULL: sf_rollout_f32 */
+/* Rollout at a frame offset, every phase of a video in ONE call (rollout_clevrer_slots.py:20-65 with frame_offset 2,
+ * rollout_physion_slots.py:22-63 with 3: the reference rolls a video forward frame_offset times, once per phase, and interleaves).
+ * slots [B, T_total, N, C]; f = frame_offset >= 1, hist = window_len (1 for a single-step rollouter, which takes f == 1 only),
+ * first = obs - hist * f >= 0.  Phase p < f burns in on frames first + p + j * f (j < hist) and writes frame obs + p + s * f at
+ * step s; all phases run S = ceil(pred_len / f) steps, so frames obs .. obs + S * f - 1 are written -- every one of them, there is
+ * no masked write: T_total >= obs + S * f, and a caller who wants exactly pred_len frames pads the buffer and slices.  Frames
+ * before `first`, the burn-in frames and frames from obs + S * f on are never written.
+ * A phase is a VIRTUAL VIDEO v = b * f + p: the call is planned, and runs the launches, of a rollout of B * f videos (whatever
+ * path that is: fused ring with or without seams, row tiles, long window, generic GEMMs, token-stationary layers), and its
+ * workspace is that of B * f videos.  Where sf_rollout_is_fused promises batch-independent bits, the result equals, bit for bit,
+ * sf_rollout_opts_f32 run once per phase on gathered copies; with f == 1 and obs == hist it IS sf_rollout_opts_f32.
+ * An argument error before any launch: f < 1, a single-step rollouter with f > 1, first < 0, a buffer that is too short, null pointers.
+ * opts == NULL: the thread's defaults. */
+size_t sf_rollout_phases_workspace_bytes(const sf_rollouter* m, int B, int frame_offset);
+int sf_rollout_phases_f32(const sf_rollouter* m, float* slots, int B, int T_total, int obs, int frame_offset, int pred_len, void* ws,
+                          size_t ws_bytes, void* stream, const sf_rollout_opts* opts);
 /* 1 when sf_rollout_f32 runs this model's Transformer layers as the fused per-video / per-row launches (d_model 256, 8 heads,
  * ffn 1024, window <= 64 tokens, packed weights, split-bf16 mode): a video's result then does not depend on the batch it is in -- bit for bit in the
  * row-tile / latency forms; with layer_tok on, to ~1e-6 per layer (a video's last bits depend on its position modulo the videos of a workgroup) */

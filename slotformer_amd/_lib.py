@@ -212,6 +212,8 @@ SIGNATURES = {
     'sf_rollout_workspace_bytes': (SZ, [C.POINTER(sf_rollouter), I]),
     'sf_rollout_f32': (I, [C.POINTER(sf_rollouter), FP, I, I, I, VP, SZ, VP]),
     'sf_rollout_opts_f32': (I, [C.POINTER(sf_rollouter), FP, I, I, I, VP, SZ, VP, C.POINTER(sf_rollout_opts)]),
+    'sf_rollout_phases_workspace_bytes': (SZ, [C.POINTER(sf_rollouter), I, I]),
+    'sf_rollout_phases_f32': (I, [C.POINTER(sf_rollouter), FP, I, I, I, I, I, VP, SZ, VP, C.POINTER(sf_rollout_opts)]),
     'sf_rollout_uses_seam': (I, [C.POINTER(sf_rollouter), I]),
     'sf_rollout_uses_seam_opts': (I, [C.POINTER(sf_rollouter), I, C.POINTER(sf_rollout_opts)]),
     'sf_rollout_is_fused': (I, [C.POINTER(sf_rollouter)]),

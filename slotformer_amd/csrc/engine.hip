@@ -301,17 +301,42 @@ __global__ void zero_words_kernel(unsigned* a, unsigned* b) {
   if (p) p[threadIdx.x] = 0u;
 }
 
-int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int pred_len, void* ws,
-                   size_t ws_bytes, void* stream) {
+// float4 i of the staged window [B][nf * N][C] of virtual videos v = b * f + p: frame j of v is frame (f0 + j) * f + p of video b
+// (fe = N * C elements per frame, a multiple of 4; n4 float4 in all)
+__global__ void gather_phase_window_kernel(const float* __restrict__ slots, long long bs, int f, long long fe, int f0, int nf,
+                                           float* __restrict__ dst, long long n4) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const long long e = 4 * i, pv = (long long)nf * fe, v = e / pv, r = e - v * pv, j = r / fe, o = r - j * fe;
+  const long long b = v / f, p = v - b * f;
+  *(float4*)(dst + e) = *(const float4*)(slots + b * bs + ((f0 + j) * f + p) * fe + o);
+}
+
+}  // extern "C"
+
+namespace {
+// The rollout of sf_rollout_f32 (f == 1, first == 0) and of sf_rollout_phases_f32 on B * f VIRTUAL videos v = b * f + p, phase p of
+// video b: frame u of v is frame first + u * f + p of video b.  The burn-in is frames 0 .. n_in-1 of every virtual video, step s
+// writes its frame n_in + s.  Everything between the in-projection and the out-projection -- the plan, the workspace, every layer
+// launch -- sees B * f videos and nothing else; `slots` is touched by the step boundary / ring initialisation (layer_fused.hip: the
+// frames the f phases of a video write in one step are consecutive, one group of f * N rows) and by the two row maps of the paths
+// without a ring.  Of those the out-projection's is the same group of f * N rows; the window's rows lie f frames apart, which a row
+// map cannot say, so for f > 1 the window is staged into contiguous rows first (one small copy launch per step, into workspace the
+// path leaves idle) -- the row map, and with it every GEMM kernel of the library, stays as it is.
+int rollout_run(const sf_rollouter* m, float* slots, int Bvid, int T_total, int first, int f, int pred_len, void* ws,
+                size_t ws_bytes, void* stream) {
   SF_REQUIRE(m && slots && ws, "null pointer");
-  SF_REQUIRE(B >= 1 && pred_len >= 0, "bad batch / pred_len");
+  SF_REQUIRE(Bvid >= 1 && pred_len >= 0 && f >= 1 && first >= 0, "bad batch / pred_len");
   SF_REQUIRE(m->num_slots >= 1 && m->slot_size > 0 && (m->slot_size % 4) == 0 && m->d_model > 0 &&
                  (m->d_model % 4) == 0 && m->ffn_dim > 0 && (m->ffn_dim % 4) == 0 && m->num_layers >= 1 &&
                  m->window_len >= 1, "bad rollouter shape");
   SF_REQUIRE(m->in_proj_w && m->in_proj_b && m->out_proj_w && m->out_proj_b && m->pe_tok, "null weight");
   SF_REQUIRE(check_layers(m->layers, m->num_layers) == 0, "null transformer-layer weight");
   const int n_in = m->single_step ? 1 : m->window_len;
-  SF_REQUIRE(T_total >= n_in + pred_len, "slots buffer shorter than burn-in + pred_len");
+  SF_REQUIRE(!(m->single_step && f > 1), "sf_rollout_phases_f32: a single-step rollouter takes frame_offset 1 only");
+  SF_REQUIRE((long long)T_total >= first + (long long)(n_in + pred_len) * f, "slots buffer shorter than burn-in + pred_len");
+  SF_REQUIRE((long long)Bvid * f <= 0x7fffffffLL / ((long long)m->window_len * m->num_slots), "batch too large");
+  const int B = Bvid * f;   // virtual videos
   SF_REQUIRE(ws_bytes >= sf_rollout_workspace_bytes(m, B), "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int N = m->num_slots, C = m->slot_size, d = m->d_model, W = m->window_len, nl = m->num_layers;
@@ -325,9 +350,18 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
   const int np = p.attn == RolloutPlan::HEAD_PAIRS ? 4 : 1;   // attention partials the FFN sums
   const int RF = W + 1;   // frames in the projection ring: the window being read + the frame being written
   const long long bs = (long long)T_total * N * C;
+  slots += (long long)first * N * C;   // frame 0 of the virtual videos
+  // f > 1 without a ring: where the window is staged -- the attention partials on the paths that run no fused layer, else the ring
+  float* stage = nullptr;
+  if (f > 1 && !ring_in) {
+    const bool in_apb = !p.fused();
+    stage = in_apb ? w.apb : w.ring;
+    SF_REQUIRE(in_apb ? C <= 8 * d : (long long)W * C <= (long long)(W + 1) * d,
+               "sf_rollout_phases_f32: slot_size too wide for this model's idle workspace (the staged window)");
+  }
   if (ring_in) {
     // in-projection (without PE) of the burn-in frames -> ring slots 0 .. n_in-1
-    SF_TRY(sf_ring_init_ex(m->out_proj_packed, m->out_proj_b, m->in_proj_packed, m->in_proj_b, slots, bs, n_in, w.ring, RF, N, B, st));
+    SF_TRY(sf_ring_init_ex(m->out_proj_packed, m->out_proj_b, m->in_proj_packed, m->in_proj_b, slots, bs, n_in, w.ring, RF, N, B, st, f));
   }
   if (p.fused() || long_ffn) {
     SF_REQUIRE(sf_ffn_tiles(B * W * N) <= 1024, "batch too large for the fused-layer tile counters");
@@ -356,7 +390,13 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
       // x = in_proj(window) + pe   (slotformer.py:115-117; single_step_slotformer.py:79-81)
       SfRowMap pmap = sf_rows(d);
       pmap.base = (long long)pe_off * d;
-      SF_TRY(sf_linear_ex(slots, sf_rows_batched(C, L, bs, (long long)f0 * N * C), m->in_proj_w, m->in_proj_b,
+      if (stage) {
+        const long long n4 = (long long)B * L * C / 4;
+        hipLaunchKernelGGL(gather_phase_window_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, slots, bs, f, (long long)N * C, f0, nf,
+                           stage, n4);
+        SF_CHECK_LAUNCH();
+      }
+      SF_TRY(sf_linear_ex(stage ? stage : slots, stage ? sf_rows(C) : sf_rows_batched(C, L, bs, (long long)f0 * N * C), m->in_proj_w, m->in_proj_b,
                           nullptr, nullptr, 0.f, m->pe_tok, pmap, L, w.x, sf_rows(d), B * L, d, C, 0, st));
       cin = w.x;
     }
@@ -382,10 +422,11 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
                          long_ffn ? w.xpb : nullptr, long_ffn ? w.counters : nullptr));
         Lc = Lq;
       }
-      // pred = out_proj(x[:, -N:]) written straight into frame n_in + s   (slotformer.py:121-124)
+      // pred = out_proj(x[:, -N:]) written straight into frame n_in + s   (slotformer.py:121-124): the f phases of a video write f
+      // consecutive frames, f * N rows
       const SfRowMap lastmap = (Lc == N) ? sf_rows(d) : sf_rows_batched(d, N, (long long)Lc * d, (long long)(Lc - N) * d);
       SF_TRY(sf_linear_ex(cin, lastmap, m->out_proj_w, m->out_proj_b, nullptr, nullptr, 0.f, nullptr, sf_rows(C), 0,
-                          slots, sf_rows_batched(C, N, bs, (long long)(n_in + s) * N * C), B * N, C, d, 0, st));
+                          slots, sf_rows_batched(C, f * N, bs, (long long)(n_in + s) * f * N * C), B * N, C, d, 0, st));
       continue;
     }
     // every other layer is two launches: the attention block, then the FFN block (which also finishes the sums)
@@ -449,12 +490,12 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
           SF_TRY(sf_seam_ex(ap, pst, lw, eps, w.xpb, pst, w.counters, m->ffn_dim, m->out_proj_packed, m->out_proj_b,
                             m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s, w.ring, RF, N, B, m->layers[0], f01,
                             m->pe_tok + (long long)((W - nf1) * N) * d, ap_next, (long long)B * Lq1 * d, L1, Lq1, w.seam_flags,
-                            (unsigned)(s + 1), st));
+                            (unsigned)(s + 1), st, f));
           ap0 = ap_next;
           attn0_done = true;
         } else {
           SF_TRY(sf_ffn_boundary_ex(ap, pst, lw, eps, w.xpb, pst, w.counters, m->ffn_dim, m->out_proj_packed, m->out_proj_b,
-                                    m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s, w.ring, RF, N, B, st, np));
+                                    m->in_proj_packed, m->in_proj_b, slots, bs, n_in + s, w.ring, RF, N, B, st, np, f));
           ap0 = w.apb;
           attn0_done = false;
         }
@@ -462,11 +503,19 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
         // last layer: FFN into finished rows, then pred = out_proj(them) written straight into frame n_in + s
         SF_TRY(sf_ffn_partial_ex(ap, pst, lw, eps, w.xpb, pst, xo, w.counters, B * Lq, m->ffn_dim, st, np));
         SF_TRY(sf_linear_ex(xo, sf_rows(d), m->out_proj_w, m->out_proj_b, nullptr, nullptr, 0.f, nullptr, sf_rows(C), 0,
-                            slots, sf_rows_batched(C, N, bs, (long long)(n_in + s) * N * C), B * N, C, d, 0, st));
+                            slots, sf_rows_batched(C, f * N, bs, (long long)(n_in + s) * f * N * C), B * N, C, d, 0, st));
       }
     }
   }
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int pred_len, void* ws,
+                   size_t ws_bytes, void* stream) {
+  return rollout_run(m, slots, B, T_total, 0, 1, pred_len, ws, ws_bytes, stream);
 }
 
 // SURVEY.md 8(b2) `sf_rollout_bf16`: the same rollout with every matrix product in SINGLE-PASS bf16 (operands rounded to
@@ -525,14 +574,8 @@ SfThreadOpts rollout_thread_opts(const sf_rollout_opts* opts) {
   if (opts->layer_tok != 0) o.layer_tok = opts->layer_tok > 0 ? 1 : -1;
   return o;
 }
-}  // namespace
 
-// sf_rollout_f32 with per-call options (include/slotformer_hip.h, sf_rollout_opts): arithmetic mode, seam launches, rows
-// per FFN workgroup, videos per attention workgroup.  The options live in thread-local state for the duration of the call,
-// so concurrent calls from other host threads (one per GPU in the reference's drivers, extract_slots.py:128) keep theirs.
-int sf_rollout_opts_f32(const sf_rollouter* m, float* slots, int B, int T_total, int pred_len, void* ws, size_t ws_bytes,
-                        void* stream, const sf_rollout_opts* opts) {
-  if (!opts) return sf_rollout_f32(m, slots, B, T_total, pred_len, ws, ws_bytes, stream);
+int check_rollout_opts(const sf_rollout_opts* opts) {
   SF_REQUIRE(opts->precision >= -1 && opts->precision <= 3, "sf_rollout_opts: precision must be -1 (default), 0, 1, 2 or 3");
   SF_REQUIRE(opts->ffn_rows == 0 || opts->ffn_rows == 32 || opts->ffn_rows == 64 || opts->ffn_rows == 128,
              "sf_rollout_opts: ffn_rows must be 0 (default), 32, 64 or 128");
@@ -541,8 +584,46 @@ int sf_rollout_opts_f32(const sf_rollouter* m, float* slots, int B, int T_total,
   SF_REQUIRE(opts->attn_qkv_rows == 0 || opts->attn_qkv_rows == 128, "sf_rollout_opts: attn_qkv_rows must be 0 (off) or 128");
   SF_REQUIRE(opts->ffn_tile >= 0 && opts->ffn_tile <= 2, "sf_rollout_opts: ffn_tile must be 0, 1 or 2");
   SF_REQUIRE(opts->cus_available >= 0 && opts->cus_available <= 256, "sf_rollout_opts: cus_available must be 0 (whole chip) .. 256");
+  return 0;
+}
+}  // namespace
+
+// sf_rollout_f32 with per-call options (include/slotformer_hip.h, sf_rollout_opts): arithmetic mode, seam launches, rows
+// per FFN workgroup, videos per attention workgroup.  The options live in thread-local state for the duration of the call,
+// so concurrent calls from other host threads (one per GPU in the reference's drivers, extract_slots.py:128) keep theirs.
+int sf_rollout_opts_f32(const sf_rollouter* m, float* slots, int B, int T_total, int pred_len, void* ws, size_t ws_bytes,
+                        void* stream, const sf_rollout_opts* opts) {
+  if (!opts) return sf_rollout_f32(m, slots, B, T_total, pred_len, ws, ws_bytes, stream);
+  SF_TRY(check_rollout_opts(opts));
   OptsScope scope(rollout_thread_opts(opts));
   return sf_rollout_f32(m, slots, B, T_total, pred_len, ws, ws_bytes, stream);
+}
+
+// Every phase of a video rolled forward at a frame offset in ONE call (rollout_clevrer_slots.py:20-65, rollout_physion_slots.py:22-63, which
+// call the model frame_offset times): phase p < f burns in on frames first + p + j * f (j < hist, first = obs - hist * f) and writes
+// frame obs + p + s * f at step s < S = ceil(pred_len / f) -- as B * f virtual videos through the plan, the workspace and the
+// launches of a rollout of that many videos (rollout_run)
+size_t sf_rollout_phases_workspace_bytes(const sf_rollouter* m, int B, int frame_offset) {
+  if (!m || B <= 0 || frame_offset <= 0 || (long long)B * frame_offset > 0x7fffffffLL) return 0;
+  return sf_rollout_workspace_bytes(m, B * frame_offset);
+}
+
+int sf_rollout_phases_f32(const sf_rollouter* m, float* slots, int B, int T_total, int obs, int frame_offset, int pred_len, void* ws,
+                          size_t ws_bytes, void* stream, const sf_rollout_opts* opts) {
+  SF_REQUIRE(m && slots && ws, "null pointer");
+  SF_REQUIRE(B >= 1 && pred_len >= 0, "bad batch / pred_len");
+  SF_REQUIRE(frame_offset >= 1, "sf_rollout_phases_f32: frame_offset >= 1");
+  SF_REQUIRE(!(m->single_step && frame_offset > 1), "sf_rollout_phases_f32: a single-step rollouter takes frame_offset 1 only");
+  SF_REQUIRE(m->window_len >= 1, "bad rollouter shape");
+  const int f = frame_offset, hist = m->single_step ? 1 : m->window_len;
+  SF_REQUIRE((long long)obs >= (long long)hist * f, "sf_rollout_phases_f32: fewer observed frames than burn-in * frame_offset");
+  const long long S = ((long long)pred_len + f - 1) / f;
+  SF_REQUIRE((long long)T_total >= obs + S * f, "slots buffer shorter than obs + ceil(pred_len / frame_offset) * frame_offset");
+  const int first = obs - hist * f;
+  if (!opts) return rollout_run(m, slots, B, T_total, first, f, (int)S, ws, ws_bytes, stream);
+  SF_TRY(check_rollout_opts(opts));
+  OptsScope scope(rollout_thread_opts(opts));
+  return rollout_run(m, slots, B, T_total, first, f, (int)S, ws, ws_bytes, stream);
 }
 
 // 1 when sf_rollout_f32 runs this model's layers as the two fused launches of layer_fused.hip (per-video / per-row kernels whose

@@ -55,20 +55,22 @@ bool sf_step_boundary_ok(int d, int slot_size);
 int sf_ffn_partial_ex(const float* ap, long long ap_stride, const sf_tfm_layer& w, float eps, float* xp,
                       long long xp_stride, float* xout, int* counters, int M, int ffn, hipStream_t st, int np = 4);
 int sf_ffn_tiles(int M);
-// in-projection of the first n_frames frames of every video -> ring slots 0 .. n_frames-1 (same arithmetic as the step kernel)
+// in-projection of the first n_frames frames of every video -> ring slots 0 .. n_frames-1 (same arithmetic as the step kernel).
+// phases > 1, here and in the two launches below: the B videos are virtual videos v = b * phases + p over the B / phases videos of
+// `slots` -- frame j of v is frame j * phases + p of video b -- and `frame` counts groups of `phases` frames
 int sf_ring_init_ex(const void* wout_packed, const float* b_out, const void* win_packed, const float* b_in, float* slots,
-                    long long slots_bs, int n_frames, float* ring, int ring_frames, int nslots, int B, hipStream_t st);
+                    long long slots_bs, int n_frames, float* ring, int ring_frames, int nslots, int B, hipStream_t st, int phases = 1);
 // last layer of a rollout step (M = B * nslots rows): FFN + fused step boundary in one launch
 int sf_ffn_boundary_ex(const float* ap, long long ap_stride, const sf_tfm_layer& w, float eps, float* xp, long long xp_stride,
                        int* counters, int ffn, const void* wout_packed, const float* b_out, const void* win_packed,
                        const float* b_in, float* slots, long long slots_bs, int frame, float* ring, int ring_frames, int nslots,
-                       int B, hipStream_t st, int np = 4);
+                       int B, hipStream_t st, int np = 4, int phases = 1);
 // ONE launch for the seam between two rollout steps: last-layer FFN + step boundary of step s (blocks [0, nffn)) and the
 // layer-0 attention of step s+1 (one block per (head pair, video)), handed over per 32-row tile through seam_flags
 int sf_seam_ex(const float* ap_ffn, long long pst_ffn, const sf_tfm_layer& wl, float eps, float* xp, long long xp_stride,
                int* counters, int ffn, const void* wout_packed, const float* b_out, const void* win_packed, const float* b_in,
                float* slots, long long slots_bs, int frame, float* ring, int ring_frames, int nslots, int B,
                const sf_tfm_layer& w0, int f0_next, const float* pe, float* ap_attn, long long pst_attn, int L, int Lq,
-               unsigned* seam_flags, unsigned epoch, hipStream_t st);
+               unsigned* seam_flags, unsigned epoch, hipStream_t st, int phases = 1);
 int sf_seam_blocks(int B, int nslots);
 bool sf_seam_window_ok(int L, int nslots);

@@ -1143,7 +1143,14 @@ struct SbArgs {
   int nslots, enabled;
   unsigned* seam_flags;   // non-NULL: ring rows are written through and seam_flags[tile] = seam_epoch is published afterwards
   unsigned seam_epoch;
+  // > 1: the rows are VIRTUAL videos v = b * phases + p (sf_rollout_phases_f32): phase p of video b, whose frames lie `phases` frames
+  // apart in `slots`.  The frames the `phases` phases of a video write in one step are consecutive, so rows v * nslots + n of a step
+  // are rows (p * nslots + n) of frame group slots_off of video b = v / phases; the ring is indexed by v as ever.  Read by the
+  // *_phases kernels only, and it sits in what was the struct's tail padding: the stride-1 kernels take the arguments, and compile to
+  // the code, they always did
+  int phases;
 };
+static_assert(sizeof(SbArgs) == 104, "SbArgs: `phases` fills the tail padding (the kernel-argument layout of the stride-1 kernels)");
 constexpr int SB_C = 128;                    // slot size
 constexpr int SB_YP = LF_D + 8, SB_PP = SB_C + 8;
 
@@ -1171,12 +1178,19 @@ __device__ __forceinline__ void sb_load(const SbArgs& a, SbFrags& f, int lane, i
 
 // Y planes [32][SB_YP] hold the rows (all threads must have passed a barrier after filling them); R [4][16][64] f32 and
 // P planes [32][SB_PP] are scratch.  Contains barriers: call from all 512 threads.
+template <bool PH = false>   // PH: rows are virtual videos (SbArgs.phases)
 __device__ __forceinline__ void sb_compute(const SbArgs& a, const SbFrags& f, const __bf16* Yh, const __bf16* Yl, float* R,
                                            __bf16* Ph, __bf16* Pl, int row0, int M, int lane, int wave) {
   const int tok = lane & 31, nb1 = wave & 3, kh = wave >> 2;
   const int c1 = nb1 * 32 + 4 * (lane >> 5), c2 = wave * 32 + 4 * (lane >> 5);
   const int m = row0 + tok;
   const int mb = min(m, M - 1) / a.nslots, mn = min(m, M - 1) - mb * a.nslots;
+  int sb = mb, sn = mn;   // video and row of the frame (group) written in `slots`
+  if constexpr (PH) {
+    const int gr = a.phases * a.nslots;
+    sb = min(m, M - 1) / gr;
+    sn = min(m, M - 1) - sb * gr;
+  }
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -1202,7 +1216,7 @@ __device__ __forceinline__ void sb_compute(const SbArgs& a, const SbFrags& f, co
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = acc[4 * g + q] + R[(nb1 * 16 + 4 * g + q) * 64 + lane] + f.bo4[g][q];
       sf_split4(Ph, Pl, tok * SB_PP + c1 + 8 * g, v);
-      if (m < M) *(f32x4*)(a.slots + mb * a.slots_bs + a.slots_off + (long long)mn * SB_C + c1 + 8 * g) = v;
+      if (m < M) *(f32x4*)(a.slots + sb * a.slots_bs + a.slots_off + (long long)sn * SB_C + c1 + 8 * g) = v;
     }
   }
   __syncthreads();
@@ -1258,7 +1272,7 @@ struct FfnArgs {
   SbArgs sb;
 };
 
-template <int NP>   // input partials per row (LF_NP, or 1: finished rows)
+template <int NP, bool PH = false>   // input partials per row (LF_NP, or 1: finished rows); PH: the boundary writes virtual videos (SbArgs.phases)
 __device__ __forceinline__ void ffn_body(const FfnArgs& F, const int blk) {
   // no floating-point contraction in this function: whether the compiler fuses a*b + c into an fma may differ between two
   // instantiations / variants of the same source, and the variants must produce the same bits (LayerNorm statistics)
@@ -1483,7 +1497,7 @@ __device__ __forceinline__ void ffn_body(const FfnArgs& F, const int blk) {
       for (int i = 0; i < 4; ++i)
         sf_split4(Ah, Al, (wave + 8 * i) * FB_AP + 4 * lane, ((oth[0][i] + oth[1][i]) + oth[2][i]) + oth[3][i]);
       __syncthreads();
-      sb_compute(sb, sbf, Ah, Al, (float*)Hh, Hh + 4 * 16 * 64 * 2, Hh + 4 * 16 * 64 * 2 + 32 * SB_PP, row0, M, lane, wave);
+      sb_compute<PH>(sb, sbf, Ah, Al, (float*)Hh, Hh + 4 * 16 * 64 * 2, Hh + 4 * 16 * 64 * 2 + 32 * SB_PP, row0, M, lane, wave);
       if (sb.seam_flags) {
         // publish the tile: every storing wave drains its write-through ring stores, then ONE lane raises the flag
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1511,6 +1525,12 @@ __global__ __launch_bounds__(LF_NT) void ffn_partial_kernel(FfnArgs F) {
   }
 }
 
+// ffn_partial_kernel whose fused step boundary writes the frames of virtual videos (SbArgs.phases > 1)
+template <int NP>
+__global__ __launch_bounds__(LF_NT) void ffn_partial_phases_kernel(FfnArgs F) {
+  ffn_body<NP, true>(F, blockIdx.x);
+}
+
 // One launch for the seam between two rollout steps: blocks [0, nffn) run the last layer's FFN + step boundary of step s,
 // the others the layer-0 attention of step s+1 (one per (head pair, video)), which requests its weights and the five old
 // frames of its window at once and waits only for the 7 new rows of ITS video.  The producers have the lower block indices
@@ -1518,6 +1538,16 @@ __global__ __launch_bounds__(LF_NT) void ffn_partial_kernel(FfnArgs F) {
 __global__ __launch_bounds__(LF_NT) void seam_kernel(FfnArgs F, AttnArgs A, SeamArgs seam, int nffn) {
   if ((int)blockIdx.x < nffn) {
     ffn_body<LF_NP>(F, blockIdx.x);
+  } else {
+    const int u = blockIdx.x - nffn;
+    attn_body<true, true>(A, u & 3, u >> 2, seam);
+  }
+}
+
+// seam_kernel on virtual videos (SbArgs.phases > 1): only the producers' write into `slots` differs
+__global__ __launch_bounds__(LF_NT) void seam_phases_kernel(FfnArgs F, AttnArgs A, SeamArgs seam, int nffn) {
+  if ((int)blockIdx.x < nffn) {
+    ffn_body<LF_NP, true>(F, blockIdx.x);
   } else {
     const int u = blockIdx.x - nffn;
     attn_body<true, true>(A, u & 3, u >> 2, seam);
@@ -1604,6 +1634,51 @@ __global__ __launch_bounds__(LF_NT) void step_boundary_kernel(const float* __res
   }
   __syncthreads();
   sb_compute(sb, f, Yh, Yl, R, Ph, Pl, row0, M, lane, wave);
+}
+
+// The proj_only form of step_boundary_kernel on virtual videos (SbArgs.phases > 1; a kernel of its own so that the one above keeps its
+// code): row gn of virtual video v = b * phases + p (sb.nslots rows each) is slot gn % fn of frame (gn / fn) * phases + p of video b
+// (fn: slots per frame); the ring row it fills is row gn of v as ever.  Same arithmetic per row.
+__global__ __launch_bounds__(LF_NT) void ring_init_phases_kernel(SbArgs sb, int M, int fn) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __bf16* Ph = (__bf16*)smem;   // [32][SB_PP]
+  __bf16* Pl = Ph + 32 * SB_PP;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int row0 = blockIdx.x * 32;
+  SbFrags f;
+  sb_load(sb, f, lane, wave);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int idx = t + LF_NT * i, r = idx >> 5, q4 = idx & 31;
+    const int gm = min(row0 + r, M - 1), gv = gm / sb.nslots, gn = gm - gv * sb.nslots;
+    const int gb = gv / sb.phases, fr = gn / fn;
+    const int vn = (fr * sb.phases + (gv - gb * sb.phases)) * fn + (gn - fr * fn);   // row of video gb
+    const f32x4 v = *(const f32x4*)(sb.slots + gb * sb.slots_bs + sb.slots_off + (long long)vn * SB_C + 4 * q4);
+    sf_split4(Ph, Pl, r * SB_PP + 4 * q4, v);
+  }
+  __syncthreads();
+  const int tok = lane & 31, c2 = wave * 32 + 4 * (lane >> 5);
+  const int m = row0 + tok;
+  const int mb = min(m, M - 1) / sb.nslots, mn = min(m, M - 1) - mb * sb.nslots;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  const int ao = tok * SB_PP + 8 * (lane >> 5);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const bf16x8 xh = *(const bf16x8*)(Ph + ao + k * 16), xl = *(const bf16x8*)(Pl + ao + k * 16);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.w2[k][0], xl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.w2[k][1], xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.w2[k][0], xh, acc, 0, 0, 0);
+  }
+  if (m < M) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 v = {acc[4 * g] + f.bi4[g][0], acc[4 * g + 1] + f.bi4[g][1], acc[4 * g + 2] + f.bi4[g][2],
+                       acc[4 * g + 3] + f.bi4[g][3]};
+      *(f32x4*)(sb.ring + mb * sb.ring_bs + sb.ring_off + (long long)mn * LF_D + c2 + 8 * g) = v;
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1999,12 +2074,21 @@ static int launch_ffn(const float* ap, long long ap_stride, const sf_tfm_layer& 
     return sf_set_err(-1, "invalid argument: fused FFN needs packed weights (sf_pack_ffn_weights) and ffn == 1024", __FILE__, __LINE__);
   SF_TRY(sf_ensure_dyn_lds((const void*)ffn_partial_kernel<LF_NP>, (size_t)(FB_LDS)));
   SF_TRY(sf_ensure_dyn_lds((const void*)ffn_partial_kernel<1>, (size_t)(FB_LDS)));
+  const bool ph = sb.enabled && sb.phases > 1;   // the boundary writes virtual videos
+  if (ph) {
+    SF_TRY(sf_ensure_dyn_lds((const void*)ffn_partial_phases_kernel<LF_NP>, (size_t)(FB_LDS)));
+    SF_TRY(sf_ensure_dyn_lds((const void*)ffn_partial_phases_kernel<1>, (size_t)(FB_LDS)));
+  }
   const int tiles = (M + FB_ROWS - 1) / FB_ROWS;
   sf_prof_begin(SF_K_FFN, st, 4.0 * M * (double)LF_D * ffn);
   FfnArgs F = make_ffn_args(ap, ap_stride, w, eps, xp, xp_stride, xout, counters, M, sb);
   F.parts_only = parts_only;
   F.np = np;
-  if (np == 1)
+  if (ph && np == 1)
+    hipLaunchKernelGGL(ffn_partial_phases_kernel<1>, dim3(ffn_blocks(tiles)), dim3(LF_NT), FB_LDS, st, F);
+  else if (ph)
+    hipLaunchKernelGGL(ffn_partial_phases_kernel<LF_NP>, dim3(ffn_blocks(tiles)), dim3(LF_NT), FB_LDS, st, F);
+  else if (np == 1)
     hipLaunchKernelGGL(ffn_partial_kernel<1>, dim3(ffn_blocks(tiles)), dim3(LF_NT), FB_LDS, st, F);
   else
     hipLaunchKernelGGL(ffn_partial_kernel<LF_NP>, dim3(ffn_blocks(tiles)), dim3(LF_NT), FB_LDS, st, F);
@@ -2086,13 +2170,15 @@ extern "C" int sf_attn_block_f32(const sf_tfm_layer* w, const float* x, float* o
 }
 
 // last layer of a rollout step: the FFN's last-arriving workgroups also run the step boundary (out-proj -> slots frame
-// `frame`, in-proj -> ring); M must be B * nslots
+// `frame`, in-proj -> ring); M must be B * nslots.  phases > 1: the B videos are virtual videos (SbArgs.phases), B / phases videos of
+// `slots`, and `frame` counts groups of `phases` frames -- the frames the phases write in this step
 int sf_ffn_boundary_ex(const float* ap, long long ap_stride, const sf_tfm_layer& w, float eps, float* xp, long long xp_stride,
                        int* counters, int ffn, const void* wout_packed, const float* b_out, const void* win_packed,
                        const float* b_in, float* slots, long long slots_bs, int frame, float* ring, int ring_frames, int nslots,
-                       int B, hipStream_t st, int np) {
-  const SbArgs sb = make_sb(wout_packed, b_out, win_packed, b_in, slots, slots_bs, (long long)frame * nslots * SB_C, ring,
-                            (long long)ring_frames * nslots * LF_D, (long long)(frame % ring_frames) * nslots * LF_D, nslots);
+                       int B, hipStream_t st, int np, int phases) {
+  SbArgs sb = make_sb(wout_packed, b_out, win_packed, b_in, slots, slots_bs, (long long)frame * phases * nslots * SB_C, ring,
+                      (long long)ring_frames * nslots * LF_D, (long long)(frame % ring_frames) * nslots * LF_D, nslots);
+  sb.phases = phases;
   return launch_ffn(ap, ap_stride, w, eps, xp, xp_stride, nullptr, counters, B * nslots, ffn, sb, st, 0, np);
 }
 
@@ -2103,13 +2189,15 @@ int sf_seam_ex(const float* ap_ffn, long long pst_ffn, const sf_tfm_layer& wl, f
                int* counters, int ffn, const void* wout_packed, const float* b_out, const void* win_packed, const float* b_in,
                float* slots, long long slots_bs, int frame, float* ring, int ring_frames, int nslots, int B,
                const sf_tfm_layer& w0, int f0_next, const float* pe, float* ap_attn, long long pst_attn, int L, int Lq,
-               unsigned* seam_flags, unsigned epoch, hipStream_t st) {
+               unsigned* seam_flags, unsigned epoch, hipStream_t st, int phases) {
   if (!wl.lin1_packed || !wl.lin2_packed || ffn != LF_NCH * LF_HC || !w0.attn_in_packed || !w0.attn_out_packed)
     return sf_set_err(-1, "invalid argument: the seam launch needs packed weights", __FILE__, __LINE__);
   constexpr size_t LDS = A2_LDS > FB_LDS ? A2_LDS : FB_LDS;
   SF_TRY(sf_ensure_dyn_lds((const void*)seam_kernel, LDS));
-  SbArgs sb = make_sb(wout_packed, b_out, win_packed, b_in, slots, slots_bs, (long long)frame * nslots * SB_C, ring,
+  if (phases > 1) SF_TRY(sf_ensure_dyn_lds((const void*)seam_phases_kernel, LDS));
+  SbArgs sb = make_sb(wout_packed, b_out, win_packed, b_in, slots, slots_bs, (long long)frame * phases * nslots * SB_C, ring,
                       (long long)ring_frames * nslots * LF_D, (long long)(frame % ring_frames) * nslots * LF_D, nslots);
+  sb.phases = phases;
   sb.seam_flags = seam_flags;
   sb.seam_epoch = epoch;
   const int M = B * nslots, tiles = (M + FB_ROWS - 1) / FB_ROWS, nffn = ffn_blocks(tiles);
@@ -2120,7 +2208,10 @@ int sf_seam_ex(const float* ap_ffn, long long pst_ffn, const sf_tfm_layer& wl, f
   // algorithmic work: the last layer's FFN on M rows + the next step's layer-0 attention
   sf_prof_begin(SF_K_SEAM, st, 4.0 * M * (double)LF_D * ffn + 6.0 * B * L * (double)LF_D * LF_D + 4.0 * (double)B * LF_NH * Lq * L * LF_HD +
                                    2.0 * B * Lq * (double)LF_D * LF_D);
-  hipLaunchKernelGGL(seam_kernel, dim3(nffn + (LF_NH / 2) * B), dim3(LF_NT), LDS, st, F, A, seam, nffn);
+  if (phases > 1)
+    hipLaunchKernelGGL(seam_phases_kernel, dim3(nffn + (LF_NH / 2) * B), dim3(LF_NT), LDS, st, F, A, seam, nffn);
+  else
+    hipLaunchKernelGGL(seam_kernel, dim3(nffn + (LF_NH / 2) * B), dim3(LF_NT), LDS, st, F, A, seam, nffn);
   sf_prof_end(SF_K_SEAM, st);
   SF_CHECK_LAUNCH();
   return 0;
@@ -2155,24 +2246,33 @@ static SbArgs make_sb(const void* wout_packed, const float* b_out, const void* w
   a.enabled = 1;
   a.seam_flags = nullptr;
   a.seam_epoch = 0;
+  a.phases = 1;
   return a;
 }
 
-static int launch_boundary(const float* y, const SbArgs& sb, int M, int proj_only, hipStream_t st) {
+// fn: slots per frame (read with sb.phases > 1 only)
+static int launch_boundary(const float* y, const SbArgs& sb, int M, int proj_only, int fn, hipStream_t st) {
+  if (sb.phases > 1 && !proj_only)
+    return sf_set_err(-1, "invalid argument: the stand-alone step boundary runs virtual videos in its proj_only form alone", __FILE__, __LINE__);
   SF_TRY(sf_ensure_dyn_lds((const void*)step_boundary_kernel, (size_t)(SB_LDS)));
   sf_prof_begin(SF_K_LINEAR, st, (proj_only ? 2.0 : 4.0) * M * (double)LF_D * SB_C);
-  hipLaunchKernelGGL(step_boundary_kernel, dim3((M + 31) / 32), dim3(LF_NT), SB_LDS, st, y, sb, M, proj_only);
+  if (sb.phases > 1)
+    hipLaunchKernelGGL(ring_init_phases_kernel, dim3((M + 31) / 32), dim3(LF_NT), (size_t)2 * 32 * SB_PP * 2, st, sb, M, fn);
+  else
+    hipLaunchKernelGGL(step_boundary_kernel, dim3((M + 31) / 32), dim3(LF_NT), SB_LDS, st, y, sb, M, proj_only);
   sf_prof_end(SF_K_LINEAR, st);
   SF_CHECK_LAUNCH();
   return 0;
 }
 
-// in-projection of the first n_frames (<= ring_frames) frames of every video -> ring slots 0 .. n_frames-1
+// in-projection of the first n_frames (<= ring_frames) frames of every video -> ring slots 0 .. n_frames-1.  phases > 1: of the B
+// virtual videos (SbArgs.phases), whose frame j is frame j * phases + p of video b
 int sf_ring_init_ex(const void* wout_packed, const float* b_out, const void* win_packed, const float* b_in, float* slots,
-                    long long slots_bs, int n_frames, float* ring, int ring_frames, int nslots, int B, hipStream_t st) {
-  const SbArgs sb = make_sb(wout_packed, b_out, win_packed, b_in, slots, slots_bs, 0, ring,
-                            (long long)ring_frames * nslots * LF_D, 0, n_frames * nslots);
-  return launch_boundary(nullptr, sb, B * n_frames * nslots, 1, st);
+                    long long slots_bs, int n_frames, float* ring, int ring_frames, int nslots, int B, hipStream_t st, int phases) {
+  SbArgs sb = make_sb(wout_packed, b_out, win_packed, b_in, slots, slots_bs, 0, ring,
+                      (long long)ring_frames * nslots * LF_D, 0, n_frames * nslots);
+  sb.phases = phases;
+  return launch_boundary(nullptr, sb, B * n_frames * nslots, 1, nslots, st);
 }
 
 extern "C" size_t sf_packed_linear_bytes(int N, int K) { return (size_t)N * K * 4; }

@@ -269,6 +269,40 @@ def rollout(r, slots_all, n_in, pred_len, ws_slot=0, opts=None):
     return slots_all
 
 
+def rollout_phases(r, slots_all, obs, pred_len, frame_offset, ws_slot=0, opts=None):
+    """In-place rollout at a frame offset, every phase of a video in one call (sf_rollout_phases_f32; rollout_clevrer_slots.py:20-65,
+    rollout_physion_slots.py:22-63).  slots_all [B, T_total, N, C] float32 contiguous on device; with f = frame_offset, hist the
+    rollouter's burn-in (`burn_in_of`) and S = ceil(pred_len / f): phase p < f burns in on frames obs - hist*f + p + j*f (j < hist) and
+    writes frame obs + p + s*f at step s < S.  ALL of frames [obs, obs + S*f) are written, so T_total >= obs + S*f: a caller who
+    wants exactly pred_len frames pads the buffer and slices.  Every other frame is left alone.  The B * f phases run as one rollout
+    of that many videos.  opts: see rollout_opts."""
+    if slots_all.dim() != 4:
+        raise ValueError(f'slotformer_amd: rollout slots are [B, T_total, N, C], got {tuple(slots_all.shape)}')
+    f, obs, pred_len, hist = int(frame_offset), int(obs), int(pred_len), burn_in_of(r)
+    B, T_total = slots_all.shape[:2]
+    if f < 1:
+        raise ValueError(f'slotformer_amd: frame_offset >= 1, got {frame_offset!r}')
+    if f > 1 and hasattr(r, 'cond_len'):
+        raise ValueError('slotformer_amd: a SingleStepSlotRollouter rolls out at frame_offset 1 only')
+    if B < 1 or pred_len < 0:
+        raise ValueError(f'slotformer_amd: rollout of {B} videos for {pred_len} frames')
+    if obs < hist * f:
+        raise ValueError(f'slotformer_amd: {obs} observed frames, but a burn-in of {hist} frames at frame_offset {f} needs {hist * f}')
+    steps = -(-pred_len // f)
+    if T_total < obs + steps * f:
+        raise ValueError(f'slotformer_amd: every phase runs {steps} steps and frames {obs} .. {obs + steps * f - 1} are written, but the buffer has '
+                         f'{T_total} frames (pad it to obs + ceil(pred_len / frame_offset) * frame_offset and slice)')
+    _require_inference(r, slots_all)
+    ops._chk(slots_all)
+    plan = rollouter_plan(r)
+    need = lib().sf_rollout_phases_workspace_bytes(C.byref(plan.struct), B, f)
+    ws = workspace(slots_all.device, need, ('roll', ws_slot))
+    o = rollout_opts(opts)
+    check(lib().sf_rollout_phases_f32(C.byref(plan.struct), slots_all.data_ptr(), B, T_total, obs, f, pred_len, ws.data_ptr(), ws.numel(),
+                                      torch.cuda.current_stream().cuda_stream, None if o is None else C.byref(o)))
+    return slots_all
+
+
 # ---------------------------------------------------------------------------------------------
 def encoder_plan(m):
     """m: StoSAVi / STEVE container."""

@@ -5,6 +5,8 @@ arithmetic; only that arithmetic and the model calls are reproduced here, operat
 """
 import torch
 
+from . import engine
+
 OBS_FRAMES = 128   # rollout_clevrer_slots.py:15
 TARGET_LEN = 160   # rollout_clevrer_slots.py:16
 
@@ -30,18 +32,32 @@ def extract_video_slots(model, videos, batch_size=1):
 
 @torch.no_grad()
 def rollout_video_slots(model, ori_slots, frame_offset, history_len=None, obs_frames=OBS_FRAMES,
-                        target_len=TARGET_LEN):
+                        target_len=TARGET_LEN, one_call=False):
     """H2 -- rollout_clevrer_slots.py:20-65 / rollout_physion_slots.py:22-63.
 
     ori_slots [B, obs_frames, N, C] -> [B, target_len, N, C]: for every offset `off` the strided
     sub-sequence start::frame_offset (start = obs - hist*offset + off) is rolled out for as many
     steps as it has frames beyond the burn-in, and the predictions are interleaved back.
+
+    one_call=False restates the reference: a gathered copy and one model call of B videos per offset, then the interleave.
+    one_call=True: the frame_offset phases of every video as ONE engine rollout of B * frame_offset videos that reads and writes the
+    frames where they lie (`engine.rollout_phases`) -- one buffer padded to whole steps, sliced to target_len (a view).
     """
     model.eval()
     hist = model.history_len if history_len is None else history_len
     dev = model.device
     ori = ori_slots.float().to(dev)
     B, _, N, C = ori.shape
+    if one_call:
+        if hist != engine.burn_in_of(model.rollouter):
+            raise ValueError(f'slotformer_amd.harness: one_call=True runs the rollouter\'s own burn-in of {engine.burn_in_of(model.rollouter)} frames, '
+                             f'got history_len={hist}')
+        pred_len = target_len - obs_frames
+        steps = -(-pred_len // frame_offset)
+        buf = torch.empty(B, obs_frames + steps * frame_offset, N, C, device=dev)
+        buf[:, :obs_frames].copy_(ori[:, :obs_frames])
+        engine.rollout_phases(model.rollouter, buf, obs_frames, pred_len, frame_offset)
+        return buf[:, :target_len]
     full = torch.cat([ori, torch.zeros(B, target_len - obs_frames, N, C, device=dev)], 1)
     preds = []
     for off in range(frame_offset):
