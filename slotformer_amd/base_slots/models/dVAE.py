@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from ...nerv_compat import BaseModel
-from ... import ops
+from ... import ops, plans
 
 
 def conv2d(in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, weight_init='xavier'):
@@ -53,23 +53,16 @@ class dVAE(BaseModel):
             Conv2dBlock(64, 64, 3, 1, 1), Conv2dBlock(64, 64, 1, 1), Conv2dBlock(64, 64, 1, 1),
             Conv2dBlock(64, 256, 1), nn.PixelShuffle(2), conv2d(64, img_channels, 1))
         self.testing = False
-        self._packed = {}
 
     # ---- HIP compute ------------------------------------------------------------------------------------
-    def _w3x3(self, w):
-        key = (w.data_ptr(), w._version)
-        if key not in self._packed:
-            self._packed = {key: None} if len(self._packed) > 8 else self._packed
-            self._packed[key] = ops.pack_conv_weight(w.detach().contiguous())
-        return self._packed[key]
-
     def _block(self, x, blk, pixel_shuffle=1):
         """x NHWC [F,H,W,Cin] -> Conv2dBlock(x) (optionally followed by PixelShuffle(2)), NHWC."""
         w = blk.m.weight.detach()
         if w.shape[2] == 1:
             y = ops.linear(x, w.reshape(w.shape[0], w.shape[1]).contiguous())
-        else:
-            y = ops.conv2d_nhwc(x, self._w3x3(w), None, relu=False)
+        else:   # (the OHWI copy of a 3x3 weight: kept on its block, rebuilt when the weight changes)
+            w3x3 = plans.cached(blk, 'w3x3', plans.signature(w), lambda: ops.pack_conv_weight(w.contiguous()))
+            y = ops.conv2d_nhwc(x, w3x3, None, relu=False)
         return ops.groupnorm1_nhwc(y, blk.weight.detach(), blk.bias.detach(), relu=True, pixel_shuffle=pixel_shuffle)
 
     def _logits_nhwc(self, imgs):
@@ -104,13 +97,10 @@ class dVAE(BaseModel):
         return z.unflatten(0, (B, -1)) if unflatten else z
 
     def _head_packed(self):
-        """The vocabulary head in the fragment order `ops.linear_argmax` streams; rebuilt when the parameter changes (as `_w3x3`)."""
+        """The vocabulary head in the fragment order `ops.linear_argmax` streams; rebuilt when the parameter changes."""
         w = self.encoder[7].weight
-        key = ('head', w.data_ptr(), w._version)
-        if key not in self._packed:
-            self._packed = {} if len(self._packed) > 8 else self._packed
-            self._packed[key] = ops.pack_head_weight(w.detach().reshape(self.vocab_size, 64).float().contiguous())
-        return self._packed[key]
+        return plans.cached(self.encoder[7], 'head', plans.signature(w),
+                            lambda: ops.pack_head_weight(w.detach().reshape(self.vocab_size, 64).float().contiguous()))
 
     @torch.no_grad()
     def tokenize_ids(self, imgs, out=None, dtype=torch.int64):
@@ -194,11 +184,8 @@ class dVAE(BaseModel):
             raise RuntimeError('detokenize_ids needs int64 token ids [F,h,w] on a HIP device; there is no CPU fallback')
         blk = self.decoder[0]
         w = blk.m.weight
-        key = ('ids', w.data_ptr(), w._version)
-        if key not in self._packed:
-            self._packed = {} if len(self._packed) > 8 else self._packed
-            self._packed[key] = w.detach().reshape(w.shape[0], w.shape[1]).t().float().contiguous()   # [V, 64]
-        y = ops.gather_rows(self._packed[key], ids.contiguous())                                   # [F,h,w,64]
+        table = plans.cached(blk, 'ids', plans.signature(w), lambda: w.detach().reshape(w.shape[0], w.shape[1]).t().float().contiguous())   # [V, 64]
+        y = ops.gather_rows(table, ids.contiguous())                                               # [F,h,w,64]
         return self._decoder_tail(ops.groupnorm1_nhwc(y, blk.weight.detach(), blk.bias.detach(), relu=True))
 
     # ---- training forward (dVAE.py:113-139) ---------------------------------------------------------------

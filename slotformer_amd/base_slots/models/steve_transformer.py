@@ -9,7 +9,7 @@ projection with the residual fused in the GEMM epilogue, FFN as two GEMMs, `sf_e
 import torch
 from torch import nn
 
-from ... import ops
+from ... import ops, plans
 
 
 def linear(in_features, out_features, bias=True, weight_init='xavier', gain=1.):
@@ -100,17 +100,11 @@ class STEVETransformerDecoder(nn.Module):
         self.tf_dec = TransformerDecoder(num_blocks=num_layers, max_len=max_len + 1, d_model=d_model, num_heads=n_head,
                                          dropout=dropout)
         self.head = nn.Linear(d_model, vocab_size, bias=False)
-        self._cat = {}
 
     # ---- HIP compute ------------------------------------------------------------------------------------
     def _catw(self, name, *ws):
         """cat of projection weights (q|k|v or k|v), rebuilt when a weight changes."""
-        key = tuple((w.data_ptr(), w._version) for w in ws)
-        hit = self._cat.get(name)
-        if hit is None or hit[0] != key:
-            hit = (key, torch.cat([w.detach() for w in ws], 0).contiguous())
-            self._cat[name] = hit
-        return hit[1]
+        return plans.cached(self, name, plans.signature(*ws), lambda: torch.cat([w.detach() for w in ws], 0).contiguous())
 
     def forward(self, slots, idx):
         """slots [B,N,d], idx int64 [B,t] (targets without the last token) -> logits [B,1+t,V]."""
@@ -152,21 +146,13 @@ class STEVETransformerDecoder(nn.Module):
     def _slate_plan(self):
         """sf_slate_decoder descriptor (device pointers of the weights + concatenated projections), rebuilt when a
         parameter changes."""
+        return plans.cached(self, 'slate', plans.signature(self), self._build_slate_plan)
+
+    def _build_slate_plan(self):
         import ctypes as C
         from ..._lib import sf_slate_block, sf_slate_decoder
-        sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        plan = getattr(self, '_plan', None)
-        if plan is not None and plan[0] == sig:
-            return plan[1]
-        keep = []
-
-        def dp(t):
-            t = t.detach()
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                t = t.float().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
+        plan = plans.Plan()
+        dp = plan.dp
         blocks = (sf_slate_block * len(self.tf_dec.blocks))()
         for i, blk in enumerate(self.tf_dec.blocks):
             sa, ca, k = blk.self_attn, blk.encoder_decoder_attn, blocks[i]
@@ -187,9 +173,9 @@ class STEVETransformerDecoder(nn.Module):
         m.lnf_g, m.lnf_b = dp(self.tf_dec.layer_norm.weight), dp(self.tf_dec.layer_norm.bias)
         m.head_w = dp(self.head.weight)
         m.blocks = C.cast(blocks, C.POINTER(sf_slate_block))
-        keep.append(blocks)
-        self._plan = (sig, (m, keep))
-        return self._plan[1]
+        plan.keep.append(blocks)
+        plan.struct = m
+        return plan
 
     def generate_cached(self, slots, steps):
         """Greedy generation with a K/V cache (`sf_slate_generate_f32`): the same arithmetic as `generate(sample=False)`,
@@ -204,7 +190,7 @@ class STEVETransformerDecoder(nn.Module):
         assert slots.shape[1] == self.num_slots and steps - 1 <= self.max_len
         slots = slots.contiguous()
         B = slots.shape[0]
-        m, _ = self._slate_plan()
+        m = self._slate_plan().struct
         tokens = torch.empty(B, steps, dtype=torch.int64, device=slots.device)
         logits = torch.empty(B, steps, self.vocab_size, dtype=torch.float32, device=slots.device)
         nb = lib().sf_slate_generate_workspace_bytes(C.byref(m), B, steps)
@@ -230,7 +216,7 @@ class STEVETransformerDecoder(nn.Module):
         assert slots.shape[1] == self.num_slots and steps - 1 <= self.max_len
         slots = slots.contiguous()
         B = slots.shape[0]
-        m, _ = self._slate_plan()
+        m = self._slate_plan().struct
         tokens = torch.empty(B, steps, dtype=torch.int64, device=slots.device)
         logits = torch.empty(B, steps, self.vocab_size, dtype=torch.float32, device=slots.device) if return_logits else None
         nb = lib().sf_slate_generate_tok_workspace_bytes(C.byref(m), B, steps)

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check, sf_tfm_layer, sf_rollouter, sf_savi_encoder, sf_savi_decoder
-from . import ops
+from . import ops, plans
 
 _WORKSPACES = {}
 
@@ -58,46 +58,9 @@ def _require_inference(module, *tensors):
             raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
 
 
-class _Plan:
-    """ctypes descriptor + the tensors it points to."""
-
-    def __init__(self):
-        self.keep = []
-        self.struct = None
-        self.sig = None
-
-    # plans hold ctypes structures with raw pointers: a copied / pickled module starts without one and rebuilds it
-    def __deepcopy__(self, memo):
-        return _Plan()
-
-    def __reduce__(self):
-        return (_Plan, ())
-
-    def dp(self, t):
-        if t is None:
-            return None
-        t = t.detach()
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            t = t.float().contiguous()
-        self.keep.append(t)
-        return t.data_ptr()
-
-
-_PLAN_ATTRS = ('_sf_plan', '_sf_train_plan', '_sf_dec_plan', '_sf_dec_train_plan', '_plan', '_cat', '_catw', '_slate_plan')
-
-
-def invalidate(module):
-    """Drop every cached plan (packed / derived weight copies) below `module`.  The caches are keyed on
-    (data_ptr, _version) of the parameters, which follows optimizer steps and ordinary in-place ops; writes that bypass
-    torch's version counter (`p.data.copy_()`, raw-pointer kernels) need this call -- or `torch._C._increment_version(p)`."""
-    for m in module.modules():
-        for a in _PLAN_ATTRS:
-            if a in m.__dict__:
-                del m.__dict__[a]
-
-
-def _signature(module):
-    return tuple((t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers()))
+# the plan cache (plans.py): one signature, one cache per module, one `invalidate`.  The caches are keyed on (data_ptr, _version) of the
+# parameters and buffers; writes that bypass torch's version counter need `invalidate(module)`.
+invalidate = plans.invalidate
 
 
 def _tfm_layers(plan, encoder, pack_ffn=False):
@@ -146,12 +109,11 @@ def rollouter_plan(r, packed=True):
     """r: SlotRollouter / SingleStepSlotRollouter container.  packed=False (training, train.py): plain torch-layout
     weights only -- the fragment-ordered copies the inference kernels read would have to be rebuilt after every
     optimizer step."""
-    sig = _signature(r)
-    attr = '_sf_plan' if packed else '_sf_train_plan'
-    plan = getattr(r, attr, None)
-    if plan is not None and plan.sig == sig:
-        return plan
-    plan = _Plan()
+    return plans.cached(r, 'rollouter' if packed else 'rollouter_train', plans.signature(r), _rollouter_plan, r, packed)
+
+
+def _rollouter_plan(r, packed):
+    plan = plans.Plan()
     s = sf_rollouter()
     single = hasattr(r, 'cond_len')
     W = r.cond_len if single else r.history_len
@@ -172,41 +134,32 @@ def rollouter_plan(r, packed=True):
     s.layers = C.cast(_tfm_layers(plan, enc, pack_ffn=packed), C.POINTER(sf_tfm_layer))
     if packed and s.d_model == 256 and s.slot_size == 128 and r.in_proj.weight.is_cuda:
         # fragment-ordered copies of in_proj / out_proj for the fused step-boundary kernel (layer_fused.hip)
-        st = torch.cuda.current_stream().cuda_stream
-        for name, lin in (('in_proj_packed', r.in_proj), ('out_proj_packed', r.out_proj)):
-            n, k = lin.weight.shape
-            buf = torch.empty(lib().sf_packed_linear_bytes(n, k), dtype=torch.uint8, device=lin.weight.device)
-            check(lib().sf_pack_linear_weights(plan.dp(lin.weight), buf.data_ptr(), n, k, st))
-            plan.keep.append(buf)
-            setattr(s, name, buf.data_ptr())
-    plan.struct, plan.sig = s, sig
-    setattr(r, attr, plan)
+        s.in_proj_packed, s.out_proj_packed = plan.packed(r.in_proj.weight), plan.packed(r.out_proj.weight)
+    plan.struct = s
     return plan
 
 
 def phyre_readout_plan(m):
     """m: phyre_planning.models.PHYREReadout on the device -> the host array of its layers with their token-stationary fragment copies
     (`plan.layers`), cached on the module and rebuilt when a parameter changes, as `rollouter_plan`."""
-    sig = _signature(m)
-    plan = getattr(m, '_sf_plan', None)
-    if plan is not None and plan.sig == sig:
-        return plan
-    plan = _Plan()
-    plan.layers = C.cast(_tfm_layers(plan, m.transformer_encoder, pack_ffn=True), C.POINTER(sf_tfm_layer))
-    plan.struct, plan.sig = plan.layers, sig
-    m._sf_plan = plan
+    return plans.cached(m, 'phyre_readout', plans.signature(m), _phyre_readout_plan, m)
+
+
+def _phyre_readout_plan(m):
+    plan = plans.Plan()
+    plan.struct = plan.layers = C.cast(_tfm_layers(plan, m.transformer_encoder, pack_ffn=True), C.POINTER(sf_tfm_layer))
     return plan
 
 
 def aloe_plan(tm):
     """tm: clevrer_vqa.models.CLEVRERTransformerModel on the device -> plan.struct, the `sf_aloe` descriptor: its layers as a host array, the
     text table P[w] = q_in_proj([q_embedding[w] | . . | 1 0]) computed once (`ops.aloe_text_table`), the position rows.  Cached on the module and
-    rebuilt when a parameter changes ((data_ptr, _version) of every parameter), as `phyre_readout_plan`."""
-    sig = _signature(tm)
-    plan = getattr(tm, '_sf_plan', None)
-    if plan is not None and plan.sig == sig:
-        return plan
-    plan = _Plan()
+    rebuilt when a parameter changes, as `phyre_readout_plan`."""
+    return plans.cached(tm, 'aloe', plans.signature(tm), _aloe_plan, tm)
+
+
+def _aloe_plan(tm):
+    plan = plans.Plan()
     s = _lib.sf_aloe()
     enc = tm.transformer_encoder
     l0 = enc.layers[0]
@@ -221,8 +174,7 @@ def aloe_plan(tm):
                                           tm.q_in_proj.bias.detach().float().contiguous())
     s.text_table = plan.dp(plan.text_table)
     s.layers = C.cast(_tfm_layers(plan, enc), C.POINTER(sf_tfm_layer))
-    plan.struct, plan.sig = s, sig
-    tm._sf_plan = plan
+    plan.struct = s
     return plan
 
 
@@ -306,11 +258,11 @@ def rollout_phases(r, slots_all, obs, pred_len, frame_offset, ws_slot=0, opts=No
 # ---------------------------------------------------------------------------------------------
 def encoder_plan(m):
     """m: StoSAVi / STEVE container."""
-    sig = _signature(m)
-    plan = getattr(m, '_sf_plan', None)
-    if plan is not None and plan.sig == sig:
-        return plan
-    plan = _Plan()
+    return plans.cached(m, 'encoder', plans.signature(m), _encoder_plan, m)
+
+
+def _encoder_plan(m):
+    plan = plans.Plan()
     s = sf_savi_encoder()
     if m.resolution[0] != m.resolution[1] or m.resolution[0] not in (64, 128):
         raise NotImplementedError(f'resolution {m.resolution}: the encoder needs 64x64 or 128x128 input '
@@ -358,14 +310,9 @@ def encoder_plan(m):
     s.mlp_w2, s.mlp_b2 = plan.dp(tr(sa.mlp[3].weight)), plan.dp(sa.mlp[3].bias)
     if (m.slot_size, m.slot_mlp_size) in ((128, 256), (192, 384)) and sa.gru.weight_ih.is_cuda:
         # fragment-ordered split-bf16 copies for the matrix-core slot update (slot_update_mfma.hip; slot_update_wide.hip at 192)
-        st = torch.cuda.current_stream().cuda_stream
-        for name, w in (('sa_gru_ih_p', sa.gru.weight_ih), ('sa_gru_hh_p', sa.gru.weight_hh), ('sa_mlp_w1_p', sa.mlp[1].weight),
-                        ('sa_mlp_w2_p', sa.mlp[3].weight), ('sa_q_w_p', sa.project_q[1].weight)):
-            n, k = w.shape
-            buf = torch.empty(lib().sf_packed_linear_bytes(n, k), dtype=torch.uint8, device=w.device)
-            check(lib().sf_pack_linear_weights(plan.dp(w), buf.data_ptr(), n, k, st))
-            plan.keep.append(buf)
-            setattr(s, name, buf.data_ptr())
+        s.sa_gru_ih_p, s.sa_gru_hh_p = plan.packed(sa.gru.weight_ih), plan.packed(sa.gru.weight_hh)
+        s.sa_mlp_w1_p, s.sa_mlp_w2_p = plan.packed(sa.mlp[1].weight), plan.packed(sa.mlp[3].weight)
+        s.sa_q_w_p = plan.packed(sa.project_q[1].weight)
     if m.slot_size == m.enc_out_channels and m.slot_size in (128, 192) and sa.project_k.bias is None and sa.project_v.bias is None:
         # key / value projections folded into project_q and the GRU input matrix (include/slotformer_hip.h, sa_fold_*)
         wk, wv = sa.project_k.weight.detach().double(), sa.project_v.weight.detach().double()
@@ -374,21 +321,9 @@ def encoder_plan(m):
         s.sa_fold_q_w, s.sa_fold_q_w_t, s.sa_fold_gru_ih_t = plan.dp(mq), plan.dp(mq.t().contiguous()), plan.dp(gih.t().contiguous())
         if mq.is_cuda and m.slot_size == 192 and ch[-1] == 64:
             # the 192-wide per-pixel chain as one launch needs fragment-ordered copies of its two matrices (pixel_mlp.hip)
-            st = torch.cuda.current_stream().cuda_stream
-            for name, w in (('enc_fc1_p', eo[1].weight), ('enc_fc2_p', eo[3].weight)):
-                n, k = w.shape
-                buf = torch.empty(lib().sf_packed_linear_bytes(n, k), dtype=torch.uint8, device=w.device)
-                check(lib().sf_pack_linear_weights(plan.dp(w), buf.data_ptr(), n, k, st))
-                plan.keep.append(buf)
-                setattr(s, name, buf.data_ptr())
+            s.enc_fc1_p, s.enc_fc2_p = plan.packed(eo[1].weight), plan.packed(eo[3].weight)
         if mq.is_cuda and (m.slot_size, m.slot_mlp_size) in ((128, 256), (192, 384)):
-            st = torch.cuda.current_stream().cuda_stream
-            for name, w in (('sa_fold_q_w_p', mq), ('sa_fold_gru_ih_p', gih)):
-                n, k = w.shape
-                buf = torch.empty(lib().sf_packed_linear_bytes(n, k), dtype=torch.uint8, device=w.device)
-                check(lib().sf_pack_linear_weights(plan.dp(w), buf.data_ptr(), n, k, st))
-                plan.keep.append(buf)
-                setattr(s, name, buf.data_ptr())
+            s.sa_fold_q_w_p, s.sa_fold_gru_ih_p = plan.packed(mq), plan.packed(gih)
     s.init_latents = plan.dp(m.init_latents.detach()[0])
     s.sa_eps = float(sa.eps)
     kd = getattr(m, 'kernel_dist_layer', None)
@@ -421,13 +356,7 @@ def encoder_plan(m):
         s.pm_w0_t, s.pm_w2_t = plan.dp(tr(base.mlp[0].weight)), plan.dp(tr(base.mlp[2].weight))
         if s.sa_mlp_w1_p and s.kd_mode == 1 and not rnn and base.mlp[0].weight.is_cuda and tuple(base.mlp[0].weight.shape) == (256, 128):
             # fragment-ordered copies for the next step's prologue at the tail of the matrix-core slot update (slot_update_mfma.hip, NEXT form)
-            st = torch.cuda.current_stream().cuda_stream
-            for name, w in (('pm_w0_p', base.mlp[0].weight), ('pm_w2_p', base.mlp[2].weight), ('kd_w0_p', kd[0].weight)):
-                n, k = w.shape
-                buf = torch.empty(lib().sf_packed_linear_bytes(n, k), dtype=torch.uint8, device=w.device)
-                check(lib().sf_pack_linear_weights(plan.dp(w), buf.data_ptr(), n, k, st))
-                plan.keep.append(buf)
-                setattr(s, name, buf.data_ptr())
+            s.pm_w0_p, s.pm_w2_p, s.kd_w0_p = plan.packed(base.mlp[0].weight), plan.packed(base.mlp[2].weight), plan.packed(kd[0].weight)
     if rnn:
         s.pred_hidden = pred.hidden_size
         s.lstm_w_ih, s.lstm_w_hh = plan.dp(pred.rnn.weight_ih_l0), plan.dp(pred.rnn.weight_hh_l0)
@@ -441,18 +370,10 @@ def encoder_plan(m):
         if rnn:
             mats += [pred.rnn.weight_ih_l0, pred.rnn.weight_hh_l0, pred.out_projector.weight]
         if all(w.shape[0] % 32 == 0 and w.shape[1] % 16 == 0 for w in mats):
-            st = torch.cuda.current_stream().cuda_stream
-            arr = (C.c_void_p * len(mats))()
-            for i, w in enumerate(mats):
-                n, k = w.shape
-                buf = torch.empty(lib().sf_packed_linear_bytes(n, k), dtype=torch.uint8, device=w.device)
-                check(lib().sf_pack_linear_weights(plan.dp(w), buf.data_ptr(), n, k, st))
-                plan.keep.append(buf)
-                arr[i] = buf.data_ptr()
+            arr = (C.c_void_p * len(mats))(*[plan.packed(w) for w in mats])
             plan.keep.append(arr)
             s.pred_packed = C.cast(arr, C.POINTER(C.c_void_p))
-    plan.struct, plan.sig = s, sig
-    m._sf_plan = plan
+    plan.struct = s
     return plan
 
 
@@ -596,20 +517,16 @@ def savi_cnn(m, img, t0, t1, out=None, ws_slot=0):
 
 
 # ---------------------------------------------------------------------------------------------
-def _module_sig(*mods):
-    return tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
-
-
 def decoder_plan(m, inference=True):
     """m: StoSAVi or SlotFormer (both hold `decoder`, `decoder_pos_embedding`, dec_* attributes).  inference=False (the training nodes,
     whose parameters change every step): the torch-layout weights only -- no fragment-ordered copies, no fp64 fold of the first layer
     (a plan rebuilt per optimizer step must stay cheap: with the fold in it a StoSAVi training step took 121 instead of 21 ms)."""
-    sig = _module_sig(m.decoder, m.decoder_pos_embedding)
-    attr = '_sf_dec_plan' if inference else '_sf_dec_train_plan'
-    plan = getattr(m, attr, None)
-    if plan is not None and plan.sig == sig:
-        return plan
-    plan = _Plan()
+    return plans.cached(m, 'decoder' if inference else 'decoder_train', plans.signature(m.decoder, m.decoder_pos_embedding),
+                        _decoder_plan, m, inference)
+
+
+def _decoder_plan(m, inference):
+    plan = plans.Plan()
     s = sf_savi_decoder()
     if m.resolution[0] != m.resolution[1] or m.dec_resolution[0] != m.dec_resolution[1]:
         raise NotImplementedError('square resolutions only')
@@ -629,16 +546,14 @@ def decoder_plan(m, inference=True):
             s.deconv_w_flipped[i] = plan.dp(packed.flip(1, 2).contiguous())
         s.deconv_b[i] = plan.dp(dc.bias)
         if inference and packed.is_cuda and tuple(dc.weight.shape) == (64, 64, 5, 5):
-            st = torch.cuda.current_stream().cuda_stream
+            frag = None
             if dc.stride[0] == 2:
                 # consumption-ordered split-bf16 fragments: the parity-class kernel with streamed weights (deconv_s2.hip)
-                frag = torch.empty(lib().sf_deconv_frag_bytes(64, 64, 5, 2), dtype=torch.uint8, device=packed.device)
-                check(lib().sf_pack_deconv_frag_weights(packed.data_ptr(), frag.data_ptr(), 64, 64, 5, 2, st))
-                plan.keep.append(frag)
-                s.deconv_w_frag[i] = frag.data_ptr()
+                frag = ops.pack_deconv_frag(packed)
             elif dc.stride[0] == 1 and i == n - 1:
                 # stride-1 last layer: the encoder's 4-row-tile convolution on the flipped kernel, 1x1 head in its epilogue (conv_rows4.hip)
                 frag = ops.pack_conv_frag(packed.flip(1, 2).contiguous())
+            if frag is not None:
                 plan.keep.append(frag)
                 s.deconv_w_frag[i] = frag.data_ptr()
     dc0 = m.decoder[0][0]
@@ -663,8 +578,7 @@ def decoder_plan(m, inference=True):
     pe = m.decoder_pos_embedding
     s.pos_table = plan.dp(ops.pos_embed_table(pe.grid.detach().float(), pe.dense.weight.detach().float().contiguous(),
                                               pe.dense.bias.detach().float().contiguous()))
-    plan.struct, plan.sig = s, sig
-    setattr(m, attr, plan)
+    plan.struct = s
     return plan
 
 

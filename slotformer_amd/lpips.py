@@ -8,7 +8,7 @@ import ctypes as C
 import torch
 from torch import nn
 
-from . import engine
+from . import engine, plans
 from ._lib import lib, check, sf_lpips_model
 
 # (slice, index inside torchvision's vgg16().features, Cin, Cout) of the thirteen convolutions, in order: THE table of state-dict names --
@@ -82,15 +82,14 @@ class LPIPS(nn.Module):
 
     # ---- the plan: packed weights + the C descriptor, rebuilt when a parameter changes --------------------------------------------------------
     def _plan(self):
-        sig = engine._signature(self)
-        plan = self.__dict__.get('_sf_plan')
-        if plan is not None and plan.sig == sig:
-            return plan
+        return plans.cached(self, 'lpips', plans.signature(self), self._build_plan)
+
+    def _build_plan(self):
         sd = dict(self.named_parameters())
         dev = sd[conv_key(0) + '.weight'].device
         if dev.type != 'cuda':
             raise RuntimeError('slotformer_amd.lpips: the module must live on a HIP device; there is no CPU fallback')
-        plan = engine._Plan()
+        plan = plans.Plan()
         m = sf_lpips_model()
         st = torch.cuda.current_stream(dev).cuda_stream
         for i, (_, _, cin, cout) in enumerate(CONVS):
@@ -103,8 +102,7 @@ class LPIPS(nn.Module):
             m.lin_w[i] = plan.dp(sd[lin_key(i)].reshape(-1))
         m.shift = plan.dp(self.scaling_layer.shift.reshape(-1))
         m.scale = plan.dp(self.scaling_layer.scale.reshape(-1))
-        plan.struct, plan.sig = m, sig
-        self.__dict__['_sf_plan'] = plan
+        plan.struct = m
         return plan
 
     @torch.no_grad()

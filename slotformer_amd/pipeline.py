@@ -392,7 +392,6 @@ class EncodeRolloutPipeline:
         if self.split:
             self.steal = 0.0   # (no stolen convolutions: the feature half IS the lane's work)
         self._plan = None
-        self._sig = None
         self.units = []
         self.spread_remainder = True
         hist_ = getattr(rollouter, 'cond_len', None) or getattr(rollouter, 'history_len', None) or self.T
@@ -489,7 +488,6 @@ class EncodeRolloutPipeline:
         # the encode graphs hold raw pointers into the SAVi encoder's plan (packed conv weights, folded Slot-Attention matrices,
         # predictor fragments): the pipeline keeps that plan alive and re-captures when the encoder's parameters change (_check_plan)
         self._enc_plan = engine.encoder_plan(self.savi)
-        self._enc_sig = self._enc_plan.sig
         self._capture_encode_graphs()
 
     def _capture_encode_graphs(self):
@@ -673,7 +671,6 @@ class EncodeRolloutPipeline:
         elif self.G > 1 and self.NU > 2 and self.tok:
             self._tails['drain'] = self._new_unit(self.G, ('drain', ), row_form=True)
         self._plan = engine.rollouter_plan(self.roll)   # keeps the packed weight copies the graphs point to alive
-        self._sig = self._plan.sig
 
     def _tail_unit(self, nb, k=0, row_form=False):
         """a unit of fewer than `group` batches (the ramp at both ends of a run, a ragged remainder); k: which of the two; row_form: the last unit of a
@@ -684,18 +681,17 @@ class EncodeRolloutPipeline:
         return self._tails[key]
 
     def _check_plan(self):
-        if engine._signature(self.roll) != self._sig or getattr(self.roll, '_sf_plan', None) is not self._plan:
+        if engine.rollouter_plan(self.roll) is not self._plan:
             # parameters changed since the capture (optimizer step, load_state_dict, invalidate): the graphs point at the
-            # old packed weight copies
+            # old packed weight copies, which self._plan keeps alive until _capture_all has replaced them
             torch.cuda.synchronize(self.dev)
             self._capture_all()
-        if engine._signature(self.savi) != self._enc_sig or getattr(self.savi, '_sf_plan', None) is not self._enc_plan:
+        if engine.encoder_plan(self.savi) is not self._enc_plan:
             # the same for the encoder: its graphs replay kernels with pointers into the OLD plan's packed / folded copies (and an
             # eager savi_encode / savi_cnn call elsewhere may have rebuilt -- and freed -- that plan)
             torch.cuda.synchronize(self.dev)
             self._enc_graphs = {}
             self._enc_plan = engine.encoder_plan(self.savi)
-            self._enc_sig = self._enc_plan.sig
             if self.split:
                 self._capture_all()   # (the unit graphs hold the slot branch: pointers into the encoder's packed copies)
             self._capture_encode_graphs()

@@ -950,8 +950,8 @@ class FlatAdam:
             check(lib().sf_adam_flat_groups_f32(self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
                                                 self.exp_avg_sq.data_ptr(), self.flat.numel(), self.steps, self._groups, len(self._groups),
                                                 float(self.betas[0]), float(self.betas[1]), self.eps, scale, st))
-        # The kernel wrote the parameters through a raw pointer: tell torch (and, through `_version`, every plan cache
-        # in engine.py that is keyed on (data_ptr, _version)) that their contents changed -- otherwise derived / packed
+        # The kernel wrote the parameters through a raw pointer: tell torch (and, through `_version`, the plan cache
+        # of plans.py, which is keyed on (data_ptr, _version)) that their contents changed -- otherwise derived / packed
         # weight copies built before this step would keep being served.
         for p in self.params:
             torch._C._increment_version(p)

@@ -133,12 +133,12 @@ def test_plan_is_rebuilt_after_load_state_dict(dev):
     m.load_state_dict(lc.seeded_weights(0))
     m = m.to(dev)
     a = m.distances(x.to(dev), y.to(dev)).cpu()
-    plan = m.__dict__['_sf_plan']
-    assert m.distances(x.to(dev), y.to(dev)) is not None and m.__dict__['_sf_plan'] is plan    # kept while nothing changes
+    plan = m._plan()
+    assert m.distances(x.to(dev), y.to(dev)) is not None and m._plan() is plan                    # kept while nothing changes
     _, _, _, ref1, emu1 = lc.case(2, 16, 16, 0, 1)                                                # the same frames, other weights
     m.load_state_dict(lc.seeded_weights(1))
     b = m.distances(x.to(dev), y.to(dev)).cpu()
-    assert m.__dict__['_sf_plan'] is not plan
+    assert m._plan() is not plan
     assert not torch.equal(a, b)
     assert lc.rel(a, ref0) <= bound_of(ref0, emu0)
     d, bound = lc.rel(b, ref1), bound_of(ref1, emu1)

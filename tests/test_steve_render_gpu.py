@@ -112,7 +112,7 @@ def test_fallback_to_the_launch_chain(dev):
     from slotformer_amd import _lib
     dec, _ = make_decoder((32, 48, 3, 31, 3, 2), 903)
     dec = dec.to(dev)
-    assert _lib.lib().sf_slate_step_ok(C.byref(dec._slate_plan()[0])) == 0
+    assert _lib.lib().sf_slate_step_ok(C.byref(dec._slate_plan().struct)) == 0
     slots = gu.seeded_normal((3, 3, 48), 1903).to(dev)
     t_chain, l_chain = dec.generate_cached(slots, 20)
     for fr in (0, 2):

@@ -55,7 +55,8 @@ class Generator:
     def __init__(self, dec, B, steps):
         from slotformer_amd._lib import lib
         self.lib, self.dec, self.B, self.steps = lib(), dec, B, steps
-        self.m, self.keep = dec._slate_plan()
+        self.keep = dec._slate_plan()
+        self.m = self.keep.struct
         dev = dec.head.weight.device
         self.slots = torch.randn(B, SHAPE[4], SHAPE[1], generator=torch.Generator().manual_seed(B)).to(dev)
         self.tokens = torch.zeros(B, steps, dtype=torch.int64, device=dev)
