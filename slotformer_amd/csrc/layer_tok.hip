@@ -13,6 +13,10 @@
 //     S^T = K Q^T) and computes v with the MFMA operands swapped, which leaves V^T fragments (lane = dim, registers = keys) in its accumulators --
 //     32 KB of LDS per head, handed over by the stage barriers; the scores of a wave's 32 queries against the (at most three) 32-key blocks that hold
 //     their videos' tokens stay in registers through the softmax and feed the PV product as its B operand.
+//   * the FFN block (LN2, lin1, ReLU, lin2: 3072 of a layer's 4896 MFMAs' worth) runs on v_mfma_f32_16x16x32_bf16 over the wave's two 16-token tiles (the
+//     lt16_* helpers of layer_tok_common.h): same MFMA cycles, same 32 KB stages of 32 fragments, and the chip holds a higher clock on that shape when the
+//     other half of it is busy (profiles/layer_tok_mfma_shape.md).  The residual stream changes layout in place at the two borders of the block, one
+//     v_permlane16_swap per register pair; the attention block, bound by VALU issue, keeps 32x32x16.
 // No activation plane, no q|k|v round trip through memory, no per-video attention launch: a layer is one launch of ceil(B / vpw) workgroups
 // (43 for a rollout unit of 128 videos at L = 42) instead of 84 FFN + 128 attention workgroups over two launches.
 #include "../../include/slotformer_hip.h"
@@ -175,6 +179,16 @@ __global__ __launch_bounds__(LT_NT) void layer_tok_kernel(LtArgs A) {
     unsigned pbo = (unsigned)(LT_PAR + 16 * h);
     asm volatile("" : "+v"(pbo));
     pb = smem + pbo;
+  }
+  // ... and as the 16x16 tiles of the FFN block read them (g16 = lane >> 4): px + LT16_FEAT(g16) floats for the vectors over the residual stream's
+  // features, pg + 4 g16 floats for the lin1 bias (a hidden accumulator's MFMA rows are its hidden units in order)
+  const int g16 = lane >> 4;
+  const char *px, *pg;
+  {
+    unsigned pxo = (unsigned)(LT_PAR + 4 * LT16_FEAT(g16)), pgo = (unsigned)(LT_PAR + 16 * g16);
+    asm volatile("" : "+v"(pxo), "+v"(pgo));
+    px = smem + pxo;
+    pg = smem + pgo;
   }
   char* const kwr = smem + LT_KV + wave * 1024 + lane * 16;          // + (s * 2 + plane) * 4096
   char* const vwr = smem + LT_VT + wave * 4096 + lane * 16;          // + (s * 2 + plane) * 1024
@@ -402,42 +416,56 @@ __global__ __launch_bounds__(LT_NT) void layer_tok_kernel(LtArgs A) {
     // ==================================================== FFN block ====================================================
     // X = x2; LN2 -> fragments; X += b2 becomes the accumulator of the second product.  Stage order W1_0, (W1_j, W2_{j-1}) for j = 1..31, W2_31: block
     // j - 1's bias / ReLU / hi | lo split is the side work of block j's first product.
-    lt_layernorm<P_LN2G, P_LN2B>(X, pb, h, A.eps, xh, xl);
-    lt_add_vec<P_B2>(X, pb);
+    // The whole block runs on 16x16x32 MFMAs (layer_tok_common.h): the residual stream moves to the 16-layout here and back behind the last slice, one
+    // v_permlane16_swap per register pair each way; a tile t = the wave's tokens 16 t .. 16 t + 15.
+    lt16_swap_layout(X);
+    lt16_layernorm<P_LN2G, P_LN2B>(X, px, g16, A.eps, xh, xl);
+    lt16_add_vec<P_B2>(X, px);
     if (l == 0) LTS(5);
-    f32x16 Ha, Hb;
-    bf16x8 hh[2], hl[2];
-    f32x4 b1q[4];   // lin1 bias of the block being converted, requested a stage ahead (a read inside the side work would hold its VALU back)
+    f32x4 Ha[2][2], Hb[2][2];   // [row half][tile]
+    bf16x8 hh[2], hl[2];        // [tile]
+    f32x4 b1q[2];   // lin1 bias of the block being converted, requested a stage ahead (a read inside the side work would hold its VALU back)
     auto b1_load = [&](int blk) {
-      const float* b1 = (const float*)pb + P_B1 + 32 * blk;
+      const float* b1 = (const float*)pg + P_B1 + 32 * blk;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) b1q[g] = *(const f32x4*)(b1 + 8 * g);
+      for (int r = 0; r < 2; ++r) b1q[r] = *(const f32x4*)(b1 + 16 * r);
     };
-    auto hconv = [&](const f32x16& Hx, int s) {
-      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 u0 = __builtin_elementwise_max(quad(Hx, 2 * s) + b1q[2 * s], z4);
-      const f32x4 u1 = __builtin_elementwise_max(quad(Hx, 2 * s + 1) + b1q[2 * s + 1], z4);
-      sf_split8(u0, u1, hh[s], hl[s]);
+    // bias, ReLU and hi | lo split of a hidden block in EIGHT pieces, one per fragment group of the product they hide under (an MFMA of 16 cycles hides two
+    // VALU instructions, a clump of forty stalls the matrix pipe): piece k = packed word k & 3 (row half (k & 3) >> 1) of the fragments of tile k >> 2
+    typedef unsigned __attribute__((ext_vector_type(4))) lt_u32x4;
+    lt_u32x4 hw[2], lw[2];
+    auto hconv_piece = [&](const f32x4 (&Hx)[2][2], int k) {
+      const int t16 = k >> 2, w = k & 3, r = w >> 1, e = 2 * (w & 1);
+      unsigned hi, lo;
+      pl_split2(fmaxf(Hx[r][t16][e] + b1q[r][e], 0.f), fmaxf(Hx[r][t16][e + 1] + b1q[r][e + 1], 0.f), hi, lo);
+      hw[t16][w] = hi;
+      lw[t16][w] = lo;
+    };
+    auto hconv_done = [&]() {
+#pragma unroll
+      for (int t16 = 0; t16 < 2; ++t16) {
+        hh[t16] = __builtin_bit_cast(bf16x8, hw[t16]);
+        hl[t16] = __builtin_bit_cast(bf16x8, lw[t16]);
+      }
     };
     // one step = [W1_j: first product of block j into Hn | bias / ReLU / split of block j - 1 (Hp)] + [W2_{j-1}: second product of block j - 1]
-    auto ffn_step = [&](f32x16& Hn, const f32x16& Hp, int j) {
+    auto ffn_step = [&](f32x4 (&Hn)[2][2], const f32x4 (&Hp)[2][2], int j) {
       {
         const LtRing R = stage_begin();
-        lt_row_product<false, 4>(R, xh, xl, Hn, [&](int g) {
-          if (g >= 1 && g < 3) hconv(Hp, g - 1);
-        });
+        lt16_row_product<2, 8>(R, xh, xl, Hn, [&](int ks) { hconv_piece(Hp, ks); });
+        hconv_done();
         asm volatile("" : "+v"(hh[0]), "+v"(hh[1]), "+v"(hl[0]), "+v"(hl[1]));   // (the conversion belongs to THIS stage's MFMA stream)
       }
       {
         const LtRing R = stage_begin();
         b1_load(j);
-        lt_kslice_product<0>(R, hh, hl, X, LtNoSide{});
+        lt16_kslice_product<0>(R, hh, hl, X, LtNoSide{});
       }
     };
     {
       const LtRing R = stage_begin();
       b1_load(0);
-      lt_row_product<false, 0>(R, xh, xl, Ha, LtNoSide{});
+      lt16_row_product<0, 8>(R, xh, xl, Ha, LtNoSide{});
     }
     ffn_step(Hb, Ha, 1);
 #pragma unroll 1
@@ -445,12 +473,14 @@ __global__ __launch_bounds__(LT_NT) void layer_tok_kernel(LtArgs A) {
       ffn_step(Ha, Hb, j);
       ffn_step(Hb, Ha, j + 1);
     }
-    hconv(Hb, 0);
-    hconv(Hb, 1);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) hconv_piece(Hb, k);
+    hconv_done();
     {
       const LtRing R = stage_begin();
-      lt_kslice_product<0>(R, hh, hl, X, LtNoSide{});
+      lt16_kslice_product<0>(R, hh, hl, X, LtNoSide{});
     }
+    lt16_swap_layout(X);
     if (l == 0) LTS(6);
 #ifdef LT_STAMPS
     if (l == 0 && blockIdx.x == 0 && threadIdx.x == 0) { lt_ts[11] = c_wait; lt_ts[12] = c_bar; lt_ts[13] = c_work; }
@@ -480,7 +510,9 @@ extern "C" size_t sf_layer_tok_packed_bytes_ex(int d_model, int num_heads, int f
   return sf_layer_tok128_shape(d_model, num_heads, ffn) ? sf_layer_tok128_packed_bytes() : 0;
 }
 
-// the layer's four matrices as fragments in consumption order + its eight vectors (all pointers of `w` device, torch layouts)
+// the layer's four matrices as fragments in consumption order + its eight vectors (all pointers of `w` device, torch layouts): 96 stages of 32 KB --
+// 32 attention stages of 32x32x16 fragments, 64 FFN stages of 16x16x32 fragments (element map: layer_tok_common.h) -- then 3328 floats: norm1 g, b,
+// in_proj b, out_proj b, norm2 g, b, lin1 b, lin2 b
 extern "C" int sf_pack_layer_tok_weights(const sf_tfm_layer* w, void* packed, int d_model, int num_heads, int ffn, void* stream) {
   SF_REQUIRE(w && packed, "sf_pack_layer_tok_weights: null pointer");
   SF_REQUIRE(w->in_proj_w && w->out_proj_w && w->lin1_w && w->lin2_w && w->norm1_g && w->norm1_b && w->in_proj_b && w->out_proj_b && w->norm2_g &&
@@ -488,8 +520,12 @@ extern "C" int sf_pack_layer_tok_weights(const sf_tfm_layer* w, void* packed, in
   hipStream_t st = (hipStream_t)stream;
   if (sf_layer_tok128_shape(d_model, num_heads, ffn)) return sf_pack_layer_tok128(w, packed, st);
   SF_REQUIRE(d_model == LT_D && num_heads == LT_NH && ffn == LT_F, "sf_pack_layer_tok_weights: (d_model, heads, ffn) = (256, 8, 1024) or (128, 8, 512) only");
-  const int total = LT_NST * 32 * 64;
-  hipLaunchKernelGGL((pack_layer_tok_kernel<LT_D, LT_F>), dim3((total + 255) / 256), dim3(256), 0, st, w->in_proj_w, w->out_proj_w, w->lin1_w, w->lin2_w, (uint4*)packed);
+  // the attention stages in the 32x32x16 fragment order (the grid stops at the first FFN stage), the FFN stages in the 16x16x32 one
+  constexpr int n_att = LT_NST_ATT * 32 * 64, n_ffn = (LT_NST - LT_NST_ATT) * 32 * 64;
+  static_assert(n_att % 256 == 0 && n_ffn % 256 == 0, "whole blocks");
+  hipLaunchKernelGGL((pack_layer_tok_kernel<LT_D, LT_F>), dim3(n_att / 256), dim3(256), 0, st, w->in_proj_w, w->out_proj_w, w->lin1_w, w->lin2_w, (uint4*)packed);
+  SF_CHECK_LAUNCH();
+  hipLaunchKernelGGL((pack_layer_tok_ffn16_kernel<LT_D, LT_F>), dim3(n_ffn / 256), dim3(256), 0, st, w->lin1_w, w->lin2_w, (uint4*)packed);
   SF_CHECK_LAUNCH();
   float* vec = (float*)((char*)packed + (size_t)LT_NST * LT_STAGE);
   const struct {

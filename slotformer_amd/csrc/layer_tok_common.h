@@ -1,6 +1,12 @@
 // What the token-stationary layer kernels (layer_tok.hip: d_model 256; layer_tok128.hip: d_model 128) share: the split-bf16 fragment helpers, the weight
 // ring as a wave sees it, the two register-resident products, LayerNorm in accumulator layout, and the kernel that packs a layer's matrices in
 // consumption order.  Sizes that differ between the shapes are template parameters deduced from the register arrays.
+// Behind them the same pieces on v_mfma_f32_16x16x32_bf16 (lt16_*: the FFN block of layer_tok.hip; layer_tok128.hip uses none of them): the products over
+// 16-token tiles, the in-place swap of the residual stream between the two accumulator layouts, LayerNorm and the vector add in the 16-layout, and the
+// packer of the FFN stages in that fragment order.
+// Element map of a packed layer (sf_pack_layer_tok_weights at d_model 256): stages 0 .. 4 NB - 1 as pack_layer_tok_kernel documents them (32x32x16 fragments,
+// lane = (row i = lane & 31, h = lane >> 5)); stages 4 NB .. as pack_layer_tok_ffn16_kernel does (16x16x32 fragments, lane = (row i = lane & 15, g = lane >> 4));
+// in both, a stage is 32 fragments x 64 lanes x 8 bf16, fragment f of plane f & 1 (0: hi = bf16(w), 1: lo = bf16(w - hi)); then the eight vectors in f32.
 #pragma once
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
@@ -348,5 +354,262 @@ __global__ void pack_layer_tok_kernel(const float* __restrict__ win, const float
     o.b[j] = pl ? (__bf16)(v - (float)hi) : hi;
   }
   out[idx] = o.u;
+}
+
+// ================================ the same products on v_mfma_f32_16x16x32_bf16 (layer_tok.hip: the FFN block) ================================
+// A wave's 32 tokens are two TILES t of 16; a lane is (token j = lane & 15 of either tile, g = lane >> 4).  A 16 x 16 accumulator holds in register q the
+// feature of MFMA row 4 g + q of a 16-feature block; two blocks of one tile read as they lie are the K = 32 B operand of the next product (elements 0..3 of
+// a lane: its four rows of the first block, 4..7: of the second), and the packer emits the A fragments in that k order.  Same FLOPs and MFMA cycles as the
+// 32x32x16 form (twice the instructions of half the length); the chip holds a higher clock on this shape (profiles/conv_mfma_shape.md).
+// The residual stream keeps its registers across the two forms: in the 16-layout register 4 (2 p + t) + q of X[ob] belongs to 16-block 2 ob + p, tile t,
+// and MFMA row 4 g + q of a block of the residual stream is feature LT16_FEAT(g) + q of it (what lt16_swap_layout makes of the 32-layout).
+#define LT_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+#define LT16_FEAT(g) (8 * ((g) & 1) + 4 * ((g) >> 1))
+// the value of lane ^ 16: one v_permlane16_swap (the odd 16-lane rows of its first operand trade places with the even rows of its second)
+__device__ __forceinline__ float lt16_xother(float v, int b4) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  return __builtin_bit_cast(float, b4 ? r[0] : r[1]);
+}
+// sum over the four lanes (g = 0..3) of a token; the same bits in all four
+__device__ __forceinline__ float lt16_xsum(float v, int g) {
+  const float t = v + lt16_xother(v, g & 1);
+  return t + lt_xother(t, g >> 1);
+}
+// 32-layout <-> 16-layout of the residual stream, in place and its own inverse: lane bit 4 is the token's bit 4 in the one and a feature bit in the other.
+// One swap per register pair (8 p + q, 8 p + 4 + q): 32-layout registers 4 gg + q = feature 8 gg + 4 h + q of token lane & 31  <->  16-layout register
+// 4 (2 p + t) + q = feature 16 p + 8 (g & 1) + 4 (g >> 1) + q of token 16 t + (lane & 15)
+template <int NOB>
+__device__ __forceinline__ void lt16_swap_layout(f32x16 (&X)[NOB]) {
+#pragma unroll
+  for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        // (scalars first: __builtin_bit_cast of a vector ELEMENT reads element 0 of the vector)
+        const float a = X[ob][8 * p + q], b = X[ob][8 * p + 4 + q];
+        const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+        const unsigned r0 = r[0], r1 = r[1];
+        X[ob][8 * p + q] = __builtin_bit_cast(float, r0);
+        X[ob][8 * p + 4 + q] = __builtin_bit_cast(float, r1);
+      }
+}
+// the issue pattern of a fragment group of either product below: its first MFMA, the four fragment reads of the next group, then the other eleven MFMAs
+// with up to NV VALU instructions of the side work behind each (an MFMA of 16 cycles leaves the vector issue free for about two)
+template <int NV, bool READS>
+__device__ __forceinline__ void lt16_group_pattern() {
+  LT_SGB(0x008, 1);
+  if constexpr (READS) LT_SGB(0x100, 4);
+#pragma unroll
+  for (int k = 0; k < 11; ++k) {
+    if constexpr (NV > 0) LT_SGB(0x002, NV);
+    LT_SGB(0x008, 1);
+  }
+  if constexpr (NV > 0) LT_SGB(0x002, NV);
+  __builtin_amdgcn_sched_barrier(0);
+}
+// fragment groups in registers: the reads of group g + LT16_NBUF - 1 go behind the first MFMA of group g (3: two groups ahead -- 1 us of a 350 us launch
+// against 2, one group ahead, at 16 more registers)
+#ifndef LT16_NBUF
+#define LT16_NBUF 3
+#endif
+// H[r][t] (rows 16 r .. + 15 of a 32-row block of W, tile t) = W block . A^T over the NKS k-steps of 32 input features: fragment group ks = (hi, lo) of
+// row half 0, (hi, lo) of row half 1.  xh / xl [NKS t + ks]: the (hi, lo) fragments of tile t.  Twelve MFMAs per group, pass by pass (x_lo w_hi, x_hi w_lo,
+// x_hi w_hi) over the FOUR accumulators: an accumulator comes round every fourth MFMA.
+template <int NV, int NKS, class Side>
+__device__ __forceinline__ void lt16_row_product(const LtRing& R, const bf16x8 (&xh)[2 * NKS], const bf16x8 (&xl)[2 * NKS], f32x4 (&H)[2][2], Side&& side) {
+  bf16x8 wb[LT16_NBUF][4];
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) H[r][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int g = 0; g < LT16_NBUF - 1; ++g)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wb[g][i] = *(const bf16x8*)(R.rd + (4 * g + i) * 1024);
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    const int b = ks % LT16_NBUF, bn = (ks + LT16_NBUF - 1) % LT16_NBUF;
+    H[0][0] = LT_MFMA16(wb[b][0], xl[ks], H[0][0]);
+    if (ks + LT16_NBUF - 1 < NKS) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wb[bn][i] = *(const bf16x8*)(R.rd + (4 * (ks + LT16_NBUF - 1) + i) * 1024);
+    }
+    lt_dma(R, ks);
+    LT_PIN();
+    H[0][1] = LT_MFMA16(wb[b][0], xl[NKS + ks], H[0][1]);
+    LT_PIN();
+    H[1][0] = LT_MFMA16(wb[b][2], xl[ks], H[1][0]);
+    LT_PIN();
+    H[1][1] = LT_MFMA16(wb[b][2], xl[NKS + ks], H[1][1]);
+    LT_PIN();
+#pragma unroll
+    for (int pass = 1; pass < 3; ++pass)   // w_lo, then w_hi, against x_hi
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          H[r][t] = LT_MFMA16(wb[b][2 * r + (pass == 1 ? 1 : 0)], xh[NKS * t + ks], H[r][t]);
+          LT_PIN();
+        }
+    side(ks);
+    if (ks + LT16_NBUF - 1 < NKS) lt16_group_pattern<NV, true>(); else lt16_group_pattern<NV, false>();
+  }
+}
+// X (16-layout, all 2 NOB blocks x 2 tiles) += W[:, 32-wide slice] . I^T in ONE K = 32 step: fragment group p = the (hi, lo) fragments of the output blocks
+// 2 p and 2 p + 1, which are the sixteen registers of X[p]; ih / il [t]: the slice's (hi, lo) fragments of tile t
+template <int NV, int NOB, class Side>
+__device__ __forceinline__ void lt16_kslice_product(const LtRing& R, const bf16x8 (&ih)[2], const bf16x8 (&il)[2], f32x16 (&X)[NOB], Side&& side) {
+  bf16x8 wb[LT16_NBUF][4];
+#pragma unroll
+  for (int g = 0; g < LT16_NBUF - 1; ++g)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wb[g][i] = *(const bf16x8*)(R.rd + (4 * g + i) * 1024);
+#pragma unroll
+  for (int p = 0; p < NOB; ++p) {
+    const int b = p % LT16_NBUF, bn = (p + LT16_NBUF - 1) % LT16_NBUF;
+    f32x4 c[2][2];   // [block 2 p + bb][tile]
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) c[bb][t] = quad(X[p], 2 * bb + t);
+    c[0][0] = LT_MFMA16(wb[b][0], il[0], c[0][0]);
+    if (p + LT16_NBUF - 1 < NOB) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wb[bn][i] = *(const bf16x8*)(R.rd + (4 * (p + LT16_NBUF - 1) + i) * 1024);
+    }
+    lt_dma(R, p);
+    LT_PIN();
+    c[0][1] = LT_MFMA16(wb[b][0], il[1], c[0][1]);
+    LT_PIN();
+    c[1][0] = LT_MFMA16(wb[b][2], il[0], c[1][0]);
+    LT_PIN();
+    c[1][1] = LT_MFMA16(wb[b][2], il[1], c[1][1]);
+    LT_PIN();
+#pragma unroll
+    for (int pass = 1; pass < 3; ++pass)
+#pragma unroll
+      for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          c[bb][t] = LT_MFMA16(wb[b][2 * bb + (pass == 1 ? 1 : 0)], ih[t], c[bb][t]);
+          LT_PIN();
+        }
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) X[p][4 * (2 * bb + t) + q] = c[bb][t][q];
+    side(p);
+    if (p + LT16_NBUF - 1 < NOB) lt16_group_pattern<NV, true>(); else lt16_group_pattern<NV, false>();
+  }
+}
+// LayerNorm over the 32 NOB features of the tokens of both tiles, X in 16-layout; gamma / beta at float offsets GOFF / BOFF behind px (= the vector block +
+// LT16_FEAT(g) floats, an opaque per-lane base): the normalised rows as the NOB hi | lo fragments of each tile, xh / xl [NOB t + ob]
+template <int GOFF, int BOFF, int NOB>
+__device__ __forceinline__ void lt16_layernorm(const f32x16 (&X)[NOB], const char* px, int g, float eps, bf16x8 (&xh)[2 * NOB], bf16x8 (&xl)[2 * NOB]) {
+  float mu[2], rs[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const int r = 4 * (2 * p + t);
+        s0 += X[ob][r];
+        s1 += X[ob][r + 1];
+        s2 += X[ob][r + 2];
+        s3 += X[ob][r + 3];
+      }
+    mu[t] = lt16_xsum((s0 + s1) + (s2 + s3), g) * (1.0f / (32 * NOB));
+    float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const int r = 4 * (2 * p + t);
+        const float d0 = X[ob][r] - mu[t], d1 = X[ob][r + 1] - mu[t], d2 = X[ob][r + 2] - mu[t], d3 = X[ob][r + 3] - mu[t];
+        q0 += d0 * d0;
+        q1 += d1 * d1;
+        q2 += d2 * d2;
+        q3 += d3 * d3;
+      }
+    rs[t] = 1.0f / sqrtf(lt16_xsum((q0 + q1) + (q2 + q3), g) * (1.0f / (32 * NOB)) + eps);
+  }
+#pragma unroll
+  for (int ob = 0; ob < NOB; ++ob) {
+    f32x4 ga[2], be[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      ga[p] = *(const f32x4*)(px + (GOFF + 32 * ob + 16 * p) * 4);
+      be[p] = *(const f32x4*)(px + (BOFF + 32 * ob + 16 * p) * 4);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+      sf_split8((quad(X[ob], t) - mu[t]) * rs[t] * ga[0] + be[0], (quad(X[ob], 2 + t) - mu[t]) * rs[t] * ga[1] + be[1], xh[NOB * t + ob], xl[NOB * t + ob]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// X (16-layout) += vec (at float offset OFF behind px)
+template <int OFF, int NOB>
+__device__ __forceinline__ void lt16_add_vec(f32x16 (&X)[NOB], const char* px) {
+#pragma unroll
+  for (int ob = 0; ob < NOB; ++ob) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const f32x4 bv = *(const f32x4*)(px + (OFF + 32 * ob + 16 * p) * 4);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) X[ob][4 * (2 * p + t) + q] += bv[q];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- the FFN stages (4 NB ..) of a layer for the 16x16x32 products: the same stages in the same order as pack_layer_tok_kernel, 32 fragments each ----
+//   lane (i = lane & 15, g = lane >> 4), element j of a fragment; hidden block hb, hi plane = bf16(w), lo plane = bf16(w - hi)
+//   row stage (lin1 rows of hidden block hb):        fragment f = 4 ks + 2 r + plane (k-step ks, row half r):
+//       W1[32 hb + 16 r + i][32 ks + 16 (j >> 2) + LT16_FEAT(g) + (j & 3)]
+//   column stage (lin2 columns of hidden block hb):  fragment f = 2 ob + plane (16-row output block ob):
+//       W2[16 ob + LT16_FEAT(i >> 2) + (i & 3)][32 hb + 16 (j >> 2) + 4 g + (j & 3)]
+//   (a hidden accumulator's MFMA row is its row of W1; a residual accumulator's MFMA row 4 g + q is feature LT16_FEAT(g) + q of its block)
+template <int D, int F>
+__global__ void pack_layer_tok_ffn16_kernel(const float* __restrict__ w1, const float* __restrict__ w2, uint4* __restrict__ out) {
+  constexpr int NB = D / 32, FPS = D / 8, NST_ATT = 4 * NB, NFF = 2 * (F / 32);
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= NFF * FPS * 64) return;
+  const int lane = idx & 63, f = (idx >> 6) % FPS, ff = idx / (64 * FPS);
+  const int pl = f & 1, g = lane >> 4, i = lane & 15;
+  bool slice;
+  int hb;
+  if (ff == 0) {
+    slice = false; hb = 0;
+  } else if (ff == NFF - 1) {
+    slice = true; hb = F / 32 - 1;
+  } else if (ff & 1) {
+    slice = false; hb = (ff + 1) >> 1;
+  } else {
+    slice = true; hb = (ff >> 1) - 1;
+  }
+  const float* src;
+  if (!slice)
+    src = w1 + (long long)(32 * hb + 16 * ((f >> 1) & 1) + i) * D + 32 * (f >> 2) + LT16_FEAT(g);
+  else
+    src = w2 + (long long)(16 * (f >> 1) + LT16_FEAT(i >> 2) + (i & 3)) * F + 32 * hb + 4 * g;
+  union {
+    __bf16 b[8];
+    uint4 u;
+  } o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float v = src[16 * (j >> 2) + (j & 3)];
+    const __bf16 hi = (__bf16)v;
+    o.b[j] = pl ? (__bf16)(v - (float)hi) : hi;
+  }
+  out[(size_t)NST_ATT * FPS * 64 + idx] = o.u;
 }
 }  // namespace
