@@ -982,6 +982,38 @@ int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* 
                              int pred_len, float dropout_p, unsigned long long seed, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* ---- SlotFormer training on clips of a device-resident table (csrc/clip_train.hip; video_prediction.fit) ----------------------------------
+ * A batch is B (video, start) pairs in two int32 DEVICE arrays, never a gathered copy.  The index arrays are TRUSTED: they are not read back,
+ * so a pair outside the table reads outside it -- validate them on the host once, before the loop (video_prediction.fit does).  What the host
+ * does know is checked: a clip of (burn-in + pred_len) frames at this frame_offset must fit T_total.
+ *
+ * sf_rollout_train_fwd_f32 whose burn-in frame j of clip b is table[clip_video[b], clip_start[b] + j * frame_offset]; table [V, T_total, N, C]
+ * float32, 16-byte aligned.  The burn-in is window_len frames, ONE frame for a single-step rollouter.  Workspace: the layout of
+ * sf_rollout_train_workspace_bytes, so sf_rollout_train_bwd_f32 follows as it is. */
+int sf_rollout_train_clips_fwd_f32(const sf_rollouter* m, const float* table, int T_total, const int* clip_video, const int* clip_start,
+                                   int frame_offset, float* pred, int B, int pred_len, float dropout_p, unsigned long long seed, void* ws,
+                                   size_t ws_bytes, void* stream);
+/* The squared-error loss of a rollout and its gradient in ONE launch (slotformer.py:289-318).  pred [B, S, E] dense; target element (b, s, e) at
+ * target[((vid(b) * T_total + start(b) + first_frame + s * frame_step) * E + e], vid(b) = clip_video[b] (NULL: b), start(b) = clip_start[b] (NULL: 0).
+ * Targets in the slot table: T_total, first_frame = burn-in * frame_offset, frame_step = frame_offset, E = N * C.  Dense targets [B, S, E]: both
+ * index arrays NULL, T_total = S, first_frame = 0, frame_step = 1.  step_w [S] device weights or NULL (1).  clip_len [B] int32 or NULL: step s of
+ * clip b counts iff hist + s < clip_len[b] (the reference's vid_len rule); count = counted elements.
+ *   d_pred [B, S, E] (may be NULL) = scale * w_s * 2 * (pred - target) / count, 0 where not counted (three float32 roundings per element)
+ *   stats [1 + 2 S] float64, every entry ADDED to: the weighted loss scale * sum_s w_s * sum (pred - target)^2 / count; the UNWEIGHTED sum of
+ *   squares of each step; the counted elements of each step.  With count == 0 the loss entry is left alone and d_pred is 0.
+ * float32 squares accumulated in float64, per-workgroup partials combined in index order by the last workgroup to arrive: bit-identical from call to
+ * call.  ws: the workspace query's bytes, 16-byte aligned, ZERO-FILLED before its first use; every call leaves its arrival counter at zero.
+ * E % 4 == 0, S <= 64; pred, target, d_pred 16-byte aligned. */
+size_t sf_clip_mse_workspace_bytes(int B, int S, long long E);
+int sf_clip_mse_f32(const float* pred, const float* target, const int* clip_video, const int* clip_start, int T_total, int first_frame,
+                    int frame_step, const float* step_w, const int* clip_len, int hist, float scale, float* d_pred, double* stats, int B, int S,
+                    long long E, void* ws, size_t ws_bytes, void* stream);
+/* Target frames of the image loss: table [V, T_total, H, W, 3] uint8, already at the model's resolution -> out [B, S, 3, H, W] float32, frame
+ * (b, s) = table[clip_video[b], clip_start[b] + first_frame + s * frame_step], normalised (x / 255 - mean_c) / std_c with the arithmetic of
+ * sf_ingest_frames_u8 at equal source and output size (the same bits).  mean3 / std3: three HOST floats each. */
+int sf_clip_frames_f32(const unsigned char* table, int T_total, const int* clip_video, const int* clip_start, int first_frame, int frame_step,
+                       const float* mean3, const float* std3, float* out, int B, int S, int H, int W, void* stream);
+
 /* StoSAVi / STEVE encoder side (savi.py:177-250,295-322,367-416; steve.py:198-240). */
 typedef struct {
   int resolution;      /* input H == W (64 or 128) */

@@ -264,6 +264,10 @@ SIGNATURES = {
     'sf_rollout_train_fwd_f32': (I, [C.POINTER(sf_rollouter), FP, FP, I, I, F32, C.c_ulonglong, VP, SZ, VP]),
     'sf_rollout_train_bwd_f32': (I, [C.POINTER(sf_rollouter), FP, FP, C.POINTER(sf_rollouter_grads), I, I, F32,
                                      C.c_ulonglong, VP, SZ, VP]),
+    'sf_rollout_train_clips_fwd_f32': (I, [C.POINTER(sf_rollouter), FP, I, VP, VP, I, FP, I, I, F32, C.c_ulonglong, VP, SZ, VP]),
+    'sf_clip_mse_workspace_bytes': (SZ, [I, I, LL]),
+    'sf_clip_mse_f32': (I, [FP, FP, VP, VP, I, I, I, FP, VP, I, F32, FP, VP, I, I, LL, VP, SZ, VP]),
+    'sf_clip_frames_f32': (I, [VP, I, VP, VP, I, I, FP, FP, FP, I, I, I, I, VP]),
     'sf_savi_encode_workspace_bytes': (SZ, [C.POINTER(sf_savi_encoder), I]),
     'sf_savi_encode_f32': (I, [C.POINTER(sf_savi_encoder), FP, FP, FP, FP, FP, I, FP, FP, FP, I, I, VP, SZ,
                                VP]),

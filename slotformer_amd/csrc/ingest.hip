@@ -12,6 +12,7 @@
 // stores.  Resampling is linear and the taps of an output sum to 1, so the normalisation (x / 255 - mean) / std = x * a_c + b_c is applied once
 // per OUTPUT value.
 #include "sf_internal.h"
+#include "ingest_norm.h"
 #include <math.h>
 
 namespace {
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(kThreads) void ingest_kernel(IngestArgs p) {
           acc.x += wk * v.x; acc.y += wk * v.y; acc.z += wk * v.z; acc.w += wk * v.w;
         }
         const float a = p.a[c], b = p.b[c];
-        acc.x = acc.x * a + b; acc.y = acc.y * a + b; acc.z = acc.z * a + b; acc.w = acc.w * a + b;
+        acc.x = sf_ingest_norm(acc.x, a, b); acc.y = sf_ingest_norm(acc.y, a, b); acc.z = sf_ingest_norm(acc.z, a, b); acc.w = sf_ingest_norm(acc.w, a, b);
         *reinterpret_cast<float4*>(p.out + (((long long)f * 3 + c) * p.H + y) * p.W + (x4 << 2)) = acc;
       }
     } else {
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void ingest_kernel(IngestArgs p) {
           const int r = min(max(fy + k, 0), nr - 1);
           acc += w[k] * T[(r * 3 + c) * p.W + x];
         }
-        p.out[(((long long)f * 3 + c) * p.H + y) * p.W + x] = acc * p.a[c] + p.b[c];
+        p.out[(((long long)f * 3 + c) * p.H + y) * p.W + x] = sf_ingest_norm(acc, p.a[c], p.b[c]);
       }
     }
     __syncthreads();   // (the next item overwrites S and T)
@@ -333,10 +334,7 @@ int sf_ingest_frames_u8(const unsigned char* src, const unsigned char* palette, 
   p.cx_count = wd + L.cx_count;
   p.cx_w = reinterpret_cast<const float*>(wd + L.cx_w);
   p.out = out;
-  for (int c = 0; c < 3; ++c) {
-    p.a[c] = (float)(1.0 / (255.0 * (double)std3[c]));
-    p.b[c] = (float)(-(double)mean3[c] / (double)std3[c]);
-  }
+  sf_ingest_norm_coeffs(mean3, std3, p.a, p.b);
   p.K = K; p.F = F; p.H0 = H0; p.W0 = W0; p.H = H; p.W = W; p.tapsY = L.tapsY; p.tapsX = L.tapsX;
   p.BH = bh;
   p.nbands = (H + bh - 1) / bh;

@@ -21,6 +21,7 @@
 
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "rollout_train.h"
 #include "bf16_planes.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1125,6 +1126,80 @@ int sf_relu_bwd_ex(float* dh, const float* h, long long n, hipStream_t st) {
   return 0;
 }
 
+// The training forward from the point where the burn-in frames lie frame-major in the workspace's slots_all ([hist][B * N][C]): their
+// in-projections, then every step.  sf_rollout_train_fwd_f32 copies x there, sf_rollout_train_clips_fwd_f32 (clip_train.hip) reads a slot table.
+int sf_rollout_train_steps_ex(const sf_rollouter* m, float* pred, int B, int pred_len, float dropout_p, unsigned long long seed, void* ws,
+                              size_t ws_bytes, hipStream_t st) {
+  Dims D;
+  SF_TRY(check_model(m, D, B, pred_len));
+  SF_REQUIRE(pred && ws, "null pointer");
+  SF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p in [0, 1)");
+  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  const Ws w = carve(D, base);
+  SF_REQUIRE(w.total_floats * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const int d = D.d, f = D.ffn, R = D.R, N = D.N, C = D.C, hd = d / D.H;
+  const uint32_t thr = drop_thresh(dropout_p);
+  const float inv_keep = 1.f / (1.f - dropout_p);
+  const float scale = 1.f / sqrtf((float)hd);
+
+  SF_TRY(gemm(w.slots_all, m->in_proj_w, m->in_proj_b, nullptr, w.tok_all, D.hist * R, d, C, 0, st));
+
+  for (int s = 0; s < D.S; ++s) {
+    const size_t so = D.off(s);
+    const int L = D.Lw(s), M = B * L;   // this step's window
+    if (s > 0) {
+      const int fr = D.hist + s - 1;
+      SF_TRY(gemm(w.slots_all + (size_t)fr * R * C, m->in_proj_w, m->in_proj_b, nullptr, w.tok_all + (size_t)fr * R * d, R,
+                  d, C, 0, st));
+    }
+    hipLaunchKernelGGL(window_assemble_kernel, dim3(cdiv((long long)M * d / 4, 256)), dim3(256), 0, st,
+                       w.tok_all + (size_t)D.f0(s) * R * d, m->pe_tok + (size_t)(D.L - L) * d, w.xin[0] + so * d, B, L, N, d / 4);
+    SF_CHECK_LAUNCH();
+    for (int l = 0; l < D.nl; ++l) {
+      const sf_tfm_layer& ly = m->layers[l];
+      float* xin = w.xin[l] + so * d;
+      float* a1 = w.a1[l] + so * d;
+      float* qkv = w.qkv[l] + so * 3 * d;
+      float* ctx = w.ctx[l] + so * d;
+      float* xmid = w.xmid[l] + so * d;
+      float* a2 = w.a2[l] + so * d;
+      float* hdn = w.hdn[l] + so * f;
+      float* xnext = (l + 1 < D.nl ? w.xin[l + 1] : w.xf) + so * d;
+      SF_TRY(sf_layernorm_ex(xin, sf_rows(d), ly.norm1_g, ly.norm1_b, a1, sf_rows(d), M, d, 1e-5f, st));
+      SF_TRY(gemm(a1, ly.in_proj_w, ly.in_proj_b, nullptr, qkv, M, 3 * d, d, 0, st));
+      SF_TRY(launch_attn_fwd(qkv, ctx, B, D.H, L, d, site_seed(seed, s, l, SITE_ATTN_P), thr, inv_keep, st));
+      SF_TRY(sf_linear_dropout_ex(ctx, ly.out_proj_w, ly.out_proj_b, xin, xmid, M, d, d, 0, site_seed(seed, s, l, SITE_ATTN_O), thr,
+                                  inv_keep, st));
+      SF_TRY(sf_layernorm_ex(xmid, sf_rows(d), ly.norm2_g, ly.norm2_b, a2, sf_rows(d), M, d, 1e-5f, st));
+      SF_TRY(sf_linear_dropout_ex(a2, ly.lin1_w, ly.lin1_b, nullptr, hdn, M, f, d, 1, site_seed(seed, s, l, SITE_FFN_H), thr, inv_keep,
+                                  st));
+      SF_TRY(sf_linear_dropout_ex(hdn, ly.lin2_w, ly.lin2_b, xmid, xnext, M, d, f, 0, site_seed(seed, s, l, SITE_FFN_O), thr,
+                                  inv_keep, st));
+    }
+    // last N tokens of every video -> xlast[s]; prediction = out_proj(xlast)  (slotformer.py:121)
+    SF_TRY(sf_copy_rows_ex(w.xf + so * d, sf_rows_batched(d, N, (long long)L * d, (long long)(L - N) * d),
+                           w.xlast + (size_t)s * R * d, sf_rows(d), R, d, st));
+    float* fr = w.slots_all + (size_t)(D.hist + s) * R * C;
+    SF_TRY(gemm(w.xlast + (size_t)s * R * d, m->out_proj_w, m->out_proj_b, nullptr, fr, R, C, d, 0, st));
+    SF_TRY(sf_copy_rows_ex(fr, sf_rows(C), pred, sf_rows_batched(C, N, (long long)D.S * N * C, (long long)s * N * C), R, C,
+                           st));
+  }
+  return 0;
+}
+
+// Where the burn-in frames of a training forward go: validates as the forward does and returns slots_all and the burn-in length.
+int sf_rollout_train_burnin_ex(const sf_rollouter* m, int B, int pred_len, void* ws, size_t ws_bytes, float** slots_all, int* hist) {
+  Dims D;
+  SF_TRY(check_model(m, D, B, pred_len));
+  SF_REQUIRE(ws, "null pointer");
+  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  const Ws w = carve(D, base);
+  SF_REQUIRE(w.total_floats * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  *slots_all = w.slots_all;
+  *hist = D.hist;
+  return 0;
+}
+
 extern "C" {
 
 // ---- differentiable building blocks for the slot-level layers (predictor, kernel distribution; savi.py:190-200,
@@ -1229,66 +1304,18 @@ size_t sf_rollout_train_workspace_bytes(const sf_rollouter* m, int B, int pred_l
 
 int sf_rollout_train_fwd_f32(const sf_rollouter* m, const float* x, float* pred, int B, int pred_len, float dropout_p,
                              unsigned long long seed, void* ws, size_t ws_bytes, void* stream) {
-  Dims D;
-  SF_TRY(check_model(m, D, B, pred_len));
-  SF_REQUIRE(x && pred && ws, "null pointer");
+  float* slots_all = nullptr;
+  int hist = 0;
+  SF_TRY(sf_rollout_train_burnin_ex(m, B, pred_len, ws, ws_bytes, &slots_all, &hist));
+  SF_REQUIRE(x && pred, "null pointer");
   SF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p in [0, 1)");
   hipStream_t st = (hipStream_t)stream;
-  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  const Ws w = carve(D, base);
-  SF_REQUIRE(w.total_floats * sizeof(float) + 256 <= ws_bytes, "workspace too small");
-  const int d = D.d, f = D.ffn, R = D.R, N = D.N, C = D.C, hd = d / D.H;
-  const uint32_t thr = drop_thresh(dropout_p);
-  const float inv_keep = 1.f / (1.f - dropout_p);
-  const float scale = 1.f / sqrtf((float)hd);
-
-  // burn-in frames -> frame-major slots_all, then their in-projections
-  for (int t = 0; t < D.hist; ++t)
-    SF_TRY(sf_copy_rows_ex(x, sf_rows_batched(C, N, (long long)D.hist * N * C, (long long)t * N * C),
-                           w.slots_all + (size_t)t * R * C, sf_rows(C), R, C, st));
-  SF_TRY(gemm(w.slots_all, m->in_proj_w, m->in_proj_b, nullptr, w.tok_all, D.hist * R, d, C, 0, st));
-
-  for (int s = 0; s < D.S; ++s) {
-    const size_t so = D.off(s);
-    const int L = D.Lw(s), M = B * L;   // this step's window
-    if (s > 0) {
-      const int fr = D.hist + s - 1;
-      SF_TRY(gemm(w.slots_all + (size_t)fr * R * C, m->in_proj_w, m->in_proj_b, nullptr, w.tok_all + (size_t)fr * R * d, R,
-                  d, C, 0, st));
-    }
-    hipLaunchKernelGGL(window_assemble_kernel, dim3(cdiv((long long)M * d / 4, 256)), dim3(256), 0, st,
-                       w.tok_all + (size_t)D.f0(s) * R * d, m->pe_tok + (size_t)(D.L - L) * d, w.xin[0] + so * d, B, L, N, d / 4);
-    SF_CHECK_LAUNCH();
-    for (int l = 0; l < D.nl; ++l) {
-      const sf_tfm_layer& ly = m->layers[l];
-      float* xin = w.xin[l] + so * d;
-      float* a1 = w.a1[l] + so * d;
-      float* qkv = w.qkv[l] + so * 3 * d;
-      float* ctx = w.ctx[l] + so * d;
-      float* xmid = w.xmid[l] + so * d;
-      float* a2 = w.a2[l] + so * d;
-      float* hdn = w.hdn[l] + so * f;
-      float* xnext = (l + 1 < D.nl ? w.xin[l + 1] : w.xf) + so * d;
-      SF_TRY(sf_layernorm_ex(xin, sf_rows(d), ly.norm1_g, ly.norm1_b, a1, sf_rows(d), M, d, 1e-5f, st));
-      SF_TRY(gemm(a1, ly.in_proj_w, ly.in_proj_b, nullptr, qkv, M, 3 * d, d, 0, st));
-      SF_TRY(launch_attn_fwd(qkv, ctx, B, D.H, L, d, site_seed(seed, s, l, SITE_ATTN_P), thr, inv_keep, st));
-      SF_TRY(sf_linear_dropout_ex(ctx, ly.out_proj_w, ly.out_proj_b, xin, xmid, M, d, d, 0, site_seed(seed, s, l, SITE_ATTN_O), thr,
-                                  inv_keep, st));
-      SF_TRY(sf_layernorm_ex(xmid, sf_rows(d), ly.norm2_g, ly.norm2_b, a2, sf_rows(d), M, d, 1e-5f, st));
-      SF_TRY(sf_linear_dropout_ex(a2, ly.lin1_w, ly.lin1_b, nullptr, hdn, M, f, d, 1, site_seed(seed, s, l, SITE_FFN_H), thr, inv_keep,
-                                  st));
-      SF_TRY(sf_linear_dropout_ex(hdn, ly.lin2_w, ly.lin2_b, xmid, xnext, M, d, f, 0, site_seed(seed, s, l, SITE_FFN_O), thr,
-                                  inv_keep, st));
-    }
-    // last N tokens of every video -> xlast[s]; prediction = out_proj(xlast)  (slotformer.py:121)
-    SF_TRY(sf_copy_rows_ex(w.xf + so * d, sf_rows_batched(d, N, (long long)L * d, (long long)(L - N) * d),
-                           w.xlast + (size_t)s * R * d, sf_rows(d), R, d, st));
-    float* fr = w.slots_all + (size_t)(D.hist + s) * R * C;
-    SF_TRY(gemm(w.xlast + (size_t)s * R * d, m->out_proj_w, m->out_proj_b, nullptr, fr, R, C, d, 0, st));
-    SF_TRY(sf_copy_rows_ex(fr, sf_rows(C), pred, sf_rows_batched(C, N, (long long)D.S * N * C, (long long)s * N * C), R, C,
+  const int N = m->num_slots, C = m->slot_size, R = B * N;
+  // burn-in frames -> frame-major slots_all
+  for (int t = 0; t < hist; ++t)
+    SF_TRY(sf_copy_rows_ex(x, sf_rows_batched(C, N, (long long)hist * N * C, (long long)t * N * C), slots_all + (size_t)t * R * C, sf_rows(C), R, C,
                            st));
-  }
-  return 0;
+  return sf_rollout_train_steps_ex(m, pred, B, pred_len, dropout_p, seed, ws, ws_bytes, st);
 }
 
 int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* d_x, const sf_rollouter_grads* g, int B,

@@ -45,6 +45,25 @@ def load_slots(path):
         return pickle.load(f)
 
 
+def stack_slot_table(video_slots, names=None):
+    """A slot dictionary {name: [T,N,C]} (one split of the pickle above) -> (float32 array [V,T,N,C], names): the table
+    `video_prediction.fit` keeps on the device, video v being names[v].  names: the order wanted (default: sorted keys).  Every video must have
+    the same shape -- CLEVRER's and OBJ3D's do; pad or bucket Physion's ragged videos first and hand their lengths to `fit` as `clip_len`."""
+    names = sorted(video_slots) if names is None else [os.path.basename(n) for n in names]
+    if not names:
+        raise ValueError('no videos to stack')
+    shape = np.shape(video_slots[names[0]])
+    if len(shape) != 3:
+        raise ValueError(f'the slots of a video are [T, N, C], got {shape}')
+    table = np.empty((len(names), ) + tuple(shape), dtype=np.float32)
+    for v, n in enumerate(names):
+        s = np.asarray(video_slots[n], dtype=np.float32)
+        if s.shape != tuple(shape):
+            raise ValueError(f'{n}: slots {s.shape}, the table holds {tuple(shape)}')
+        table[v] = s
+    return table, names
+
+
 def read_clip(video_slots, video_path, start_idx, n_sample_frames, frame_offset):
     """datasets/clevrer.py:323-335: strided clip [n_sample_frames,N,C] of one video's slots."""
     try:

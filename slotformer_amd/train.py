@@ -98,33 +98,59 @@ class _Rollout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_pred):
-        B, pred_len, p_drop, seed, xshape = ctx.args
-        r, plan, params = ctx.r, ctx.plan, ctx.params
-        d_pred = d_pred.float().contiguous()
-        # the weights' gradients, then (learnable tables only) the gradient of the folded table pe_tok [window tokens, d_model]
-        tables = learnable_tables(r)
-        params = params[:len(params) - len(tables)]
-        nw = sum(p.numel() for p in params)
-        W, N, d = plan.struct.window_len, plan.struct.num_slots, plan.struct.d_model
+        d_x, grads = _rollout_backward(ctx, d_pred, ctx.args[4] if ctx.needs_input_grad[1] else None)
+        return (None, d_x, None, None, None) + tuple(g_ if ctx.needs_input_grad[5 + i] else None for i, g_ in enumerate(grads))
+
+
+def _rollout_backward(ctx, d_pred, xshape=None, grad_out=None):
+    """sf_rollout_train_bwd_f32 on the workspace a rollout forward node kept (ctx.r, plan, ws, args, params).  Returns (d_x or None, the
+    gradients of ctx.params).  grad_out None: the gradients are views of one fresh flat buffer (`r.last_grad_bucket`).  grad_out: a caller's flat
+    fp32 buffer laid out as a FlatAdam bucket over ctx.params (the weights, then the learnable tables) -- the kernels write the weights' gradients
+    straight into it, nothing is allocated for them, and the returned gradients are views of it."""
+    B, pred_len, p_drop, seed = ctx.args[:4]
+    r, plan, params = ctx.r, ctx.plan, ctx.params
+    d_pred = d_pred.float().contiguous()
+    # the weights' gradients, then (learnable tables only) the gradient of the folded table pe_tok [window tokens, d_model]
+    tables = learnable_tables(r)
+    params = params[:len(params) - len(tables)]
+    nw = sum(p.numel() for p in params)
+    W, N, d = plan.struct.window_len, plan.struct.num_slots, plan.struct.d_model
+    if grad_out is None:
         flat = torch.empty(nw + (W * N * d if tables else 0), dtype=torch.float32, device=d_pred.device)
-        g, keep = _grad_descriptor(flat, params, len(r.transformer_encoder.layers), nw if tables else None)
-        d_x = torch.empty(xshape, dtype=torch.float32, device=d_pred.device) if ctx.needs_input_grad[1] else None
-        check(lib().sf_rollout_train_bwd_f32(C.byref(plan.struct), d_pred.data_ptr(), d_x.data_ptr() if d_x is not None else None,
-                                             C.byref(g), B, pred_len, p_drop, seed, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                             torch.cuda.current_stream().cuda_stream))
-        del keep
-        ctx.ws = None
+        pe = flat[nw:]
+    else:
+        if grad_out.dtype != torch.float32 or not grad_out.is_contiguous() or grad_out.numel() != nw + sum(p.numel() for p in tables):
+            raise ValueError('slotformer_amd: grad_out must be a contiguous float32 bucket over the rollouter parameters and its learnable tables')
+        flat = grad_out
+        pe = torch.empty(W * N * d, dtype=torch.float32, device=d_pred.device) if tables else None
+    g, keep = _grad_descriptor(flat, params, len(r.transformer_encoder.layers), None)
+    g.pe_tok = pe.data_ptr() if tables else None
+    d_x = torch.empty(xshape, dtype=torch.float32, device=d_pred.device) if xshape is not None else None
+    check(lib().sf_rollout_train_bwd_f32(C.byref(plan.struct), d_pred.data_ptr(), d_x.data_ptr() if d_x is not None else None,
+                                         C.byref(g), B, pred_len, p_drop, seed, ctx.ws.data_ptr(), ctx.ws.numel(),
+                                         torch.cuda.current_stream().cuda_stream))
+    del keep
+    ctx.ws = None
+    if grad_out is None:
         if getattr(r, 'ddp_flat_bucket', False):
             # data-parallel training (config C3): ONE all-reduce of the whole bucket over RCCL / xGMI, averaged
             parallel.allreduce_flat(flat)
         r.last_grad_bucket = flat
-        grads = _split(flat, params)
-        if tables:
-            # pe_tok[t * N + n] = enc_t_pe[t] + enc_slots_pe[n]  (slotformer.py:103-109): sum the folded gradient over slots / frames
-            dpe = flat[nw:].view(W, N, d)
-            for p in tables:
-                grads.append((dpe.sum(1) if p is getattr(r, 'enc_t_pe', None) else dpe.sum(0)).view_as(p))
-        return (None, d_x, None, None, None) + tuple(g_ if ctx.needs_input_grad[5 + i] else None for i, g_ in enumerate(grads))
+    grads = _split(flat, params)
+    if tables:
+        # pe_tok[t * N + n] = enc_t_pe[t] + enc_slots_pe[n]  (slotformer.py:103-109): sum the folded gradient over slots / frames
+        dpe = pe.view(W, N, d)
+        off = nw
+        for p in tables:
+            dim = 1 if p is getattr(r, 'enc_t_pe', None) else 0
+            if grad_out is None:
+                grads.append(dpe.sum(dim).view_as(p))
+            else:
+                view = flat[off:off + p.numel()]
+                torch.sum(dpe, dim, out=view.view(dpe.shape[1 - dim], d))
+                grads.append(view.view_as(p))
+                off += p.numel()
+    return d_x, grads
 
 
 def rollout_with_grad(r, x, pred_len):
@@ -136,6 +162,182 @@ def rollout_with_grad(r, x, pred_len):
     # (learnable position tables ride along as extra leaves: the kernels read them folded into pe_tok, engine.rollouter_plan, and
     # sf_rollout_train_bwd_f32 returns the folded table's gradient)
     return _Rollout.apply(r, x, pred_len, p_drop, seed, *rollouter_parameters(r), *learnable_tables(r))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Training on clips of a device-resident table (video_prediction.fit): csrc/clip_train.hip
+# ---------------------------------------------------------------------------------------------------------------------
+def burnin_len(r):
+    """Frames a rollouter reads before it predicts: history_len, ONE for the single-step rollouter (whose window grows to cond_len)."""
+    return 1 if hasattr(r, 'cond_len') else r.history_len
+
+
+def _index_i32(t, n, name):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError(f'slotformer_amd: {name} must live on a HIP device; there is no CPU fallback')
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f'slotformer_amd: {name} must be a contiguous int32 [{n}] tensor, got {t.dtype} {tuple(t.shape)}')
+    return t
+
+
+def _check_table(table, tail, name='table'):
+    if not (torch.is_tensor(table) and table.is_cuda):
+        raise RuntimeError(f'slotformer_amd: the {name} must live on a HIP device; there is no CPU fallback')
+    if table.dtype != torch.float32 or table.dim() < 3 or not table.is_contiguous() or (tail is not None and tuple(table.shape[2:]) != tuple(tail)):
+        raise ValueError(f'slotformer_amd: the {name} must be a contiguous float32 [V, T{"".join(", %d" % k for k in (tail or ()))}] tensor, got '
+                         f'{table.dtype} {tuple(table.shape)}')
+    return table
+
+
+def _clips_forward(r, table, clip_video, clip_start, frame_offset, pred_len, p_drop, seed, ws=None):
+    """sf_rollout_train_clips_fwd_f32 -> (pred [B, pred_len, N, C], plan, workspace).  The index tensors are trusted (never read back); what the
+    host knows is checked by the library: a clip of burn-in + pred_len frames at this offset must fit the table's T."""
+    plan = engine.rollouter_plan(r, packed=False)
+    N, Cs = plan.struct.num_slots, plan.struct.slot_size
+    _check_table(table, (N, Cs))
+    B = clip_video.numel() if torch.is_tensor(clip_video) else 0
+    _index_i32(clip_video, B, 'clip_video')
+    _index_i32(clip_start, B, 'clip_start')
+    nbytes = lib().sf_rollout_train_workspace_bytes(C.byref(plan.struct), B, pred_len)
+    if nbytes == 0:
+        check(-1)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=table.device)
+    pred = torch.empty(B, pred_len, N, Cs, dtype=torch.float32, device=table.device)
+    check(lib().sf_rollout_train_clips_fwd_f32(C.byref(plan.struct), table.data_ptr(), table.shape[1], clip_video.data_ptr(), clip_start.data_ptr(),
+                                               int(frame_offset), pred.data_ptr(), B, pred_len, float(p_drop), int(seed), ws.data_ptr(), ws.numel(),
+                                               torch.cuda.current_stream().cuda_stream))
+    return pred, plan, ws
+
+
+class _RolloutClips(torch.autograd.Function):
+    """pred = rollouter(burn-in frames of B clips of a slot table, pred_len) as a single autograd node; the table is data (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, r, table, clip_video, clip_start, frame_offset, pred_len, p_drop, seed, grad_out, *params):
+        pred, plan, ws = _clips_forward(r, table, clip_video, clip_start, frame_offset, pred_len, p_drop, seed)
+        ctx.r, ctx.plan, ctx.ws, ctx.args = r, plan, ws, (pred.shape[0], pred_len, float(p_drop), int(seed))
+        ctx.params, ctx.grad_out = params, grad_out
+        return pred
+
+    @staticmethod
+    def backward(ctx, d_pred):
+        _, grads = _rollout_backward(ctx, d_pred, None, ctx.grad_out)
+        if ctx.grad_out is not None:   # the caller's bucket holds them: nothing for autograd to accumulate
+            grads = [None] * len(grads)
+        return (None, ) * 9 + tuple(g_ if (g_ is not None and ctx.needs_input_grad[9 + i]) else None for i, g_ in enumerate(grads))
+
+
+def rollout_clips_with_grad(r, table, clip_video, clip_start, frame_offset, pred_len, seed=None, grad_out=None):
+    """`rollout_with_grad` on clips that stay where they lie: table [V, T, N, C] float32 and int32 [B] clip_video / clip_start on the device; burn-in
+    frame j of clip b is table[clip_video[b], clip_start[b] + j * frame_offset] (burnin_len(r) frames).  -> pred [B, pred_len, N, C], bit for bit
+    what `rollout_with_grad` returns on a gathered copy.  Dropout as there (active iff r.training, p of the first layer); seed: the dropout seed
+    (default: r.dropout_seed_override, else a fresh one from torch's CPU generator).
+    grad_out: a flat fp32 buffer laid out as FlatAdam's bucket over rollouter_parameters(r) + learnable_tables(r) (`FlatAdam.grad`): the backward
+    writes the gradients there -- then step with `FlatAdam.step(gathered=True)` -- and the parameters' `.grad` are left alone."""
+    if not (torch.is_tensor(table) and table.is_cuda):
+        raise RuntimeError('slotformer_amd: the slot table must live on a HIP device; there is no CPU fallback')
+    layer0 = r.transformer_encoder.layers[0]
+    p_drop = float(layer0.dropout.p) if r.training else 0.0
+    if seed is None:
+        seed = int(torch.randint(0, 2**62, (1, )).item()) if p_drop > 0 else 0
+        seed = getattr(r, 'dropout_seed_override', None) or seed
+    return _RolloutClips.apply(r, table, clip_video, clip_start, int(frame_offset), int(pred_len), p_drop, int(seed), grad_out,
+                               *rollouter_parameters(r), *learnable_tables(r))
+
+
+_CLIP_MSE_WS = {}
+
+
+def _clip_mse_ws(device, nbytes):
+    """The loss launch's workspace, one per device: zero-filled once; every launch leaves its arrival counter at zero.  Launches that share it must
+    be ordered (one stream at a time), as everything in this module is."""
+    ws = _CLIP_MSE_WS.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _CLIP_MSE_WS[device] = torch.zeros(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def clip_mse_launch(pred, target, clip_video, clip_start, frame_offset, hist, step_w, clip_len, scale, d_pred, stats):
+    """sf_clip_mse_f32.  pred [B, S, ...] float32.  clip_video None: `target` is dense, of pred's shape.  Otherwise `target` is a table [V, T, ...] and
+    step s of clip b is compared with target[clip_video[b], clip_start[b] + (hist + s) * frame_offset].  step_w [S] float32 on the device or None;
+    clip_len int32 [B] or None (step s counts iff hist + s < clip_len[b]).  d_pred (pred's shape, or None) receives scale * w_s * 2 * (pred - target) /
+    count; stats float64 [1 + 2 S] has the loss, the per-step sums of squares and the per-step counts ADDED to it."""
+    if not (torch.is_tensor(pred) and pred.is_cuda and torch.is_tensor(target) and target.is_cuda):
+        raise RuntimeError('slotformer_amd: clip_mse needs tensors on a HIP device; there is no CPU fallback')
+    B, S = pred.shape[:2]
+    E = pred[0, 0].numel()
+    if pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise ValueError('slotformer_amd: clip_mse takes a contiguous float32 prediction')
+    if clip_video is None:
+        if clip_start is not None or tuple(target.shape) != tuple(pred.shape) or target.dtype != torch.float32 or not target.is_contiguous():
+            raise ValueError(f'slotformer_amd: a dense target is contiguous float32 of the shape of pred {tuple(pred.shape)}, got {tuple(target.shape)}')
+        T_total, first, fstep = S, 0, 1
+    else:
+        _check_table(target, tuple(pred.shape[2:]), 'target table')
+        _index_i32(clip_video, B, 'clip_video')
+        _index_i32(clip_start, B, 'clip_start')
+        T_total, first, fstep = target.shape[1], int(hist) * int(frame_offset), int(frame_offset)
+    if step_w is not None and (step_w.dtype != torch.float32 or step_w.numel() != S or not step_w.is_cuda or not step_w.is_contiguous()):
+        raise ValueError(f'slotformer_amd: step_w is a contiguous float32 [{S}] device tensor')
+    if clip_len is not None:
+        _index_i32(clip_len, B, 'clip_len')
+    if stats.dtype != torch.float64 or stats.numel() != 1 + 2 * S or not stats.is_contiguous():
+        raise ValueError(f'slotformer_amd: stats is a contiguous float64 [{1 + 2 * S}] device tensor')
+    nbytes = lib().sf_clip_mse_workspace_bytes(B, S, E)
+    if nbytes == 0:
+        raise NotImplementedError(f'slotformer_amd: clip_mse takes 1 to 64 steps and rows of a multiple of 4 elements, got S {S}, E {E}')
+    ws = _clip_mse_ws(pred.device, nbytes)
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    check(lib().sf_clip_mse_f32(pred.data_ptr(), target.data_ptr(), p(clip_video), p(clip_start), T_total, first, fstep, p(step_w), p(clip_len),
+                                int(hist), float(scale), p(d_pred), stats.data_ptr(), B, S, E, ws.data_ptr(), ws.numel(),
+                                torch.cuda.current_stream().cuda_stream))
+
+
+class _ClipMse(torch.autograd.Function):
+    """(loss, stats) of sf_clip_mse_f32; the gradient w.r.t. pred was written by the forward launch."""
+
+    @staticmethod
+    def forward(ctx, pred, target, clip_video, clip_start, frame_offset, hist, step_w, clip_len, scale):
+        pred = pred.detach().float().contiguous()
+        S = pred.shape[1]
+        d_pred = torch.empty_like(pred)
+        stats = torch.zeros(1 + 2 * S, dtype=torch.float64, device=pred.device)
+        clip_mse_launch(pred, target, clip_video, clip_start, frame_offset, hist, step_w, clip_len, scale, d_pred, stats)
+        ctx.save_for_backward(d_pred)
+        ctx.mark_non_differentiable(stats)
+        return stats[0].float(), stats
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_stats):
+        d_pred, = ctx.saved_tensors
+        return (d_pred * d_loss, ) + (None, ) * 8
+
+
+def clip_mse(pred, target, clip_video=None, clip_start=None, frame_offset=1, hist=0, step_w=None, clip_len=None, scale=1.):
+    """The rollout loss of slotformer.py:289-318 under autograd, one launch (see `clip_mse_launch` for the operands): -> (loss, stats).
+    loss = scale * sum_s w_s * sum (pred - target)^2 / count over the counted steps, a float32 scalar; stats float64 [1 + 2 S] = (loss, the
+    UNWEIGHTED per-step sums of squares, the per-step counts), not differentiable: stats[1 + k] / stats[1 + S + k] is `slot_recon_loss_{k+1}`."""
+    return _ClipMse.apply(pred, target, clip_video, clip_start, int(frame_offset), int(hist), step_w, clip_len, float(scale))
+
+
+def clip_frames(frames, clip_video, clip_start, frame_offset, hist, S, mean=0.5, std=0.5):
+    """sf_clip_frames_f32: the S target frames of every clip from a uint8 table [V, T, H, W, 3] (already at the model's resolution) ->
+    float32 [B, S, 3, H, W] = (x / 255 - mean) / std, the bits `FrameIngest` gives at equal source and output size.  mean / std: a float or three."""
+    if not (torch.is_tensor(frames) and frames.is_cuda):
+        raise RuntimeError('slotformer_amd: the frame table must live on a HIP device; there is no CPU fallback')
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError(f'slotformer_amd: the frame table is a contiguous uint8 [V, T, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)}')
+    B = clip_video.numel() if torch.is_tensor(clip_video) else 0
+    _index_i32(clip_video, B, 'clip_video')
+    _index_i32(clip_start, B, 'clip_start')
+    three = lambda v: (C.c_float * 3)(*([float(v)] * 3 if not hasattr(v, '__len__') else [float(x) for x in v]))  # noqa: E731
+    H, W = frames.shape[2:4]
+    out = torch.empty(B, int(S), 3, H, W, dtype=torch.float32, device=frames.device)
+    check(lib().sf_clip_frames_f32(frames.data_ptr(), frames.shape[1], clip_video.data_ptr(), clip_start.data_ptr(), int(hist) * int(frame_offset),
+                                   int(frame_offset), three(mean), three(std), out.data_ptr(), B, int(S), H, W,
+                                   torch.cuda.current_stream().cuda_stream))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -923,9 +1125,11 @@ class FlatAdam:
         for p in self.params:
             p.grad = None
 
-    def step(self):
+    def step(self, gathered=False):
+        """One update.  gathered=True: the gradients already sit in `self.grad` (a backward that wrote into the bucket:
+        `rollout_clips_with_grad(..., grad_out=opt.grad)`), so the per-parameter copies out of `p.grad` are skipped."""
         off = 0
-        for p in self.params:
+        for p in (() if gathered else self.params):
             k = p.numel()
             if p.grad is None:
                 self.grad[off:off + k].zero_()
@@ -955,6 +1159,61 @@ class FlatAdam:
         # weight copies built before this step would keep being served.
         for p in self.params:
             torch._C._increment_version(p)
+
+
+    def state_dict(self):
+        """torch.optim.Adam's state dict: per parameter (ids in bucket order) `step`, `exp_avg`, `exp_avg_sq` -- the moments are VIEWS of the
+        flat buffers, clone them to keep a snapshot -- and `param_groups` with torch's keys (weight_decay 0, amsgrad False).  What a
+        torch.optim.Adam over the same parameters in the same order loads, and what the reference's checkpoints hold under 'optimizer'."""
+        state, groups, off, i = {}, [], 0, 0
+        for g in self.param_groups:
+            ids = []
+            for p in g['params']:
+                k = p.numel()
+                if self.steps > 0:   # (torch has no state before the first step)
+                    state[i] = {'step': torch.tensor(float(self.steps)), 'exp_avg': self.exp_avg[off:off + k].view_as(p),
+                                'exp_avg_sq': self.exp_avg_sq[off:off + k].view_as(p)}
+                ids.append(i)
+                off += k
+                i += 1
+            groups.append({'lr': g['lr'], 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False, 'maximize': False,
+                           'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None, 'decoupled_weight_decay': False,
+                           'params': ids})
+        return {'state': state, 'param_groups': groups}
+
+    def load_state_dict(self, sd):
+        """Resume from `state_dict()`'s layout -- FlatAdam's own or torch.optim.Adam's over the same parameters in the same order.  The moments are
+        copied into the flat buffers; lr, betas and eps are taken from the groups.  Raises ValueError for what the flat update cannot express:
+        other group sizes, weight decay, amsgrad, maximize, or parameters at different step counts."""
+        groups = sd['param_groups']
+        if len(groups) != len(self.param_groups) or any(len(a['params']) != len(b['params']) for a, b in zip(groups, self.param_groups)):
+            raise ValueError('slotformer_amd: FlatAdam.load_state_dict: the parameter groups do not match')
+        for a in groups:
+            if a.get('weight_decay', 0) or a.get('amsgrad', False) or a.get('maximize', False):
+                raise ValueError('slotformer_amd: FlatAdam has no weight decay, amsgrad or maximize')
+        betas, eps = tuple(groups[0].get('betas', self.betas)), float(groups[0].get('eps', self.eps))
+        if any(tuple(a.get('betas', betas)) != betas or float(a.get('eps', eps)) != eps for a in groups):
+            raise ValueError('slotformer_amd: FlatAdam has one betas / eps for all groups')
+        ids = [i for a in groups for i in a['params']]
+        state = sd['state']
+        steps = {int(float(state[i]['step'])) for i in ids if i in state}
+        if len(steps) > 1 or (state and any(i not in state for i in ids)):
+            raise ValueError('slotformer_amd: FlatAdam keeps ONE step count: every parameter must have the same')
+        off = 0
+        for i, p in zip(ids, self.params):
+            k = p.numel()
+            for buf, key in ((self.exp_avg, 'exp_avg'), (self.exp_avg_sq, 'exp_avg_sq')):
+                if i in state:
+                    if state[i][key].numel() != k:
+                        raise ValueError(f'slotformer_amd: FlatAdam.load_state_dict: parameter {i} has {k} elements, its {key} {state[i][key].numel()}')
+                    buf[off:off + k].copy_(state[i][key].reshape(-1))
+                else:
+                    buf[off:off + k].zero_()
+            off += k
+        self.steps = steps.pop() if steps else 0
+        self.betas, self.eps = betas, eps
+        for g, a in zip(self.param_groups, groups):
+            g['lr'] = float(a['lr'])
 
 
 def warmup_cosine_lr(step, total_steps, warmup_steps, max_lr, min_lr=0.):
