@@ -775,7 +775,8 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
 
 /* Per-call options of a rollout: they apply to THIS call on the calling thread only (thread-local inside the library; the
  * reference drives forward() from one host thread per GPU, base_slots/extract_slots.py:128), whereas sf_set_precision /
- * sf_set_seam_fused / sf_set_ffn_rows64 set process-wide DEFAULTS.  Every choice is bit-identical except `precision` and `layer_tok` (see there). */
+ * sf_set_seam_fused / sf_set_ffn_rows64 set process-wide DEFAULTS.  Every choice is bit-identical except `precision` and `layer_tok` (see there).
+ * A process-wide switch is read when a call plans its launches.  A hipGraph captured earlier keeps the form it was captured with. */
 typedef struct {
   int precision;    /* -1: default; 0 exact f32, 1 split-bf16, 2 single-pass bf16 (= sf_rollout_bf16), 3 single-pass fp16 (a
                      * measurement probe: the linear layers on one fp16 MFMA per product, profiles/r03_probes.txt) */

@@ -316,20 +316,6 @@ __global__ __launch_bounds__(NT) void conv5x5_rows4_kernel(const float* __restri
 
 extern "C" size_t sf_conv_frag_bytes(int Cout, int Cin, int ks) { return (Cout == CH && Cin == CH && ks == KS) ? (size_t)FRAG_BYTES + FRAG16_BYTES : 0; }
 
-// opt-in arithmetic of the 4-row-tile convolution: 0 (default) split-bf16, three products; 1 activations as two fp16 terms x weights as ONE fp16, two products
-static int g_conv_fp16x2 = -1;
-extern "C" int sf_set_conv_fp16x2(int on) {
-  g_conv_fp16x2 = on ? 1 : 0;
-  return 0;
-}
-extern "C" int sf_get_conv_fp16x2(void) {
-  if (g_conv_fp16x2 < 0) {
-    const char* e = getenv("SF_CONV_FP16X2");   // (a product switch: the opt-in arithmetic)
-    g_conv_fp16x2 = (e && e[0] == '1') ? 1 : 0;
-  }
-  return g_conv_fp16x2;
-}
-
 // w_ohwi [Cout][ks][ks][Cin] (sf_pack_conv_weight_f32) -> fragment-ordered split-bf16 copy for conv5x5_rows4_kernel (64 -> 64, 5 x 5)
 extern "C" int sf_pack_conv_frag_weights(const float* w_ohwi, void* frag, int Cout, int Cin, int ks, void* stream) {
   SF_REQUIRE(w_ohwi && frag, "sf_pack_conv_frag_weights: null pointer");
@@ -346,7 +332,7 @@ int sf_conv5x5_rows4_ex(const float* in, const void* w_frag, const float* bias, 
   if (!w_frag || W != TW || Cin != CH || Cout != CH || ks != KS || (H % TR) != 0 || F <= 0 || sf_get_precision() != 1) return 1;
   static const int dbg = sf_dbg("conv");
   // (the LDS attribute first: a failure here must not leave the class timer's pending event open)
-  const bool f16 = sf_get_conv_fp16x2();
+  const bool f16 = sf_switch(SF_SW_CONV_FP16X2);
   SF_TRY(sf_ensure_dyn_lds(f16 ? (const void*)conv5x5_rows4_kernel<true> : (const void*)conv5x5_rows4_kernel<false>, LDS_BYTES));
   sf_prof_begin(SF_K_CONV_NHWC, st, 2.0 * (double)F * H * W * Cout * ks * ks * Cin);
   if (f16)

@@ -21,7 +21,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-extern "C" int sf_get_conv_fp16x2(void);
 namespace {
 constexpr int CH = 64, KS = 5, TW = 64, NTAP = KS * KS;
 constexpr int HWD = TW + KS - 1;                  // 68 pixels per halo row
@@ -347,19 +346,18 @@ int sf_conv5x5_ws_ex(const float* in, const void* w_frag, const float* bias, con
                      int relu, int n_workgroups, hipStream_t st) {
   if (!w_frag || W != TW || Cin != CH || Cout != CH || ks != KS || H < 1 || F <= 0 || relu < 0 || relu > 1 || sf_get_precision() != 1) return 1;
   // (the opt-in two-product fp16 arithmetic lives in the 4-row-tile kernel only: with it on, every stream takes that kernel -- one arithmetic per process)
-  if (sf_get_conv_fp16x2()) return 1;
+  if (sf_switch(SF_SW_CONV_FP16X2)) return 1;
   static const int dbg = sf_dbg("conv");
   const long long rows = (long long)F * H;
   int nwg = n_workgroups;
   if (nwg <= 0) {
     // one workgroup per CU of the stream; a launch too small to give each of them four rows does not pay for 410 KB of weights per workgroup
-    static const bool on = []() { const char* e = getenv("SF_CONV_WS"); return !(e && e[0] == '0'); }();
     // ... of a stream whose CUs are its own: one made by sf_stream_create_cu_mask, or one that captures for such a stream (sf_stream_set_cus).  On any
     // other stream the launch shares the chip with whatever else runs, and a workgroup that holds its CU for the whole launch (0.5 ms at 192 frames)
     // keeps the latency-bound rollout launches and the masked encode lane waiting: those keep the 4-row tiles (27 us per workgroup) -- measured in
     // the pipeline: hybrid-lane encodes with persistent workgroups cost 6 % at 60 batches
     nwg = sf_stream_cus_known((void*)st);
-    if (!on || nwg <= 0 || rows < 4LL * nwg) return 1;
+    if (!sf_switch(SF_SW_CONV_WS) || nwg <= 0 || rows < 4LL * nwg) return 1;
   }
   if (nwg > rows) nwg = (int)rows;
   const void* kfn = bias ? (add ? (const void*)conv5x5_ws_kernel<true, true> : (const void*)conv5x5_ws_kernel<true, false>)

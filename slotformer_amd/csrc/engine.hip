@@ -174,9 +174,9 @@ RolloutPlan plan_rollout(const sf_rollouter* m, int B, const SfThreadOpts& o) {
     packed = packed && w.lin1_packed && w.lin2_packed && w.attn_in_packed && w.attn_out_packed;
     if (l + 1 < nl) tok_packed = tok_packed && w.tok_packed;
   }
-  const int precision = o.precision >= 0 ? o.precision : sf_get_precision();
+  const int precision = sf_precision(o);
   const bool fusable = packed && !plain_gemms(o) && precision >= 1 && m->norm_first;
-  const bool tok_on = tok_packed && (o.layer_tok > 0 || (o.layer_tok == 0 && sf_get_layer_tok() != 0));
+  const bool tok_on = tok_packed && sf_layer_tok_on(o);
   if (fusable && sf_layer_fused_ok(d, m->num_heads, m->ffn_dim, Lmax)) {
     p.path = (m->in_proj_packed && m->out_proj_packed && sf_step_boundary_ok(d, m->slot_size)) ? RolloutPlan::FUSED_RING
                                                                                                : RolloutPlan::FUSED_ROWS;
@@ -189,7 +189,7 @@ RolloutPlan plan_rollout(const sf_rollouter* m, int B, const SfThreadOpts& o) {
       p.ffn = (p.attn == RolloutPlan::ROW_TILES && o.ffn_tile == 2) ? RolloutPlan::TILE_QKV : RolloutPlan::TILE;
     const int cus = o.cus > 0 && o.cus < 160 ? o.cus : 160;
     p.seam = p.path == RolloutPlan::FUSED_RING && p.attn == RolloutPlan::HEAD_PAIRS &&
-             (o.seam >= 0 ? o.seam != 0 : sf_get_seam_fused() != 0) && sf_seam_blocks(B, N) <= cus;
+             sf_seam_on(o) && sf_seam_blocks(B, N) <= cus;
   } else if (fusable && sf_layer_fused_ok(d, m->num_heads, m->ffn_dim, 1) && Lmax > 64 && sf_ffn_tiles(B * Lmax) <= 1024) {
     p.path = RolloutPlan::LONG_WINDOW;
     if (tok_on && Lmax <= 96 && !m->single_step && sf_layer_tok_ok(Lmax)) p.tok_layers = nl - 1;   // one video per workgroup
@@ -518,40 +518,6 @@ int sf_rollout_f32(const sf_rollouter* m, float* slots, int B, int T_total, int 
   return rollout_run(m, slots, B, T_total, 0, 1, pred_len, ws, ws_bytes, stream);
 }
 
-// SURVEY.md 8(b2) `sf_rollout_bf16`: the same rollout with every matrix product in SINGLE-PASS bf16 (operands rounded to
-// 8 mantissa bits, f32 accumulation; f32 storage, LayerNorm, softmax) -- the arithmetic of the reference's `--fp16` AMP
-// (scripts/train.py:84,105) and of BASELINE.json's literal "bf16".  Measured on the 6+50 path of config C2 against the
-// reference fixture: ~8e-3 relative (tools/precision_probe.py, tests/test_engine_gpu.py), i.e. OUTSIDE the 1e-3 parity bar --
-// which is why sf_rollout_f32 (split-bf16, 1e-5) is the default and the product path.  Same arguments as sf_rollout_f32.
-// Seam launches on / off (default: on unless SF_SEAM_FUSED=0).  A seam launch saves a kernel boundary on the critical path of
-// ONE rollout chain; its 128 consumer workgroups spin until the 28 producers are done, which is CU time a second chain running
-// on the same CUs could use -- the 'pair' pipeline captures its graphs with the seam off.
-// Process default of the token-stationary layer launches (sf_rollout_opts.layer_tok == 0): OFF unless SF_LAYER_TOK=1 / sf_set_layer_tok(1)
-static int g_layer_tok = -1;
-extern "C" int sf_get_layer_tok(void) {
-  if (g_layer_tok < 0) {
-    const char* e = getenv("SF_LAYER_TOK");
-    g_layer_tok = (e && e[0] == '1') ? 1 : 0;   // (off until the round's validation is complete)
-  }
-  return g_layer_tok;
-}
-extern "C" int sf_set_layer_tok(int on) {
-  g_layer_tok = on ? 1 : 0;
-  return 0;
-}
-static int g_seam_fused = -1;
-extern "C" int sf_get_seam_fused(void) {
-  if (g_seam_fused < 0) {
-    const char* e = getenv("SF_SEAM_FUSED");
-    g_seam_fused = !(e && e[0] == '0');
-  }
-  return g_seam_fused;
-}
-extern "C" int sf_set_seam_fused(int on) {
-  g_seam_fused = on ? 1 : 0;
-  return 0;
-}
-
 namespace {
 // the calling thread's options for the duration of one engine call
 struct OptsScope {
@@ -661,6 +627,11 @@ int sf_rollout_uses_seam_opts(const sf_rollouter* m, int B, const sf_rollout_opt
 }
 int sf_rollout_uses_seam(const sf_rollouter* m, int B) { return sf_rollout_uses_seam_opts(m, B, nullptr); }
 
+// SURVEY.md 8(b2) `sf_rollout_bf16`: the same rollout with every matrix product in SINGLE-PASS bf16 (operands rounded to
+// 8 mantissa bits, f32 accumulation; f32 storage, LayerNorm, softmax) -- the arithmetic of the reference's `--fp16` AMP
+// (scripts/train.py:84,105) and of BASELINE.json's literal "bf16".  Measured on the 6+50 path of config C2 against the
+// reference fixture: ~8e-3 relative (tools/precision_probe.py, tests/test_engine_gpu.py), i.e. OUTSIDE the 1e-3 parity bar --
+// which is why sf_rollout_f32 (split-bf16, 1e-5) is the default and the product path.  Same arguments as sf_rollout_f32.
 int sf_rollout_bf16(const sf_rollouter* m, float* slots, int B, int T_total, int pred_len, void* ws, size_t ws_bytes,
                     void* stream) {
   sf_rollout_opts o = {2, -1, 0, 0};
@@ -784,7 +755,7 @@ EncodePlan plan_encode(const sf_savi_encoder* m, int B, int T, int n_pre, bool f
   const int Cl = m->enc_channels[m->enc_layers];
   const bool feat192 = Cl == 64 && Ce == 192 && m->enc_fc1_p && m->enc_fc2_p;
   const bool fold = precision >= 1 && m->sa_fold_q_w && m->sa_fold_q_w_t && m->sa_fold_gru_ih_t && Ce == D && (sf_pixel_mlp_feat_ok(Cl, Ce) || feat192);
-  const bool planes = fold && !feat192 && sf_get_slot_attn_planes() && sf_slot_attn_planes_ok(HW, D, N) && Cl == 64 && P == HW / 256;
+  const bool planes = fold && !feat192 && sf_switch(SF_SW_SLOT_ATTN_PLANES) && sf_slot_attn_planes_ok(HW, D, N) && Cl == 64 && P == HW / 256;
   p.feat = fold ? (feat192 ? EncodePlan::FOLD_192 : planes ? EncodePlan::FOLD_PLANES : EncodePlan::FOLD_ROWS)
                 : (precision >= 1 ? EncodePlan::KV_FUSED : EncodePlan::KV_GEMMS);
   p.q_w = fold ? m->sa_fold_q_w : m->sa_q_w;
@@ -800,12 +771,12 @@ EncodePlan plan_encode(const sf_savi_encoder* m, int B, int T, int n_pre, bool f
   p.pred_step = m->pred_type == 1 && m->pred_packed && precision >= 1;
   p.prologue = m->pred_type == 0 && !m->pred_rnn && m->kd_mode == 1 && m->pm_w0_t && m->pm_w2_t && m->kd_w0_t && p.q_w_t;
   p.fuse_next = p.prologue && p.update == EncodePlan::MFMA && m->pm_w0_p && m->pm_w2_p && m->kd_w0_p && m->pm_ln_g && m->pm_ln_b && m->pm_b0 &&
-                m->pm_b2 && m->kd_b0 && sf_get_encode_fuse_next();
+                m->pm_b2 && m->kd_b0 && sf_switch(SF_SW_ENCODE_FUSE_NEXT);
   // (the CLEVRER shape of StoSAVi: savi.py:76-100, 393-402)
   p.chain_model = precision == 1 && fold && p.feat != EncodePlan::FOLD_192 && p.update == EncodePlan::MFMA && p.fuse_next &&
                   sf_slot_chain_ok(D, Hm, HW, N) && m->init_latents && m->enc_fc1_w && m->enc_fc2_w;
   p.batched = !fork && n_pre == 0 && enc_batched_ok(m, B, T, precision);
-  p.chain = p.batched && p.chain_model && sf_get_slot_chain();
+  p.chain = p.batched && p.chain_model && sf_switch(SF_SW_SLOT_CHAIN);
   // without room for the feature planes: the per-iteration launches; without room for the batched activations: the per-step convolutions
   if (p.chain && ws_bytes < enc_ws_bytes(m, B, T, p)) p.chain = false;
   if (p.batched && ws_bytes < enc_ws_bytes(m, B, T, p)) p.batched = false;
@@ -1095,23 +1066,6 @@ int enc_iterations(const EncodeArgs& a, const EncodePlan& p, const EncodeWs& w, 
 }  // namespace
 
 extern "C" {
-
-// the slot branch of a batched encode as one video-stationary launch (slot_chain.hip): OPT-IN (sf_set_slot_chain(1)); the default keeps
-// the per-iteration launches (Slot-Attention iteration over the batch + slot update), which are faster for a batch alone on its CUs
-static int g_slot_chain = 0;
-int sf_get_slot_chain(void) { return g_slot_chain; }
-// the Slot-Attention iterations of the per-step encode on feature rows kept as bf16 hi | lo (sa_attn_planes_kernel, slot_chain.hip: split-bf16 16x16x32
-// MFMAs) instead of f32 rows and the exact-f32 tile kernel: process default below; sf_set_slot_attn_planes(0 / 1)
-static int g_sa_planes = 1;
-int sf_get_slot_attn_planes(void) { return g_sa_planes; }
-int sf_set_slot_attn_planes(int on) { g_sa_planes = on ? 1 : 0; return 0; }
-int sf_set_slot_chain(int on) { g_slot_chain = on ? 1 : 0; return 0; }
-
-// the slot prologue of step t + 1 at the tail of step t's last slot update (slot_update_mfma.hip, NEXT form): on by default where it applies;
-// sf_set_encode_fuse_next(0): the prologue as its own launch (sa_slot_prologue_kernel) on every step
-static int g_enc_fuse_next = 1;
-int sf_set_encode_fuse_next(int on) { g_enc_fuse_next = on ? 1 : 0; return 0; }
-int sf_get_encode_fuse_next(void) { return g_enc_fuse_next; }
 
 size_t sf_savi_encode_workspace_bytes(const sf_savi_encoder* m, int B) {
   return (m && B > 0) ? enc_ws_bytes(m, B, 1, plan_encode(m, B, 1, 0, false, 0)) : 0;

@@ -646,25 +646,6 @@ static int launch_by_id(int id, const SfGemmArgs& a, hipStream_t st) {
   return sf_set_err(-1, "unknown GEMM configuration id", __FILE__, __LINE__);
 }
 
-// 0: exact f32 MFMA everywhere; 1: split-bf16 MFMA (default); 2: single-pass bf16 MFMA with f32 accumulation in the GEMM / conv
-// / weight-gradient cores (the "AMP-bf16" policy of the training path: fp32 storage and master weights, one bf16 rounding of
-// each operand; kernels without a single-pass variant keep mode 1).  SF_PRECISION=f32 | bf16 selects 0 | 2 at load time.
-static int g_precision = -1;
-extern "C" int sf_get_precision(void) {
-  const int t = sf_thread_opts().precision;   // a per-call option of this thread (sf_rollout_opts) wins over the process default
-  if (t >= 0) return t;
-  if (g_precision < 0) {
-    const char* e = getenv("SF_PRECISION");
-    g_precision = (e && (e[0] == 'f' || e[0] == '0')) ? 0 : ((e && strcmp(e, "bf16") == 0) ? 2 : 1);
-  }
-  return g_precision;
-}
-extern "C" int sf_set_precision(int mode) {
-  if (mode < 0 || mode > 2) return sf_set_err(-1, "invalid argument: precision mode must be 0 (f32), 1 (bf16x3) or 2 (bf16)", __FILE__, __LINE__);   // (3 = single-pass fp16 exists per call only: sf_rollout_opts.precision, a measurement probe)
-  g_precision = mode;
-  return 0;
-}
-
 template <int ALOAD, bool LN>
 static int dispatch_tiles(const SfGemmArgs& a, hipStream_t stream) {
   auto tiles = [&](int bm, int bn) {

@@ -1943,13 +1943,6 @@ __global__ __launch_bounds__(LF_NT) void ffn_wide_parts_kernel(FfnArgs F) {
   WTS(9);
 }
 
-static int g_ffn_rows64 = 0;
-extern "C" int sf_set_ffn_rows64(int on) {
-  g_ffn_rows64 = on ? 1 : 0;
-  return 0;
-}
-extern "C" int sf_get_ffn_rows64(void) { return g_ffn_rows64; }
-
 // ------------------------------------------------------------------------------------------------
 // timing ablations (wrong results): 1 FFN reads one head partial, 2 FFN skips the W2 loads, 4 attention reads one
 // input partial, 8 attention stores one column block
@@ -2126,7 +2119,7 @@ int sf_ffn_parts_ex(const float* ap, long long ap_stride, const sf_tfm_layer& w,
                     int ffn, hipStream_t st, int np) {
   SbArgs sb;
   memset(&sb, 0, sizeof(sb));
-  int rows = sf_thread_opts().ffn_rows > 0 ? sf_thread_opts().ffn_rows : (g_ffn_rows64 ? 64 : 32);
+  int rows = sf_ffn_rows(sf_thread_opts());
   while (rows > 32 && M < rows) rows >>= 1;
   if (rows <= 32) return launch_ffn(ap, ap_stride, w, eps, xp, xp_stride, nullptr, nullptr, M, ffn, sb, st, 1, np);
   if (!w.lin1_packed || !w.lin2_packed || ffn != LF_NCH * LF_HC)

@@ -13,14 +13,6 @@
 #include "slot_chain.h"
 #include <stdlib.h>
 
-// the per-pixel chain in its pixel-stationary form (pixel_feat_tok_kernel below): process default; sf_set_pixel_tok(0): the tile kernels
-static int g_pixel_tok = 1;
-extern "C" int sf_get_pixel_tok(void) { return g_pixel_tok; }
-extern "C" int sf_set_pixel_tok(int on) {
-  g_pixel_tok = on ? 1 : 0;
-  return 0;
-}
-
 namespace {
 constexpr int PM_NT = 512, PM_ROWS = 128, PM_C0 = 64, PM_C1 = 128, PM_ND = 256;
 constexpr int PM_LB0 = PM_C0 + 8, PM_LB1 = PM_C1 + 8;                 // bf16 row strides (odd # of 16-B slots)
@@ -262,7 +254,7 @@ int sf_pixel_mlp_feat_ex(const float* x, const float* ln0_g, const float* ln0_b,
   if (M <= 0) return 0;
   // weights resident in registers, PF_TPW tiles per workgroup (pixel_feat_stream_kernel below)
   constexpr int stream = 1;
-  if (sf_get_pixel_tok()) return sf_pixel_feat_tok_launch<false>(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, feat, M, eps, st);
+  if (sf_switch(SF_SW_PIXEL_TOK)) return sf_pixel_feat_tok_launch<false>(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, feat, M, eps, st);
   if (stream) return sf_pixel_feat_stream_launch(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, feat, M, eps, st);
   SF_TRY(sf_ensure_dyn_lds((const void*)pixel_mlp_kv_kernel<true>, (size_t)(PM_LDS)));
   sf_prof_begin(SF_K_LINEAR, st, 2.0 * M * (double)(PM_C0 * PM_C1 + PM_C1 * PM_C1));
@@ -935,7 +927,7 @@ static int sf_pixel_feat_tok_launch(const float* x, const float* ln0_g, const fl
 // the same with the result as bf16 hi | lo rows of 512 B (slot_chain.h): the Slot-Attention inputs of the video-stationary slot branch
 int sf_pixel_mlp_feat_planes_ex(const float* x, const float* ln0_g, const float* ln0_b, const float* w1, const float* b1, const float* w2,
                                 const float* b2, const float* ln1_g, const float* ln1_b, void* planes, int M, float eps, hipStream_t st) {
-  if (sf_get_pixel_tok()) return sf_pixel_feat_tok_launch<true>(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, planes, M, eps, st);
+  if (sf_switch(SF_SW_PIXEL_TOK)) return sf_pixel_feat_tok_launch<true>(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, planes, M, eps, st);
   return sf_pixel_feat_stream_launch_t<64, true>(x, ln0_g, ln0_b, w1, b1, w2, b2, ln1_g, ln1_b, (float*)planes, M, eps, st);
 }
 

@@ -1,6 +1,7 @@
 // Internal C++ entry points shared between the translation units of libslotformer_hip.so.
 #pragma once
 #include "sf_common.h"
+#include "sf_switches.h"
 
 // Per-call options of the calling THREAD (the reference drives `forward` from one host thread per GPU,
 // base_slots/extract_slots.py:128): set by the *_opts entry points for the duration of a call, never process-wide.
@@ -17,6 +18,11 @@ struct SfThreadOpts {
   int cus = 0;           // CUs the call's stream may use (its CU mask); 0: the whole chip.  Seam launches need all their workgroups co-resident
 };
 SfThreadOpts& sf_thread_opts();
+// What a call under options `o` runs with: the option where it is set, else the process switch (sf_switches.h)
+inline int sf_precision(const SfThreadOpts& o) { return o.precision < 0 ? sf_switch(SF_SW_PRECISION) : o.precision; }
+inline bool sf_seam_on(const SfThreadOpts& o) { return (o.seam < 0 ? sf_switch(SF_SW_SEAM_FUSED) : o.seam) != 0; }
+inline bool sf_layer_tok_on(const SfThreadOpts& o) { return (o.layer_tok == 0 ? sf_switch(SF_SW_LAYER_TOK) : o.layer_tok) > 0; }
+inline int sf_ffn_rows(const SfThreadOpts& o) { return o.ffn_rows > 0 ? o.ffn_rows : (sf_switch(SF_SW_FFN_ROWS64) ? 64 : 32); }   // per workgroup
 // hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device) -- a process may drive several GPUs
 int sf_ensure_dyn_lds(const void* kernel, size_t bytes);
 
@@ -96,7 +102,6 @@ void sf_prof_end(int cls, hipStream_t st);
 void sf_prof_suppress(int on);
 int sf_qkv_attn_ex(const float* x, const float* ln_g, const float* ln_b, float ln_eps, const float* in_proj_w,
                    const float* in_proj_b, float* out, int B, int L, int Lq, int d, int nheads, hipStream_t st);
-extern "C" int sf_get_precision(void);
 // weights-stationary form of the same convolution (conv_ws.hip; the same bits); returns 1 when it does not apply
 int sf_conv5x5_ws_ex(const float* in, const void* w_frag, const float* bias, const float* add, float* out, int F, int H, int W, int Cin, int Cout, int ks,
                      int relu, int n_workgroups, hipStream_t st);

@@ -813,7 +813,7 @@ int sf_slate_attention_train_bwd_f32(const float* q, const float* k, const float
   constexpr bool bwd48 = true;
   if (bf3 && head_dim > 32 && head_dim <= 48 && bwd48 && ldk % 4 == 0 && ldv % 4 == 0) {
     constexpr size_t lds48 = ((size_t)3 * 64 * 52 + 2 * 64 * 68 + 128) * sizeof(float);
-    static const bool v1 = getenv("SF_DBG") && strstr(getenv("SF_DBG"), "sab1");   // (probes: the packed-word kernel this one replaced)
+    static const bool v1 = sf_dbg("sab1") != 0;   // (probes: the packed-word kernel this one replaced)
     hipLaunchKernelGGL((slate_attn_stats_kernel<64, true>), g1, dim3(256), lds1, st, a, head_dim);
     if (v1) {
       SF_TRY(sf_ensure_dyn_lds((const void*)slate_attn_bwd48_kernel, (size_t)(lds48)));

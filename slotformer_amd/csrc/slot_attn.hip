@@ -920,11 +920,8 @@ bool sf_slot_attn_sparse_records(const float* k, const float* v, int HW, int D) 
 // 9 .. 16 slots, keys == values: the one-pass tile kernel (default; at 84,480 B of LDS ONE workgroup per CU) or, sf_set_slot_attn_tile16(0), the
 // two-pass kernel.  The record structure follows the kernel (sf_slot_attn_sparse_records_n): engine.hip's plan asks before it lets the slot update
 // skip the odd records.  profiles/slots16.md has the measurement behind the default.
-static int g_sa_tile16 = 1;
-extern "C" int sf_set_slot_attn_tile16(int on) { g_sa_tile16 = on ? 1 : 0; return 0; }
-extern "C" int sf_get_slot_attn_tile16(void) { return g_sa_tile16; }
 bool sf_slot_attn_sparse_records_n(const float* k, const float* v, int HW, int D, int N) {
-  return sf_slot_attn_sparse_records(k, v, HW, D) && (N <= SA_NMAX || g_sa_tile16);
+  return sf_slot_attn_sparse_records(k, v, HW, D) && (N <= SA_NMAX || sf_switch(SF_SW_SLOT_ATTN_TILE16));
 }
 
 int sf_slot_attn_iter_ex(const float* k, const float* v, int ld, long long batch_stride, const float* q,

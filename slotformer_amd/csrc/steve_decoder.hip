@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256, SLATE_BF3_WPS) void slate_flash_bf3_kernel(con
 }
 // (probes: SF_DBG=flash1 keeps the exact-f32 flash kernel in the split-bf16 modes)
 static bool slate_flash_f32_forced() {
-  static const bool f = getenv("SF_DBG") && strstr(getenv("SF_DBG"), "flash1");
+  static const bool f = sf_dbg("flash1") != 0;
   return f;
 }
 template <int HD>

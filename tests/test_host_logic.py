@@ -229,7 +229,7 @@ def test_slot_file_link_next_to_the_weights(tmp_path):
 
 def test_switch_table_and_environment_check():
     """slotformer_amd/switches.py: at most 15 SF_* variables, each with a kind and a description; check_environment separates the ones that are
-    set from the ones the table does not know (bench.py refuses to run with those)."""
+    set from the ones the table does not know (bench.py refuses to run with those).  Every variable the Python side or the library reads is in it."""
     from slotformer_amd import switches
     assert 0 < len(switches.SWITCHES) <= 15
     assert all(k.startswith('SF_') and kind in ('product', 'tools') and len(text) > 10 for k, (kind, text) in switches.SWITCHES.items())
@@ -244,6 +244,18 @@ def test_switch_table_and_environment_check():
     for rel in ('bench.py', 'slotformer_amd/pipeline.py', 'slotformer_amd/engine.py', 'slotformer_amd/_lib.py', 'slotformer_amd/harness.py', 'slotformer_amd/build.py'):
         seen |= set(re.findall(r"environ(?:\.get)?[\[(]\s*'(SF_[A-Z0-9_]+)'", open(os.path.join(root, rel)).read()))
     assert seen and seen <= set(switches.SWITCHES), sorted(seen - set(switches.SWITCHES))
+    # ... and every variable the library reads, which it does in two files only: the switch table and sf_dbg
+    csrc = os.path.join(root, 'slotformer_amd', 'csrc')
+    reads = {}
+    for f in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, f), errors='replace').read() if os.path.isfile(os.path.join(csrc, f)) else ''
+        if 'getenv(' in src:
+            # (the table's getenv takes the name from a row: its names are the quoted ones of the file)
+            reads[f] = set(re.findall(r'"(SF_[A-Z0-9_]+)"' if f == 'sf_switches.cpp' else r'getenv\(\s*"(SF_[A-Z0-9_]+)"', src))
+    assert sorted(reads) == ['sf_runtime.cpp', 'sf_switches.cpp'], sorted(reads)
+    assert reads['sf_runtime.cpp'] == {'SF_DBG'}
+    assert reads['sf_switches.cpp'] == {env for _, _, env, _, _ in switches.PROCESS.values() if env} | {'SF_CONV_WS'}
+    assert set().union(*reads.values()) <= set(switches.SWITCHES)
 
 
 def test_capture_gate_orders_captures_and_calls():
