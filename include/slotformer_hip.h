@@ -563,6 +563,45 @@ int sf_dvae_patch_embed_f32(const float* img, const float* w, float* y, int F, i
 int sf_dvae_head_argmax_f32(const float* x, long long ld, const void* w_packed, const float* bias, long long* ids_i64, short* ids_i16, long long R,
                             int V, int K, void* stream);
 
+/* ---- the vocabulary head and its cross-entropy without the logits (steve_slotformer.py:150-161; csrc/head_ce.hip) --------------------------------
+ * The token loss of a frozen decoder head W [V,K] (nn.Linear without bias) on rows x [R,K] against token ids t [R], forward and backward, with the
+ * logits [R,V] in MFMA accumulators only:
+ *   lse[r] = log sum_v exp(W[v] . x[r]),  loss[r] = lse[r] - W[t_r] . x[r],  dx[r,:] = c_r (sum_v exp(W[v] . x[r] - lse[r]) W[v,:] - W[t_r,:]).
+ * The target's logit (forward) and the one-hot (backward) are picked by comparing the swept word index with t_r, never by an address formed from
+ * it: a target outside [0, V) matches no word -- loss[r] = lse[r], dx[r,:] = c_r sum_v p W[v,:] -- and reads nothing.  There is no gradient for W.
+ * Arithmetic: split-bf16 (every f32 operand = bf16 hi + bf16 lo, three products, f32 accumulation) WHATEVER sf_set_precision says, as for the dVAE
+ * tokens; the exponentials are summed against the running maximum; every sum in a fixed order, no atomics, no communication between workgroups: two
+ * calls give the same bits, and a row's results do not depend on its place in the batch.
+ *
+ * sf_head_ce_ok reads shapes only: 1 exactly when K is a multiple of 32 with 32 <= K <= 256 and V a multiple of 32 with 32 <= V <= 2^20. */
+int sf_head_ce_ok(int V, int K);
+/* Bytes of the packed head weight: V * K * 8 (two fragment-ordered copies, each a bf16 hi plane of V * K elements and its lo plane); 0 unless
+ * sf_head_ce_ok.  Bytes of the forward's workspace for R rows (one pair of float64 per tile of 64 rows; needs no initial value); 0 for a bad R. */
+size_t sf_head_ce_packed_bytes(int V, int K);
+size_t sf_head_ce_workspace_bytes(long long R);
+/* w [V,K] f32 (torch's layout) -> packed: four planes of n = V * K bf16 elements, A hi | A lo | B hi | B lo; hi = bf16 of the value (round to
+ * nearest even), lo = bf16 of the remainder (value - hi).  Both copies are sequences of fragments of 64 lanes x 8 elements, element (f * 64 + l) * 8 + j
+ * of a plane being lane l's element j of fragment f:
+ *   copy A, fragment f = vb * (K / 16) + ks (block vb of 32 words, k-step ks of 16 features):  W[32 vb + (l & 31)][16 ks + 8 (l >> 5) + j];
+ *   copy B, fragment f = (vb * 2 + c) * (K / 32) + kfb (half c of block vb, block kfb of 32 features):
+ *                                                   W[32 vb + 16 c + 8 (j >> 2) + 4 (l >> 5) + (j & 3)][32 kfb + (l & 31)].
+ * The _host twin takes and fills HOST memory with the same bytes. */
+int sf_head_ce_pack_weights(const float* w, void* packed, int V, int K, void* stream);
+int sf_head_ce_pack_weights_host(const float* w, void* packed, int V, int K);
+/* Forward.  x [R,K] f32 with row stride ld >= K (a multiple of 4); targets as int64 (target_i64) or int16 (target_i16, the dtype of the token files,
+ * refused when V > 32768): exactly one of the two.  group_w [R / group] or NULL (all 1): the weight w of each run of `group` consecutive rows (a
+ * frame's tokens); R % group == 0.  lse [R] is written; loss_rows [R] (the unweighted loss[r]; may be NULL) too.  stats (may be NULL) is float64 [2] and has
+ * sum_r w(r) loss[r] and sum_r w(r) ADDED to it (rows of weight 0 add nothing, whatever their loss), the tiles' partial sums combined in index order by
+ * a one-workgroup launch; it needs ws of sf_head_ce_workspace_bytes(R), 8-byte aligned.  x and w_packed 16-byte aligned. */
+int sf_head_ce_fwd_f32(const float* x, long long ld, const void* w_packed, const long long* target_i64, const short* target_i16,
+                       const float* group_w, int group, float* lse, float* loss_rows, double* stats, long long R, int V, int K, void* ws,
+                       size_t ws_bytes, void* stream);
+/* Backward.  x, ld, w_packed, targets, group_w, group as in the forward, lse [R] from it; g: ONE float on the device (no host read),
+ * c_r = g[0] * w(r).  dx [R,K] with row stride ldx >= K is written; a row of weight 0 receives exact zeros. */
+int sf_head_ce_bwd_f32(const float* x, long long ld, const void* w_packed, const long long* target_i64, const short* target_i16,
+                       const float* group_w, int group, const float* lse, const float* g, float* dx, long long ldx, long long R, int V, int K,
+                       void* stream);
+
 /* ---- Physion VQA readout on rolled-out slots (physion_vqa/models/readout.py; csrc/physion_readout.hip) -------------------------------------------
  * logit[k][b] = max_t ( w2_k . agg_{i<j} ( W1_k cat(s_ti, s_tj) + b1_k ) + b2_k ) for a stack of K heads, agg = 0 max / 1 sum / 2 mean over the
  * N (N - 1) / 2 slot pairs in itertools.combinations order.  linear1 of a pair is U_i + V_j (U = S W1[:, :C]^T + b1, V = S W1[:, C:]^T): one product

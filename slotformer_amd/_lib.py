@@ -302,6 +302,13 @@ SIGNATURES = {
     'sf_dvae_pack_head_weights_host': (I, [VP, VP, I, I]),
     'sf_dvae_patch_embed_f32': (I, [FP, FP, FP, I, I, I, I, VP]),
     'sf_dvae_head_argmax_f32': (I, [FP, LL, VP, FP, VP, VP, LL, I, I, VP]),
+    'sf_head_ce_ok': (I, [I, I]),
+    'sf_head_ce_packed_bytes': (SZ, [I, I]),
+    'sf_head_ce_workspace_bytes': (SZ, [LL]),
+    'sf_head_ce_pack_weights': (I, [FP, VP, I, I, VP]),
+    'sf_head_ce_pack_weights_host': (I, [VP, VP, I, I]),
+    'sf_head_ce_fwd_f32': (I, [FP, LL, VP, VP, VP, FP, I, FP, FP, VP, LL, I, I, VP, SZ, VP]),
+    'sf_head_ce_bwd_f32': (I, [FP, LL, VP, VP, VP, FP, I, FP, FP, FP, LL, LL, I, I, VP]),
     'sf_physion_readout_ok': (I, [I, I, I]),
     'sf_physion_readout_fwd_f32': (I, [FP, LL, LL, I, VP, FP, FP, FP, FP, FP, VP, FP, VP, I, I, I, I, I, I, I, VP]),
     'sf_physion_readout_bwd_workspace_bytes': (SZ, [I, I, I]),

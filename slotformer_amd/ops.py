@@ -478,6 +478,74 @@ def gather_rows(table, ids):
     return out
 
 
+def pack_head_ce_weight(w):
+    """[V,K] -> the two split-bf16 fragment-order copies `head_ce_forward` / `head_ce_backward` stream (uint8 buffer, `sf_head_ce_pack_weights`)."""
+    _chk(w)
+    V, K = w.shape
+    nb = lib().sf_head_ce_packed_bytes(V, K)
+    if nb == 0:
+        raise RuntimeError(f'slotformer_amd pack_head_ce_weight: K a multiple of 32 in [32, 256] and V a multiple of 32 in [32, 2^20], got [{V}, {K}]')
+    out = torch.empty(nb, device=w.device, dtype=torch.uint8)
+    check(lib().sf_head_ce_pack_weights(_p(w), out.data_ptr(), V, K, _stream()))
+    return out
+
+
+def _head_ce_args(x, w_packed, target, group_w, group, V):
+    """Checks shared by the two head_ce launches -> (ld, R, K, target_i64 pointer, target_i16 pointer)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]):
+        raise RuntimeError('slotformer_amd head_ce: x is a float32 [R, K] device tensor with unit column stride; there is no CPU fallback')
+    if not (torch.is_tensor(w_packed) and w_packed.is_cuda and w_packed.dtype == torch.uint8 and w_packed.is_contiguous()):
+        raise RuntimeError('slotformer_amd head_ce: w_packed is the uint8 device buffer of pack_head_ce_weight; there is no CPU fallback')
+    R, K = x.shape
+    if w_packed.numel() != lib().sf_head_ce_packed_bytes(int(V), K) or w_packed.numel() == 0:
+        raise ValueError(f'slotformer_amd head_ce: w_packed does not hold a [{V}, {K}] head')
+    if not (torch.is_tensor(target) and target.is_cuda and target.dtype in (torch.int64, torch.int16) and target.is_contiguous()
+            and target.numel() == R):
+        raise TypeError(f'slotformer_amd head_ce: target is a contiguous int64 or int16 device tensor of {R} elements')
+    group = int(group)
+    if group < 1 or R % group:
+        raise ValueError(f'slotformer_amd head_ce: group {group} does not divide {R} rows')
+    if group_w is not None:
+        _chk(group_w)
+        if group_w.numel() != R // group:
+            raise ValueError(f'slotformer_amd head_ce: group_w has {group_w.numel()} elements for {R // group} groups')
+    i64 = target.dtype == torch.int64
+    return x.stride(0), R, K, target.data_ptr() if i64 else None, None if i64 else target.data_ptr()
+
+
+def head_ce_forward(x, w_packed, target, V, group_w=None, group=1, stats=None, want_rows=True):
+    """lse[r] = logsumexp_v(W[v] . x[r]) and loss[r] = lse[r] - W[target[r]] . x[r] WITHOUT the logits in memory (`sf_head_ce_fwd_f32`).
+    x [R, K] (rows may be strided), w_packed = pack_head_ce_weight(W [V,K]), target int64 / int16 [R]; group_w [R / group] weighs runs of `group`
+    rows.  stats: float64 [2] on the device, has (sum w loss, sum w) ADDED to it.  -> (lse [R], loss_rows [R], or None with want_rows=False)."""
+    ld, R, K, t64, t16 = _head_ce_args(x, w_packed, target, group_w, group, V)
+    lse = torch.empty(R, device=x.device, dtype=torch.float32)
+    rows = torch.empty(R, device=x.device, dtype=torch.float32) if want_rows else None
+    ws = None
+    if stats is not None:
+        if not (stats.is_cuda and stats.dtype == torch.float64 and stats.numel() == 2 and stats.is_contiguous()):
+            raise TypeError('slotformer_amd head_ce: stats is a contiguous float64 [2] device tensor')
+        ws = torch.empty(lib().sf_head_ce_workspace_bytes(R) // 8, device=x.device, dtype=torch.float64)
+    check(lib().sf_head_ce_fwd_f32(x.data_ptr(), ld, w_packed.data_ptr(), t64, t16, _p(group_w), int(group), _p(lse), _p(rows), _p(stats), R, int(V), K,
+                                   _p(ws), 0 if ws is None else ws.numel() * 8, _stream()))
+    return lse, rows
+
+
+def head_ce_backward(x, w_packed, target, V, lse, g, group_w=None, group=1, out=None):
+    """dx[r] = g * w(r) * (softmax(W x[r]) - onehot(target[r])) @ W, the logits recomputed from x and `lse` (`sf_head_ce_bwd_f32`).  g: a float32
+    device tensor of one element (never read on the host).  out: float32 [R, K] with unit column stride to write into."""
+    ld, R, K, t64, t16 = _head_ce_args(x, w_packed, target, group_w, group, V)
+    _chk(lse, g)
+    if lse.numel() != R or g.numel() != 1:
+        raise ValueError(f'slotformer_amd head_ce: lse has {R} elements and g one')
+    if out is None:
+        out = torch.empty(R, K, device=x.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (R, K) and out.stride(1) == 1 and out.stride(0) >= K):
+        raise TypeError(f'slotformer_amd head_ce: out is a float32 [{R}, {K}] device tensor with unit column stride')
+    check(lib().sf_head_ce_bwd_f32(x.data_ptr(), ld, w_packed.data_ptr(), t64, t16, _p(group_w), int(group), _p(lse), _p(g), out.data_ptr(),
+                                   out.stride(0), R, int(V), K, _stream()))
+    return out
+
+
 def cross_entropy(logits, target):
     """F.cross_entropy(logits [R,V], target int64 [R]) with mean reduction -> 0-dim tensor."""
     _chk(logits)

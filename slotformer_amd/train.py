@@ -839,6 +839,12 @@ def slate_decoder_forward(dec, slots, idx):
     """STEVETransformerDecoder.forward (steve_transformer.py:275-303) under autograd: slots [B,N,d], idx int64 [B,t] ->
     logits [B,1+t,V], as a chain of HIP-backed nodes; every dropout of the reference modules (embedding, attention weights,
     attention output, FFN) is active iff the decoder is in train() mode."""
+    return linear(slate_decoder_hidden(dec, slots, idx), dec.head)
+
+
+def slate_decoder_hidden(dec, slots, idx):
+    """`slate_decoder_forward` up to and including the final LayerNorm -> [B,1+t,d]: the rows the vocabulary head is applied to, for
+    `head_cross_entropy`, which takes them to the token loss without the logits."""
     tr = dec.training
     B, T = idx.shape
     H = dec.n_head
@@ -863,11 +869,68 @@ def slate_decoder_forward(dec, slots, idx):
         x = x + dropout(linear(att, ca.proj_o), ca.output_dropout.p, tr)
         y = layer_norm(x, blk.ffn_layer_norm)
         x = x + dropout(linear(linear(y, blk.ffn[0], relu=True), blk.ffn[2]), blk.ffn[3].p, tr)
-    return linear(layer_norm(x, dec.tf_dec.layer_norm), dec.head)
+    return layer_norm(x, dec.tf_dec.layer_norm)
 
 
 def token_cross_entropy(logits, target):
     return _TokenCrossEntropy.apply(logits, target.to(torch.int64).contiguous())
+
+
+class _HeadCrossEntropy(torch.autograd.Function):
+    """(weighted mean loss, stats) of sf_head_ce_fwd_f32 / sf_head_ce_bwd_f32: the head's product and the cross-entropy in one pass each way.
+    Saved for the backward: x, lse [R] and the targets -- nothing of R * V elements exists at any time."""
+
+    @staticmethod
+    def forward(ctx, x, w_packed, target, group_w, group, V):
+        from . import ops
+        K = x.shape[-1]
+        xd = x.detach().float().reshape(-1, K)
+        if xd.stride(1) != 1 or xd.stride(0) < K or xd.stride(0) % 4 or xd.data_ptr() % 16:
+            xd = xd.contiguous()
+        stats = torch.zeros(2, dtype=torch.float64, device=xd.device)
+        lse, _ = ops.head_ce_forward(xd, w_packed, target, V, group_w, group, stats, want_rows=False)
+        ctx.save_for_backward(xd, w_packed, target, group_w, lse, stats)
+        ctx.group, ctx.V, ctx.xshape = group, V, tuple(x.shape)
+        ctx.mark_non_differentiable(stats)
+        n = stats[1]
+        return torch.where(n > 0, stats[0] / n, torch.zeros_like(n)).float(), stats
+
+    @staticmethod
+    def backward(ctx, g, _d_stats):
+        from . import ops
+        xd, w_packed, target, group_w, lse, stats = ctx.saved_tensors
+        n = stats[1]
+        gd = torch.where(n > 0, g.double() / n, torch.zeros_like(n)).float().reshape(1)   # stays on the device
+        dx = ops.head_ce_backward(xd, w_packed, target, ctx.V, lse, gd, group_w, ctx.group)
+        return dx.view(ctx.xshape), None, None, None, None, None
+
+
+def head_cross_entropy(x, weight, target, group_w=None, group=1):
+    """The token loss of a FROZEN vocabulary head without its logits: x [..., K] (the rows behind the decoder's final LayerNorm,
+    `slate_decoder_hidden`), weight = the head, an nn.Linear without bias or its [V, K] weight, target int64 / int16 ids of x's leading shape ->
+    (loss, stats).  loss: the mean over the rows of logsumexp(W x[r]) - W[target[r]] . x[r], weighted by group_w [R / group] float32 (the weight of
+    each run of `group` consecutive rows -- a frame's tokens; 0 drops the frame), a float32 device scalar; stats float64 [2] = (sum w loss, sum w),
+    not differentiable.  The gradient reaches x only: a head that requires grad is refused (STEVE's own training keeps the `linear` +
+    `token_cross_entropy` path).  The packed copy of the weight is cached on its owner and rebuilt when the weight's version changes."""
+    from . import ops, plans
+    w = weight.weight if isinstance(weight, torch.nn.Module) else weight
+    if isinstance(weight, torch.nn.Module) and getattr(weight, 'bias', None) is not None:
+        raise NotImplementedError('slotformer_amd: head_cross_entropy takes a head without bias')
+    if not (torch.is_tensor(w) and w.is_cuda and w.dim() == 2):
+        raise RuntimeError('slotformer_amd: head_cross_entropy needs a [V, K] weight on a HIP device; there is no CPU fallback')
+    if w.requires_grad:
+        raise NotImplementedError('slotformer_amd: head_cross_entropy has no gradient for the head weight (the weight gradient of the fused head is '
+                                  'not implemented); freeze it, or use train.linear + train.token_cross_entropy')
+    V, K = w.shape
+    if x.shape[-1] != K or not lib().sf_head_ce_ok(V, K):
+        raise NotImplementedError(f'slotformer_amd: head_cross_entropy takes K a multiple of 32 in [32, 256] and V a multiple of 32 in [32, 2^20], '
+                                  f'got x [..., {x.shape[-1]}] and a [{V}, {K}] head')
+    if target.dtype not in (torch.int64, torch.int16) or target.numel() != x.numel() // K:
+        raise ValueError(f'slotformer_amd: head_cross_entropy targets are int64 or int16 ids, one per row of x, got {target.dtype} {tuple(target.shape)}')
+    if group_w is not None:
+        group_w = group_w.detach().float().contiguous()
+    packed = plans.cached(weight, 'head_ce', plans.signature(w), lambda: ops.pack_head_ce_weight(w.detach().float().contiguous()))
+    return _HeadCrossEntropy.apply(x, packed, target.contiguous().reshape(-1), group_w, int(group), V)
 
 
 class _LinearCat(torch.autograd.Function):

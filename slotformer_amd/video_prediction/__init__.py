@@ -137,13 +137,56 @@ def _image_step(model, table, frames, cv, cs, frame_offset, hist, S, seed, grad_
     return pred, slot_loss, img_loss, slot_stats, img_stats
 
 
+def _token_table(tokens, table, model, who):
+    """The checks of a tokens= argument: an int16 / int64 device tensor [V, T, h*w] beside the slot table, for a model with a dVAE."""
+    if not hasattr(model, 'dvae'):
+        raise ValueError(f'slotformer_amd.video_prediction.{who}: tokens= is the target of the STEVE token loss; this model has no dVAE (its image '
+                         'loss takes frames=)')
+    hw = int(model.h) * int(model.w)
+    if not torch.is_tensor(tokens) or tokens.dtype not in (torch.int16, torch.int64) or tokens.dim() != 3 or \
+            tuple(tokens.shape[:2]) != tuple(table.shape[:2]) or tokens.shape[2] != hw or not tokens.is_contiguous():
+        raise ValueError(f'slotformer_amd.video_prediction.{who}: tokens are contiguous int16 or int64 ids [{table.shape[0]}, {table.shape[1]}, {hw}], '
+                         f'got {getattr(tokens, "dtype", type(tokens).__name__)} {tuple(getattr(tokens, "shape", ()))}')
+    if not tokens.is_cuda:
+        raise RuntimeError('slotformer_amd: the token table must live on a HIP device; there is no CPU fallback')
+    return tokens
+
+
+def _frame_weights(clip_len, hist, S):
+    """clip_len int32 [..., B] -> float32 [..., B * S]: 1 where step s of clip b counts (hist + s < clip_len[b], clip_mse's rule), else 0."""
+    return (hist + torch.arange(S, device=clip_len.device) < clip_len[..., None]).float().flatten(-2)
+
+
+def _clip_token_ids(tokens, cv, cs, frame_offset, hist, S):
+    """The ids of the S predicted frames of every clip, picked from the token table on the device -> [B * S, h*w] in the table's dtype."""
+    t = cs.long()[:, None] + (hist + torch.arange(S, device=cs.device)) * frame_offset
+    return tokens[cv.long()[:, None], t].flatten(0, 1)
+
+
+def _token_step(model, table, tokens, cv, cs, frame_offset, hist, S, seed, grad_out, step_w, clip_len, frame_w, loss_w):
+    """One forward of `fit` with the STEVE token loss (steve_slotformer.py:124-161) as autograd nodes: the clip rollout, the frozen Transformer
+    decoder on the predicted slots up to its final LayerNorm, and the vocabulary head fused with the cross-entropy against the table's ids -- no
+    logits -> (pred, slot loss, token loss (weighted by loss_w[1]), slot stats, the token loss itself).  frame_w [B * S] or None: `_frame_weights`
+    of clip_len.  Backward of the sum of the two losses fills grad_out."""
+    from .. import train
+    pred = train.rollout_clips_with_grad(model.rollouter, table, cv, cs, frame_offset, S, seed=seed, grad_out=grad_out)
+    ids = _clip_token_ids(tokens, cv, cs, frame_offset, hist, S)
+    hidden = train.slate_decoder_hidden(model.decoder, pred.flatten(0, 1), ids[:, :-1].contiguous())
+    ce, _ = train.head_cross_entropy(hidden, model.decoder.head, ids, frame_w, ids.shape[1])
+    slot_loss, slot_stats = train.clip_mse(pred, table, cv, cs, frame_offset, hist, step_w, clip_len, loss_w[0])
+    return pred, slot_loss, ce * float(loss_w[1]), slot_stats, ce.detach()
+
+
 def fit(model, table, clips, epochs, batch_size, lr, seed, frame_offset, warmup_pct=0.05, min_lr_ratio=0.01, clip_grad=None, loss_decay_pct=None,
-        clip_len=None, frames=None, mean=0.5, std=0.5, loss_w=(1., 1.), resume=None, allreduce=False, stop_after=None):
+        clip_len=None, frames=None, mean=0.5, std=0.5, loss_w=(1., 1.), resume=None, allreduce=False, stop_after=None, tokens=None):
     """Train `model.rollouter` in place on clips of a device-resident slot table [V, T, N, C] (SlotFormer, SingleStepSlotFormer, and
-    STEVESlotFormer without its token loss): the reference's SlotFormerMethod run -- Adam at `lr` with linear warm-up over warmup_pct of the steps
+    STEVESlotFormer): the reference's SlotFormerMethod run -- Adam at `lr` with linear warm-up over warmup_pct of the steps
     and cosine decay to lr * min_lr_ratio, gradient clipping (`clip_grad`), the step weights of `loss_decay_weights` (`loss_decay_pct`), the
     vid_len truncation (`clip_len`: the length of every clip, [M]) and, with `frames` (uint8 [V, T, H, W, 3] at the decoder's resolution) and
-    `model.use_img_recon_loss`, the image loss through the frozen decoder, the two terms weighted by `loss_w`.
+    `model.use_img_recon_loss`, the image loss through the frozen decoder, the two terms weighted by `loss_w`.  A STEVESlotFormer takes its image
+    term from `tokens` instead (int16 or int64 ids [V, T, h*w] on the device, what `extract_video_tokens(to_host=False)` returns and the token
+    files hold): the cross-entropy of the frozen Transformer decoder against the ids of the predicted frames, its vocabulary head fused with
+    the loss (`train.head_cross_entropy`), so that no step allocates anything of rows x vocabulary elements.
 
     clips: (video, start) pairs [M, 2] (`clip_index`); a clip is burn-in + model.rollout_len frames, frame_offset apart.  All host work happens
     before the loop: the clips are validated against the table, the whole schedule (`clip_schedule(M, epochs, batch_size, seed)`) and the whole
@@ -151,7 +194,7 @@ def fit(model, table, clips, epochs, batch_size, lr, seed, frame_offset, warmup_
     whose gradient the backward turns into the optimiser's bucket directly -- and `FlatAdam.step(gathered=True)`: no synchronisation, no `.item()`
     and no host-to-device copy inside an epoch, one seed -> one result, bit for bit.
 
-    Returns {'loss': the mean slot loss of every epoch run [epochs run] (device), 'img_loss': the same for the image term or None, 'state':
+    Returns {'loss': the mean slot loss of every epoch run [epochs run] (device), 'img_loss': the same for the image / token term or None, 'state':
     {'optimizer', 'step', 'seed', 'epochs'}}.  stop_after: run only that many epochs of the `epochs` the schedule is laid out for; `state` fed
     back as resume= (same seed, epochs and data) continues where that run stopped and ends where the straight run would have."""
     from .. import train
@@ -163,7 +206,11 @@ def fit(model, table, clips, epochs, batch_size, lr, seed, frame_offset, warmup_
     M = clips.shape[0]
     use_img = frames is not None and bool(getattr(model, 'use_img_recon_loss', False))
     if use_img and not hasattr(model, 'decoder_pos_embedding'):
-        raise NotImplementedError('slotformer_amd.video_prediction.fit: the image loss needs the SAVi decoder (the STEVE token loss is not part of fit)')
+        raise NotImplementedError('slotformer_amd.video_prediction.fit: frames= is the image loss of the SAVi decoder; a STEVE model trains its token '
+                                  'loss from tokens= (the ids of extract_video_tokens)')
+    if tokens is not None:
+        _token_table(tokens, table, model, 'fit')
+    use_tok = tokens is not None and bool(getattr(model, 'use_img_recon_loss', False))
     if use_img and (tuple(frames.shape[:2]) != tuple(table.shape[:2]) or tuple(frames.shape[2:4]) != tuple(model.resolution)):
         raise ValueError(f'slotformer_amd.video_prediction.fit: frames are uint8 [{table.shape[0]}, {table.shape[1]}, {model.resolution[0]}, '
                          f'{model.resolution[1]}, 3], got {tuple(frames.shape)}')
@@ -181,6 +228,7 @@ def fit(model, table, clips, epochs, batch_size, lr, seed, frame_offset, warmup_
         if clip_len.numel() != M:
             raise ValueError(f'slotformer_amd.video_prediction.fit: {M} clips, clip_len of {clip_len.numel()}')
         sched_len = clip_len[order].contiguous().to(dev)
+    sched_fw = _frame_weights(sched_len, hist, S) if use_tok and sched_len is not None else None   # [total, B * S]
     rows = [loss_decay_weights(s, total, loss_decay_pct, S) for s in range(total)]
     n_decay = sum(w is not None for w in rows)   # (the factor only grows: the decaying steps come first)
     w_table = torch.stack([w.float() for w in rows[:n_decay]]).to(dev) if n_decay else None
@@ -201,6 +249,7 @@ def fit(model, table, clips, epochs, batch_size, lr, seed, frame_offset, warmup_
     e1 = len(sched) if stop_after is None else min(len(sched), e0 + int(stop_after))
     stats = torch.zeros(max(e1 - e0, 0), 1 + 2 * S, dtype=torch.float64, device=dev)
     img_stats = torch.zeros_like(stats) if use_img else None
+    tok_sum = torch.zeros(stats.shape[0], dtype=torch.float64, device=dev) if use_tok else None
     warmup = float(warmup_pct) * total
     was_training = r.training
     r.train()
@@ -217,6 +266,12 @@ def fit(model, table, clips, epochs, batch_size, lr, seed, frame_offset, warmup_
                 (slot_loss + img_loss).backward()
                 stats[e - e0] += st
                 img_stats[e - e0] += ist
+            elif use_tok:
+                fw = None if sched_fw is None else sched_fw[step]
+                _, slot_loss, tok_loss, st, ce = _token_step(model, table, tokens, cv, cs, f, hist, S, sd, opt.grad, sw, cl, fw, loss_w)
+                (slot_loss + tok_loss).backward()
+                stats[e - e0] += st
+                tok_sum[e - e0] += ce
             else:
                 with torch.no_grad():
                     p_drop = float(r.transformer_encoder.layers[0].dropout.p)
@@ -235,16 +290,17 @@ def fit(model, table, clips, epochs, batch_size, lr, seed, frame_offset, warmup_
     sd_opt = opt.state_dict()
     sd_opt['state'] = {i: {k: v.clone() for k, v in s.items()} for i, s in sd_opt['state'].items()}
     return {'loss': (stats[:, 0] / (n * (float(loss_w[0]) or 1.))).float(),
-            'img_loss': (img_stats[:, 0] / (n * (float(loss_w[1]) or 1.))).float() if use_img else None,
+            'img_loss': (img_stats[:, 0] / (n * (float(loss_w[1]) or 1.))).float() if use_img else (tok_sum / n).float() if use_tok else None,
             'state': {'optimizer': sd_opt, 'step': step, 'seed': int(seed), 'epochs': int(epochs)}}
 
 
 @torch.no_grad()
-def evaluate(model, table, clips, batch_size, frame_offset, clip_len=None):
+def evaluate(model, table, clips, batch_size, frame_offset, clip_len=None, tokens=None):
     """The reference's eval branch (slotformer.py:291-295,318) over all `clips` of a device-resident slot table, without gradients and without
     dropout: -> {'slot_recon_loss': the mean squared error over every counted element, 'slot_recon_loss_1' .. '_k', k = min(6, rollout_len): the
     same per rollout step} as Python floats.  Batches of `batch_size` clips in order (the last one ragged); the sums stay on the device and are
-    downloaded once at the end.  clip_len [M]: the vid_len truncation."""
+    downloaded once at the end.  clip_len [M]: the vid_len truncation.  tokens (a STEVESlotFormer with use_img_recon_loss; the table of `fit`):
+    adds 'img_recon_loss', the mean token cross-entropy over every counted frame."""
     from .. import train
     _device_table(table)
     r = model.rollouter
@@ -260,15 +316,27 @@ def evaluate(model, table, clips, batch_size, frame_offset, clip_len=None):
         cl_all = torch.as_tensor(clip_len).to(torch.int32).flatten().to(dev)
         if cl_all.numel() != M:
             raise ValueError(f'slotformer_amd.video_prediction.evaluate: {M} clips, clip_len of {cl_all.numel()}')
+    if tokens is not None:
+        _token_table(tokens, table, model, 'evaluate')
+    use_tok = tokens is not None and bool(getattr(model, 'use_img_recon_loss', False))
     stats = torch.zeros(1 + 2 * S, dtype=torch.float64, device=dev)
+    tok_stats = torch.zeros(2, dtype=torch.float64, device=dev)
+    fw_all = _frame_weights(cl_all, hist, S).reshape(M, S) if use_tok and cl_all is not None else None
     ws = None
     for s in range(0, M, int(batch_size)):
         e = min(s + int(batch_size), M)
         pred, _, ws = train._clips_forward(r, table, cv_all[s:e], cs_all[s:e], f, S, 0., 0, ws)
         train.clip_mse_launch(pred, table, cv_all[s:e], cs_all[s:e], f, hist, None, None if cl_all is None else cl_all[s:e], 1., None, stats)
+        if use_tok:
+            ids = _clip_token_ids(tokens, cv_all[s:e], cs_all[s:e], f, hist, S)
+            hidden = train.slate_decoder_hidden(model.decoder, pred.flatten(0, 1), ids[:, :-1].contiguous())
+            tok_stats += train.head_cross_entropy(hidden, model.decoder.head, ids, None if fw_all is None else fw_all[s:e].reshape(-1), ids.shape[1])[1]
     h = stats.cpu()
     sums, counts = h[1:1 + S], h[1 + S:]
     out = {'slot_recon_loss': float(sums.sum() / counts.sum())}
+    if use_tok:
+        th = tok_stats.cpu()
+        out['img_recon_loss'] = float(th[0] / th[1])
     for k in range(min(6, S)):
         out[f'slot_recon_loss_{k + 1}'] = float(sums[k] / counts[k])
     return out
