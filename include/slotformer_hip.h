@@ -1022,6 +1022,46 @@ int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* 
                              int pred_len, float dropout_p, unsigned long long seed, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* ---- Training of the PHYRE task-success readout (csrc/phyre_readout_train.hip; phyre_planning.fit) ------------------------------------------
+ * PHYREReadout.forward in train mode + the gradient of its logits: tokens as sf_phyre_readout_fwd_f32 builds them (slots read in place through
+ * (stride_v, stride_t), batch entry b = video video_index[b] or b, sel [T] HOST frame numbers, -1 = a frame of zeros), then ONE launch per layer
+ * in each direction and one for the head.  Limits: sf_phyre_readout_ok.  Split-bf16 products whatever sf_set_precision says -- any other process
+ * precision is refused.  All parameter pointers are DEVICE memory in torch layouts (`layers`: a HOST array, the torch-layout leaves only; the
+ * packed copies are not read); the calls split / transpose what their kernels need into the workspace themselves, every call, so the weights may
+ * change between steps.  Dropout (p of nn.TransformerEncoderLayer; 0: no mask is evaluated): a pure function of (seed, layer, site, element) --
+ * csrc/dropout_mask.h, train.dropout_keep_mask; pass the same dropout_p / seed / slot arguments to both calls and leave the workspace (16-byte
+ * aligned, sf_phyre_readout_train_workspace_bytes; 0 for unsupported arguments) untouched in between.
+ * video_index is TRUSTED, as the index arrays of sf_rollout_train_clips_fwd_f32: it is not read back; an entry outside [0, V) gives NaN logits and
+ * contributes nothing to d in_proj_w, never an address -- validate it on the host once (phyre_planning.fit does).
+ * Every argument error (shape, NULL, alignment, workspace too small, sel outside [-1, T_all), process precision) is a negative return code before
+ * any launch.  No allocation and no synchronisation inside the calls; equal inputs give equal bits (fixed summation orders, no float atomics). */
+typedef struct {
+  int num_slots, slot_size, d_model, num_heads, ffn_dim, num_layers;
+  const float *in_proj_w, *in_proj_b; /* [d_model, slot_size], [d_model] */
+  const float *enc_t_pe, *cls;        /* [T, d_model], [d_model] */
+  const sf_tfm_layer* layers;         /* HOST array [num_layers] */
+  const float *mlp_w1, *mlp_b1, *mlp_w2, *mlp_b2; /* cls_mlp: [d_model, d_model], [d_model], [d_model], [1] */
+} sf_phyre_readout_model;
+
+/* The same leaves; gradients are WRITTEN, not accumulated (slices of a flat optimiser bucket are fine; the layer leaves 16-byte aligned). */
+typedef struct {
+  float *in_proj_w, *in_proj_b;
+  float *enc_t_pe, *cls;              /* enc_t_pe: NULL for a fixed ('sin') table */
+  const sf_tfm_layer_grads* layers;   /* HOST array [num_layers] */
+  float *mlp_w1, *mlp_b1, *mlp_w2, *mlp_b2;
+} sf_phyre_readout_grads;
+
+size_t sf_phyre_readout_train_workspace_bytes(const sf_phyre_readout_model* m, int B, int T);
+/* -> logits [B].  gates (or NULL): [num_layers][B * L][ffn_dim] bytes, the ReLU decisions of the layers (1: passed); head_gates (or NULL):
+ * [B][d_model] bytes, those of the head.  The backward reads the decisions the forward kept in the workspace, it never re-decides a sign. */
+int sf_phyre_readout_train_fwd_f32(const sf_phyre_readout_model* m, const float* slots, long long stride_v, long long stride_t, int V, int T_all,
+                                   const int* video_index, const int* sel, int B, int T, float dropout_p, unsigned long long seed, float* logits,
+                                   unsigned char* gates, unsigned char* head_gates, void* ws, size_t ws_bytes, void* stream);
+/* g [B] = d loss / d logit -> every parameter gradient in *grads (the slots are frozen inputs and get none) */
+int sf_phyre_readout_train_bwd_f32(const sf_phyre_readout_model* m, const float* slots, long long stride_v, long long stride_t, int V, int T_all,
+                                   const int* video_index, const int* sel, int B, int T, const float* g, const sf_phyre_readout_grads* grads,
+                                   float dropout_p, unsigned long long seed, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- SlotFormer training on clips of a device-resident table (csrc/clip_train.hip; video_prediction.fit) ----------------------------------
  * A batch is B (video, start) pairs in two int32 DEVICE arrays, never a gathered copy.  The index arrays are TRUSTED: they are not read back,
  * so a pair outside the table reads outside it -- validate them on the host once, before the loop (video_prediction.fit does).  What the host

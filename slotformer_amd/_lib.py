@@ -42,6 +42,17 @@ class sf_tfm_layer_grads(C.Structure):
         'norm2_g', 'norm2_b', 'lin1_w', 'lin1_b', 'lin2_w', 'lin2_b')]
 
 
+class sf_phyre_readout_model(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('num_slots', 'slot_size', 'd_model', 'num_heads', 'ffn_dim', 'num_layers')] + [
+        (n, FP) for n in ('in_proj_w', 'in_proj_b', 'enc_t_pe', 'cls')] + [('layers', C.POINTER(sf_tfm_layer))] + [
+            (n, FP) for n in ('mlp_w1', 'mlp_b1', 'mlp_w2', 'mlp_b2')]
+
+
+class sf_phyre_readout_grads(C.Structure):
+    _fields_ = [(n, FP) for n in ('in_proj_w', 'in_proj_b', 'enc_t_pe', 'cls')] + [('layers', C.POINTER(sf_tfm_layer_grads))] + [
+        (n, FP) for n in ('mlp_w1', 'mlp_b1', 'mlp_w2', 'mlp_b2')]
+
+
 class sf_rollouter_grads(C.Structure):
     _fields_ = [(n, FP) for n in ('in_proj_w', 'in_proj_b', 'out_proj_w', 'out_proj_b')] + [
         ('layers', C.POINTER(sf_tfm_layer_grads)), ('pe_tok', FP)]
@@ -319,6 +330,11 @@ SIGNATURES = {
     'sf_phyre_readout_fwd_f32': (I, [FP, LL, LL, I, I, VP, C.POINTER(C.c_int), FP, FP, FP, FP, C.POINTER(sf_tfm_layer), I, I, I, I, FP, FP, FP, FP, FP,
                                      FP, VP, FP, LL, I, I, I, I, VP, SZ, VP]),
     'sf_phyre_auccess_f32': (I, [FP, VP, VP, I, I, VP]),
+    'sf_phyre_readout_train_workspace_bytes': (SZ, [C.POINTER(sf_phyre_readout_model), I, I]),
+    'sf_phyre_readout_train_fwd_f32': (I, [C.POINTER(sf_phyre_readout_model), FP, LL, LL, I, I, VP, C.POINTER(C.c_int), I, I, F32, C.c_ulonglong, FP,
+                                           VP, VP, VP, SZ, VP]),
+    'sf_phyre_readout_train_bwd_f32': (I, [C.POINTER(sf_phyre_readout_model), FP, LL, LL, I, I, VP, C.POINTER(C.c_int), I, I, FP,
+                                           C.POINTER(sf_phyre_readout_grads), F32, C.c_ulonglong, VP, SZ, VP]),
     'sf_aloe_ok': (I, [I, I, I, I, I, I, I, I]),
     'sf_aloe_workspace_bytes': (SZ, [I, I, I, I, I, I]),
     'sf_aloe_text_table_f32': (I, [FP, FP, FP, FP, I, I, I, VP]),

@@ -217,6 +217,26 @@ inline bool ph_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
+// The token rows alone, for the training forward (phyre_readout_train.hip): ph_embed_kernel on arguments its caller has validated as
+// sf_phyre_readout_fwd_f32 validates its own (shape, strides, sel in [-1, T_all), 16-byte alignment); x [B][1 + T N][128].
+int sf_phyre_embed_ex(const float* slots, long long stride_v, long long stride_t, int V, const int* video_index, const int* sel, const float* in_proj_w,
+                      const float* in_proj_b, const float* enc_t_pe, const float* cls, float* x, int B, int T, int N, int C, hipStream_t st) {
+  PhSel table;
+  for (int t = 0; t < PH_MAXL; ++t) table.v[t] = t < T ? sel[t] : -1;
+  PhEmbed a;
+  a.slots = slots; a.stride_v = stride_v; a.stride_t = stride_t; a.V = V; a.video_index = video_index;
+  a.W = in_proj_w; a.bias = in_proj_b; a.pe = enc_t_pe; a.cls = cls; a.x = x;
+  a.B = B; a.T = T; a.N = N; a.C = C;
+  a.rows = (long long)B * T * N;
+  SF_REQUIRE((a.rows + PH_ROWS - 1) / PH_ROWS + (B + PH_CLS_PER_WG - 1) / PH_CLS_PER_WG < (1LL << 31), "sf_phyre_embed_ex: batch too large for one launch");
+  a.ntiles = (int)((a.rows + PH_ROWS - 1) / PH_ROWS);
+  const size_t lds = ph_embed_lds(C);
+  SF_TRY(sf_ensure_dyn_lds((const void*)ph_embed_kernel, lds));
+  hipLaunchKernelGGL(ph_embed_kernel, dim3((unsigned)(a.ntiles + (B + PH_CLS_PER_WG - 1) / PH_CLS_PER_WG)), dim3(PH_THREADS), lds, st, a, table);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
+
 #define PH_LIMITS "1 <= num_slots <= 16, slot_size a multiple of 32 in [32, 256], T >= 1, 1 + T * num_slots <= 96, (d_model, heads, ffn) = (128, 8, 512), 1 <= num_layers <= 8"
 
 extern "C" {

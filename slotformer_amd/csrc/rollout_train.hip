@@ -23,19 +23,7 @@
 #include "sf_internal.h"
 #include "rollout_train.h"
 #include "bf16_planes.h"
-
-// ---------------------------------------------------------------------------------------------------------------------
-// dropout mask
-// ---------------------------------------------------------------------------------------------------------------------
-enum { SITE_ATTN_P = 0, SITE_ATTN_O = 1, SITE_FFN_H = 2, SITE_FFN_O = 3 };
-static inline uint32_t site_seed(unsigned long long seed, int step, int layer, int site) {
-  const uint32_t tag = (uint32_t)((step * 64 + layer) * 4 + site);
-  return sf_mix32((uint32_t)seed ^ sf_mix32((uint32_t)(seed >> 32) + 0x9e3779b9u * (tag + 1u)));
-}
-__device__ __forceinline__ bool sf_keep(uint32_t sseed, uint32_t idx, uint32_t thresh) {
-  return (sf_mix32(idx ^ sseed) >> 8) >= thresh;
-}
-static inline uint32_t drop_thresh(float p) { return (uint32_t)((double)p * 16777216.0); }
+#include "dropout_mask.h"   // site_seed / sf_keep / drop_thresh: the mask convention, shared with phyre_readout_train.hip
 
 // y = res + keep(x) / (1 - p)   (res may be NULL); n4 float4 elements
 __global__ __launch_bounds__(256) void residual_dropout_kernel(const float* __restrict__ x, const float* __restrict__ res,

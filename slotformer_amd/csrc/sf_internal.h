@@ -139,6 +139,9 @@ int sf_grad_ln_ex(const float* x, const float* dy, float* dgamma, float* dbeta, 
 int sf_ln_bwd_ex(const float* x, const float* dy, const float* gamma, const float* dres, float* out, long long rows, int D,
                  float eps, hipStream_t st);
 int sf_transpose_ex(const float* in, float* out, int R, int Cn, hipStream_t st);
+// the token rows of the PHYRE readout (phyre_readout.hip: ph_embed_kernel) for its training forward; arguments validated by the caller
+int sf_phyre_embed_ex(const float* slots, long long stride_v, long long stride_t, int V, const int* video_index, const int* sel, const float* in_proj_w,
+                      const float* in_proj_b, const float* enc_t_pe, const float* cls, float* x, int B, int T, int N, int C, hipStream_t st);
 int sf_relu_bwd_ex(float* dh, const float* h, long long n, hipStream_t st);
 int sf_conv2d_nhwc_strided_ex(const float* in, const float* w_packed, const float* bias, float* out, int F, int Hin, int Win,
                               int Cin, int Cout, int ks, int stride, int relu, hipStream_t stream, const float* relu_mask = nullptr);

@@ -761,6 +761,97 @@ def phyre_readout_fwd(slots, sel, in_proj_w, in_proj_b, enc_t_pe, cls, layers, n
     return logits, conf
 
 
+PHYRE_LAYER_FIELDS = ('norm1_g', 'norm1_b', 'in_proj_w', 'in_proj_b', 'out_proj_w', 'out_proj_b', 'norm2_g', 'norm2_b', 'lin1_w', 'lin1_b', 'lin2_w',
+                      'lin2_b')
+
+
+def phyre_grad_layout(slot_size, T, num_layers, learnable_pe, d_model=128, ffn=512):
+    """[(name, numel)] of the flat gradient buffer `phyre_readout_train_bwd` writes -- the order of `train.phyre_readout_parameters`: in_proj.weight,
+    in_proj.bias, CLS, enc_t_pe (learnable tables only), each layer's twelve leaves (PHYRE_LAYER_FIELDS), cls_mlp.0.weight, cls_mlp.0.bias,
+    cls_mlp.2.weight, cls_mlp.2.bias.  Every leaf but the last starts on a multiple of four floats."""
+    d, f = int(d_model), int(ffn)
+    out = [('in_proj_w', d * int(slot_size)), ('in_proj_b', d), ('cls', d)]
+    if learnable_pe:
+        out.append(('enc_t_pe', int(T) * d))
+    sizes = (d, d, 3 * d * d, 3 * d, d * d, d, d, d, f * d, f, d * f, d)
+    for i in range(int(num_layers)):
+        out += [(f'layers.{i}.{n}', k) for n, k in zip(PHYRE_LAYER_FIELDS, sizes)]
+    return out + [('mlp_w1', d * d), ('mlp_b1', d), ('mlp_w2', d), ('mlp_b2', 1)]
+
+
+def _phyre_train_args(model, slots, sel, video_index):
+    import ctypes as C
+    slots, T_all = _readout_slots(slots, None)
+    V, _, N, Cs = slots.shape
+    if (N, Cs) != (model.num_slots, model.slot_size):
+        raise ValueError(f'slotformer_amd: the readout takes slots [V, T, {model.num_slots}, {model.slot_size}], got {tuple(slots.shape)}')
+    sel = [int(s) for s in sel]
+    video_index = _index32(video_index, slots.device)
+    B = V if video_index is None else video_index.numel()
+    return slots, T_all, V, sel, (C.c_int * max(len(sel), 1))(*sel), video_index, B
+
+
+def phyre_readout_train_workspace_bytes(model, B, T):
+    """Bytes of the workspace the two training calls share for a batch of B (`sf_phyre_readout_train_workspace_bytes`; 0: unsupported)."""
+    import ctypes as C
+    return int(lib().sf_phyre_readout_train_workspace_bytes(C.byref(model), int(B), int(T)))
+
+
+def phyre_readout_train_fwd(model, slots, sel, video_index=None, p=0., seed=0, want_gates=False, ws=None):
+    """The training forward of the PHYRE readout (`sf_phyre_readout_train_fwd_f32`: the token rows, ONE launch per layer with dropout at its four
+    sites, the head).  model: an `sf_phyre_readout_model` descriptor (train.phyre_readout_model); slots / sel / video_index as
+    `phyre_readout_fwd`.  p, seed: the dropout rate and the seed of its masks (train.dropout_keep_mask restates them).  ws: a uint8 workspace to
+    reuse (a larger one is fine), else one is allocated.  -> (logits [B], ws, gates, head_gates): the workspace holds what the backward reads;
+    with want_gates the ReLU decisions the forward took, uint8 [num_layers, B * L, 512] and [B, 128], else None."""
+    import ctypes as C
+    slots, T_all, V, sel, sel_c, video_index, B = _phyre_train_args(model, slots, sel, video_index)
+    dev, T = slots.device, len(sel)
+    nbytes = phyre_readout_train_workspace_bytes(model, B, T)
+    if nbytes == 0:
+        raise NotImplementedError(f'slotformer_amd: the PHYRE readout has no training kernel for these shapes: {PHYRE_LIMITS}')
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L = 1 + T * model.num_slots
+    logits = torch.empty(B, dtype=torch.float32, device=dev)
+    gates = torch.empty(model.num_layers, B * L, model.ffn_dim, dtype=torch.uint8, device=dev) if want_gates else None
+    head_gates = torch.empty(B, model.d_model, dtype=torch.uint8, device=dev) if want_gates else None
+    check(lib().sf_phyre_readout_train_fwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), sel_c, B, T,
+                                               float(p), int(seed), _p(logits), _p(gates), _p(head_gates), ws.data_ptr(), ws.numel(), _stream()))
+    return logits, ws, gates, head_gates
+
+
+def phyre_readout_train_bwd(model, slots, sel, g, ws, video_index=None, p=0., seed=0, learnable_pe=False, out=None):
+    """Every parameter gradient of the PHYRE readout from g [B] = dL/dlogit and the workspace of `phyre_readout_train_fwd` (same slots, sel,
+    video_index, p, seed): `sf_phyre_readout_train_bwd_f32`, ONE launch per layer for the activation gradients.  The gradients are WRITTEN into one
+    flat float32 buffer in `phyre_grad_layout` order (out: a caller's buffer of that size, e.g. `FlatAdam.grad`); learnable_pe: whether enc_t_pe
+    has a slot in it.  -> the flat buffer."""
+    import ctypes as C
+    from ._lib import sf_phyre_readout_grads, sf_tfm_layer_grads
+    slots, T_all, V, sel, sel_c, video_index, B = _phyre_train_args(model, slots, sel, video_index)
+    T = len(sel)
+    layout = phyre_grad_layout(model.slot_size, T, model.num_layers, learnable_pe, model.d_model, model.ffn_dim)
+    n = sum(k for _, k in layout)
+    flat = torch.empty(n, dtype=torch.float32, device=slots.device) if out is None else out
+    if not (torch.is_tensor(flat) and flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous() and flat.numel() == n):
+        raise ValueError(f'slotformer_amd: the PHYRE readout gradient buffer holds {n} contiguous float32 elements on the device')
+    g = g.detach().float().reshape(B).contiguous()
+    gs = sf_phyre_readout_grads()
+    arr = (sf_tfm_layer_grads * model.num_layers)()
+    off = 0
+    for name, k in layout:
+        ptr = flat.data_ptr() + 4 * off
+        if name.startswith('layers.'):
+            _, i, field = name.split('.')
+            setattr(arr[int(i)], field, ptr)
+        else:
+            setattr(gs, name, ptr)
+        off += k
+    gs.layers = C.cast(arr, C.POINTER(sf_tfm_layer_grads))
+    check(lib().sf_phyre_readout_train_bwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), sel_c, B, T,
+                                               _p(g), C.byref(gs), float(p), int(seed), ws.data_ptr(), ws.numel(), _stream()))
+    return flat
+
+
 def phyre_auccess_ranks(conf, status):
     """first_rank [tasks] int32 (`sf_phyre_auccess_f32`): for every task the number of valid actions (status != 0) whose confidence lies strictly
     above the best solved action's (status > 0) -- `actions` when no action of the task is solved.  conf [tasks, actions] float32 and status

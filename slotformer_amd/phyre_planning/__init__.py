@@ -1,10 +1,12 @@
-"""slotformer.phyre_planning counterpart: build_model, the frame table the planning driver feeds the classifier with, and AUCCESS
-(test_phyre_planning.py: collect_results) from a table of confidences.  Inference and planning only; the driver itself is
-`harness.phyre_plan`."""
+"""slotformer.phyre_planning counterpart: build_model, the two drivers around the classifier -- `fit` (the reference's nerv training run of
+readout_phyre_params-fold0.py) and `evaluate` -- on a device-resident slots tensor, the frame table the planning driver feeds the classifier
+with, and AUCCESS (test_phyre_planning.py: collect_results) from a table of confidences.  The planning driver itself is `harness.phyre_plan`."""
 import numpy as np
 import torch
 
 from .models import build_model, PHYREReadout
+from .models.readout import ACC_THRESHS
+from ..physion_vqa import batch_schedule   # (one rule for the batches of both readouts)
 from .. import ops
 
 # phyre.SimulationStatus, as the simulation caches store it
@@ -20,7 +22,103 @@ def build_dataset(params, *a, **k):
 
 
 def build_method(*a, **k):
-    raise NotImplementedError('the nerv trainer is outside the hot path (SURVEY.md 2.1 row 12); the training kernels of PHYREReadout are not built')
+    raise NotImplementedError('the nerv trainer is outside the hot path (SURVEY.md 2.1 row 12); the training kernels of PHYREReadout are reached through '
+                              'phyre_planning.fit / train.phyre_readout_with_grad; a trainer object is not built')
+
+
+def step_seed(seed, step):
+    """The dropout seed of optimiser step `step` of a `fit` run seeded with `seed`: the run's seed in the high word, the step in the low one."""
+    return ((int(seed) & 0xffffffff) << 32) | (int(step) & 0xffffffff)
+
+
+def fit(readout, slots, labels, epochs, batch_size=256, lr=1e-3, seed=0, warmup_steps_pct=0.1, sel=None):
+    """Train `readout` in place on slots [V, T_all, N, C] and labels [V] that live on the device (readout_phyre_params-fold0.py: Adam at 1e-3,
+    10 % linear warm-up then cosine decay to 0, batches of 256, dropout 0.1 from nn.TransformerEncoderLayer).  A batch is picked by `video_index`
+    (`physion_vqa.batch_schedule` on `seed`), never gathered; a step is the training forward (one launch per layer), the score (loss and
+    dL/dlogit), the backward (one launch per layer for the activation gradients) -- which writes every gradient straight into the optimiser's flat
+    bucket -- and one `FlatAdam` launch.  The dropout masks of step k come from `step_seed(seed, k)`.  Nothing is uploaded, downloaded or waited
+    for inside an epoch, and everything is deterministic: one seed, one result, bit for bit.  sel: the frame table (default readout.sel_slots).
+    Leaves the module in eval() with its cached plans dropped, so the next `logits_of` sees the trained weights.  Returns the mean loss of every
+    epoch, [epochs] on the device."""
+    from .. import plans
+    from ..train import FlatAdam, warmup_cosine_lr, phyre_readout_parameters, phyre_readout_model, phyre_learnable_pe
+    if not torch.is_tensor(slots) or slots.dim() != 4 or tuple(slots.shape[2:]) != (readout.num_slots, readout.slot_size):
+        raise ValueError(f'slotformer_amd.phyre_planning: slots are a [V, T, {readout.num_slots}, {readout.slot_size}] tensor, got '
+                         f'{tuple(getattr(slots, "shape", ()))}')
+    dev = slots.device
+    V, T_all = slots.shape[:2]
+    labels = torch.as_tensor(labels, device=dev).float().flatten()
+    if labels.numel() != V:
+        raise ValueError(f'slotformer_amd.phyre_planning: {V} videos, {labels.numel()} labels')
+    sel = list(readout.sel_slots) if sel is None else [int(s) for s in sel]
+    if len(sel) != readout.T or any(s < -1 or s >= T_all for s in sel):
+        raise IndexError(f'slotformer_amd.phyre_planning: frame table {sel} ({readout.T} entries of -1 or a frame number) on slots of {T_all} frames')
+    sched = batch_schedule(V, epochs, batch_size, seed)   # (raises for batch_size < 1; its indices are a permutation of range(V): in range)
+    total = sum(len(e) for e in sched)
+    if not (slots.is_cuda and readout.CLS.is_cuda):   # (what the host can check comes first, so that it is checked without a device too)
+        raise RuntimeError('slotformer_amd: PHYREReadout trains on a HIP device only; there is no CPU fallback')
+    params = phyre_readout_parameters(readout)
+    for p in params:
+        p.requires_grad_(True)
+    opt = FlatAdam(params, lr=lr)
+    model, keep = phyre_readout_model(readout)   # (after FlatAdam: the parameters now live in its bucket)
+    p_drop = float(readout.transformer_encoder.layers[0].dropout.p)
+    pe = phyre_learnable_pe(readout)
+    batches = [[idx.to(dev) for idx in e] for e in sched]             # every index tensor goes up before the first step
+    targets = [[labels[idx.long()] for idx in e] for e in batches]
+    warm = int(round(float(warmup_steps_pct) * total))
+    step, losses, ws = 0, [], None
+    readout.train()
+    with torch.no_grad():
+        for e_idx, e_lab in zip(batches, targets):
+            epoch_loss = torch.zeros((), dtype=torch.float32, device=dev)
+            for idx, lab in zip(e_idx, e_lab):
+                s = step_seed(seed, step)
+                logits, ws, _, _ = ops.phyre_readout_train_fwd(model, slots, sel, video_index=idx, p=p_drop, seed=s, ws=ws)
+                loss, g, _, _ = ops.physion_readout_score(logits, lab)
+                ops.phyre_readout_train_bwd(model, slots, sel, g, ws, video_index=idx, p=p_drop, seed=s, learnable_pe=pe, out=opt.grad)
+                opt.lr = warmup_cosine_lr(step, total, warm, lr, 0.)
+                opt.step(gathered=True)
+                step += 1
+                epoch_loss += loss[0] * (idx.numel() / V)
+            losses.append(epoch_loss)
+    del keep
+    readout.eval()
+    plans.invalidate(readout)
+    return torch.stack(losses) if losses else torch.zeros(0, device=dev)
+
+
+@torch.no_grad()
+def evaluate(readout, slots, labels, batch_size=512):
+    """calc_eval_loss over a whole set: slots [V, T_all, N, C] and labels [V] on the device -> {'loss', 'acc_0.10', ..., 'acc_0.90'} (floats).
+    Every batch is the eval-mode forward and one score launch that adds its hits to int32 counters on the device; the loss sum and the counts
+    come back in ONE download at the end."""
+    if int(batch_size) < 1:
+        raise ValueError(f'slotformer_amd.phyre_planning: batch_size >= 1, got {batch_size!r}')
+    V = slots.shape[0]
+    if torch.as_tensor(labels).numel() != V:
+        raise ValueError(f'slotformer_amd.phyre_planning: {V} videos, {torch.as_tensor(labels).numel()} labels')
+    if not (torch.is_tensor(slots) and slots.is_cuda):
+        raise RuntimeError('slotformer_amd: PHYREReadout runs on a HIP device only; there is no CPU fallback')
+    dev = slots.device
+    labels = torch.as_tensor(labels, device=dev).float().flatten()
+    was_training = readout.training
+    readout.eval()
+    counts = None
+    loss_sum = torch.zeros(1, dtype=torch.float32, device=dev)
+    try:
+        for s in range(0, V, int(batch_size)):
+            idx = torch.arange(s, min(s + int(batch_size), V), dtype=torch.int32, device=dev)
+            logits = readout.logits_of(slots, video_index=idx)[0]
+            loss, _, counts, _ = ops.physion_readout_score(logits, labels[s:s + idx.numel()], threshs=ACC_THRESHS, want_grad=False, counts=counts)
+            loss_sum += loss * (idx.numel() / V)
+    finally:
+        readout.train(was_training)
+    host = torch.cat([loss_sum, counts[0].float()]).cpu()
+    out = {'loss': float(host[0])}
+    for i, thresh in enumerate(ACC_THRESHS):
+        out[f'acc_{thresh:.2f}'] = float(host[1 + i]) / V
+    return out
 
 
 def frame_table(sel_slots, reference_indexing=True):

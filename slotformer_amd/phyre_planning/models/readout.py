@@ -6,7 +6,8 @@ holds the parameters under the reference's state-dict names (`CLS`, `in_proj.*`,
 `cls_mlp.2.*`); the forward is three launches of csrc/phyre_readout.hip and csrc/layer_tok128.hip (`sf_phyre_readout_fwd_f32`): the token rows
 straight from the slots tensor (no gathered copy), all layers at once, the head.
 
-Inference only: the training kernels of this readout are not built, and `forward` says so when the module is in training mode."""
+Training runs through `phyre_planning.fit` / `train.phyre_readout_with_grad` (csrc/phyre_readout_train.hip: one launch per layer in each
+direction); a differentiable `Module.forward` is not built, and `forward` says so when the module is in training mode."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -50,8 +51,8 @@ class PHYREReadout(BaseModel):
     def _check(self, slots):
         """An uncovered readout_dict constructs (its checkpoints load); it is refused at first use."""
         if self.training:
-            raise NotImplementedError('slotformer_amd: PHYREReadout is inference-only -- the training kernels of this readout (backward, fit) are '
-                                      'not built; call .eval() first')
+            raise NotImplementedError('slotformer_amd: the training kernels of this readout run through phyre_planning.fit / '
+                                      'train.phyre_readout_with_grad; a differentiable Module.forward is not built -- call .eval() first')
         if not self.shape_ok():
             rd = self.readout_dict
             raise NotImplementedError(f'PHYREReadout(num_slots={self.num_slots}, slot_size={self.slot_size}, sel_slots={list(self.sel_slots)}, '

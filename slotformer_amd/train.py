@@ -1220,8 +1220,11 @@ class FlatAdam:
         # The kernel wrote the parameters through a raw pointer: tell torch (and, through `_version`, the plan cache
         # of plans.py, which is keyed on (data_ptr, _version)) that their contents changed -- otherwise derived / packed
         # weight copies built before this step would keep being served.
-        for p in self.params:
-            torch._C._increment_version(p)
+        try:
+            torch._C._increment_version(self.params)   # (one call for the list: a call per tensor costs the host ~80 us each)
+        except TypeError:   # a torch whose _increment_version takes one tensor
+            for p in self.params:
+                torch._C._increment_version(p)
 
 
     def state_dict(self):
@@ -1321,7 +1324,7 @@ class amp_bf16:
 
 
 def dropout_keep_mask(seed, step, layer, site, numel, p):
-    """Host restatement of the library's dropout mask (rollout_train.hip: sf_keep / site_seed) for tests and tools:
+    """Host restatement of the library's dropout mask (csrc/dropout_mask.h: sf_keep / site_seed) for tests and tools:
     bool [numel], True = kept.  site: 0 attention weights, 1 attention output, 2 FFN hidden, 3 FFN output."""
     import numpy as np
 
@@ -1398,3 +1401,101 @@ def readout_with_grad(readout, slots, video_index=None, video_len=None, return_s
 def readout_loss(logits, labels):
     """F.binary_cross_entropy_with_logits(logits, labels) (readout.py:81-87) on the score kernel, differentiable in `logits`."""
     return _ReadoutLoss.apply(logits, labels)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# PHYRE task-success readout (phyre_planning/models/readout.py) under autograd: ONE node over the two calls of
+# csrc/phyre_readout_train.hip -- a layer is one launch forward and one launch backward
+# ---------------------------------------------------------------------------------------------------------------------
+def phyre_learnable_pe(readout):
+    return bool(isinstance(readout.enc_t_pe, torch.nn.Parameter) and readout.enc_t_pe.requires_grad)
+
+
+def phyre_readout_parameters(readout):
+    """The trainable leaves of a PHYREReadout in bucket order -- the order `ops.phyre_grad_layout` lays the gradients out in: in_proj, CLS, enc_t_pe
+    (when learnable), every layer's leaves, cls_mlp.  (cls_mlp.2.bias, the one leaf of odd size, comes last: every other leaf of a flat bucket
+    over this list starts 16-byte aligned.)"""
+    ps = [readout.in_proj.weight, readout.in_proj.bias, readout.CLS]
+    if phyre_learnable_pe(readout):
+        ps.append(readout.enc_t_pe)
+    for layer in readout.transformer_encoder.layers:
+        ps += [_leaf(layer, n) for n in _LAYER_LEAVES]
+    return ps + [readout.cls_mlp[0].weight, readout.cls_mlp[0].bias, readout.cls_mlp[2].weight, readout.cls_mlp[2].bias]
+
+
+def phyre_readout_model(readout):
+    """The `sf_phyre_readout_model` descriptor of a PHYREReadout on the device: raw pointers to its float32 parameters in their torch layouts (no
+    packed copy: the training calls split what they need every step).  -> (struct, keep): hold `keep` while the struct is in use.  The pointers
+    follow the parameters' storage, so build it after a FlatAdam has re-pointed them at its bucket."""
+    from ._lib import sf_phyre_readout_model, sf_tfm_layer
+    if not readout.shape_ok():
+        from . import ops
+        raise NotImplementedError(f'PHYREReadout({readout.readout_dict!r}) has no training kernel: {ops.PHYRE_LIMITS}')
+    keep = []
+
+    def dp(t):
+        t = t.detach()
+        if not t.is_cuda:
+            raise RuntimeError('slotformer_amd: PHYREReadout trains on a HIP device only; there is no CPU fallback')
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('slotformer_amd: PHYREReadout trains on contiguous float32 parameters')
+        keep.append(t)
+        return t.data_ptr()
+
+    rd = readout.readout_dict
+    m = sf_phyre_readout_model()
+    m.num_slots, m.slot_size, m.d_model, m.num_heads, m.ffn_dim, m.num_layers = (readout.num_slots, readout.slot_size, rd['d_model'], rd['num_heads'],
+                                                                                 rd['ffn_dim'], rd['num_layers'])
+    m.in_proj_w, m.in_proj_b, m.enc_t_pe, m.cls = dp(readout.in_proj.weight), dp(readout.in_proj.bias), dp(readout.enc_t_pe), dp(readout.CLS)
+    arr = (sf_tfm_layer * rd['num_layers'])()
+    for i, layer in enumerate(readout.transformer_encoder.layers):
+        for leaf, field in zip(_LAYER_LEAVES, _LAYER_FIELDS):
+            setattr(arr[i], field, dp(_leaf(layer, leaf)))
+    m.layers = C.cast(arr, C.POINTER(sf_tfm_layer))
+    m.mlp_w1, m.mlp_b1 = dp(readout.cls_mlp[0].weight), dp(readout.cls_mlp[0].bias)
+    m.mlp_w2, m.mlp_b2 = dp(readout.cls_mlp[2].weight), dp(readout.cls_mlp[2].bias)
+    keep.append(arr)
+    return m, keep
+
+
+class _PhyreReadout(torch.autograd.Function):
+    """logits [B] = PHYREReadout(slots) as a single autograd node; the slots are frozen inputs, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, readout, slots, sel, video_index, p, seed, grad_out, *params):
+        from . import ops
+        model, keep = phyre_readout_model(readout)
+        logits, ws, _, _ = ops.phyre_readout_train_fwd(model, slots, sel, video_index=video_index, p=p, seed=seed)
+        ctx.keep = (readout, model, keep, slots, sel, video_index, p, seed, grad_out, ws, params)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        readout, model, keep, slots, sel, video_index, p, seed, grad_out, ws, params = ctx.keep
+        flat = ops.phyre_readout_train_bwd(model, slots, sel, g, ws, video_index=video_index, p=p, seed=seed, learnable_pe=phyre_learnable_pe(readout),
+                                           out=grad_out)
+        ctx.keep = None
+        if grad_out is not None:   # the caller's bucket holds them: nothing for autograd to accumulate
+            return (None, ) * (7 + len(params))
+        readout.last_grad_bucket = flat
+        return (None, ) * 7 + tuple(g_ if ctx.needs_input_grad[7 + i] else None for i, g_ in enumerate(_split(flat, params)))
+
+
+def phyre_readout_with_grad(readout, slots, sel=None, video_index=None, p=None, seed=None, grad_out=None):
+    """PHYREReadout.forward under autograd (readout.py: in_proj + temporal position row, CLS, the pre-LN encoder with its dropout, cls_mlp on the CLS
+    row): slots [V, T_all, N, C] on the device -> logits [B], differentiable in every parameter.  One node over `sf_phyre_readout_train_fwd_f32` /
+    `sf_phyre_readout_train_bwd_f32`.  sel: the frame of every token group (default readout.sel_slots; -1: a frame of zeros); video_index [B]:
+    picks the batch out of the slots without a gather.  p: the dropout rate -- default the layers' own when readout.training, else 0; seed: the
+    seed of the masks (default a fresh one).  grad_out: a flat fp32 buffer laid out as FlatAdam's bucket over phyre_readout_parameters(readout)
+    (`FlatAdam.grad`): the backward writes the gradients there -- then step with `FlatAdam.step(gathered=True)` -- and leaves `.grad` alone."""
+    if not (torch.is_tensor(slots) and slots.is_cuda):
+        raise RuntimeError('slotformer_amd: the slots must live on a HIP device; there is no CPU fallback')
+    if p is None:
+        p = float(readout.transformer_encoder.layers[0].dropout.p) if readout.training else 0.0
+    if seed is None:
+        seed = _new_seed() if p > 0 else 0
+    sel = list(readout.sel_slots) if sel is None else [int(s) for s in sel]
+    if len(sel) != readout.T:
+        raise ValueError(f'PHYREReadout: the frame table holds {readout.T} entries (len(sel_slots)), got {len(sel)}')
+    return _PhyreReadout.apply(readout, slots, sel, video_index, float(p), int(seed), grad_out, *phyre_readout_parameters(readout))
