@@ -448,7 +448,12 @@ int sf_slate_attention_f32(const float* q, const float* k, const float* v, float
 size_t sf_slate_attention_bwd_workspace_bytes(int B, int Lq, int num_heads);
 /* The same pair with dropout on the attention WEIGHTS (the nn.Dropout inside steve_transformer.py's MultiHeadAttention, active
  * in train() mode): masks are a pure function of (seed, sequence, head, query, key).  The forward also returns the row
- * log-sum-exp lse [B][H][Lq], which the backward takes instead of recomputing it (lse == NULL: recompute). */
+ * log-sum-exp lse [B][H][Lq], which the backward takes instead of recomputing it (lse == NULL: recompute).
+ * sf_slate_attention_train_bwd_f32 takes head_dim = every multiple of 4 up to 64 (the forward every even one) and reads q and
+ * d_out with 16-byte loads: q, d_out, ldq, ldo, q_bs and o_bs must be multiples of 16 bytes (4 floats), or the call is refused
+ * before anything is launched.  k and v may sit anywhere: the 48-wide split-bf16 kernel (32 < head_dim <= 48) is chosen only when
+ * k, v, ldk, ldv, k_bs and v_bs are multiples of 16 bytes too, otherwise the generic kernel reads them float by float.  dq is
+ * cleared over the head columns of its Lq rows per sequence only: columns and rows next to them are not written. */
 int sf_slate_attention_train_fwd_f32(const float* q, const float* k, const float* v, float* out, float* lse, int ldq, int ldk,
                                      int ldv, int ldo, long long q_bs, long long k_bs, long long v_bs, long long o_bs, int B,
                                      int Lq, int Lk, int num_heads, int head_dim, int causal, float dropout_p,

@@ -760,6 +760,7 @@ size_t sf_slate_attention_bwd_workspace_bytes(int B, int Lq, int num_heads) {
 
 // Adjoint of sf_slate_attention_strided_f32: dq / dk / dv have the layouts of q / k / v, d_out and out the layout of out.
 // dq must not alias q (it is zeroed here and accumulated with float atomics: its low bits depend on the arrival order).
+// q and d_out, their rows and their batches must start on 16-byte boundaries (refused otherwise); k and v need not.
 int sf_slate_attention_train_bwd_f32(const float* q, const float* k, const float* v, const float* out, const float* d_out,
                                      const float* lse, float* dq, float* dk, float* dv, int ldq, int ldk, int ldv, int ldo,
                                      long long q_bs, long long k_bs, long long v_bs, long long o_bs, int B, int Lq, int Lk,
@@ -770,6 +771,9 @@ int sf_slate_attention_train_bwd_f32(const float* q, const float* k, const float
   SF_REQUIRE(B > 0 && Lq > 0 && Lk > 0 && num_heads > 0, "bad sizes");
   SF_REQUIRE(head_dim >= 4 && head_dim <= 64 && head_dim % 4 == 0, "head_dim must be a multiple of 4, at most 64");
   SF_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0, "rows must be 16-byte aligned");
+  // every kernel below reads q and d_out with 16-byte loads from base + b * bs + row * ld (+ h * head_dim)
+  SF_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)d_out % 16 == 0, "q and d_out must be 16-byte aligned");
+  SF_REQUIRE(q_bs % 4 == 0 && o_bs % 4 == 0, "batch strides of q and d_out must be 16-byte aligned");
   SF_REQUIRE(!causal || Lq == Lk, "causal attention needs Lq == Lk");
   SF_REQUIRE(ws_bytes >= sf_slate_attention_bwd_workspace_bytes(B, Lq, num_heads), "workspace too small");
   SF_REQUIRE(q_bs >= (long long)(Lq - 1) * ldq + num_heads * head_dim, "dq is cleared over whole batches: q_bs too small");
@@ -811,7 +815,9 @@ int sf_slate_attention_train_bwd_f32(const float* q, const float* k, const float
   }
   const bool bf3 = sf_get_precision() >= 1;
   constexpr bool bwd48 = true;
-  if (bf3 && head_dim > 32 && head_dim <= 48 && bwd48 && ldk % 4 == 0 && ldv % 4 == 0) {
+  // the 48-wide kernel reads k and v with 16-byte loads too; the generic kernel reads them float by float
+  const bool kv16 = ldk % 4 == 0 && ldv % 4 == 0 && k_bs % 4 == 0 && v_bs % 4 == 0 && (uintptr_t)k % 16 == 0 && (uintptr_t)v % 16 == 0;
+  if (bf3 && head_dim > 32 && head_dim <= 48 && bwd48 && kv16) {
     constexpr size_t lds48 = ((size_t)3 * 64 * 52 + 2 * 64 * 68 + 128) * sizeof(float);
     static const bool v1 = sf_dbg("sab1") != 0;   // (probes: the packed-word kernel this one replaced)
     hipLaunchKernelGGL((slate_attn_stats_kernel<64, true>), g1, dim3(256), lds1, st, a, head_dim);
