@@ -81,7 +81,9 @@ int sf_conv2d_nchw_in_grouped_f32(const float* img, long long frame_stride, int 
 
 /* Encoder convs i > 0 (savi.py:231-239): stride 1, padding ks/2, NHWC in -> NHWC out,
  * w_packed [Cout,ks,ks,Cin] (sf_pack_conv_weight_f32); `add` as above (used for the soft
- * position embedding, utils.py:60-63 / savi.py:370). */
+ * position embedding, utils.py:60-63 / savi.py:370).
+ * relu: 0 none, 1 ReLU, 2 = the backward-data form of training: `add` [F,H,W,Cout] is then laid out like `out` (one mask PER FRAME, not a table) and
+ * gates it, out = add > 0 ? conv + bias : +0.0.  The same three values hold for sf_conv5x5_frag_f32 below. */
 int sf_conv2d_nhwc_f32(const float* in, const float* w_packed, const float* bias, const float* add, float* out,
                        int F, int H, int W, int Cin, int Cout, int ks, int relu, void* stream);
 int sf_pack_conv_weight_f32(const float* w_oihw, float* w_ohwi, int Cout, int Cin, int ks, void* stream);
@@ -1298,6 +1300,41 @@ int sf_savi_decode_train_fwd_f32(const sf_savi_decoder* m, const float* slots, f
 int sf_savi_decode_train_bwd_f32(const sf_savi_decoder* m, const float* const* deconv_w_bwd, const float* d_recon,
                                  float* d_slots, const float* pos_grid, const sf_savi_decoder_grads* g, int F, void* ws,
                                  size_t ws_bytes, void* stream);
+
+/* Kernel-level entry points of the two training paths above (sf_savi_features_train_bwd_f32, sf_savi_decode_train_bwd_f32), one launch group at a
+ * time, for tests against plain references.  Each is the block the module path itself calls; none adds arithmetic.
+ *
+ * Weight gradient of a 5 x 5 "same" convolution (s = 1: A = dY, X = the layer input) or of a transposed convolution of stride s (A = the layer
+ * input, X = dY on the s times finer grid):  dW[n][k][ky][kx] = sum over (f, y, x) of A[f, y, x, n] * X[f, y*s + ky - 2, x*s + kx - 2, k], zero
+ * outside the X grid.  A [rows, CA] NHWC on an H x W grid, X [F, Hx, Wx, 64] NHWC, dW [CA, 64, 5, 5] (the torch layout of either weight).
+ * partial: scratch of `partial_floats` floats, at most sf_conv_wgrad_partial_floats(CA, ks); every float of it that the reduction reads is written
+ * first.  Refused before any launch: ks != 5, CA % 64 != 0, rows != F * H * W, Hx != H * s or Wx != W * s, a partial buffer smaller than the call's
+ * row splits need, and an A, X or partial that is not 16-byte aligned (the kernels load four floats at a time). */
+size_t sf_conv_wgrad_partial_floats(int CA, int ks);
+int sf_conv_wgrad_f32(const float* A, int CA, int F, int H, int W, const float* X, int Hx, int Wx, int s, int ks, long long rows, float* dW,
+                      float* partial, size_t partial_floats, void* stream);
+/* Backward-data pass of a convolution layer: Conv2d(ks, stride, padding ks/2) of the gradient `in` [F,Hin,Win,Cin] NHWC with w_packed
+ * [Cout][ks][ks][Cin] -> out [F,Hin/stride,Win/stride,Cout], no bias; relu_mask (optional, laid out like out): out = relu_mask > 0 ? conv : 0.
+ * With w_packed = sf_pack_conv_weight_f32(ConvTranspose2d weight) this is the adjoint of sf_conv_transpose2d_nhwc_f32; with
+ * sf_pack_conv_bwd_weight_f32(Conv2d weight) and stride 1 the adjoint of sf_conv2d_nhwc_f32 (= that function with relu = 2). */
+int sf_conv2d_nhwc_bwd_data_f32(const float* in, const float* w_packed, const float* relu_mask, float* out, int F, int Hin, int Win, int Cin,
+                                int Cout, int ks, int stride, void* stream);
+/* w_bwd[ci][ky][kx][co] = w_oihw[co][ci][ks-1-ky][ks-1-kx]: the packed weight of the backward-data pass of a "same" Conv2d. */
+int sf_pack_conv_bwd_weight_f32(const float* w_oihw, float* w_bwd, int Cout, int Cin, int ks, void* stream);
+/* conv0's weight gradient dW [64,3,5,5] from the NCHW image (frame f at img + f * frame_stride floats; 64 x 64 at stride 1 or 128 x 128 at stride
+ * 2) and dY [F*4096, 64]: im2col with K = 75 padded to 128, the TN contraction of sf_linear_bwd_f32, the 75 live columns. */
+size_t sf_conv_first_wgrad_workspace_bytes(int F);
+int sf_conv_first_wgrad_f32(const float* img, long long frame_stride, int resolution, const float* dY, int F, float* dW, void* ws,
+                            size_t ws_bytes, void* stream);
+/* SoftPositionEmbed gradients from d [F,HW,C] (the table grid W^T + b is added to every frame): dw [C,4], db [C]; grid [HW,4]; dtab: scratch
+ * [HW*C], holds the frame sum of d on return. */
+int sf_pos_dense_grad_f32(const float* d, int F, int HW, int C, const float* grid, float* dw, float* db, float* dtab, void* stream);
+/* Head block of the decoder backward: dec [F*N,HW,4] (rgb | mask logit), d_recon [F,3,HW], act [F*N*HW,Cl] (post-ReLU output of the last
+ * transposed conv), out_w [4,Cl] -> d_dec [F*N,HW,4], d_act [F*N*HW,Cl] = act > 0 ? d_dec . out_w : 0, and d_out_w [4,Cl] / d_out_b [4] (either
+ * may be NULL).  Cl a multiple of 4, at most 64; dec, d_dec, act 16-byte aligned. */
+size_t sf_savi_decode_head_bwd_workspace_bytes(int Cl);
+int sf_savi_decode_head_bwd_f32(const float* dec, const float* d_recon, const float* act, const float* out_w, float* d_dec, float* d_act,
+                                float* d_out_w, float* d_out_b, int F, int N, int HW, int Cl, void* ws, size_t ws_bytes, void* stream);
 
 
 /* ---- K/V producer (SURVEY.md 8(b2) sf_kv_producer_*) ---------------------------------------- */

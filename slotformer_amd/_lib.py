@@ -257,6 +257,15 @@ SIGNATURES = {
     'sf_savi_decode_train_fwd_f32': (I, [C.POINTER(sf_savi_decoder), FP, FP, FP, FP, I, VP, SZ, VP]),
     'sf_savi_decode_train_bwd_f32': (I, [C.POINTER(sf_savi_decoder), C.POINTER(C.c_void_p), FP, FP, FP, C.POINTER(sf_savi_decoder_grads),
                                          I, VP, SZ, VP]),
+    'sf_conv_wgrad_partial_floats': (SZ, [I, I]),
+    'sf_conv_wgrad_f32': (I, [FP, I, I, I, I, FP, I, I, I, I, LL, FP, FP, SZ, VP]),
+    'sf_conv2d_nhwc_bwd_data_f32': (I, [FP, FP, FP, FP, I, I, I, I, I, I, I, VP]),
+    'sf_pack_conv_bwd_weight_f32': (I, [FP, FP, I, I, I, VP]),
+    'sf_conv_first_wgrad_workspace_bytes': (SZ, [I]),
+    'sf_conv_first_wgrad_f32': (I, [FP, LL, I, FP, I, FP, VP, SZ, VP]),
+    'sf_pos_dense_grad_f32': (I, [FP, I, I, I, FP, FP, FP, FP, VP]),
+    'sf_savi_decode_head_bwd_workspace_bytes': (SZ, [I]),
+    'sf_savi_decode_head_bwd_f32': (I, [FP, FP, FP, FP, FP, FP, FP, FP, I, I, I, I, VP, SZ, VP]),
     'sf_savi_features_train_workspace_bytes': (SZ, [C.POINTER(sf_savi_features), I]),
     'sf_savi_features_train_fwd_f32': (I, [C.POINTER(sf_savi_features), FP, LL, I, FP, VP, SZ, VP]),
     'sf_savi_features_train_bwd_f32': (I, [C.POINTER(sf_savi_features), FP, LL, FP, C.POINTER(sf_savi_features_grads), I, VP, SZ, VP]),

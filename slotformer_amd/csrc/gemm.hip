@@ -809,6 +809,12 @@ int sf_conv2d_nhwc_strided_ex(const float* in, const float* w_packed, const floa
 }
 
 extern "C" {
+// The strided convolution above as the training code calls it: no bias, no activation, optional ReLU mask laid out like `out`.
+int sf_conv2d_nhwc_bwd_data_f32(const float* in, const float* w_packed, const float* relu_mask, float* out, int F, int Hin, int Win, int Cin,
+                                int Cout, int ks, int stride, void* stream) {
+  return sf_conv2d_nhwc_strided_ex(in, w_packed, nullptr, out, F, Hin, Win, Cin, Cout, ks, stride, 0, (hipStream_t)stream, relu_mask);
+}
+
 // ConvTranspose2d(k, stride, padding=k/2, output_padding=stride-1): NHWC in [F,Hin,Win,Cin] -> NHWC out
 // [F,Hin*stride,Win*stride,Cout]; w_packed [Cout][ks][ks][Cin] = torch weight[Cin,Cout,k,k].permute(1,2,3,0).
 int sf_conv_transpose2d_nhwc_f32(const float* in, const float* w_packed, const float* bias, float* out, int F,

@@ -80,6 +80,32 @@ __global__ __launch_bounds__(256) void head_grad_reduce_kernel(const float* __re
   out[i] = a;
 }
 
+// The head block of the backward: d_recon [F,3,HW] -> d_dec [F*N,HW,4] (recombination + softmax adjoint), the 1x1 head's weight [4,Cl] and bias [4]
+// gradients (optional), and d_act [F*N*HW,Cl] = d_dec . W_out gated by act > 0 (the ReLU of the last transposed conv; the GEMM core wants the
+// transpose of W_out [4,Cl] as its weight operand).  wout_t [4*Cl], partial [HEAD_PARTIAL_FLOATS]: scratch.
+static constexpr size_t HEAD_PARTIAL_FLOATS = (size_t)513 * 2 * 256;   // bias column sums, head partials
+static int head_bwd(const float* dec, const float* d_recon, const float* act, const float* out_w, float* d_dec, float* d_act, float* d_out_w,
+                    float* d_out_b, int F, int N, int HW, int Cl, float* wout_t, float* partial, hipStream_t st) {
+  const long long rows = (long long)F * N * HW;
+  {
+    const long long total = (long long)F * HW;
+    hipLaunchKernelGGL(decode_combine_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dec, d_recon, d_dec, F, N, HW);
+    SF_CHECK_LAUNCH();
+  }
+  if (d_out_w) {
+    int G = 512;
+    const int rpg = (int)((rows + G - 1) / G);
+    G = (int)((rows + rpg - 1) / rpg);
+    hipLaunchKernelGGL(head_grad_partial_kernel, dim3(G), dim3(256), 0, st, d_dec, act, partial, rows, rpg, Cl);
+    SF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(head_grad_reduce_kernel, dim3(1), dim3(256), 0, st, partial, d_out_w, G, 4 * Cl);
+    SF_CHECK_LAUNCH();
+  }
+  if (d_out_b) SF_TRY(sf_grad_bias_ex(d_dec, d_out_b, rows, 4, partial, st));
+  SF_TRY(sf_transpose_ex(out_w, wout_t, 4, Cl, st));
+  return sf_linear_masked_ex(d_dec, wout_t, act, 1.f, d_act, rows, Cl, 4, st);
+}
+
 namespace {
 struct DecWs {
   float* act[9];   // act[0]: broadcast input, act[l+1]: output of transposed conv l (post-ReLU)
@@ -113,7 +139,7 @@ DecWs carve(const sf_savi_decoder* m, int F, float* base) {
   w.gb = take(gmax);
   w.wout_t = take((size_t)4 * m->dec_channels[m->dec_layers]);
   {
-    size_t pf = (size_t)513 * 2 * 256;   // bias column sums, head partials
+    size_t pf = HEAD_PARTIAL_FLOATS;
     for (int l = 0; l < m->dec_layers; ++l) {
       const size_t a = sf_conv_wgrad_partial_floats(m->dec_channels[l], m->dec_ks);
       pf = a > pf ? a : pf;
@@ -202,27 +228,9 @@ int sf_savi_decode_train_bwd_f32(const sf_savi_decoder* m, const float* const* d
   hipStream_t st = (hipStream_t)stream;
   const int N = m->num_slots, D = m->slot_size, R = F * N, HW = m->resolution * m->resolution, L = m->dec_layers;
   const int Cl = m->dec_channels[L];
-  {
-    const long long total = (long long)F * HW;
-    hipLaunchKernelGGL(decode_combine_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w.dec, d_recon, w.gb, F, N,
-                       HW);
-    SF_CHECK_LAUNCH();
-  }
-  if (g_out) {   // 1x1 head: weight [4, Cl] and bias [4]
-    const long long rows = (long long)R * HW;
-    int G = 512;
-    const int rpg = (int)((rows + G - 1) / G);
-    G = (int)((rows + rpg - 1) / rpg);
-    hipLaunchKernelGGL(head_grad_partial_kernel, dim3(G), dim3(256), 0, st, w.gb, w.act[L], w.partial, rows, rpg, Cl);
-    SF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(head_grad_reduce_kernel, dim3(1), dim3(256), 0, st, w.partial, g_out->out_w, G, 4 * Cl);
-    SF_CHECK_LAUNCH();
-    SF_TRY(sf_grad_bias_ex(w.gb, g_out->out_b, rows, 4, w.partial, st));
-  }
-  // head: d_act[L] = d_dec . W_out   (W_out [4, Cl]; the GEMM core wants its transpose as the weight operand), gated in the
-  // epilogue by the ReLU of the last transposed conv (mask = its saved output)
-  SF_TRY(sf_transpose_ex(m->out_w, w.wout_t, 4, Cl, st));
-  SF_TRY(sf_linear_masked_ex(w.gb, w.wout_t, w.act[L], 1.f, w.ga, (long long)R * HW, Cl, 4, st));
+  // head / recombination adjoint: w.gb = d_dec, w.ga = the gradient w.r.t. the pre-activation output of the last transposed conv
+  SF_TRY(head_bwd(w.dec, d_recon, w.act[L], m->out_w, w.gb, w.ga, g_out ? g_out->out_w : nullptr, g_out ? g_out->out_b : nullptr, F, N, HW, Cl,
+                  w.wout_t, w.partial, st));
   float* g = w.ga;   // gradient w.r.t. the pre-activation output of layer l
   float* o = w.gb;
   int h = m->resolution;
@@ -252,6 +260,23 @@ int sf_savi_decode_train_bwd_f32(const sf_savi_decoder* m, const float* const* d
   hipLaunchKernelGGL(broadcast_bwd_kernel, dim3(R), dim3(256), 0, st, g, d_slots, m->dec_res * m->dec_res, D);
   SF_CHECK_LAUNCH();
   return 0;
+}
+
+size_t sf_savi_decode_head_bwd_workspace_bytes(int Cl) {
+  if (Cl < 4 || Cl > 64 || Cl % 4) return 0;
+  return (pad64((size_t)4 * Cl) + HEAD_PARTIAL_FLOATS) * sizeof(float) + 256;
+}
+
+int sf_savi_decode_head_bwd_f32(const float* dec, const float* d_recon, const float* act, const float* out_w, float* d_dec, float* d_act,
+                                float* d_out_w, float* d_out_b, int F, int N, int HW, int Cl, void* ws, size_t ws_bytes, void* stream) {
+  SF_REQUIRE(dec && d_recon && act && out_w && d_dec && d_act && ws, "sf_savi_decode_head_bwd_f32: null pointer");
+  SF_REQUIRE(Cl >= 4 && Cl <= 64 && Cl % 4 == 0, "sf_savi_decode_head_bwd_f32: Cl must be a multiple of 4, at most 64");
+  SF_REQUIRE(F >= 1 && N >= 1 && HW >= 1 && (long long)F * N * HW < (1LL << 31), "sf_savi_decode_head_bwd_f32: bad shape");
+  SF_REQUIRE(((uintptr_t)dec & 15) == 0 && ((uintptr_t)d_dec & 15) == 0 && ((uintptr_t)act & 15) == 0,
+             "sf_savi_decode_head_bwd_f32: dec, d_dec and act must be 16-byte aligned");
+  SF_REQUIRE(sf_savi_decode_head_bwd_workspace_bytes(Cl) <= ws_bytes, "sf_savi_decode_head_bwd_f32: workspace too small");
+  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  return head_bwd(dec, d_recon, act, out_w, d_dec, d_act, d_out_w, d_out_b, F, N, HW, Cl, base, base + pad64((size_t)4 * Cl), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -285,15 +285,23 @@ __global__ __launch_bounds__(256) void pos_dense_grad_kernel(const float* __rest
 
 // weight gradient of a 64-input-channel "same" convolution (s = 1, A = dY) or of a transposed convolution (A = its input, X = dY
 // on the finer grid), written in torch layout [CA][64][ks][ks]
-int sf_conv_wgrad_ex(const float* A, int CA, int H, int W, const float* X, int Hx, int Wx, int s, int ks, long long rows,
-                     float* out_oihw, float* partial, hipStream_t st) {
-  SF_REQUIRE(CA % 64 == 0 && ks == 5 && rows > 0 && rows < (1LL << 31), "conv weight gradient: channel multiple of 64, 5x5 kernels");
-  const int taps = ks * ks, nt = CA / 64;
-  int splits = 768 / (ks * nt);
+// row splits of the contraction: about 768 workgroups, at least 64 rows each, in whole 32-row chunks (so a window chunk never straddles an
+// image row); with the round-up the trailing splits can start past the last row -- they write zero partials
+static void conv_wgrad_splits(long long rows, int CA, int ks, int& splits, int& rps) {
+  const int nt = CA / 64;
+  splits = 768 / (ks * nt);
   if (splits < 1) splits = 1;
   if ((long long)splits * 64 > rows) splits = (int)((rows + 63) / 64);
-  int rps = (int)((rows + splits - 1) / splits);
+  rps = (int)((rows + splits - 1) / splits);
   rps = (rps + 31) & ~31;
+}
+
+int sf_conv_wgrad_ex(const float* A, int CA, int H, int W, const float* X, int Hx, int Wx, int s, int ks, long long rows,
+                     float* out_oihw, float* partial, hipStream_t st) {
+  SF_REQUIRE(CA > 0 && CA % 64 == 0 && ks == 5 && rows > 0 && rows < (1LL << 31), "conv weight gradient: channel multiple of 64, 5x5 kernels");
+  const int taps = ks * ks, nt = CA / 64;
+  int splits, rps;
+  conv_wgrad_splits(rows, CA, ks, splits, rps);
   const dim3 grid(ks * nt, splits);
   const int mode = sf_get_precision();
   constexpr bool win_on = true;
@@ -321,7 +329,32 @@ int sf_conv_wgrad_ex(const float* A, int CA, int H, int W, const float* X, int H
   SF_CHECK_LAUNCH();
   return 0;
 }
-size_t sf_conv_wgrad_partial_floats(int CA, int ks) { return (size_t)160 * CA * ks * ks * 64; }
+extern "C" size_t sf_conv_wgrad_partial_floats(int CA, int ks) { return (size_t)160 * CA * ks * ks * 64; }
+
+extern "C" int sf_conv_wgrad_f32(const float* A, int CA, int F, int H, int W, const float* X, int Hx, int Wx, int s, int ks, long long rows,
+                                 float* dW, float* partial, size_t partial_floats, void* stream) {
+  SF_REQUIRE(A && X && dW && partial, "sf_conv_wgrad_f32: null pointer");
+  SF_REQUIRE(ks == 5, "sf_conv_wgrad_f32: 5x5 kernels only");
+  SF_REQUIRE(CA > 0 && CA % 64 == 0, "sf_conv_wgrad_f32: CA must be a multiple of 64");
+  SF_REQUIRE(F >= 1 && H >= 1 && W >= 1 && s >= 1 && rows == (long long)F * H * W && rows < (1LL << 31),
+             "sf_conv_wgrad_f32: rows must equal F * H * W");
+  SF_REQUIRE(Hx == H * s && Wx == W * s, "sf_conv_wgrad_f32: the X grid must be H * s by W * s");
+  int splits, rps;
+  conv_wgrad_splits(rows, CA, ks, splits, rps);
+  SF_REQUIRE(partial_floats >= (size_t)splits * CA * ks * ks * 64, "sf_conv_wgrad_f32: partial buffer too small (sf_conv_wgrad_partial_floats)");
+  SF_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)partial & 15) == 0,
+             "sf_conv_wgrad_f32: A, X and partial must be 16-byte aligned");
+  return sf_conv_wgrad_ex(A, CA, H, W, X, Hx, Wx, s, ks, rows, dW, partial, (hipStream_t)stream);
+}
+
+extern "C" int sf_pack_conv_bwd_weight_f32(const float* w_oihw, float* w_bwd, int Cout, int Cin, int ks, void* stream) {
+  SF_REQUIRE(w_oihw && w_bwd, "sf_pack_conv_bwd_weight_f32: null pointer");
+  SF_REQUIRE(Cout > 0 && Cin > 0 && ks > 0 && (long long)Cout * Cin * ks * ks < (1LL << 31), "sf_pack_conv_bwd_weight_f32: bad shape");
+  hipLaunchKernelGGL(pack_conv_bwd_kernel, dim3((Cout * Cin * ks * ks + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_oihw, w_bwd, Cout, Cin,
+                     ks);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
 
 // SoftPositionEmbed gradients from d [F][HW][C] (the table is added to every frame); dtab: scratch [HW*C]
 int sf_pos_dense_grad_ex(const float* d, int F, int HW, int C, const float* grid, float* dw, float* db, float* dtab, hipStream_t st) {
@@ -331,6 +364,61 @@ int sf_pos_dense_grad_ex(const float* d, int F, int HW, int C, const float* grid
   hipLaunchKernelGGL(pos_dense_grad_kernel, dim3(C), dim3(256), 0, st, dtab, grid, dw, db, HW, C);
   SF_CHECK_LAUNCH();
   return 0;
+}
+extern "C" int sf_pos_dense_grad_f32(const float* d, int F, int HW, int C, const float* grid, float* dw, float* db, float* dtab, void* stream) {
+  SF_REQUIRE(d && grid && dw && db && dtab, "sf_pos_dense_grad_f32: null pointer");
+  SF_REQUIRE(F >= 1 && HW >= 1 && C >= 1 && (long long)HW * 4 < (1LL << 31), "sf_pos_dense_grad_f32: bad shape");
+  return sf_pos_dense_grad_ex(d, F, HW, C, grid, dw, db, dtab, (hipStream_t)stream);
+}
+
+// conv0's weight gradient [C][3][5][5] against the image patches: im2col (K = 75 padded to 128) -> TN contraction -> the 75 live columns.
+// P [M * 128], dw0 [C * 128], partial [sf_grad_partial_floats(M, C, 128)]
+static int conv_first_wgrad(const float* img, long long frame_stride, int res, const float* dY, long long M, int C, float* P, float* dw0,
+                            float* partial, float* dW, hipStream_t st) {
+  const long long n = M * 128;
+  hipLaunchKernelGGL(im2col_first_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, img, frame_stride, P, M, 3, res, res, 64, 64, 5,
+                     res == 128 ? 2 : 1, 128);
+  SF_CHECK_LAUNCH();
+  SF_TRY(sf_grad_weight_ex(dY, P, dw0, M, C, 128, partial, st));
+  hipLaunchKernelGGL(crop_cols_kernel, dim3((C * 75 + 255) / 256), dim3(256), 0, st, dw0, dW, C, 128, 75);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
+namespace {
+struct CfwWs {
+  float *P, *dw0, *partial;
+  size_t total;
+};
+CfwWs cfw_carve(int F, float* base) {
+  CfwWs w;
+  size_t off = 0;
+  auto take = [&](size_t n) {
+    float* p = base ? base + off : nullptr;
+    off += (n + 63) & ~(size_t)63;
+    return p;
+  };
+  const size_t M = (size_t)F * 4096;
+  w.P = take(M * 128);
+  w.dw0 = take((size_t)64 * 128);
+  w.partial = take(sf_grad_partial_floats((long long)M, 64, 128));
+  w.total = off;
+  return w;
+}
+}  // namespace
+extern "C" size_t sf_conv_first_wgrad_workspace_bytes(int F) {
+  if (F < 1 || F > 4096) return 0;
+  return cfw_carve(F, nullptr).total * sizeof(float) + 256;
+}
+extern "C" int sf_conv_first_wgrad_f32(const float* img, long long frame_stride, int resolution, const float* dY, int F, float* dW, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  SF_REQUIRE(img && dY && dW && ws, "sf_conv_first_wgrad_f32: null pointer");
+  SF_REQUIRE(resolution == 64 || resolution == 128, "sf_conv_first_wgrad_f32: resolution must be 64 or 128");
+  SF_REQUIRE(F >= 1 && F <= 4096, "sf_conv_first_wgrad_f32: bad frame count");
+  SF_REQUIRE(frame_stride >= 3LL * resolution * resolution, "sf_conv_first_wgrad_f32: frame_stride smaller than a frame");
+  SF_REQUIRE(((uintptr_t)dY & 15) == 0, "sf_conv_first_wgrad_f32: dY must be 16-byte aligned");
+  const CfwWs w = cfw_carve(F, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
+  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "sf_conv_first_wgrad_f32: workspace too small");
+  return conv_first_wgrad(img, frame_stride, resolution, dY, (long long)F * 4096, 64, w.P, w.dw0, w.partial, dW, (hipStream_t)stream);
 }
 
 namespace {
@@ -464,8 +552,7 @@ int sf_savi_features_train_bwd_f32(const sf_savi_features* m, const float* img, 
     SF_TRY(sf_grad_bias_ex(cur, g->conv_b[i], M, C, w.partial, st));
     SF_TRY(sf_conv_wgrad_ex(cur, C, 64, 64, w.a[i - 1], 64, 64, 1, 5, M, g->conv_w[i], w.partial, st));
     // data gradient: convolution with the flipped / transposed kernel, then the ReLU of the layer below
-    hipLaunchKernelGGL(pack_conv_bwd_kernel, dim3((C * C * 25 + 255) / 256), dim3(256), 0, st, m->conv_w[i], w.wb[i], C, C, 5);
-    SF_CHECK_LAUNCH();
+    SF_TRY(sf_pack_conv_bwd_weight_f32(m->conv_w[i], w.wb[i], C, C, 5, st));
     SF_TRY(conv5(cur, w.wb[i], w.wf[i], nullptr, w.a[i - 1], nxt, F, C, 2, st));   // relu = 2: gated by a[i-1] > 0
     float* t = cur;
     cur = nxt;
@@ -473,15 +560,7 @@ int sf_savi_features_train_bwd_f32(const sf_savi_features* m, const float* img, 
   }
   // conv0: bias + weight gradient against the image patches
   SF_TRY(sf_grad_bias_ex(cur, g->conv_b[0], M, C, w.partial, st));
-  {
-    const long long n = M * 128;
-    hipLaunchKernelGGL(im2col_first_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, img, frame_stride, w.g1, M, 3, d.res,
-                       d.res, 64, 64, 5, d.stride, 128);
-    SF_CHECK_LAUNCH();
-    SF_TRY(sf_grad_weight_ex(cur, w.g1, w.dw0, M, C, 128, w.partial, st));
-    hipLaunchKernelGGL(crop_cols_kernel, dim3((C * 75 + 255) / 256), dim3(256), 0, st, w.dw0, g->conv_w[0], C, 128, 75);
-    SF_CHECK_LAUNCH();
-  }
+  SF_TRY(conv_first_wgrad(img, frame_stride, d.res, cur, M, C, w.g1, w.dw0, w.partial, g->conv_w[0], st));
   return 0;
 }
 

@@ -188,6 +188,73 @@ def conv2d_nhwc(x, w_packed, bias, relu=True, add=None):
     return out
 
 
+def conv_wgrad(a, x, stride=1, partial=None):
+    """a [F,H,W,CA], x [F,H*s,W*s,64] NHWC -> dW [CA,64,5,5]: the weight gradient of a 5x5 "same" convolution (a = dY, x = its input, s = 1) or
+    of a transposed convolution (a = its input, x = dY on the finer grid).  partial: scratch (float32, any size the call's splits fit in)."""
+    _chk(a, x, partial)
+    F_, H, W, CA = a.shape
+    _, Hx, Wx, _ = x.shape
+    if partial is None:
+        partial = torch.empty(lib().sf_conv_wgrad_partial_floats(CA, 5), device=a.device, dtype=torch.float32)
+    out = torch.empty(CA, 64, 5, 5, device=a.device, dtype=torch.float32)
+    check(lib().sf_conv_wgrad_f32(_p(a), CA, F_, H, W, _p(x), Hx, Wx, int(stride), 5, F_ * H * W, _p(out), _p(partial), partial.numel(), _stream()))
+    return out
+
+
+def pack_conv_bwd_weight(w):
+    """Conv2d weight [Cout,Cin,k,k] -> [Cin,k,k,Cout], flipped: the packed weight of its backward-data convolution."""
+    _chk(w)
+    out = torch.empty(w.shape[1], w.shape[2], w.shape[3], w.shape[0], device=w.device, dtype=torch.float32)
+    check(lib().sf_pack_conv_bwd_weight_f32(_p(w), _p(out), w.shape[0], w.shape[1], w.shape[2], _stream()))
+    return out
+
+
+def conv2d_nhwc_bwd_data(g, w_packed, stride=1, relu_mask=None):
+    """g [F,H,W,Cin] NHWC, w_packed [Cout,k,k,Cin] -> [F,H/s,W/s,Cout] = Conv2d(k, s, padding k//2)(g), zero where relu_mask <= 0."""
+    _chk(g, w_packed, relu_mask)
+    F_, H, W, Cin = g.shape
+    Cout, ks = w_packed.shape[0], w_packed.shape[1]
+    out = torch.empty(F_, H // stride, W // stride, Cout, device=g.device, dtype=torch.float32)
+    check(lib().sf_conv2d_nhwc_bwd_data_f32(_p(g), _p(w_packed), _p(relu_mask), _p(out), F_, H, W, Cin, Cout, ks, int(stride), _stream()))
+    return out
+
+
+def conv_first_wgrad(img, dy, frame_stride=None):
+    """img [F,3,R,R] NCHW (R 64 or 128), dy [F*4096,64] -> dW [64,3,5,5] of the encoder's first convolution."""
+    _chk(img, dy)
+    F_, res = img.shape[0], img.shape[-1]
+    nb = lib().sf_conv_first_wgrad_workspace_bytes(F_)
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=img.device)
+    out = torch.empty(64, 3, 5, 5, device=img.device, dtype=torch.float32)
+    check(lib().sf_conv_first_wgrad_f32(_p(img), int(frame_stride or 3 * res * res), res, _p(dy), F_, _p(out), ws.data_ptr(), nb, _stream()))
+    return out
+
+
+def pos_dense_grad(d, grid):
+    """d [F,HW,C], grid [HW,4] -> (dw [C,4], db [C], frame sum of d [HW,C])."""
+    _chk(d, grid)
+    F_, HW, C_ = d.shape
+    dw, db = torch.empty(C_, 4, device=d.device), torch.empty(C_, device=d.device)
+    dtab = torch.empty(HW, C_, device=d.device)
+    check(lib().sf_pos_dense_grad_f32(_p(d), F_, HW, C_, _p(grid), _p(dw), _p(db), _p(dtab), _stream()))
+    return dw, db, dtab
+
+
+def savi_decode_head_bwd(dec, d_recon, act, out_w, want_param_grads=True):
+    """dec [F,N,HW,4], d_recon [F,3,HW], act [F*N*HW,Cl], out_w [4,Cl] -> (d_dec, d_act, d_out_w | None, d_out_b | None)."""
+    _chk(dec, d_recon, act, out_w)
+    F_, N, HW, _ = dec.shape
+    Cl = out_w.shape[1]
+    d_dec, d_act = torch.empty_like(dec), torch.empty_like(act)
+    gw = torch.empty(4, Cl, device=dec.device) if want_param_grads else None
+    gb = torch.empty(4, device=dec.device) if want_param_grads else None
+    nb = lib().sf_savi_decode_head_bwd_workspace_bytes(Cl)
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dec.device)
+    check(lib().sf_savi_decode_head_bwd_f32(_p(dec), _p(d_recon), _p(act), _p(out_w), _p(d_dec), _p(d_act), _p(gw), _p(gb), F_, N, HW, Cl,
+                                            ws.data_ptr(), nb, _stream()))
+    return d_dec, d_act, gw, gb
+
+
 def slot_attn_iter(k, v, q, eps=1e-6, want_attn=False):
     """k, v [B,HW,D]; q [B,N,D] -> (part_num [B,P,N,D], part_den [B,P,N], attn [B,N,HW] | None)."""
     _chk(k, v, q)
