@@ -326,10 +326,13 @@ extern "C" int sf_pack_conv_frag_weights(const float* w_ohwi, void* frag, int Co
   return 0;
 }
 
+static bool rows4_applies(const void* w_frag, int F, int H, int W, int Cin, int Cout, int ks) {
+  return w_frag && W == TW && Cin == CH && Cout == CH && ks == KS && (H % TR) == 0 && F > 0 && sf_get_precision() == 1;
+}
 // Returns 1 when the kernel does not apply (caller falls back to sf_conv2d_nhwc_f32's kernels).
 int sf_conv5x5_rows4_ex(const float* in, const void* w_frag, const float* bias, const float* add, float* out, int F, int H, int W,
                         int Cin, int Cout, int ks, int relu, hipStream_t st) {
-  if (!w_frag || W != TW || Cin != CH || Cout != CH || ks != KS || (H % TR) != 0 || F <= 0 || sf_get_precision() != 1) return 1;
+  if (!rows4_applies(w_frag, F, H, W, Cin, Cout, ks)) return 1;
   static const int dbg = sf_dbg("conv");
   // (the LDS attribute first: a failure here must not leave the class timer's pending event open)
   const bool f16 = sf_switch(SF_SW_CONV_FP16X2);
@@ -342,6 +345,15 @@ int sf_conv5x5_rows4_ex(const float* in, const void* w_frag, const float* bias, 
   sf_prof_end(SF_K_CONV_NHWC, st);
   SF_CHECK_LAUNCH();
   return 0;
+}
+
+// The same from OHWI weights (the training nodes, whose weights change every step): packs them into the scratch w_frag [sf_conv_frag_bytes] first.
+// Returns 1 before launching anything, the pack included, when the kernel does not apply; each caller has its own fallback.
+int sf_conv5x5_rows4_ohwi_ex(const float* in, const float* w_ohwi, void* w_frag, const float* bias, const float* add, float* out, int F, int H,
+                             int W, int Cin, int Cout, int ks, int relu, hipStream_t st) {
+  if (!rows4_applies(w_frag, F, H, W, Cin, Cout, ks)) return 1;
+  SF_TRY(sf_pack_conv_frag_weights(w_ohwi, w_frag, Cout, Cin, ks, st));
+  return sf_conv5x5_rows4_ex(in, w_frag, bias, add, out, F, H, W, Cin, Cout, ks, relu, st);
 }
 
 // The decoder's stride-1 last layer + 1x1 head (HEAD form above).  Returns 1 when the kernel does not apply.

@@ -15,6 +15,7 @@
 // place by the out_proj GEMM epilogue.
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "sf_arena.h"
 #include <map>
 #include <vector>
 #include "layer_fused.h"
@@ -22,27 +23,6 @@
 #include <stdlib.h>
 
 namespace {
-
-inline size_t pad256(size_t nfloat) { return ((nfloat * sizeof(float)) + 255) & ~(size_t)255; }
-
-// Carves 256-byte aligned float buffers off a workspace; over a NULL base it only counts the bytes (`used`)
-struct Bump {
-  char* p;
-  size_t left;
-  bool ok = true;
-  size_t used = 0;
-  float* take(size_t nfloat) {
-    const size_t bytes = pad256(nfloat);
-    if (bytes > left) {
-      ok = false;
-      return nullptr;
-    }
-    float* r = p ? (float*)(p + used) : nullptr;
-    used += bytes;
-    left -= bytes;
-    return r;
-  }
-};
 
 // the per-call single-pass modes (sf_rollout_opts.precision 2 / 3): every contraction on the generic GEMM core, which honours them, none
 // on the split-bf16-only fused kernels.  A process default of 2 (sf_set_precision, SF_PRECISION=bf16) keeps the fused kernels.
@@ -52,11 +32,7 @@ struct TfmWs {
   float *x2, *qkv, *att, *hid, *y;
 };
 
-size_t tfm_ws_bytes(int M, int d, int ffn) {
-  return pad256((size_t)M * d) * 3 + pad256((size_t)M * 3 * d) + pad256((size_t)M * ffn);
-}
-
-bool tfm_ws_take(Bump& bp, TfmWs& w, int M, int d, int ffn) {
+bool tfm_ws_take(SfArena& bp, TfmWs& w, int M, int d, int ffn) {
   w.x2 = bp.take((size_t)M * d);
   w.qkv = bp.take((size_t)M * 3 * d);
   w.att = bp.take((size_t)M * d);
@@ -214,7 +190,7 @@ struct RolloutWs {
   float* planes;   // q / k / v^T fragment planes of the row-tile attention form (sf_attn_rows_plane_bytes)
 };
 
-bool rollout_ws_take(Bump& bp, RolloutWs& w, const sf_rollouter* m, int B) {
+bool rollout_ws_take(SfArena& bp, RolloutWs& w, const sf_rollouter* m, int B) {
   const size_t M = (size_t)B * m->window_len * m->num_slots, d = m->d_model;
   w.x = bp.take(M * d);
   tfm_ws_take(bp, w.tw, (int)M, (int)d, m->ffn_dim);
@@ -236,10 +212,10 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 size_t sf_rollout_workspace_bytes(const sf_rollouter* m, int B) {
   if (!m || B <= 0) return 0;
-  Bump bp{nullptr, ~(size_t)0};
+  SfArena bp(nullptr);
   RolloutWs w;
   rollout_ws_take(bp, w, m, B);
-  return bp.used;
+  return bp.bytes();
 }
 
 // a[0..n) = b[0..n) = 0 (n a multiple of 4, both 16-byte aligned)
@@ -341,7 +317,7 @@ int rollout_run(const sf_rollouter* m, float* slots, int Bvid, int T_total, int 
   hipStream_t st = (hipStream_t)stream;
   const int N = m->num_slots, C = m->slot_size, d = m->d_model, W = m->window_len, nl = m->num_layers;
   const float eps = 1e-5f;
-  Bump bp{(char*)ws, ws_bytes};
+  SfArena bp(ws, ws_bytes);
   RolloutWs w;
   if (!rollout_ws_take(bp, w, m, B)) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
   const RolloutPlan p = plan_rollout(m, B, sf_thread_opts());
@@ -656,13 +632,13 @@ int enc_cmax(const sf_savi_encoder* m) {
   return cmax;
 }
 // n CNN activation buffers of `frames` frames each
-void enc_cnn_take(Bump& bp, float** buf, int n, const sf_savi_encoder* m, size_t frames) {
+void enc_cnn_take(SfArena& bp, float** buf, int n, const sf_savi_encoder* m, size_t frames) {
   for (int i = 0; i < n; ++i) buf[i] = bp.take(frames * ENC_HW * enc_cmax(m));
 }
 
 // the slot branch's four [rows][D] buffers: ping-pong slots, the predictor's latents, q (the video-stationary launch's row buffers too)
 struct SlotRows { float *a, *b, *lat, *q; };
-void slot_rows_take(Bump& bp, SlotRows& r, size_t rows, int D) {
+void slot_rows_take(SfArena& bp, SlotRows& r, size_t rows, int D) {
   for (float** f : {&r.a, &r.b, &r.lat, &r.q}) *f = bp.take(rows * D);
 }
 
@@ -708,7 +684,7 @@ struct EncodeWs {
   float* planes;          // chain: their Slot-Attention inputs as bf16 hi | lo rows of 512 B
 };
 
-bool enc_ws_take(Bump& bp, EncodeWs& w, const sf_savi_encoder* m, int B, int T, const EncodePlan& p) {
+bool enc_ws_take(SfArena& bp, EncodeWs& w, const sf_savi_encoder* m, int B, int T, const EncodePlan& p) {
   const int N = m->num_slots, D = m->slot_size, Ce = m->enc_out_channels, P = sf_sa_pick_partials(ENC_HW);
   const size_t R = (size_t)B * N, Bc = enc_chunk(B), HW = ENC_HW;
   enc_cnn_take(bp, w.feat, 2, m, Bc);
@@ -730,10 +706,10 @@ bool enc_ws_take(Bump& bp, EncodeWs& w, const sf_savi_encoder* m, int B, int T, 
 }
 
 size_t enc_ws_bytes(const sf_savi_encoder* m, int B, int T, const EncodePlan& p) {
-  Bump bp{nullptr, ~(size_t)0};
+  SfArena bp(nullptr);
   EncodeWs w;
   enc_ws_take(bp, w, m, B, T, p);
-  return bp.used + 8192;
+  return bp.bytes() + 8192;
 }
 
 bool enc_batched_ok(const sf_savi_encoder* m, int B, int T, int precision) {
@@ -1083,10 +1059,10 @@ size_t sf_savi_encode_batched_workspace_bytes(const sf_savi_encoder* m, int B, i
 
 size_t sf_savi_cnn_workspace_bytes(const sf_savi_encoder* m, int B) {
   if (!m || B <= 0) return 0;
-  Bump bp{nullptr, ~(size_t)0};
+  SfArena bp(nullptr);
   float* feat[2];
   enc_cnn_take(bp, feat, 2, m, enc_chunk(B));
-  return bp.used + 4096;
+  return bp.bytes() + 4096;
 }
 
 // CNN features of time steps [t0, t1) of every video: feat [t1-t0][B][64*64][C_last].  Independent of the slots, so a
@@ -1101,7 +1077,7 @@ int sf_savi_cnn_f32(const sf_savi_encoder* m, const float* img, int B, int T, in
   SF_REQUIRE(ws_bytes >= sf_savi_cnn_workspace_bytes(m, B), "workspace too small");
   for (int i = 0; i < m->enc_layers; ++i) SF_REQUIRE(m->conv_w[i] != nullptr, "null conv weight");
   const int Bc = enc_chunk(B), HW = ENC_HW, Cl = m->enc_channels[m->enc_layers];
-  Bump bp{(char*)ws, ws_bytes};
+  SfArena bp(ws, ws_bytes);
   float* fb[2];
   enc_cnn_take(bp, fb, 2, m, Bc);
   if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
@@ -1127,10 +1103,10 @@ int sf_savi_chain_ok(const sf_savi_encoder* m, int B, int T) {
 size_t sf_savi_planes_bytes(const sf_savi_encoder* m, int B, int T) { return (m && B > 0 && T > 0) ? (size_t)B * T * ENC_HW * 512 : 0; }
 size_t sf_savi_features_workspace_bytes(const sf_savi_encoder* m, int B, int T) {
   if (!m || B <= 0 || T <= 0) return 0;
-  Bump bp{nullptr, ~(size_t)0};
+  SfArena bp(nullptr);
   float* big[3];
   enc_cnn_take(bp, big, 3, m, (size_t)B * T);
-  return bp.used + 4096;
+  return bp.bytes() + 4096;
 }
 // Image features of B videos x T frames as the Slot-Attention inputs of the video-stationary slot branch: CNN (savi.py:231-244), encoder_out_layer
 // (:245-250) and SlotAttention.norm_inputs (:66) -> planes [T][B][64 * 64] rows of 512 B (bf16 hi 128 | lo 128).  Independent of any slots.
@@ -1138,7 +1114,7 @@ int sf_savi_features_planes_f32(const sf_savi_encoder* m, const float* img, int 
   SF_REQUIRE(m && img && planes && ws, "sf_savi_features_planes_f32: null pointer");
   SF_REQUIRE(B >= 1 && T >= 1 && sf_savi_chain_ok(m, B, T), "sf_savi_features_planes_f32: the video-stationary slot branch does not apply (sf_savi_chain_ok)");
   SF_REQUIRE(ws_bytes >= sf_savi_features_workspace_bytes(m, B, T), "workspace too small");
-  Bump bp{(char*)ws, ws_bytes};
+  SfArena bp(ws, ws_bytes);
   float* big[3];
   enc_cnn_take(bp, big, 3, m, (size_t)B * T);
   if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
@@ -1146,10 +1122,10 @@ int sf_savi_features_planes_f32(const sf_savi_encoder* m, const float* img, int 
 }
 size_t sf_savi_slots_chain_workspace_bytes(const sf_savi_encoder* m, int videos) {
   if (!m || videos <= 0) return 0;
-  Bump bp{nullptr, ~(size_t)0};
+  SfArena bp(nullptr);
   SlotRows r;
   slot_rows_take(bp, r, (size_t)videos * m->num_slots, m->slot_size);
-  return bp.used + 4096;
+  return bp.bytes() + 4096;
 }
 // The slot branch of NB batches of B videos over their T frames (StoSAVi.encode's per-step chain, savi.py:393-416, and the Slot-Attention iterations,
 // :76-100) from sf_savi_features_planes_f32 rows: planes [NB][T][B][64 * 64][256 bf16]; noise NULL or [NB * B][T][N][D]; prev_slots NULL or [NB * B][N][D];
@@ -1161,7 +1137,7 @@ int sf_savi_slots_chain_f32(const sf_savi_encoder* m, const void* planes, const 
              "sf_savi_slots_chain_f32: the video-stationary slot branch does not apply (sf_savi_chain_ok)");
   SF_REQUIRE(noise == nullptr || m->kd_mode != 0, "noise given but the model has no kernel_dist layer");
   SF_REQUIRE(ws_bytes >= sf_savi_slots_chain_workspace_bytes(m, NB * B), "workspace too small");
-  Bump bp{(char*)ws, ws_bytes};
+  SfArena bp(ws, ws_bytes);
   SlotRows r;
   slot_rows_take(bp, r, (size_t)NB * B * m->num_slots, m->slot_size);
   if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
@@ -1217,7 +1193,7 @@ int sf_savi_encode_fork_f32(const sf_savi_encoder* m, const float* img, const fl
                    m->lstm_b_hh && m->proj_w && m->proj_b, "null LSTM state / weight");
   const EncodePlan p = plan_encode(m, B, T, n_pre, side_stream != nullptr && side_stream != stream, ws_bytes);
   for (int i = 0; i < m->enc_layers; ++i) SF_REQUIRE(m->conv_w[i] != nullptr, "null conv weight");
-  Bump bp{(char*)ws, ws_bytes};
+  SfArena bp(ws, ws_bytes);
   EncodeWs w;
   SF_REQUIRE(ws_bytes >= enc_ws_bytes(m, B, T, p) && enc_ws_take(bp, w, m, B, T, p), "workspace too small");
   const hipStream_t st_main = (hipStream_t)stream, st = p.fork ? (hipStream_t)side_stream : st_main;   // st: the slot branch
@@ -1284,10 +1260,20 @@ static int dec_chunk(const sf_savi_decoder* m, int F) {
   return fc < F ? fc : F;
 }
 
+struct DecodeWs {
+  float *bufA, *bufB, *dec;
+  unsigned* slot_max;
+};
+static DecodeWs dec_ws_take(SfArena& bp, const sf_savi_decoder* m, int F) {
+  const size_t R = (size_t)dec_chunk(m, F) * m->num_slots, HW = (size_t)m->resolution * m->resolution;
+  float *a = bp.take(R * dec_maxact(m)), *b = bp.take(R * dec_maxact(m)), *dec = bp.take(R * HW * 4);
+  return DecodeWs{a, b, dec, bp.take<unsigned>(R)};
+}
 size_t sf_savi_decode_workspace_bytes(const sf_savi_decoder* m, int F) {
   if (!m || F <= 0) return 0;
-  const size_t R = (size_t)dec_chunk(m, F) * m->num_slots, HW = (size_t)m->resolution * m->resolution;
-  return 2 * pad256(R * dec_maxact(m)) + pad256(R * HW * 4) + pad256(R) + 4096;
+  SfArena bp(nullptr);
+  dec_ws_take(bp, m, F);
+  return bp.bytes() + 4096;
 }
 
 int sf_savi_decode_f32(const sf_savi_decoder* m, const float* slots, float* recon_combined, float* recons,
@@ -1312,12 +1298,10 @@ int sf_savi_decode_seg_f32(const sf_savi_decoder* m, const float* slots, float* 
   hipStream_t st = (hipStream_t)stream;
   const int N = m->num_slots, D = m->slot_size, res = m->resolution, HW = res * res;
   const int Fc = dec_chunk(m, F);
-  const size_t maxact = dec_maxact(m);
-  Bump bp{(char*)ws, ws_bytes};
-  float* bufA = bp.take((size_t)Fc * N * maxact);
-  float* bufB = bp.take((size_t)Fc * N * maxact);
-  float* dec = bp.take((size_t)Fc * N * HW * 4);
-  unsigned* slot_max = (unsigned*)bp.take((size_t)Fc * N);
+  SfArena bp(ws, ws_bytes);
+  const DecodeWs dw = dec_ws_take(bp, m, F);
+  float *bufA = dw.bufA, *bufB = dw.bufB, *dec = dw.dec;
+  unsigned* slot_max = dw.slot_max;
   if (!bp.ok) return sf_set_err(-1, "workspace too small", __FILE__, __LINE__);
   const bool bf3 = sf_get_precision() == 1;
   const int nl = m->dec_layers, Cl = m->dec_channels[nl];

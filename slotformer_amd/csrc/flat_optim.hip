@@ -1,4 +1,4 @@
-// The optimiser step over ONE flat fp32 bucket beyond plain Adam (rollout_train.hip: sf_adam_flat_f32):
+// The optimiser step over ONE flat fp32 bucket: plain Adam (sf_adam_flat_f32, at the end of the file) and beyond it
 //   sf_grad_clip_coef_f32    global L2 norm of the gradient bucket, torch.nn.utils.clip_grad_norm_'s coefficient and a non-finite
 //                            flag, in one launch (base_slots/method.py: backward -> clip_grad -> Adam; clip_grad = 0.05 in the
 //                            StoSAVi / SAVi / STEVE configurations)
@@ -121,7 +121,7 @@ __device__ __forceinline__ float group_lr(const AdamGroups& G, long long e) {
   return lr;
 }
 
-// adam_flat_kernel's update of one element (rollout_train.hip): the same expression in the same order.  That kernel compiles
+// adam_flat_kernel's update of one element (below): the same expression in the same order.  That kernel compiles
 // to separate multiplies and adds (its products are packed in pairs before anything could be fused); four elements per thread
 // pack differently, so contraction is switched off here to keep every product and sum rounded on its own, as there
 // (tests/test_flat_adam_gpu.py compares the bits).
@@ -214,6 +214,32 @@ int sf_adam_flat_groups_f32(float* param, const float* grad, float* exp_avg, flo
   else
     hipLaunchKernelGGL(adam_flat_groups_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, nv, G,
                        beta1, beta2, eps, bc1, sqrtf(bc2), grad_scale);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
+
+// torch.optim.Adam (no amsgrad, no weight decay: the reference's optimiser, slotformer_clevrer_params.py:16-19) over ONE flat
+// fp32 bucket: p, g, m, v [n]; step = the 1-based step count.  One launch per optimiser step.
+extern "C" __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
+                                                        float bc1, float bc2_sqrt) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float gi = g[i];
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi;
+  v[i] = vi;
+  // torch: denom = sqrt(v) / sqrt(bias_correction2) + eps;  p -= (lr / bias_correction1) * m / denom
+  p[i] -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
+}
+int sf_adam_flat_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr, float beta1,
+                     float beta2, float eps, void* stream) {
+  SF_REQUIRE(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1, "bad Adam arguments");
+  if (n == 0) return 0;
+  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
+                     beta1, beta2, eps, bc1, sqrtf(bc2));
   SF_CHECK_LAUNCH();
   return 0;
 }

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "sf_internal.h"
+#include "train_blocks.h"
 
 enum { ALOAD_PLAIN = 0, ALOAD_CONV_NHWC = 1, ALOAD_CONV_NCHW = 2, ALOAD_DECONV_NHWC = 3 };
 

@@ -23,6 +23,7 @@
 
 #include "../../include/slotformer_hip.h"
 #include "sf_common.h"
+#include "sf_arena.h"
 #include "bf16_planes.h"
 
 namespace {
@@ -338,7 +339,6 @@ __global__ void lp_mean_kernel(const float* __restrict__ scores, double* __restr
   mean[t] = s / (double)B;
 }
 
-inline size_t lp_align(size_t n) { return (n + 255) & ~(size_t)255; }
 inline bool lp_shape_ok(int H, int W, int chunk) {
   return H >= LP_MIN_HW && W >= LP_MIN_HW && chunk >= 1 && chunk <= 16384 && 2ll * chunk * H * W < (1ll << 31) / 64;
 }
@@ -353,8 +353,20 @@ inline LpStages lp_stages(int H, int W, int* np_total) {
   *np_total = n;
   return st;
 }
-// one activation buffer: both planes of the widest map (stage 1: 2 chunk images x H x W x 64 channels; every later map is smaller)
-inline size_t lp_act_bytes(int H, int W, int chunk) { return lp_align((size_t)2 * chunk * H * W * LP_C1 * 4); }
+struct LpWs {
+  char* bufs[2];     // two activation buffers, each both planes of the widest map (stage 1: 2 chunk images x H x W x 64 channels; every later map is smaller)
+  double* partial;   // [chunk][np]: the tap kernel's block sums
+  size_t bytes;
+};
+constexpr size_t LP_WS_SLACK = 256;
+inline LpWs lp_carve(void* ws, int H, int W, int chunk, int np) {
+  SfArena a(ws);
+  LpWs w;
+  for (char*& b : w.bufs) b = a.take<char>((size_t)2 * chunk * H * W * LP_C1 * 4);
+  w.partial = a.take<double>((size_t)chunk * np);
+  w.bytes = a.bytes();
+  return w;
+}
 inline bool lp_channels_ok(int Cout, int Cin) {
   if (Cin == 3) return Cout == LP_C1;
   return (Cin == 64 || Cin == 128 || Cin == 256 || Cin == 512) && (Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512);
@@ -403,7 +415,7 @@ size_t sf_lpips_workspace_bytes(int H, int W, int chunk) {
   if (!lp_shape_ok(H, W, chunk)) return 0;
   int np = 0;
   lp_stages(H, W, &np);
-  return 2 * lp_act_bytes(H, W, chunk) + lp_align((size_t)chunk * np * sizeof(double)) + 256;
+  return lp_carve(nullptr, H, W, chunk, np).bytes + LP_WS_SLACK;
 }
 
 int sf_lpips_f32(const sf_lpips_model* m, const float* x, const float* y, float* out, int F, int H, int W, int chunk, int normalize,
@@ -419,10 +431,9 @@ int sf_lpips_f32(const sf_lpips_model* m, const float* x, const float* y, float*
   hipStream_t st = (hipStream_t)stream;
   int np = 0;
   const LpStages stages = lp_stages(H, W, &np);
-  char* base = static_cast<char*>(workspace);
-  const size_t act = lp_act_bytes(H, W, chunk);
-  char* bufs[2] = {base, base + act};
-  double* partial = reinterpret_cast<double*>(base + 2 * act);
+  const LpWs ws = lp_carve(workspace, H, W, chunk, np);
+  char* const* bufs = ws.bufs;
+  double* partial = ws.partial;
   for (int f0 = 0; f0 < F; f0 += chunk) {
     const int c = F - f0 < chunk ? F - f0 : chunk;
     const int N = 2 * c;

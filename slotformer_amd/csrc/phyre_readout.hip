@@ -22,6 +22,7 @@
 // every other process precision instead of computing the same logit two ways.  Every sum has a fixed order; no atomics on floats anywhere.
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
 #include "layer_fused.h"
 
 namespace {

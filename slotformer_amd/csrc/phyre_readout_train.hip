@@ -27,6 +27,8 @@
 // site 2: (b L + tok) 512 + j  -- train.dropout_keep_mask restates them.
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
+#include "sf_arena.h"
 #include "split_bf16.h"
 #include "dropout_mask.h"
 
@@ -878,9 +880,8 @@ __global__ __launch_bounds__(256) void pt_transpose_kernel(const PtTrJobs jobs) 
 }
 
 inline bool pt_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline size_t pt_up(size_t n) { return (n + 63) & ~(size_t)63; }
 
-// the workspace, in floats
+// the workspace, in floats from the caller's (16-byte aligned) ws: offsets, so the arena below only ever counts
 struct PtWs {
   size_t X, xn1, qkv, o, x2, xn2, hact, gate, hrelu, hgate, dx, dy2, dh, dxn2, do2, dqkv, dxn1, wT, partial, tokp, total;
   size_t M;   // rows B L
@@ -891,9 +892,9 @@ inline int pt_splits(long long M) { const long long s = (M + 511) / 512; return 
 inline int pt_ln_groups(long long M) { const long long g = (M + 63) / 64; return (int)(g < 1 ? 1 : g > 64 ? 64 : g); }      // row groups of d gamma
 inline PtWs pt_ws(int B, int L, int nl) {
   PtWs w;
-  size_t off = 0;
+  SfArena a(nullptr);
   const size_t M = (size_t)B * L;
-  auto take = [&](size_t n) { const size_t at = off; off += pt_up(n); return at; };
+  auto take = [&](size_t n) { const size_t at = a.bytes() / sizeof(float); a.take(n); return at; };
   w.M = M;
   w.X = take((size_t)(nl + 1) * M * PT_D);
   w.xn1 = take(nl * M * PT_D);
@@ -916,7 +917,7 @@ inline PtWs pt_ws(int B, int L, int nl) {
   w.wT = take(nl * PT_WT);
   w.partial = take((size_t)pt_splits((long long)M) * nl * (PT_WT + PT_BIAS) + (size_t)2 * nl * pt_ln_groups((long long)M) * 2 * PT_D);
   w.tokp = take((size_t)PT_TOK_RS * PT_D * 256);   // d in_proj.weight per row split, at the widest slot
-  w.total = off;
+  w.total = a.bytes() / sizeof(float);
   return w;
 }
 inline int pt_tok_splits(long long rows) { const long long s = rows / 256; return (int)(s < 1 ? 1 : s > PT_TOK_RS ? PT_TOK_RS : s); }

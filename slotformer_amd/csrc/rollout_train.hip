@@ -7,10 +7,8 @@
 //     is every gradient that feeds a weight gradient;
 //   * the backward-through-time loop only runs the data-gradient chain (dX = dY . W on the forward GEMM core against
 //     transposed weight copies, LayerNorm / attention / dropout backward kernels);
-//   * after the loop each weight gradient is ONE contraction over all S*M rows: dW = dY^T . X on a split-bf16 MFMA kernel
-//     that reads both operands in their natural row-major layout (no transposes), split over row ranges into partial
-//     tiles that a second kernel sums in a fixed order (deterministic; no atomics);
-//   * bias and LayerNorm-parameter gradients are column sums over the same stacked buffers.
+//   * after the loop each weight gradient is ONE contraction over all S*M rows, bias and LayerNorm-parameter gradients are column sums over the
+//     same stacked buffers (train_blocks.hip).
 // Gradients are written (not accumulated) into caller-owned buffers (sf_rollouter_grads), which the host lays out as one
 // flat bucket for the data-parallel all-reduce.
 //
@@ -22,7 +20,8 @@
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
 #include "rollout_train.h"
-#include "bf16_planes.h"
+#include "train_blocks.h"
+#include "sf_arena.h"
 #include "dropout_mask.h"   // site_seed / sf_keep / drop_thresh: the mask convention, shared with phyre_readout_train.hip
 
 // y = res + keep(x) / (1 - p)   (res may be NULL); n4 float4 elements
@@ -39,20 +38,6 @@ __global__ __launch_bounds__(256) void residual_dropout_kernel(const float* __re
   r.z += sf_keep(sseed, e + 2, thresh) ? v.z * inv_keep : 0.f;
   r.w += sf_keep(sseed, e + 3, thresh) ? v.w * inv_keep : 0.f;
   reinterpret_cast<float4*>(y)[i] = r;
-}
-
-// dpre = hdn > 0 ? dh * inv_keep : 0   (hdn is the saved post-ReLU, post-dropout hidden activation)
-__global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(float* __restrict__ dh, const float* __restrict__ hdn,
-                                                               long long n4, float inv_keep) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  float4 g = reinterpret_cast<float4*>(dh)[i];
-  const float4 h = reinterpret_cast<const float4*>(hdn)[i];
-  g.x = h.x > 0.f ? g.x * inv_keep : 0.f;
-  g.y = h.y > 0.f ? g.y * inv_keep : 0.f;
-  g.z = h.z > 0.f ? g.z * inv_keep : 0.f;
-  g.w = h.w > 0.f ? g.w * inv_keep : 0.f;
-  reinterpret_cast<float4*>(dh)[i] = g;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -110,25 +95,10 @@ __global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ y,
   reinterpret_cast<float4*>(y)[i] = a;
 }
 
-// out[c][r] = in[r][c]
-__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int Cn) {
-  __shared__ float t[32][33];
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8)
-    if (r0 + i < R && c0 + tx < Cn) t[i][tx] = in[(long long)(r0 + i) * Cn + c0 + tx];
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8)
-    if (c0 + i < Cn && r0 + tx < R) out[(long long)(c0 + i) * R + r0 + tx] = t[tx][i];
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // attention with saved-nothing backward: one workgroup per (head, video); L <= 128, head_dim <= 64.
 // qkv [B*L, 3d] (q|k|v); ctx / dctx [B*L, d]; dqkv [B*L, 3d].  Dropout acts on the softmax weights (nn.MultiheadAttention).
 // ---------------------------------------------------------------------------------------------------------------------
-struct AttnLds {
-  float *q, *k, *v, *g, *P, *dS;
-};
 __device__ __forceinline__ void attn_probs(const float* qkv, int L, int d, int hd, int b, int h, float scale, float* q,
                                            float* k, float* v, float* P, int hp, int lp) {
   const int tid = threadIdx.x;
@@ -447,83 +417,6 @@ __global__ __launch_bounds__(256) void attn_train_bwd_mfma_kernel(const float* _
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// LayerNorm backward (one wave per row, D <= 1024, D % 4 == 0):  out = dres + dLN(dy; x, gamma)
-// ---------------------------------------------------------------------------------------------------------------------
-// out2 (optional): the same gradient pushed through the dropout of the block below it (mask * out / keep), i.e. the
-// gradient w.r.t. that block's pre-dropout output -- saves a separate pass over the tensor.
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                     const float* __restrict__ gamma, const float* __restrict__ dres,
-                                                     float* __restrict__ out, float* __restrict__ out2, uint32_t sseed2,
-                                                     uint32_t thresh, float inv_keep, int rows, int D, float eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const int n4 = D >> 2;
-  const float4* xr = reinterpret_cast<const float4*>(x + (long long)row * D);
-  const float4* gr = reinterpret_cast<const float4*>(dy + (long long)row * D);
-  const float4* gm = reinterpret_cast<const float4*>(gamma);
-  float4 xv[4], gv[4];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = lane + 64 * i;
-    xv[i] = c < n4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    s += (xv[i].x + xv[i].y) + (xv[i].z + xv[i].w);
-  }
-  const float mean = sf_wave_sum(s) / D;
-  float var = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = lane + 64 * i;
-    if (c < n4) {
-      xv[i].x -= mean; xv[i].y -= mean; xv[i].z -= mean; xv[i].w -= mean;
-      var += (xv[i].x * xv[i].x + xv[i].y * xv[i].y) + (xv[i].z * xv[i].z + xv[i].w * xv[i].w);
-    }
-  }
-  const float rstd = rsqrtf(sf_wave_sum(var) / D + eps);
-  float m1 = 0.f, m2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = lane + 64 * i;
-    if (c < n4) {
-      const float4 w = gm[c];
-      float4 g = gr[c];
-      g.x *= w.x; g.y *= w.y; g.z *= w.z; g.w *= w.w;
-      xv[i].x *= rstd; xv[i].y *= rstd; xv[i].z *= rstd; xv[i].w *= rstd;   // x-hat
-      gv[i] = g;
-      m1 += (g.x + g.y) + (g.z + g.w);
-      m2 += (g.x * xv[i].x + g.y * xv[i].y) + (g.z * xv[i].z + g.w * xv[i].w);
-    }
-  }
-  m1 = sf_wave_sum(m1) / D;
-  m2 = sf_wave_sum(m2) / D;
-  const float4* rr = dres ? reinterpret_cast<const float4*>(dres + (long long)row * D) : nullptr;
-  float4* orow = reinterpret_cast<float4*>(out + (long long)row * D);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = lane + 64 * i;
-    if (c < n4) {
-      float4 r = rr ? rr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-      r.x += rstd * (gv[i].x - m1 - xv[i].x * m2);
-      r.y += rstd * (gv[i].y - m1 - xv[i].y * m2);
-      r.z += rstd * (gv[i].z - m1 - xv[i].z * m2);
-      r.w += rstd * (gv[i].w - m1 - xv[i].w * m2);
-      orow[c] = r;
-      if (out2) {
-        if (thresh) {
-          const uint32_t e = (uint32_t)(row * D + 4 * c);
-          r.x = sf_keep(sseed2, e, thresh) ? r.x * inv_keep : 0.f;
-          r.y = sf_keep(sseed2, e + 1, thresh) ? r.y * inv_keep : 0.f;
-          r.z = sf_keep(sseed2, e + 2, thresh) ? r.z * inv_keep : 0.f;
-          r.w = sf_keep(sseed2, e + 3, thresh) ? r.w * inv_keep : 0.f;
-        }
-        reinterpret_cast<float4*>(out2 + (long long)row * D)[c] = r;
-      }
-    }
-  }
-}
-
 // gradient w.r.t. the final layer output: zero except the last N tokens of every video (dxlast [B*N, d]); dfo = the same
 // pushed through the top layer's FFN-output dropout
 __global__ __launch_bounds__(256) void scatter_last_kernel(const float* __restrict__ dxlast, float* __restrict__ dx,
@@ -545,264 +438,6 @@ __global__ __launch_bounds__(256) void scatter_last_kernel(const float* __restri
     r.w = sf_keep(sseed, e + 3, thresh) ? r.w * inv_keep : 0.f;
   }
   reinterpret_cast<float4*>(dfo)[i] = r;
-}
-
-// LayerNorm parameter gradients, stage 1: workgroup g handles rows [g*rpg, (g+1)*rpg); partial[g][0][D] = sum dy*xhat,
-// partial[g][1][D] = sum dy.  D <= 1024, D % 4 == 0.
-__global__ __launch_bounds__(256) void ln_param_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                               float* __restrict__ partial, long long rows, int rpg, int D,
-                                                               float eps) {
-  __shared__ float red[3][2][1024];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n4 = D >> 2;
-  float4 ag[4], ab[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) ag[i] = ab[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const long long r0 = (long long)blockIdx.x * rpg;
-  const long long r1 = r0 + rpg < rows ? r0 + rpg : rows;
-  for (long long row = r0 + wave; row < r1; row += 4) {
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
-    const float4* gr = reinterpret_cast<const float4*>(dy + row * D);
-    float4 xv[4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + 64 * i;
-      xv[i] = c < n4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-      s += (xv[i].x + xv[i].y) + (xv[i].z + xv[i].w);
-    }
-    const float mean = sf_wave_sum(s) / D;
-    float var = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + 64 * i;
-      if (c < n4) {
-        xv[i].x -= mean; xv[i].y -= mean; xv[i].z -= mean; xv[i].w -= mean;
-        var += (xv[i].x * xv[i].x + xv[i].y * xv[i].y) + (xv[i].z * xv[i].z + xv[i].w * xv[i].w);
-      }
-    }
-    const float rstd = rsqrtf(sf_wave_sum(var) / D + eps);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + 64 * i;
-      if (c < n4) {
-        const float4 g = gr[c];
-        ag[i].x += g.x * xv[i].x * rstd; ag[i].y += g.y * xv[i].y * rstd;
-        ag[i].z += g.z * xv[i].z * rstd; ag[i].w += g.w * xv[i].w * rstd;
-        ab[i].x += g.x; ab[i].y += g.y; ab[i].z += g.z; ab[i].w += g.w;
-      }
-    }
-  }
-  if (wave > 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + 64 * i;
-      if (c < n4) {
-        reinterpret_cast<float4*>(red[wave - 1][0])[c] = ag[i];
-        reinterpret_cast<float4*>(red[wave - 1][1])[c] = ab[i];
-      }
-    }
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + 64 * i;
-      if (c < n4) {
-        for (int w = 0; w < 3; ++w) {
-          const float4 a = reinterpret_cast<float4*>(red[w][0])[c], b = reinterpret_cast<float4*>(red[w][1])[c];
-          ag[i].x += a.x; ag[i].y += a.y; ag[i].z += a.z; ag[i].w += a.w;
-          ab[i].x += b.x; ab[i].y += b.y; ab[i].z += b.z; ab[i].w += b.w;
-        }
-        reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2) * D)[c] = ag[i];
-        reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2 + 1) * D)[c] = ab[i];
-      }
-    }
-  }
-}
-
-// column sums, stage 1: partial[g][n] = sum over rows [g*rpg, (g+1)*rpg) of y[row][n].  The 256 threads of a workgroup
-// cover min(n, 256) columns x 256 / that many row lanes (narrow matrices -- conv / head gradients have n = 4 .. 64 and
-// millions of rows -- keep every lane busy), four loads in flight per lane, row lanes combined through LDS.
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ y, float* __restrict__ partial,
-                                                             long long rows, int rpg, int n) {
-  __shared__ float red[256];
-  int cols = 1;
-  while (cols < n && cols < 256) cols <<= 1;   // columns per workgroup (power of two)
-  const int lanes = 256 / cols;
-  const int cl = threadIdx.x % cols, rl = threadIdx.x / cols;
-  const int c = blockIdx.x * cols + cl;
-  const long long r0 = (long long)blockIdx.y * rpg;
-  const long long r1 = r0 + rpg < rows ? r0 + rpg : rows;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (c < n) {
-    long long r = r0 + rl;
-    for (; r + 3LL * lanes < r1; r += 4LL * lanes) {
-      s0 += y[r * n + c];
-      s1 += y[(r + lanes) * n + c];
-      s2 += y[(r + 2LL * lanes) * n + c];
-      s3 += y[(r + 3LL * lanes) * n + c];
-    }
-    for (; r < r1; r += lanes) s0 += y[r * n + c];
-  }
-  red[threadIdx.x] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (rl == 0 && c < n) {
-    float a = red[cl];
-    for (int i = 1; i < lanes; ++i) a += red[i * cols + cl];
-    partial[(long long)blockIdx.y * n + c] = a;
-  }
-}
-
-// stage 2 of every split reduction: out[i] = sum_g partial[g][i]  (fixed order: four interleaved chains, then their sum)
-// (columns >= n4a go to out2 when it is given: one launch writes d_gamma and d_beta of a LayerNorm)
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partial, float* __restrict__ out,
-                                                              int G, long long n4, float* __restrict__ out2, long long n4a) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const float4* p = reinterpret_cast<const float4*>(partial) + i;
-  float4 a[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) a[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-  int g = 0;
-  for (; g + 4 <= G; g += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float4 b = p[(long long)(g + u) * n4];
-      a[u].x += b.x; a[u].y += b.y; a[u].z += b.z; a[u].w += b.w;
-    }
-  }
-  for (; g < G; ++g) {
-    const float4 b = p[(long long)g * n4];
-    a[0].x += b.x; a[0].y += b.y; a[0].z += b.z; a[0].w += b.w;
-  }
-  float4 r;
-  r.x = (a[0].x + a[1].x) + (a[2].x + a[3].x);
-  r.y = (a[0].y + a[1].y) + (a[2].y + a[3].y);
-  r.z = (a[0].z + a[1].z) + (a[2].z + a[3].z);
-  r.w = (a[0].w + a[1].w) + (a[2].w + a[3].w);
-  if (out2 && i >= n4a) reinterpret_cast<float4*>(out2)[i - n4a] = r;
-  else reinterpret_cast<float4*>(out)[i] = r;
-}
-
-// the same reduction for few columns and many partials (bias / LayerNorm / 64x64 weight gradients: up to 512 partials of 16
-// to 1024 float4 columns, where one thread per column leaves the chip idle behind a handful of long serial chains): a
-// workgroup takes 16 columns, its 16 thread rows each sum every 16th partial, LDS combines the rows in a fixed tree.
-__global__ __launch_bounds__(256) void reduce_partials_wide_kernel(const float* __restrict__ partial, float* __restrict__ out,
-                                                                   int G, long long n4, float* __restrict__ out2, long long n4a) {
-  const int c = threadIdx.x & 15, q = threadIdx.x >> 4;
-  const long long i = (long long)blockIdx.x * 16 + c;
-  __shared__ f32x4 sh[16][17];
-  f32x4 a = {0.f, 0.f, 0.f, 0.f};
-  if (i < n4) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(partial) + i;
-    for (int g = q; g < G; g += 16) a += p[(long long)g * n4];
-  }
-  sh[q][c] = a;
-  __syncthreads();
-#pragma unroll
-  for (int w = 8; w > 0; w >>= 1) {
-    if (q < w) sh[q][c] += sh[q + w][c];
-    __syncthreads();
-  }
-  if (q == 0 && i < n4) {
-    if (out2 && i >= n4a) reinterpret_cast<f32x4*>(out2)[i - n4a] = sh[0][c];
-    else reinterpret_cast<f32x4*>(out)[i] = sh[0][c];
-  }
-}
-inline void launch_reduce_partials(const float* partial, float* out, int G, long long n4, hipStream_t st, float* out2 = nullptr,
-                                   long long n4a = 0) {
-  if (G >= 32 && n4 <= 16384)
-    hipLaunchKernelGGL(reduce_partials_wide_kernel, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, partial, out, G, n4, out2, n4a);
-  else
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, partial, out, G, n4, out2, n4a);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// weight-gradient contraction  dW[n][k] = sum_m Y[m][n] * X[m][k]   (Y [rows, N], X [rows, K], both row-major)
-// split-bf16 on v_mfma_f32_32x32x16_bf16; 64x64 output tile per workgroup (4 waves, one 32x32 quadrant each), the
-// contraction index is the row index: a chunk of 32 rows of both operands is staged in LDS as f32 and every lane reads
-// its 8 values per k16 step with a stride of one LDS row (pitch 68: the two half-waves hit disjoint banks).
-// grid (N/64 * K/64, splits): split z handles rows [z*rps, (z+1)*rps) and writes partial[z][N][K].
-// ---------------------------------------------------------------------------------------------------------------------
-#define TN_P 68
-// The 32-row chunk of both operands lives in LDS as bf16 hi / lo PLANES (bf16_planes.h; every element split once, where it is staged, instead of once per
-// wave that reads it): the contraction index is the tile's ROW index, so the operand fragments come out through ds_read_b64_tr_b16 -- two transposing
-// reads per plane and k16 step instead of eight scalar reads + a conversion chain.  Row pitch 192 bytes: the four rows x two 16-column groups a
-// half-wave touches per read land on disjoint banks.
-#define TN_PB 192
-template <int MODE>   // 0: hi*hi + hi*lo + lo*hi + lo*lo, 1: without lo*lo (split-bf16), 2: hi*hi only (single-pass bf16)
-__global__ __launch_bounds__(256) void grad_gemm_tn_kernel(const float* __restrict__ Y, const float* __restrict__ X,
-                                                           float* __restrict__ partial, long long rows, int rps, int N,
-                                                           int K) {
-  constexpr int PT = 32 * TN_PB, YH = 0, YL = PT, XH = 2 * PT, XL = 3 * PT;
-  __shared__ __attribute__((aligned(16))) char tsm[4 * PT + 64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tk = K / 64;
-  const int n0 = (blockIdx.x / tk) * 64, k0 = (blockIdx.x % tk) * 64;
-  const long long r0 = (long long)blockIdx.y * rps;
-  const long long r1 = r0 + rps < rows ? r0 + rps : rows;
-  const int wn = (wave >> 1) * 32, wk = (wave & 1) * 32;
-  // loader: thread -> (row = tid >> 4 (+16), float4 column = tid & 15)
-  const int lr = tid >> 4, lc = (tid & 15) * 4;
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  const int nrows = (int)(r1 - r0);   // <= rps
-  const float* Yb = Y + r0 * N + n0 + lc;
-  const float* Xb = X + r0 * K + k0 + lc;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 py0 = zero4, py1 = zero4, px0 = zero4, px1 = zero4;
-  if (lr < nrows) {
-    py0 = *reinterpret_cast<const float4*>(Yb + (long long)lr * N);
-    px0 = *reinterpret_cast<const float4*>(Xb + (long long)lr * K);
-  }
-  if (lr + 16 < nrows) {
-    py1 = *reinterpret_cast<const float4*>(Yb + (long long)(lr + 16) * N);
-    px1 = *reinterpret_cast<const float4*>(Xb + (long long)(lr + 16) * K);
-  }
-  auto stage = [&](const float4 v, int hoff, int loff, int row) {
-    unsigned h0, l0, h1, l1;
-    pl_split2(v.x, v.y, h0, l0);
-    pl_split2(v.z, v.w, h1, l1);
-    *(u32x2*)(tsm + hoff + row * TN_PB + lc * 2) = u32x2{h0, h1};
-    if (MODE != 2) *(u32x2*)(tsm + loff + row * TN_PB + lc * 2) = u32x2{l0, l1};
-  };
-  for (int rb = 0; rb < nrows; rb += 32) {
-    __syncthreads();
-    stage(py0, YH, YL, lr);
-    stage(py1, YH, YL, lr + 16);
-    stage(px0, XH, XL, lr);
-    stage(px1, XH, XL, lr + 16);
-    __syncthreads();
-    py0 = py1 = px0 = px1 = zero4;
-    const int ra = rb + 32 + lr;
-    if (ra < nrows) {
-      py0 = *reinterpret_cast<const float4*>(Yb + (long long)ra * N);
-      px0 = *reinterpret_cast<const float4*>(Xb + (long long)ra * K);
-    }
-    if (ra + 16 < nrows) {
-      py1 = *reinterpret_cast<const float4*>(Yb + (long long)(ra + 16) * N);
-      px1 = *reinterpret_cast<const float4*>(Xb + (long long)(ra + 16) * K);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const PlFrag a = pl_rd_tr(tsm, YH, MODE != 2 ? YL : YH, TN_PB, 16 * t, wn, lane);   // lane (n, kk): rows 16 t + 8 kk .. + 7 of column wn + n
-      const PlFrag b = pl_rd_tr(tsm, XH, MODE != 2 ? XL : XH, TN_PB, 16 * t, wk, lane);
-      if (MODE != 2) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, acc, 0, 0, 0);
-      }
-      if (MODE == 0) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.l, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
-    }
-  }
-  float* out = partial + (long long)blockIdx.y * N * K;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int n = n0 + wn + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    out[(long long)n * K + k0 + wk + (lane & 31)] = acc[r];
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -834,71 +469,57 @@ struct Ws {
   float *dqkv[16], *dao[16], *dpre[16], *dfo[16], *da1[16], *da2[16];
   float *wt_in[16], *wt_o[16], *wt_1[16], *wt_2[16], *wt_inproj, *wt_outproj;
   float* partial;
-  size_t partial_floats;
-  size_t total_floats;
+  size_t bytes;   // of the carve
 };
 
 inline size_t tn_partial_floats(const Dims& D);
 
-Ws carve(const Dims& D, float* base) {
+constexpr size_t WS_SLACK = 256;   // bytes a caller's workspace holds beyond the carve
+
+Ws carve(const Dims& D, void* ws) {
   Ws w;
   memset(&w, 0, sizeof(w));
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + 63) & ~(size_t)63;
-    return p;
-  };
+  SfArena a(ws);
   const size_t M = D.M, R = D.R, S = D.S, d = D.d, f = D.ffn, Mt = D.off(D.S);
-  w.slots_all = take((size_t)D.T * R * D.C);
-  w.tok_all = take((size_t)D.T * R * d);
-  w.xf = take(Mt * d);
-  w.xlast = take(S * R * d);
-  w.tmp = take(M * (f > 3 * d ? f : 3 * d));
+  w.slots_all = a.take((size_t)D.T * R * D.C);
+  w.tok_all = a.take((size_t)D.T * R * d);
+  w.xf = a.take(Mt * d);
+  w.xlast = a.take(S * R * d);
+  w.tmp = a.take(M * (f > 3 * d ? f : 3 * d));
   for (int l = 0; l < D.nl; ++l) {
-    w.xin[l] = take(Mt * d);
-    w.a1[l] = take(Mt * d);
-    w.qkv[l] = take(Mt * 3 * d);
-    w.ctx[l] = take(Mt * d);
-    w.xmid[l] = take(Mt * d);
-    w.a2[l] = take(Mt * d);
-    w.hdn[l] = take(Mt * f);
+    w.xin[l] = a.take(Mt * d);
+    w.a1[l] = a.take(Mt * d);
+    w.qkv[l] = a.take(Mt * 3 * d);
+    w.ctx[l] = a.take(Mt * d);
+    w.xmid[l] = a.take(Mt * d);
+    w.a2[l] = a.take(Mt * d);
+    w.hdn[l] = a.take(Mt * f);
   }
-  w.dtok = take((size_t)D.T * R * d);
-  w.dpred = take(S * R * D.C);
-  w.dx = take(M * d);
-  w.dx2 = take(M * d);
-  w.dctx = take(M * d);
-  w.dxlast = take(R * d);
+  w.dtok = a.take((size_t)D.T * R * d);
+  w.dpred = a.take(S * R * D.C);
+  w.dx = a.take(M * d);
+  w.dx2 = a.take(M * d);
+  w.dctx = a.take(M * d);
+  w.dxlast = a.take(R * d);
   for (int l = 0; l < D.nl; ++l) {
-    w.dqkv[l] = take(Mt * 3 * d);
-    w.dao[l] = take(Mt * d);
-    w.dpre[l] = take(Mt * f);
-    w.dfo[l] = take(Mt * d);
-    w.da1[l] = take(Mt * d);
-    w.da2[l] = take(Mt * d);
-    w.wt_in[l] = take(3 * d * d);
-    w.wt_o[l] = take(d * d);
-    w.wt_1[l] = take(f * d);
-    w.wt_2[l] = take(f * d);
+    w.dqkv[l] = a.take(Mt * 3 * d);
+    w.dao[l] = a.take(Mt * d);
+    w.dpre[l] = a.take(Mt * f);
+    w.dfo[l] = a.take(Mt * d);
+    w.da1[l] = a.take(Mt * d);
+    w.da2[l] = a.take(Mt * d);
+    w.wt_in[l] = a.take(3 * d * d);
+    w.wt_o[l] = a.take(d * d);
+    w.wt_1[l] = a.take(f * d);
+    w.wt_2[l] = a.take(f * d);
   }
-  w.wt_inproj = take((size_t)D.C * d);
-  w.wt_outproj = take((size_t)D.C * d);
-  w.partial_floats = tn_partial_floats(D);
-  w.partial = take(w.partial_floats);
-  w.total_floats = off;
+  w.wt_inproj = a.take((size_t)D.C * d);
+  w.wt_outproj = a.take((size_t)D.C * d);
+  w.partial = a.take(tn_partial_floats(D));
+  w.bytes = a.bytes();
   return w;
 }
 
-// number of row splits of a weight-gradient contraction: enough workgroups to fill the chip a few times over
-inline int tn_splits(long long rows, int N, int K) {
-  const long long tiles = (long long)(N / 64) * (K / 64);
-  long long s = (512 + tiles - 1) / tiles;
-  const long long max_s = (rows + 63) / 64;
-  if (s > max_s) s = max_s;
-  if (s < 1) s = 1;
-  return (int)s;
-}
 inline size_t tn_partial_floats(const Dims& D) {
   const long long rows = (long long)D.off(D.S);
   size_t best = 0;
@@ -912,8 +533,8 @@ inline size_t tn_partial_floats(const Dims& D) {
   upd(rows, D.d, D.ffn);
   upd((long long)D.T * D.R, D.d, D.C);
   upd((long long)D.S * D.R, D.C, D.d);
-  // column-sum / LayerNorm partials share the buffer: at most 512 groups x 2 x max width
-  const size_t cs = (size_t)512 * 2 * (size_t)(D.ffn > 3 * D.d ? D.ffn : 3 * D.d);
+  // column-sum / LayerNorm partials share the buffer (the LayerNorms are d wide: their scratch record fits behind the group records of 3 d)
+  const size_t cs = sf_colsum_partial_floats(D.ffn > 3 * D.d ? D.ffn : 3 * D.d, 0);
   return best > cs ? best : cs;
 }
 
@@ -945,12 +566,6 @@ int check_model(const sf_rollouter* m, Dims& D, int B, int pred_len) {
   SF_REQUIRE(D.d % D.H == 0 && D.d / D.H <= 64, "head_dim <= 64");
   SF_REQUIRE(D.L <= 128, "window of at most 128 tokens");
   SF_REQUIRE(attn_shape_fits(D.L, D.d / D.H), "attention tile does not fit the 160 KB of LDS");   // (the largest window needs the most)
-  return 0;
-}
-
-int launch_transpose(const float* in, float* out, int R, int Cn, hipStream_t st) {
-  hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(Cn, 32), cdiv(R, 32)), dim3(256), 0, st, in, out, R, Cn);
-  SF_CHECK_LAUNCH();
   return 0;
 }
 
@@ -1014,105 +629,7 @@ int launch_attn_bwd(const float* qkv, const float* dctx, float* dqkv, int B, int
   return 0;
 }
 
-// dW = Y^T X over `rows` rows, written to dW [N, K]
-int grad_weight(const float* Y, const float* X, float* dW, long long rows, int N, int K, const Ws& w, hipStream_t st) {
-  const int splits = tn_splits(rows, N, K);
-  int rps = (int)((rows + splits - 1) / splits);
-  rps = (rps + 31) & ~31;
-  float* dst = splits == 1 ? dW : w.partial;
-  const dim3 grid((N / 64) * (K / 64), splits);
-  if (sf_get_precision() == 0)
-    hipLaunchKernelGGL(grad_gemm_tn_kernel<0>, grid, dim3(256), 0, st, Y, X, dst, rows, rps, N, K);
-  else if (sf_get_precision() == 1)
-    hipLaunchKernelGGL(grad_gemm_tn_kernel<1>, grid, dim3(256), 0, st, Y, X, dst, rows, rps, N, K);
-  else
-    hipLaunchKernelGGL(grad_gemm_tn_kernel<2>, grid, dim3(256), 0, st, Y, X, dst, rows, rps, N, K);
-  SF_CHECK_LAUNCH();
-  if (splits > 1) {
-    const long long n4 = (long long)N * K / 4;
-    launch_reduce_partials(w.partial, dW, splits, n4, st);
-    SF_CHECK_LAUNCH();
-  }
-  return 0;
-}
-
-int grad_bias(const float* Y, float* db, long long rows, int n, const Ws& w, hipStream_t st) {
-  int G = (int)((rows + 127) / 128);
-  if (G > 512) G = 512;
-  const int rpg = (int)((rows + G - 1) / G);
-  G = (int)((rows + rpg - 1) / rpg);
-  int cols = 1;
-  while (cols < n && cols < 256) cols <<= 1;
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(cdiv(n, cols), G), dim3(256), 0, st, Y, w.partial, rows, rpg, n);
-  SF_CHECK_LAUNCH();
-  launch_reduce_partials(w.partial, db, G, (long long)n / 4, st);
-  SF_CHECK_LAUNCH();
-  return 0;
-}
-
-int grad_ln(const float* x, const float* dy, float* dgamma, float* dbeta, long long rows, int D, float eps, const Ws& w,
-            hipStream_t st) {
-  int G = (int)((rows + 63) / 64);
-  if (G > 512) G = 512;
-  const int rpg = (int)((rows + G - 1) / G);
-  G = (int)((rows + rpg - 1) / rpg);
-  hipLaunchKernelGGL(ln_param_partial_kernel, dim3(G), dim3(256), 0, st, x, dy, w.partial, rows, rpg, D, eps);
-  SF_CHECK_LAUNCH();
-  // partial is [G][2][D]: one reduction over both rows, the first D columns to d_gamma and the rest to d_beta
-  if ((((uintptr_t)dgamma | (uintptr_t)dbeta) & 15) == 0) {
-    launch_reduce_partials(w.partial, dgamma, G, (long long)2 * D / 4, st, dbeta, (long long)D / 4);
-    SF_CHECK_LAUNCH();
-    return 0;
-  }
-  // destinations that are not 16-byte aligned (views at odd offsets of a flat bucket): through a [2][D] scratch behind the partials
-  float* both = w.partial + (size_t)G * 2 * D;
-  launch_reduce_partials(w.partial, both, G, (long long)2 * D / 4, st);
-  SF_CHECK_LAUNCH();
-  hipError_t e = hipMemcpyAsync(dgamma, both, D * sizeof(float), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(dbeta, both + D, D * sizeof(float), hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return sf_set_err((int)e, hipGetErrorString(e), __FILE__, __LINE__);
-  return 0;
-}
-
 }  // namespace
-
-// ---- the same building blocks for the other training nodes (slot_attn_train.hip); declared in sf_internal.h ----
-size_t sf_grad_partial_floats(long long rows, int N, int K) {
-  const size_t a = (size_t)tn_splits(rows, N, K) * N * K;
-  const size_t b = (size_t)513 * 2 * (size_t)(N > K ? N : K);   // column-sum / LayerNorm partials
-  return a > b ? a : b;
-}
-int sf_grad_weight_ex(const float* Y, const float* X, float* dW, long long rows, int N, int K, float* partial, hipStream_t st) {
-  SF_REQUIRE(N % 64 == 0 && K % 64 == 0, "weight-gradient contraction needs multiples of 64");
-  Ws w;
-  w.partial = partial;
-  return grad_weight(Y, X, dW, rows, N, K, w, st);
-}
-int sf_grad_bias_ex(const float* Y, float* db, long long rows, int n, float* partial, hipStream_t st) {
-  Ws w;
-  w.partial = partial;
-  return grad_bias(Y, db, rows, n, w, st);
-}
-int sf_grad_ln_ex(const float* x, const float* dy, float* dgamma, float* dbeta, long long rows, int D, float eps, float* partial,
-                  hipStream_t st) {
-  Ws w;
-  w.partial = partial;
-  return grad_ln(x, dy, dgamma, dbeta, rows, D, eps, w, st);
-}
-int sf_ln_bwd_ex(const float* x, const float* dy, const float* gamma, const float* dres, float* out, long long rows, int D,
-                 float eps, hipStream_t st) {
-  SF_REQUIRE(D % 4 == 0 && D <= 1024, "LayerNorm width");
-  hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, dy, gamma, dres, out, (float*)nullptr, 0u, 0u, 1.f,
-                     (int)rows, D, eps);
-  SF_CHECK_LAUNCH();
-  return 0;
-}
-int sf_transpose_ex(const float* in, float* out, int R, int Cn, hipStream_t st) { return launch_transpose(in, out, R, Cn, st); }
-int sf_relu_bwd_ex(float* dh, const float* h, long long n, hipStream_t st) {
-  hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, dh, h, n / 4, 1.f);
-  SF_CHECK_LAUNCH();
-  return 0;
-}
 
 // The training forward from the point where the burn-in frames lie frame-major in the workspace's slots_all ([hist][B * N][C]): their
 // in-projections, then every step.  sf_rollout_train_fwd_f32 copies x there, sf_rollout_train_clips_fwd_f32 (clip_train.hip) reads a slot table.
@@ -1122,9 +639,8 @@ int sf_rollout_train_steps_ex(const sf_rollouter* m, float* pred, int B, int pre
   SF_TRY(check_model(m, D, B, pred_len));
   SF_REQUIRE(pred && ws, "null pointer");
   SF_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p in [0, 1)");
-  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  const Ws w = carve(D, base);
-  SF_REQUIRE(w.total_floats * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const Ws w = carve(D, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   const int d = D.d, f = D.ffn, R = D.R, N = D.N, C = D.C, hd = d / D.H;
   const uint32_t thr = drop_thresh(dropout_p);
   const float inv_keep = 1.f / (1.f - dropout_p);
@@ -1180,9 +696,8 @@ int sf_rollout_train_burnin_ex(const sf_rollouter* m, int B, int pred_len, void*
   Dims D;
   SF_TRY(check_model(m, D, B, pred_len));
   SF_REQUIRE(ws, "null pointer");
-  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  const Ws w = carve(D, base);
-  SF_REQUIRE(w.total_floats * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const Ws w = carve(D, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   *slots_all = w.slots_all;
   *hist = D.hist;
   return 0;
@@ -1190,32 +705,6 @@ int sf_rollout_train_burnin_ex(const sf_rollouter* m, int B, int pred_len, void*
 
 extern "C" {
 
-// ---- differentiable building blocks for the slot-level layers (predictor, kernel distribution; savi.py:190-200,
-// predictor.py:47-73): backward of y = act(x W^T + b) and of LayerNorm, on the same kernels as the big nodes ----
-size_t sf_linear_bwd_workspace_bytes(long long M, int N, int K) {
-  return (sf_grad_partial_floats(M, N, K) + (size_t)N * K + 128) * sizeof(float) + 256;
-}
-// dy [M,N] is overwritten when relu != 0 (masked by y > 0).  dx [M,K] (may be NULL), dW [N,K], db [N] (may be NULL).
-int sf_linear_bwd_f32(const float* x, const float* W, const float* y, float* dy, float* dx, float* dW, float* db, long long M,
-                      int N, int K, int relu, void* ws, size_t ws_bytes, void* stream) {
-  SF_REQUIRE(x && W && dy && dW && ws && M > 0, "null pointer");
-  SF_REQUIRE(N % 64 == 0 && K % 64 == 0, "linear backward needs multiples of 64");
-  SF_REQUIRE(ws_bytes >= sf_linear_bwd_workspace_bytes(M, N, K), "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  float* wt = partial + ((sf_grad_partial_floats(M, N, K) + 63) & ~(size_t)63);
-  if (relu) {
-    SF_REQUIRE(y != nullptr, "relu backward needs the forward output");
-    SF_TRY(sf_relu_bwd_ex(dy, y, M * N, st));
-  }
-  SF_TRY(sf_grad_weight_ex(dy, x, dW, M, N, K, partial, st));
-  if (db) SF_TRY(sf_grad_bias_ex(dy, db, M, N, partial, st));
-  if (dx) {
-    SF_TRY(launch_transpose(W, wt, N, K, st));   // [N,K] -> [K,N]
-    SF_TRY(sf_linear_ex(dy, sf_rows(N), wt, nullptr, nullptr, nullptr, 0.f, nullptr, sf_rows(K), 0, dx, sf_rows(K), (int)M, K, N, 0, st));
-  }
-  return 0;
-}
 // attention core of nn.MultiheadAttention for training (qkv [B*L, 3d] -> ctx [B*L, d]; dropout on the softmax weights, masks
 // a pure function of (seed, element)) and its backward (recomputes the probabilities; nothing saved but qkv)
 int sf_mha_train_fwd_f32(const float* qkv, float* ctx, int B, int L, int d_model, int num_heads, float dropout_p,
@@ -1246,48 +735,10 @@ int sf_dropout_f32(const float* x, const float* res, float* y, long long n, floa
   return 0;
 }
 
-// torch.optim.Adam (no amsgrad, no weight decay: the reference's optimiser, slotformer_clevrer_params.py:16-19) over ONE flat
-// fp32 bucket: p, g, m, v [n]; step = the 1-based step count.  One launch per optimiser step.
-__global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
-                                                        float bc1, float bc2_sqrt) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float gi = g[i];
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  // torch: denom = sqrt(v) / sqrt(bias_correction2) + eps;  p -= (lr / bias_correction1) * m / denom
-  p[i] -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-}
-int sf_adam_flat_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, int step, float lr, float beta1,
-                     float beta2, float eps, void* stream) {
-  SF_REQUIRE(param && grad && exp_avg && exp_avg_sq && n >= 0 && step >= 1, "bad Adam arguments");
-  if (n == 0) return 0;
-  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adam_flat_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                     beta1, beta2, eps, bc1, sqrtf(bc2));
-  SF_CHECK_LAUNCH();
-  return 0;
-}
-
-size_t sf_layernorm_bwd_workspace_bytes(int D) { return ((size_t)513 * 2 * D + 128) * sizeof(float) + 256; }
-int sf_layernorm_bwd_f32(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta, long long rows,
-                         int D, float eps, void* ws, size_t ws_bytes, void* stream) {
-  SF_REQUIRE(x && dy && gamma && dx && dgamma && dbeta && ws && rows > 0, "null pointer");
-  SF_REQUIRE(D > 0 && D % 4 == 0 && D <= 1024, "LayerNorm width");   // (before the parameter-gradient launch, which assumes it too)
-  SF_REQUIRE(ws_bytes >= sf_layernorm_bwd_workspace_bytes(D), "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  SF_TRY(sf_grad_ln_ex(x, dy, dgamma, dbeta, rows, D, eps, partial, st));
-  return sf_ln_bwd_ex(x, dy, gamma, nullptr, dx, rows, D, eps, st);
-}
-
 size_t sf_rollout_train_workspace_bytes(const sf_rollouter* m, int B, int pred_len) {
   Dims D;
   if (check_model(m, D, B, pred_len) != 0) return 0;
-  return carve(D, nullptr).total_floats * sizeof(float) + 256;
+  return carve(D, nullptr).bytes + WS_SLACK;
 }
 
 int sf_rollout_train_fwd_f32(const sf_rollouter* m, const float* x, float* pred, int B, int pred_len, float dropout_p,
@@ -1313,9 +764,8 @@ int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* 
   SF_TRY(check_model(m, D, B, pred_len));
   SF_REQUIRE(d_pred && g && g->layers && ws, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  const Ws w = carve(D, base);
-  SF_REQUIRE(w.total_floats * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const Ws w = carve(D, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   const int d = D.d, f = D.ffn, R = D.R, N = D.N, C = D.C, hd = d / D.H;
   const uint32_t thr = drop_thresh(dropout_p);
   const float inv_keep = 1.f / (1.f - dropout_p);
@@ -1324,13 +774,13 @@ int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* 
   // transposed weight copies: the data-gradient GEMMs run on the forward core (C = A . W^T)
   for (int l = 0; l < D.nl; ++l) {
     const sf_tfm_layer& ly = m->layers[l];
-    SF_TRY(launch_transpose(ly.in_proj_w, w.wt_in[l], 3 * d, d, st));   // [3d,d] -> [d,3d]
-    SF_TRY(launch_transpose(ly.out_proj_w, w.wt_o[l], d, d, st));
-    SF_TRY(launch_transpose(ly.lin1_w, w.wt_1[l], f, d, st));           // [f,d] -> [d,f]
-    SF_TRY(launch_transpose(ly.lin2_w, w.wt_2[l], d, f, st));           // [d,f] -> [f,d]
+    SF_TRY(sf_transpose_ex(ly.in_proj_w, w.wt_in[l], 3 * d, d, st));   // [3d,d] -> [d,3d]
+    SF_TRY(sf_transpose_ex(ly.out_proj_w, w.wt_o[l], d, d, st));
+    SF_TRY(sf_transpose_ex(ly.lin1_w, w.wt_1[l], f, d, st));           // [f,d] -> [d,f]
+    SF_TRY(sf_transpose_ex(ly.lin2_w, w.wt_2[l], d, f, st));           // [d,f] -> [f,d]
   }
-  SF_TRY(launch_transpose(m->in_proj_w, w.wt_inproj, d, C, st));        // [d,C] -> [C,d]
-  SF_TRY(launch_transpose(m->out_proj_w, w.wt_outproj, C, d, st));      // [C,d] -> [d,C]
+  SF_TRY(sf_transpose_ex(m->in_proj_w, w.wt_inproj, d, C, st));        // [d,C] -> [C,d]
+  SF_TRY(sf_transpose_ex(m->out_proj_w, w.wt_outproj, C, d, st));      // [C,d] -> [d,C]
 
   hipError_t e = hipMemsetAsync(w.dtok, 0, (size_t)D.T * R * d * sizeof(float), st);
   if (e != hipSuccess) return sf_set_err((int)e, hipGetErrorString(e), __FILE__, __LINE__);
@@ -1371,18 +821,15 @@ int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* 
       SF_TRY(sf_linear_masked_ex(dfo, w.wt_2[l], w.hdn[l] + so * f, thr ? inv_keep : 1.f, dpre, M, f, d, st));
       SF_TRY(gemm(dpre, w.wt_1[l], nullptr, nullptr, da2, M, d, f, 0, st));
       // xmid = xin + drop(attn_o): dxo = gradient w.r.t. xmid, dao = the same through the attention-output dropout
-      hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, w.xmid[l] + so * d, da2, ly.norm2_g, dx, dxo, dao,
-                         site_seed(seed, s, l, SITE_ATTN_O), thr, inv_keep, M, d, 1e-5f);
-      SF_CHECK_LAUNCH();
+      SF_TRY(sf_ln_bwd_dropout_ex(w.xmid[l] + so * d, da2, ly.norm2_g, dx, dxo, dao, site_seed(seed, s, l, SITE_ATTN_O), thr, inv_keep, M, d,
+                                  1e-5f, st));
       SF_TRY(gemm(dao, w.wt_o[l], nullptr, nullptr, w.dctx, M, d, d, 0, st));
       SF_TRY(launch_attn_bwd(w.qkv[l] + so * 3 * d, w.dctx, dqkv, B, D.H, L, d, site_seed(seed, s, l, SITE_ATTN_P), thr, inv_keep,
                              st));
       SF_TRY(gemm(dqkv, w.wt_in[l], nullptr, nullptr, da1, M, d, 3 * d, 0, st));
       // dx = gradient w.r.t. this layer's input = the output of layer l-1, whose FFN-output dropout is folded in
-      hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, w.xin[l] + so * d, da1, ly.norm1_g, dxo, dx,
-                         l > 0 ? w.dfo[l - 1] + so * d : (float*)nullptr, site_seed(seed, s, l > 0 ? l - 1 : 0, SITE_FFN_O), thr,
-                         inv_keep, M, d, 1e-5f);
-      SF_CHECK_LAUNCH();
+      SF_TRY(sf_ln_bwd_dropout_ex(w.xin[l] + so * d, da1, ly.norm1_g, dxo, dx, l > 0 ? w.dfo[l - 1] + so * d : (float*)nullptr,
+                                  site_seed(seed, s, l > 0 ? l - 1 : 0, SITE_FFN_O), thr, inv_keep, M, d, 1e-5f, st));
     }
     hipLaunchKernelGGL(window_scatter_kernel, dim3(cdiv(Md4, 256)), dim3(256), 0, st, dx, w.dtok + (size_t)D.f0(s) * R * d, B, L,
                        N, d / 4);
@@ -1406,22 +853,22 @@ int sf_rollout_train_bwd_f32(const sf_rollouter* m, const float* d_pred, float* 
   // last predicted frame is never fed back).
   const long long rows = (long long)D.off(D.S);
   const long long in_rows = (long long)(D.T - 1) * R;
-  SF_TRY(grad_weight(w.dtok, w.slots_all, g->in_proj_w, in_rows, d, C, w, st));
-  SF_TRY(grad_bias(w.dtok, g->in_proj_b, in_rows, d, w, st));
-  SF_TRY(grad_weight(w.dpred, w.xlast, g->out_proj_w, (long long)D.S * R, C, d, w, st));
-  SF_TRY(grad_bias(w.dpred, g->out_proj_b, (long long)D.S * R, C, w, st));
+  SF_TRY(sf_grad_weight_ex(w.dtok, w.slots_all, g->in_proj_w, in_rows, d, C, w.partial, st));
+  SF_TRY(sf_grad_bias_ex(w.dtok, g->in_proj_b, in_rows, d, w.partial, st));
+  SF_TRY(sf_grad_weight_ex(w.dpred, w.xlast, g->out_proj_w, (long long)D.S * R, C, d, w.partial, st));
+  SF_TRY(sf_grad_bias_ex(w.dpred, g->out_proj_b, (long long)D.S * R, C, w.partial, st));
   for (int l = 0; l < D.nl; ++l) {
     const sf_tfm_layer_grads& gl = g->layers[l];
-    SF_TRY(grad_weight(w.dqkv[l], w.a1[l], gl.in_proj_w, rows, 3 * d, d, w, st));
-    SF_TRY(grad_bias(w.dqkv[l], gl.in_proj_b, rows, 3 * d, w, st));
-    SF_TRY(grad_weight(w.dao[l], w.ctx[l], gl.out_proj_w, rows, d, d, w, st));
-    SF_TRY(grad_bias(w.dao[l], gl.out_proj_b, rows, d, w, st));
-    SF_TRY(grad_weight(w.dpre[l], w.a2[l], gl.lin1_w, rows, f, d, w, st));
-    SF_TRY(grad_bias(w.dpre[l], gl.lin1_b, rows, f, w, st));
-    SF_TRY(grad_weight(w.dfo[l], w.hdn[l], gl.lin2_w, rows, d, f, w, st));
-    SF_TRY(grad_bias(w.dfo[l], gl.lin2_b, rows, d, w, st));
-    SF_TRY(grad_ln(w.xin[l], w.da1[l], gl.norm1_g, gl.norm1_b, rows, d, 1e-5f, w, st));
-    SF_TRY(grad_ln(w.xmid[l], w.da2[l], gl.norm2_g, gl.norm2_b, rows, d, 1e-5f, w, st));
+    SF_TRY(sf_grad_weight_ex(w.dqkv[l], w.a1[l], gl.in_proj_w, rows, 3 * d, d, w.partial, st));
+    SF_TRY(sf_grad_bias_ex(w.dqkv[l], gl.in_proj_b, rows, 3 * d, w.partial, st));
+    SF_TRY(sf_grad_weight_ex(w.dao[l], w.ctx[l], gl.out_proj_w, rows, d, d, w.partial, st));
+    SF_TRY(sf_grad_bias_ex(w.dao[l], gl.out_proj_b, rows, d, w.partial, st));
+    SF_TRY(sf_grad_weight_ex(w.dpre[l], w.a2[l], gl.lin1_w, rows, f, d, w.partial, st));
+    SF_TRY(sf_grad_bias_ex(w.dpre[l], gl.lin1_b, rows, f, w.partial, st));
+    SF_TRY(sf_grad_weight_ex(w.dfo[l], w.hdn[l], gl.lin2_w, rows, d, f, w.partial, st));
+    SF_TRY(sf_grad_bias_ex(w.dfo[l], gl.lin2_b, rows, d, w.partial, st));
+    SF_TRY(sf_grad_ln_ex(w.xin[l], w.da1[l], gl.norm1_g, gl.norm1_b, rows, d, 1e-5f, w.partial, st));
+    SF_TRY(sf_grad_ln_ex(w.xmid[l], w.da2[l], gl.norm2_g, gl.norm2_b, rows, d, 1e-5f, w.partial, st));
   }
   return 0;
 }

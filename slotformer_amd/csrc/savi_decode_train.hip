@@ -9,6 +9,8 @@
 //            (sf_conv2d_nhwc_strided_ex on the GEMM core's im2col loader), then the sum over the broadcast grid.
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
+#include "sf_arena.h"
 
 // d_dec [F*N, HW, 4] from d_recon [F, 3, HW]:  d_rgb_n = m_n d_recon;  d_alpha_n = m_n (rgb_n.d_recon - sum_k m_k rgb_k.d_recon)
 __global__ __launch_bounds__(256) void decode_combine_bwd_kernel(const float* __restrict__ dec, const float* __restrict__ d_recon,
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void head_grad_reduce_kernel(const float* __re
 // The head block of the backward: d_recon [F,3,HW] -> d_dec [F*N,HW,4] (recombination + softmax adjoint), the 1x1 head's weight [4,Cl] and bias [4]
 // gradients (optional), and d_act [F*N*HW,Cl] = d_dec . W_out gated by act > 0 (the ReLU of the last transposed conv; the GEMM core wants the
 // transpose of W_out [4,Cl] as its weight operand).  wout_t [4*Cl], partial [HEAD_PARTIAL_FLOATS]: scratch.
-static constexpr size_t HEAD_PARTIAL_FLOATS = (size_t)513 * 2 * 256;   // bias column sums, head partials
+static constexpr size_t HEAD_PARTIAL_FLOATS = sf_colsum_partial_floats(256);   // bias column sums, head partials
 static int head_bwd(const float* dec, const float* d_recon, const float* act, const float* out_w, float* d_dec, float* d_act, float* d_out_w,
                     float* d_out_b, int F, int N, int HW, int Cl, float* wout_t, float* partial, hipStream_t st) {
   const long long rows = (long long)F * N * HW;
@@ -93,7 +95,7 @@ static int head_bwd(const float* dec, const float* d_recon, const float* act, co
     SF_CHECK_LAUNCH();
   }
   if (d_out_w) {
-    int G = 512;
+    int G = SF_GRAD_MAX_GROUPS;
     const int rpg = (int)((rows + G - 1) / G);
     G = (int)((rows + rpg - 1) / rpg);
     hipLaunchKernelGGL(head_grad_partial_kernel, dim3(G), dim3(256), 0, st, d_dec, act, partial, rows, rpg, Cl);
@@ -111,54 +113,48 @@ struct DecWs {
   float* act[9];   // act[0]: broadcast input, act[l+1]: output of transposed conv l (post-ReLU)
   float *dec, *ga, *gb, *wout_t, *partial, *dtab;
   float* wf;       // fragment-ordered copy of a stride-1 64 -> 64 layer's weights (forward, then backward-data) for conv_rows4.hip
-  size_t total;
+  size_t bytes;
 };
-size_t pad64(size_t n) { return (n + 63) & ~(size_t)63; }
+constexpr size_t WS_SLACK = 256;   // bytes a caller's workspace holds beyond either carve of this file
 
-DecWs carve(const sf_savi_decoder* m, int F, float* base) {
+DecWs carve(const sf_savi_decoder* m, int F, void* ws) {
   DecWs w;
   memset(&w, 0, sizeof(w));
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += pad64(n);
-    return p;
-  };
+  SfArena ar(ws);
   const size_t R = (size_t)F * m->num_slots;
   int h = m->dec_res;
   size_t gmax = R * h * h * m->dec_channels[0];
-  w.act[0] = take(gmax);
+  w.act[0] = ar.take(gmax);
   for (int l = 0; l < m->dec_layers; ++l) {
     h *= m->dec_strides[l];
     const size_t n = R * h * h * m->dec_channels[l + 1];
-    w.act[l + 1] = take(n);
+    w.act[l + 1] = ar.take(n);
     gmax = n > gmax ? n : gmax;
   }
-  w.dec = take(R * h * h * 4);
-  w.ga = take(gmax);
-  w.gb = take(gmax);
-  w.wout_t = take((size_t)4 * m->dec_channels[m->dec_layers]);
+  w.dec = ar.take(R * h * h * 4);
+  w.ga = ar.take(gmax);
+  w.gb = ar.take(gmax);
+  w.wout_t = ar.take((size_t)4 * m->dec_channels[m->dec_layers]);
   {
     size_t pf = HEAD_PARTIAL_FLOATS;
     for (int l = 0; l < m->dec_layers; ++l) {
       const size_t a = sf_conv_wgrad_partial_floats(m->dec_channels[l], m->dec_ks);
       pf = a > pf ? a : pf;
     }
-    w.partial = take(pf);
+    w.partial = ar.take(pf);
   }
-  w.dtab = take((size_t)m->dec_res * m->dec_res * m->slot_size);
-  w.wf = take((sf_conv_frag_bytes(64, 64, 5) + 3) / 4);
-  w.total = off;
+  w.dtab = ar.take((size_t)m->dec_res * m->dec_res * m->slot_size);
+  w.wf = ar.take((sf_conv_frag_bytes(64, 64, 5) + 3) / 4);
+  w.bytes = ar.bytes();
   return w;
 }
 
-// stride-1 5x5 64 -> 64 layer on a 64-pixel-wide map: the 4-row-tile kernel on a fragment-ordered copy of the OHWI weights (conv_rows4.hip: the same
-// products in the same order as the halo kernel behind sf_conv2d_nhwc_f32); 1 = not that shape / arithmetic mode
-int conv5_rows4(const float* in, const float* w_ohwi, float* w_frag, const float* bias, const float* add, float* out, int R, int h, int cin, int cout,
-                int ks, int relu, hipStream_t st) {
-  if (!w_frag || h != 64 || sf_get_precision() != 1 || !sf_conv_frag_bytes(cout, cin, ks)) return 1;
-  SF_TRY(sf_pack_conv_frag_weights(w_ohwi, w_frag, cout, cin, ks, st));
-  return sf_conv5x5_rows4_ex(in, w_frag, bias, add, out, R, h, h, cin, cout, ks, relu, st);
+// the scratch of the head backward alone (sf_savi_decode_head_bwd_f32)
+struct HeadWs { float *wout_t, *partial; size_t bytes; };
+HeadWs head_carve(int Cl, void* ws) {
+  SfArena ar(ws);
+  float* wout_t = ar.take((size_t)4 * Cl);
+  return HeadWs{wout_t, ar.take(HEAD_PARTIAL_FLOATS), ar.bytes()};
 }
 
 int check(const sf_savi_decoder* m, int F) {
@@ -181,23 +177,24 @@ extern "C" {
 
 size_t sf_savi_decode_train_workspace_bytes(const sf_savi_decoder* m, int F) {
   if (check(m, F) != 0) return 0;
-  return carve(m, F, nullptr).total * sizeof(float) + 256;
+  return carve(m, F, nullptr).bytes + WS_SLACK;
 }
 
 int sf_savi_decode_train_fwd_f32(const sf_savi_decoder* m, const float* slots, float* recon_combined, float* recons, float* masks,
                                  int F, void* ws, size_t ws_bytes, void* stream) {
   SF_TRY(check(m, F));
   SF_REQUIRE(slots && recon_combined && ws, "null pointer");
-  const DecWs w = carve(m, F, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const DecWs w = carve(m, F, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int N = m->num_slots, D = m->slot_size, R = F * N, HW = m->resolution * m->resolution;
   SF_TRY(sf_slot_broadcast_f32(slots, m->pos_table, w.act[0], R, m->dec_res * m->dec_res, D, st));
   int hin = m->dec_res;
   for (int l = 0; l < m->dec_layers; ++l) {
     if (m->dec_strides[l] == 1 && m->deconv_w_flipped[l]) {   // = convolution with the flipped kernel (4-row-tile / halo-resident 5x5 paths)
-      int rc = conv5_rows4(w.act[l], m->deconv_w_flipped[l], w.wf, m->deconv_b[l], nullptr, w.act[l + 1], R, hin, m->dec_channels[l],
-                           m->dec_channels[l + 1], m->dec_ks, 1, st);
+      // the 4-row-tile kernel on a fragment-ordered copy of the OHWI weights where it applies (conv_rows4.hip: the same products in the same order)
+      int rc = sf_conv5x5_rows4_ohwi_ex(w.act[l], m->deconv_w_flipped[l], w.wf, m->deconv_b[l], nullptr, w.act[l + 1], R, hin, hin,
+                                        m->dec_channels[l], m->dec_channels[l + 1], m->dec_ks, 1, st);
       if (rc == 1)
         rc = sf_conv2d_nhwc_f32(w.act[l], m->deconv_w_flipped[l], m->deconv_b[l], nullptr, w.act[l + 1], R, hin, hin, m->dec_channels[l],
                                 m->dec_channels[l + 1], m->dec_ks, 1, st);
@@ -223,8 +220,8 @@ int sf_savi_decode_train_bwd_f32(const sf_savi_decoder* m, const float* const* d
     for (int l = 0; l < m->dec_layers; ++l)
       SF_REQUIRE(m->dec_channels[l + 1] == 64 && m->dec_channels[l] % 64 == 0 && m->dec_channels[m->dec_layers] <= 64,
                  "decoder weight gradients need 64-channel layers (the reference decoder)");
-  const DecWs w = carve(m, F, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const DecWs w = carve(m, F, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int N = m->num_slots, D = m->slot_size, R = F * N, HW = m->resolution * m->resolution, L = m->dec_layers;
   const int Cl = m->dec_channels[L];
@@ -246,7 +243,8 @@ int sf_savi_decode_train_bwd_f32(const sf_savi_decoder* m, const float* const* d
     // (act[0] is the broadcast input: no ReLU there)
     int rc = 1;
     if (m->dec_strides[l] == 1 && l >= 1)
-      rc = conv5_rows4(g, deconv_w_bwd[l], w.wf, nullptr, w.act[l], o, R, h, m->dec_channels[l + 1], m->dec_channels[l], m->dec_ks, 2, st);
+      rc = sf_conv5x5_rows4_ohwi_ex(g, deconv_w_bwd[l], w.wf, nullptr, w.act[l], o, R, h, h, m->dec_channels[l + 1], m->dec_channels[l], m->dec_ks, 2,
+                                    st);
     if (rc == 1)
       rc = sf_conv2d_nhwc_strided_ex(g, deconv_w_bwd[l], nullptr, o, R, h, h, m->dec_channels[l + 1], m->dec_channels[l], m->dec_ks,
                                      m->dec_strides[l], 0, st, l >= 1 ? w.act[l] : nullptr);
@@ -264,7 +262,7 @@ int sf_savi_decode_train_bwd_f32(const sf_savi_decoder* m, const float* const* d
 
 size_t sf_savi_decode_head_bwd_workspace_bytes(int Cl) {
   if (Cl < 4 || Cl > 64 || Cl % 4) return 0;
-  return (pad64((size_t)4 * Cl) + HEAD_PARTIAL_FLOATS) * sizeof(float) + 256;
+  return head_carve(Cl, nullptr).bytes + WS_SLACK;
 }
 
 int sf_savi_decode_head_bwd_f32(const float* dec, const float* d_recon, const float* act, const float* out_w, float* d_dec, float* d_act,
@@ -275,8 +273,8 @@ int sf_savi_decode_head_bwd_f32(const float* dec, const float* d_recon, const fl
   SF_REQUIRE(((uintptr_t)dec & 15) == 0 && ((uintptr_t)d_dec & 15) == 0 && ((uintptr_t)act & 15) == 0,
              "sf_savi_decode_head_bwd_f32: dec, d_dec and act must be 16-byte aligned");
   SF_REQUIRE(sf_savi_decode_head_bwd_workspace_bytes(Cl) <= ws_bytes, "sf_savi_decode_head_bwd_f32: workspace too small");
-  float* base = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  return head_bwd(dec, d_recon, act, out_w, d_dec, d_act, d_out_w, d_out_b, F, N, HW, Cl, base, base + pad64((size_t)4 * Cl), (hipStream_t)stream);
+  const HeadWs w = head_carve(Cl, ws);
+  return head_bwd(dec, d_recon, act, out_w, d_dec, d_act, d_out_w, d_out_b, F, N, HW, Cl, w.wout_t, w.partial, (hipStream_t)stream);
 }
 
 }  // extern "C"

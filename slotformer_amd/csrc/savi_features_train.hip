@@ -3,7 +3,7 @@
 //
 //   forward : conv0 (NCHW image, 3 -> 64, stride 2 at 128x128) + ReLU, convs 1.. (64 -> 64 on the halo-resident 5x5 kernel)
 //             + ReLU except after the last, + position table, LN -> Linear + ReLU -> Linear.  All layer outputs are kept.
-//   backward: MLP (weight gradients on the split-bf16 TN contraction of rollout_train.hip), LayerNorm, position-embedding
+//   backward: MLP (weight gradients on the split-bf16 TN contraction of train_blocks.hip), LayerNorm, position-embedding
 //             Linear(4 -> C) from the frame-summed gradient, then per conv: bias = column sum, weight gradient =
 //             conv_wgrad_kernel (the same TN contraction with the activation rows shifted by the tap: one 64x64 output
 //             tile per tap, no im2col buffer), data gradient = the convolution of the gradient with the flipped /
@@ -11,6 +11,8 @@
 //             an im2col matrix of the image (K = 75 padded to 128; the only materialised patch matrix).
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
+#include "sf_arena.h"
 
 #define CW_P 68
 
@@ -385,29 +387,25 @@ static int conv_first_wgrad(const float* img, long long frame_stride, int res, c
   return 0;
 }
 namespace {
+constexpr size_t WS_SLACK = 256;   // bytes a caller's workspace holds beyond either carve of this file
 struct CfwWs {
   float *P, *dw0, *partial;
-  size_t total;
+  size_t bytes;
 };
-CfwWs cfw_carve(int F, float* base) {
+CfwWs cfw_carve(int F, void* ws) {
   CfwWs w;
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + 63) & ~(size_t)63;
-    return p;
-  };
+  SfArena a(ws);
   const size_t M = (size_t)F * 4096;
-  w.P = take(M * 128);
-  w.dw0 = take((size_t)64 * 128);
-  w.partial = take(sf_grad_partial_floats((long long)M, 64, 128));
-  w.total = off;
+  w.P = a.take(M * 128);
+  w.dw0 = a.take((size_t)64 * 128);
+  w.partial = a.take(sf_grad_partial_floats((long long)M, 64, 128));
+  w.bytes = a.bytes();
   return w;
 }
 }  // namespace
 extern "C" size_t sf_conv_first_wgrad_workspace_bytes(int F) {
   if (F < 1 || F > 4096) return 0;
-  return cfw_carve(F, nullptr).total * sizeof(float) + 256;
+  return cfw_carve(F, nullptr).bytes + WS_SLACK;
 }
 extern "C" int sf_conv_first_wgrad_f32(const float* img, long long frame_stride, int resolution, const float* dY, int F, float* dW, void* ws,
                                        size_t ws_bytes, void* stream) {
@@ -416,8 +414,8 @@ extern "C" int sf_conv_first_wgrad_f32(const float* img, long long frame_stride,
   SF_REQUIRE(F >= 1 && F <= 4096, "sf_conv_first_wgrad_f32: bad frame count");
   SF_REQUIRE(frame_stride >= 3LL * resolution * resolution, "sf_conv_first_wgrad_f32: frame_stride smaller than a frame");
   SF_REQUIRE(((uintptr_t)dY & 15) == 0, "sf_conv_first_wgrad_f32: dY must be 16-byte aligned");
-  const CfwWs w = cfw_carve(F, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "sf_conv_first_wgrad_f32: workspace too small");
+  const CfwWs w = cfw_carve(F, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "sf_conv_first_wgrad_f32: workspace too small");
   return conv_first_wgrad(img, frame_stride, resolution, dY, (long long)F * 4096, 64, w.P, w.dw0, w.partial, dW, (hipStream_t)stream);
 }
 
@@ -431,39 +429,34 @@ struct FWs {
   float* wb[8];    // backward-data weights (layers >= 1)
   float* wf[8];    // fragment-ordered copy of the weights in use (forward, then backward-data) for the 4-row-tile kernel (conv_rows4.hip)
   float *table, *a[8], *xn, *h1, *g1, *ga, *gb, *w1t, *w2t, *dtab, *dw0, *partial;
-  size_t total;
+  size_t bytes;
 };
-FWs carve(const FDims& d, float* base) {
+FWs carve(const FDims& d, void* ws) {
   FWs w;
   memset(&w, 0, sizeof(w));
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + 63) & ~(size_t)63;
-    return p;
-  };
+  SfArena ar(ws);
   const size_t M = d.M, C = d.C, wsz = C * 25 * C;
   for (int i = 1; i < d.L; ++i) {
-    w.wp[i] = take(wsz);
-    w.wb[i] = take(wsz);
-    w.wf[i] = take((sf_conv_frag_bytes((int)C, (int)C, 5) + 3) / 4);
+    w.wp[i] = ar.take(wsz);
+    w.wb[i] = ar.take(wsz);
+    w.wf[i] = ar.take((sf_conv_frag_bytes((int)C, (int)C, 5) + 3) / 4);
   }
-  w.table = take((size_t)4096 * C);
-  for (int i = 0; i < d.L; ++i) w.a[i] = take(M * C);
-  w.xn = take(M * C);
-  w.h1 = take(M * d.Hd);
-  w.g1 = take(M * (d.Hd > 128 ? d.Hd : 128));
-  w.ga = take(M * (C > d.Co ? C : d.Co));
-  w.gb = take(M * C);
-  w.w1t = take((size_t)d.Hd * C);
-  w.w2t = take((size_t)d.Hd * d.Co);
-  w.dtab = take((size_t)4096 * C);
-  w.dw0 = take((size_t)C * 128);
+  w.table = ar.take((size_t)4096 * C);
+  for (int i = 0; i < d.L; ++i) w.a[i] = ar.take(M * C);
+  w.xn = ar.take(M * C);
+  w.h1 = ar.take(M * d.Hd);
+  w.g1 = ar.take(M * (d.Hd > 128 ? d.Hd : 128));
+  w.ga = ar.take(M * (C > d.Co ? C : d.Co));
+  w.gb = ar.take(M * C);
+  w.w1t = ar.take((size_t)d.Hd * C);
+  w.w2t = ar.take((size_t)d.Hd * d.Co);
+  w.dtab = ar.take((size_t)4096 * C);
+  w.dw0 = ar.take((size_t)C * 128);
   size_t pf = sf_grad_partial_floats(d.M, d.Hd, d.C);
   const size_t alt[] = {sf_grad_partial_floats(d.M, d.Co, d.Hd), sf_grad_partial_floats(d.M, C, 128), sf_conv_wgrad_partial_floats(C, 5)};
   for (size_t x : alt) pf = x > pf ? x : pf;
-  w.partial = take(pf);
-  w.total = off;
+  w.partial = ar.take(pf);
+  w.bytes = ar.bytes();
   return w;
 }
 int check(const sf_savi_features* m, FDims& d, int F) {
@@ -484,12 +477,8 @@ int gemm(const float* A, const float* W, const float* bias, float* C, long long 
 // 5x5 64 -> 64 convolution on the 64 x 64 grid: the 4-row-tile kernel on a fragment-ordered copy of the OHWI weights (conv_rows4.hip; the same
 // products in the same order as the halo kernel behind sf_conv2d_nhwc_f32, which stays the fallback for the arithmetic modes rows4 does not cover)
 int conv5(const float* in, const float* w_ohwi, float* w_frag, const float* bias, const float* add, float* out, int F, int C, int relu, hipStream_t st) {
-  if (w_frag && sf_get_precision() == 1 && sf_conv_frag_bytes(C, C, 5)) {
-    SF_TRY(sf_pack_conv_frag_weights(w_ohwi, w_frag, C, C, 5, st));
-    const int rc = sf_conv5x5_rows4_ex(in, w_frag, bias, add, out, F, 64, 64, C, C, 5, relu, st);
-    if (rc != 1) return rc;
-  }
-  return sf_conv2d_nhwc_f32(in, w_ohwi, bias, add, out, F, 64, 64, C, C, 5, relu, st);
+  const int rc = sf_conv5x5_rows4_ohwi_ex(in, w_ohwi, w_frag, bias, add, out, F, 64, 64, C, C, 5, relu, st);
+  return rc != 1 ? rc : sf_conv2d_nhwc_f32(in, w_ohwi, bias, add, out, F, 64, 64, C, C, 5, relu, st);
 }
 }  // namespace
 
@@ -498,7 +487,7 @@ extern "C" {
 size_t sf_savi_features_train_workspace_bytes(const sf_savi_features* m, int F) {
   FDims d;
   if (check(m, d, F) != 0) return 0;
-  return carve(d, nullptr).total * sizeof(float) + 256;
+  return carve(d, nullptr).bytes + WS_SLACK;
 }
 
 int sf_savi_features_train_fwd_f32(const sf_savi_features* m, const float* img, long long frame_stride, int F, float* out, void* ws,
@@ -506,8 +495,8 @@ int sf_savi_features_train_fwd_f32(const sf_savi_features* m, const float* img, 
   FDims d;
   SF_TRY(check(m, d, F));
   SF_REQUIRE(img && out && ws, "null pointer");
-  const FWs w = carve(d, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const FWs w = carve(d, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int C = d.C, L = d.L;
   SF_TRY(sf_pos_embed_table_f32(m->pos_grid, m->pos_w, m->pos_b, w.table, 4096, C, st));
@@ -527,8 +516,8 @@ int sf_savi_features_train_bwd_f32(const sf_savi_features* m, const float* img, 
   FDims d;
   SF_TRY(check(m, d, F));
   SF_REQUIRE(img && d_out && g && ws, "null pointer");
-  const FWs w = carve(d, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const FWs w = carve(d, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int C = d.C, L = d.L, Hd = d.Hd, Co = d.Co;
   const long long M = d.M;

@@ -1,5 +1,6 @@
 // Internal C++ entry points shared between the translation units of libslotformer_hip.so.
 #pragma once
+#include "../../include/slotformer_hip.h"
 #include "sf_common.h"
 #include "sf_switches.h"
 
@@ -112,6 +113,16 @@ int sf_dbg(const char* key);
 extern "C" int sf_stream_cus_known(void* stream);   // 0: not a stream of sf_stream_create_cu_mask / sf_stream_set_cus
 int sf_conv5x5_rows4_ex(const float* in, const void* w_frag, const float* bias, const float* add, float* out, int F, int H, int W,
                         int Cin, int Cout, int ks, int relu, hipStream_t st);
+// ... from OHWI weights, packed into the scratch w_frag first; 1 (nothing launched, the pack neither) when the kernel does not apply
+int sf_conv5x5_rows4_ohwi_ex(const float* in, const float* w_ohwi, void* w_frag, const float* bias, const float* add, float* out, int F, int H,
+                             int W, int Cin, int Cout, int ks, int relu, hipStream_t st);
+// Workspace of STEVE's token generation (steve_decoder.hip), shared by the launch chain and the one-launch-per-token form (slate_step.hip): slots ->
+// memory, every block's cross-attention k|v, every block's cache of cache_w floats per token; chain: the launch chain's row buffers behind them
+struct SfSlateGenWs {
+  float *mem, *memkv[16], *cache[16], *x, *xn, *att, *qc, *x2, *x3, *hid, *lg;
+  size_t bytes;
+};
+SfSlateGenWs sf_slate_gen_carve(void* ws, const sf_slate_decoder* m, int B, int steps, size_t cache_w, bool chain);
 // decoder layers on fragment weights (deconv_s2.hip, conv_rows4.hip); return 1 when the kernel does not apply
 int sf_deconv5x5s2_ex(const float* in, const void* w_frag, const float* bias, const float* head_w, const float* head_b, float* out, int R,
                       int H, int W, int Cin, int Cout, int ks, int stride, int relu, hipStream_t st);
@@ -129,27 +140,3 @@ int sf_conv_first_grouped_ex(const float* img, long long frame_stride, int fgrou
                              const float* add, float* out, int F, int Cin, int Hin, int Win, int Cout, int ks, int stride, int relu, hipStream_t st);
 int sf_conv_first_ex(const float* img, long long frame_stride, const float* w, const float* bias, const float* add,
                      float* out, int F, int Cin, int Hin, int Win, int Cout, int ks, int stride, int relu, hipStream_t st);
-
-// training building blocks (rollout_train.hip), shared with slot_attn_train.hip
-size_t sf_grad_partial_floats(long long rows, int N, int K);
-int sf_grad_weight_ex(const float* Y, const float* X, float* dW, long long rows, int N, int K, float* partial, hipStream_t st);
-int sf_grad_bias_ex(const float* Y, float* db, long long rows, int n, float* partial, hipStream_t st);
-int sf_grad_ln_ex(const float* x, const float* dy, float* dgamma, float* dbeta, long long rows, int D, float eps, float* partial,
-                  hipStream_t st);
-int sf_ln_bwd_ex(const float* x, const float* dy, const float* gamma, const float* dres, float* out, long long rows, int D,
-                 float eps, hipStream_t st);
-int sf_transpose_ex(const float* in, float* out, int R, int Cn, hipStream_t st);
-// the token rows of the PHYRE readout (phyre_readout.hip: ph_embed_kernel) for its training forward; arguments validated by the caller
-int sf_phyre_embed_ex(const float* slots, long long stride_v, long long stride_t, int V, const int* video_index, const int* sel, const float* in_proj_w,
-                      const float* in_proj_b, const float* enc_t_pe, const float* cls, float* x, int B, int T, int N, int C, hipStream_t st);
-int sf_relu_bwd_ex(float* dh, const float* h, long long n, hipStream_t st);
-int sf_conv2d_nhwc_strided_ex(const float* in, const float* w_packed, const float* bias, float* out, int F, int Hin, int Win,
-                              int Cin, int Cout, int ks, int stride, int relu, hipStream_t stream, const float* relu_mask = nullptr);
-int sf_linear_masked_ex(const float* A, const float* W, const float* mask, float scale, float* C, long long M, int N, int K,
-                        hipStream_t stream);
-int sf_conv_wgrad_ex(const float* A, int CA, int H, int W, const float* X, int Hx, int Wx, int s, int ks, long long rows,
-                     float* out_oihw, float* partial, hipStream_t st);
-int sf_pos_dense_grad_ex(const float* d, int F, int HW, int C, const float* grid, float* dw, float* db, float* dtab, hipStream_t st);
-int sf_slate_flash_train_ex(const float* q, const float* k, const float* v, float* out, float* lse, int ldq, int ldk, int ldv, int ldo,
-                            long long q_bs, long long k_bs, long long v_bs, long long o_bs, int B, int L, int num_heads, int head_dim,
-                            unsigned drop_seed, unsigned drop_thresh, float drop_scale, hipStream_t st);

@@ -11,6 +11,8 @@
 
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
+#include "sf_arena.h"
 #include "bf16_planes.h"
 
 // both operands k-contiguous in LDS (rows 16-byte aligned): A[i][k] at arow + i * pa, B[j][k] at brow + j * pb -- two ds_read_b128
@@ -754,9 +756,9 @@ int sf_slate_attention_train_fwd_f32(const float* q, const float* k, const float
   return 0;
 }
 
-size_t sf_slate_attention_bwd_workspace_bytes(int B, int Lq, int num_heads) {
-  return (size_t)2 * B * num_heads * Lq * sizeof(float) + 256;
-}
+// one block of two [B, H, Lq] halves: the log-sum-exp (when the caller has none) | dsum
+static size_t sab_ws_floats(int B, int Lq, int num_heads) { return (size_t)2 * B * num_heads * Lq; }
+size_t sf_slate_attention_bwd_workspace_bytes(int B, int Lq, int num_heads) { return sab_ws_floats(B, Lq, num_heads) * sizeof(float) + 256; }
 
 // Adjoint of sf_slate_attention_strided_f32: dq / dk / dv have the layouts of q / k / v, d_out and out the layout of out.
 // dq must not alias q (it is zeroed here and accumulated with float atomics: its low bits depend on the arrival order).
@@ -781,10 +783,10 @@ int sf_slate_attention_train_bwd_f32(const float* q, const float* k, const float
   SabArgs a;
   memset(&a, 0, sizeof(a));
   a.q = q; a.k = k; a.v = v; a.o = out; a.dout = d_out; a.dq = dq; a.dk = dk; a.dv = dv;
-  float* wsf = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  float* wsf = SfArena(ws).take(sab_ws_floats(B, Lq, num_heads));
   a.have_lse = lse != nullptr;
   a.lse = lse ? const_cast<float*>(lse) : wsf;
-  a.dsum = wsf + (size_t)B * num_heads * Lq;
+  a.dsum = wsf + sab_ws_floats(B, Lq, num_heads) / 2;
   a.drop_seed = sab_site_seed(seed); a.drop_thresh = (uint32_t)((double)dropout_p * 16777216.0); a.drop_scale = 1.f / (1.f - dropout_p);
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
   a.Lq = Lq; a.Lk = Lk; a.H = num_heads; a.causal = causal; a.scale = 1.f / sqrtf((float)head_dim);

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
   ((f32x4*)out)[i] = ((const f32x4*)table)[id * d4 + c4];
 }
 
-size_t pad256(size_t nfloat) { return ((nfloat * sizeof(float)) + 255) & ~(size_t)255; }
+constexpr size_t STEP_WS_SLACK = 4096;
 
 // The library's own choice of frames per workgroup for B frames; 0 = the launch chain.  From the table of profiles/steve_render.md (Physion decoder,
 // 1024 steps, one MI355X): one frame per workgroup took 0.88 / 0.82 / 0.77 / 0.70 of the chain's time at 1 / 12 / 64 / 192 frames, every one a win
@@ -406,8 +406,7 @@ size_t sf_slate_generate_tok_workspace_bytes(const sf_slate_decoder* m, int B, i
   if (!m || B <= 0 || steps <= 0) return 0;
   const size_t chain = sf_slate_generate_workspace_bytes(m, B, steps);
   if (!sf_slate_step_ok(m)) return chain;
-  const size_t d = m->d_model, N = m->num_slots, L = m->num_layers;
-  const size_t fused = pad256((size_t)B * N * d) + L * pad256((size_t)B * N * 2 * d) + L * pad256((size_t)B * steps * 2 * d) + 4096;
+  const size_t fused = sf_slate_gen_carve(nullptr, m, B, steps, (size_t)2 * m->d_model, false).bytes + STEP_WS_SLACK;   // a k|v cache, no row buffers
   return fused > chain ? fused : chain;
 }
 
@@ -427,15 +426,10 @@ int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int
   hipStream_t st = (hipStream_t)stream;
   const int d = m->d_model, N = m->num_slots, NL = m->num_layers;
   const float eps = 1e-5f;
-  char* p = (char*)ws;
-  auto take = [&](size_t nfloat) {
-    float* r = (float*)p;
-    p += pad256(nfloat);
-    return r;
-  };
+  const SfSlateGenWs w = sf_slate_gen_carve(ws, m, B, steps, (size_t)2 * d, false);
   StepArgs a;
   memset(&a, 0, sizeof(a));
-  float* mem = take((size_t)B * N * d);
+  float* mem = w.mem;
   const SfRowMap rd = sf_rows(d);
   // slots -> memory, and every block's cross-attention keys / values (once), as sf_slate_generate_f32 does
   SF_TRY(sf_linear_ex(slots, rd, m->in_proj_w, m->in_proj_b, nullptr, nullptr, eps, nullptr, rd, 0, mem, rd, B * N, d, d, 0, st));
@@ -443,7 +437,7 @@ int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int
     const sf_slate_block& k = m->blocks[i];
     SF_REQUIRE(k.ln1_g && k.ln1_b && k.wqkv && k.wo && k.ln2_g && k.ln2_b && k.wq_c && k.wkv_c && k.wo_c && k.ln3_g && k.ln3_b &&
                    k.w1 && k.b1 && k.w2 && k.b2, "sf_slate_generate_tok_f32: null block weight");
-    float* memkv = take((size_t)B * N * 2 * d);
+    float* memkv = w.memkv[i];
     SF_TRY(sf_linear_ex(mem, rd, k.wkv_c, nullptr, nullptr, nullptr, eps, nullptr, rd, 0, memkv, sf_rows(2 * d), B * N, 2 * d, d, 0, st));
     StepBlock& s = a.blk[i];
     s.ln1_g = k.ln1_g, s.ln1_b = k.ln1_b, s.wqkv = k.wqkv, s.wo = k.wo;
@@ -452,7 +446,7 @@ int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int
     s.memkv = memkv;
     s.is_first = k.is_first;
   }
-  for (int i = 0; i < NL; ++i) a.blk[i].cache = take((size_t)B * steps * 2 * d);
+  for (int i = 0; i < NL; ++i) a.blk[i].cache = w.cache[i];
   a.tok_emb = m->tok_emb, a.pos_emb = m->pos_emb, a.lnf_g = m->lnf_g, a.lnf_b = m->lnf_b, a.head_w = m->head_w;
   a.tokens = tokens_out, a.logits = logits_out;
   a.d = d, a.H = m->num_heads, a.NL = NL, a.V = m->vocab_size, a.N = N, a.B = B, a.steps = steps;

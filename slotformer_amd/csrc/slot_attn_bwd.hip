@@ -17,6 +17,7 @@
 // dq partial record, summed in a fixed order by a second kernel (deterministic).
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "sf_arena.h"
 
 #define SAB_NMAX 8      // the first instantiation: every N <= 8, as before the second existed
 #define SAB_NMAX16 16   // 9 .. 16 slots (sf_slot_attn_iter_bwd16_f32)
@@ -201,10 +202,20 @@ __global__ __launch_bounds__(256) void sa_bwd_dq_reduce_kernel(const float* __re
   dq[(long long)b * ND + i] = a * scale;
 }
 
-static size_t sab_workspace_bytes(int B, int HW, int N, int D) {
-  const size_t nchunks = (size_t)(HW + SAB_PIX - 1) / SAB_PIX;
-  return ((size_t)B * N * D + (size_t)B * N + (size_t)B * nchunks * N * D) * sizeof(float) + 256;
+// The workspace is ONE block off the arena, packed at 16 bytes inside (the pinned size has no room for 256 per buffer): float offsets of
+// c [B, N] and the dq partials [B, nchunks, N, D] behind g [B, N, D].  `floats` counts c unpadded; the up to 12 bytes that start the partials
+// on a 16-byte boundary come out of the slack, with the base alignment.
+struct SabWs { size_t c, part, floats; };
+static constexpr size_t SAB_WS_SLACK = 256;
+static SabWs sab_layout(int B, int HW, int N, int D) {
+  const size_t nchunks = (size_t)(HW + SAB_PIX - 1) / SAB_PIX, bn = (size_t)B * N;
+  SabWs w;
+  w.c = bn * D;
+  w.part = w.c + ((bn + 3) & ~(size_t)3);
+  w.floats = w.c + bn + (size_t)B * nchunks * N * D;
+  return w;
 }
+static size_t sab_workspace_bytes(int B, int HW, int N, int D) { return sab_layout(B, HW, N, D).floats * sizeof(float) + SAB_WS_SLACK; }
 
 // both entry points: nmax = 8 (sf_slot_attn_iter_bwd_f32, whose callers rely on 9 slots being refused) or 16 (sf_slot_attn_iter_bwd16_f32)
 static int sab_run(const float* k, const float* v, int ld, long long batch_stride, const float* q, const float* part_num,
@@ -218,9 +229,10 @@ static int sab_run(const float* k, const float* v, int ld, long long batch_strid
   SF_REQUIRE(ws_bytes >= sab_workspace_bytes(B, HW, N, D), "workspace too small");
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  float* g = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  float* c = g + (size_t)B * N * D;
-  float* part = c + (((size_t)B * N + 3) & ~(size_t)3);
+  const SabWs w = sab_layout(B, HW, N, D);
+  float* g = SfArena(ws).take(w.floats);
+  float* c = g + w.c;
+  float* part = g + w.part;
   const int nchunks = (HW + SAB_PIX - 1) / SAB_PIX;
   hipLaunchKernelGGL(sa_bwd_prep_kernel, dim3(N, B), dim3(64), 0, st, part_num, part_den, P, d_updates, g, c, N, D);
   SF_CHECK_LAUNCH();

@@ -11,6 +11,8 @@
 
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
+#include "sf_arena.h"
 
 // updates[r][:] = sum_p num / sum_p den, r = b * N + n
 __global__ __launch_bounds__(128) void sa_updates_kernel(const float* __restrict__ pn, const float* __restrict__ pd, int P,
@@ -80,40 +82,37 @@ struct SaWs {
   float *dh, *dupd, *dsp, *dhp;
   float *w2t, *w1t, *wiht, *whht, *wqt, *wkvt, *dwkv;
   float *iter_ws, *partial;
-  size_t iter_ws_bytes, total;
+  size_t iter_ws_bytes, bytes;
 };
 
-SaWs carve(const SaDims& d, float* base) {
+constexpr size_t WS_SLACK = 256;   // bytes a caller's workspace holds beyond the carve
+
+SaWs carve(const SaDims& d, void* ws) {
   SaWs w;
   memset(&w, 0, sizeof(w));
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + 63) & ~(size_t)63;
-    return p;
-  };
+  SfArena a(ws);
   const size_t M = d.M, R = d.R, D = d.D, I = d.I, H = d.H, C = d.Cin;
-  w.wkv = take(2 * D * C);
-  w.xn = take(M * C);
-  w.kv = take(M * 2 * D);
-  w.sp = take(I * R * D); w.sn = take(I * R * D); w.q = take(I * R * D);
-  w.pn = take(I * (size_t)d.B * d.P * d.N * D); w.pd = take(I * (size_t)d.B * d.P * d.N);
-  w.upd = take(I * R * D); w.gi = take(I * R * 3 * D); w.gh = take(I * R * 3 * D);
-  w.h = take(I * R * D); w.hn = take(I * R * D); w.hid = take(I * R * H);
-  w.dkv = take(M * 2 * D); w.dxn = take(M * C);
-  w.ds = take(I * R * D); w.dpre = take(I * R * H); w.dhn = take(I * R * D);
-  w.dgi = take(I * R * 3 * D); w.dgh = take(I * R * 3 * D); w.dq = take(I * R * D); w.dsn = take(I * R * D);
-  w.dh = take(R * D); w.dupd = take(R * D); w.dsp = take(R * D); w.dhp = take(R * D);
-  w.w2t = take(H * D); w.w1t = take(H * D); w.wiht = take(3 * D * D); w.whht = take(3 * D * D); w.wqt = take(D * D);
-  w.wkvt = take(2 * D * C); w.dwkv = take(2 * D * C);
+  w.wkv = a.take(2 * D * C);
+  w.xn = a.take(M * C);
+  w.kv = a.take(M * 2 * D);
+  w.sp = a.take(I * R * D); w.sn = a.take(I * R * D); w.q = a.take(I * R * D);
+  w.pn = a.take(I * (size_t)d.B * d.P * d.N * D); w.pd = a.take(I * (size_t)d.B * d.P * d.N);
+  w.upd = a.take(I * R * D); w.gi = a.take(I * R * 3 * D); w.gh = a.take(I * R * 3 * D);
+  w.h = a.take(I * R * D); w.hn = a.take(I * R * D); w.hid = a.take(I * R * H);
+  w.dkv = a.take(M * 2 * D); w.dxn = a.take(M * C);
+  w.ds = a.take(I * R * D); w.dpre = a.take(I * R * H); w.dhn = a.take(I * R * D);
+  w.dgi = a.take(I * R * 3 * D); w.dgh = a.take(I * R * 3 * D); w.dq = a.take(I * R * D); w.dsn = a.take(I * R * D);
+  w.dh = a.take(R * D); w.dupd = a.take(R * D); w.dsp = a.take(R * D); w.dhp = a.take(R * D);
+  w.w2t = a.take(H * D); w.w1t = a.take(H * D); w.wiht = a.take(3 * D * D); w.whht = a.take(3 * D * D); w.wqt = a.take(D * D);
+  w.wkvt = a.take(2 * D * C); w.dwkv = a.take(2 * D * C);
   w.iter_ws_bytes = sf_slot_attn_iter_bwd16_workspace_bytes(d.B, d.HW, d.N, d.D);   // (the same count as the 8-slot query for N <= 8)
-  w.iter_ws = take(w.iter_ws_bytes / 4 + 64);
+  w.iter_ws = a.take(w.iter_ws_bytes / 4 + 64);
   size_t pf = sf_grad_partial_floats(d.M, 2 * d.D, d.Cin);
   const size_t alt[] = {sf_grad_partial_floats(I * R, 3 * d.D, d.D), sf_grad_partial_floats(I * R, d.H, d.D),
                         sf_grad_partial_floats(I * R, d.D, d.H), sf_grad_partial_floats(I * R, d.D, d.D)};
-  for (size_t a : alt) pf = a > pf ? a : pf;
-  w.partial = take(pf);
-  w.total = off;
+  for (size_t x : alt) pf = x > pf ? x : pf;
+  w.partial = a.take(pf);
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -149,7 +148,7 @@ extern "C" {
 size_t sf_slot_attention_train_workspace_bytes(const sf_slot_attention* m, int B, int HW, int iters) {
   SaDims d;
   if (check(m, d, B, HW, iters) != 0) return 0;
-  return carve(d, nullptr).total * sizeof(float) + 256;
+  return carve(d, nullptr).bytes + WS_SLACK;
 }
 
 int sf_slot_attention_train_fwd_f32(const sf_slot_attention* m, const float* inputs, const float* slots_in, int B, int HW,
@@ -158,8 +157,8 @@ int sf_slot_attention_train_fwd_f32(const sf_slot_attention* m, const float* inp
   SF_TRY(check(m, d, B, HW, iters));
   SF_REQUIRE(inputs && slots_in && slots_out && ws, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const SaWs w = carve(d, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const SaWs w = carve(d, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   const int D = d.D, C = d.Cin, H = d.H, N = d.N;
   const long long M = d.M, R = d.R;
   const float scale = 1.f / sqrtf((float)D);
@@ -199,8 +198,8 @@ int sf_slot_attention_train_bwd_f32(const sf_slot_attention* m, const float* inp
   SF_TRY(check(m, d, B, HW, iters));
   SF_REQUIRE(inputs && d_slots_out && d_slots_in && g && ws, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const SaWs w = carve(d, (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  SF_REQUIRE(w.total * sizeof(float) + 256 <= ws_bytes, "workspace too small");
+  const SaWs w = carve(d, ws);
+  SF_REQUIRE(w.bytes + WS_SLACK <= ws_bytes, "workspace too small");
   const int D = d.D, C = d.Cin, H = d.H, N = d.N, I = d.I;
   const long long M = d.M, R = d.R;
   const float scale = 1.f / sqrtf((float)D);

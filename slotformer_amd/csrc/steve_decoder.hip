@@ -4,6 +4,8 @@
 // what is specific to these models.
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
+#include "sf_arena.h"
 #include "bf16_planes.h"
 
 namespace {
@@ -1175,12 +1177,24 @@ int sf_groupnorm1_nhwc_f32(const float* x, const float* gamma, const float* beta
 
 // ---- backward of the two calls above (row N1: the dVAE under autograd, dVAE.py:113-139) ----
 static size_t gn_bwd_blocks(int H, int W, int C) { return (((size_t)H * W * C) / 4 + 255) / 256; }
-static size_t gn_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-size_t sf_groupnorm1_bwd_workspace_bytes(int F, int H, int W, int C) {
-  if (F <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
+struct GnBwdWs {
+  double* part;   // the forward's statistics partials
+  float *gb, *gxb, *sums, *means, *partial;
+  size_t bytes;
+};
+static constexpr size_t GN_BWD_SLACK = 256;
+static GnBwdWs gn_bwd_carve(void* ws, int F, int H, int W, int C) {
   const size_t n = (size_t)H * W * C, nb = gn_bwd_blocks(H, W, C);
-  return gn_pad(sf_groupnorm1_workspace_bytes(F)) + 2 * gn_pad((size_t)F * n * sizeof(float)) + gn_pad((size_t)F * nb * 2 * sizeof(float)) +
-         gn_pad((size_t)F * 2 * sizeof(float)) + gn_pad(sf_grad_partial_floats((long long)F * H * W, C, C) * sizeof(float)) + 256;
+  SfArena a(ws);
+  GnBwdWs w;
+  w.part = (double*)a.take<char>(sf_groupnorm1_workspace_bytes(F));
+  w.gb = a.take(F * n), w.gxb = a.take(F * n), w.sums = a.take(F * nb * 2), w.means = a.take((size_t)F * 2);
+  w.partial = a.take(sf_grad_partial_floats((long long)F * H * W, C, C));
+  w.bytes = a.bytes();
+  return w;
+}
+size_t sf_groupnorm1_bwd_workspace_bytes(int F, int H, int W, int C) {
+  return F <= 0 || H <= 0 || W <= 0 || C <= 0 ? 0 : gn_bwd_carve(nullptr, F, H, W, C).bytes + GN_BWD_SLACK;
 }
 // x: the INPUT of the forward call; dy: gradient of its output ([F,H,W,C], or [F,2H,2W,C/4] with pixel_shuffle 2).
 // dx [F,H,W,C]; dgamma / dbeta [C] (overwritten).
@@ -1194,18 +1208,9 @@ int sf_groupnorm1_nhwc_bwd_f32(const float* x, const float* gamma, const float* 
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)H * W * C;
   const unsigned nb = (unsigned)gn_bwd_blocks(H, W, C);
-  char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  double* part = (double*)p;
-  p += gn_pad(sf_groupnorm1_workspace_bytes(F));
-  float* gb = (float*)p;
-  p += gn_pad((size_t)F * n * sizeof(float));
-  float* gxb = (float*)p;
-  p += gn_pad((size_t)F * n * sizeof(float));
-  float* sums = (float*)p;
-  p += gn_pad((size_t)F * nb * 2 * sizeof(float));
-  float* means = (float*)p;
-  p += gn_pad((size_t)F * 2 * sizeof(float));
-  float* partial = (float*)p;
+  const GnBwdWs w = gn_bwd_carve(ws, F, H, W, C);
+  double* part = w.part;
+  float *gb = w.gb, *gxb = w.gxb, *sums = w.sums, *means = w.means, *partial = w.partial;
   hipLaunchKernelGGL(gn_stats_kernel, dim3(GN_P, F), dim3(256), 0, st, x, part, n);
   SF_CHECK_LAUNCH();
   hipLaunchKernelGGL(gn_bwd_prep_kernel, dim3(nb, F), dim3(256), 0, st, x, (const double*)part, gamma, beta, dy, gb, gxb, sums, H, W, C,
@@ -1239,12 +1244,9 @@ int sf_softmax_rows_bwd_f32(const float* y, const float* dy, float scale, float*
 
 // ---- K/V-cached greedy generation (STEVETransformerDecoder.generate with sample=False, steve_transformer.py:305-333,
 //      computed one token per step; the arithmetic of a step is that of the reference's forward on the prefix) ----
+static constexpr size_t SLATE_GEN_SLACK = 4096;
 size_t sf_slate_generate_workspace_bytes(const sf_slate_decoder* m, int B, int steps) {
-  if (!m || B <= 0 || steps <= 0) return 0;
-  const size_t d = m->d_model, N = m->num_slots, L = m->num_layers;
-  auto pad = [](size_t nfloat) { return ((nfloat * sizeof(float)) + 255) & ~(size_t)255; };
-  return pad(B * N * d) + L * pad(B * N * 2 * d) + L * pad((size_t)B * steps * 3 * d) + 6 * pad(B * d) + pad(B * 4 * d) +
-         pad((size_t)B * m->vocab_size) + 4096;
+  return !m || B <= 0 || steps <= 0 ? 0 : sf_slate_gen_carve(nullptr, m, B, steps, (size_t)3 * m->d_model, true).bytes + SLATE_GEN_SLACK;
 }
 
 int sf_slate_generate_f32(const sf_slate_decoder* m, const float* slots, int B, int steps, long long* tokens_out,
@@ -1259,26 +1261,10 @@ int sf_slate_generate_f32(const sf_slate_decoder* m, const float* slots, int B, 
   hipStream_t st = (hipStream_t)stream;
   const int d = m->d_model, H = m->num_heads, N = m->num_slots, V = m->vocab_size, NL = m->num_layers;
   const float eps = 1e-5f;
-  char* p = (char*)ws;
-  auto take = [&](size_t nfloat) {
-    float* r = (float*)p;
-    p += ((nfloat * sizeof(float)) + 255) & ~(size_t)255;
-    return r;
-  };
-  float* mem = take((size_t)B * N * d);
-  float* memkv[16];
-  float* cache[16];
   SF_REQUIRE(NL <= 16, "sf_slate_generate_f32: at most 16 decoder blocks");
-  for (int i = 0; i < NL; ++i) memkv[i] = take((size_t)B * N * 2 * d);
-  for (int i = 0; i < NL; ++i) cache[i] = take((size_t)B * steps * 3 * d);
-  float* x = take((size_t)B * d);
-  float* xn = take((size_t)B * d);
-  float* att = take((size_t)B * d);
-  float* qc = take((size_t)B * d);
-  float* x2 = take((size_t)B * d);
-  float* x3 = take((size_t)B * d);
-  float* hid = take((size_t)B * 4 * d);
-  float* lg = take((size_t)B * V);
+  const SfSlateGenWs w = sf_slate_gen_carve(ws, m, B, steps, (size_t)3 * d, true);
+  float *const mem = w.mem, *const *memkv = w.memkv, *const *cache = w.cache;
+  float *x = w.x, *xn = w.xn, *att = w.att, *qc = w.qc, *x2 = w.x2, *x3 = w.x3, *hid = w.hid, *lg = w.lg;
   const SfRowMap rd = sf_rows(d);
   // slots -> memory, and every block's cross-attention keys / values (once)
   SF_TRY(sf_linear_ex(slots, rd, m->in_proj_w, m->in_proj_b, nullptr, nullptr, eps, nullptr, rd, 0, mem, rd, B * N, d, d, 0, st));
@@ -1338,3 +1324,21 @@ int sf_slate_generate_f32(const sf_slate_decoder* m, const float* slots, int B, 
 }
 
 }  // extern "C"
+
+SfSlateGenWs sf_slate_gen_carve(void* ws, const sf_slate_decoder* m, int B, int steps, size_t cache_w, bool chain) {
+  const size_t d = m->d_model, N = m->num_slots, V = m->vocab_size;
+  SfArena a(ws);
+  SfSlateGenWs w;
+  w.mem = a.take(B * N * d);
+  for (int k = 0; k < 2; ++k)   // every block's cross-attention keys / values, then every block's cache
+    for (int i = 0; i < m->num_layers; ++i) {
+      float* p = a.take(k == 0 ? B * N * 2 * d : (size_t)B * steps * cache_w);
+      if (i < 16) (k == 0 ? w.memkv : w.cache)[i] = p;   // (the calls refuse more blocks; the query counts them)
+    }
+  if (chain) {
+    for (float** f : {&w.x, &w.xn, &w.att, &w.qc, &w.x2, &w.x3}) *f = a.take(B * d);
+    w.hid = a.take(B * 4 * d), w.lg = a.take(B * V);
+  }
+  w.bytes = a.bytes();
+  return w;
+}

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "sf_common.h"
+#include "sf_arena.h"
 
 namespace {
 
@@ -380,10 +381,12 @@ __global__ void vp_mean_kernel(const double* __restrict__ pv, double* __restrict
   out[idx] = s / (double)B;
 }
 
-inline size_t vp_align(size_t n) { return (n + 255) & ~(size_t)255; }
 inline int vp_tiles_x(int W) { return (W - 2 * VP_R + VP_TW - 1) / VP_TW; }
 inline int vp_tiles_y(int H) { return (H - 2 * VP_R + VP_TH - 1) / VP_TH; }
-inline size_t vp_table_bytes(int F) { return vp_align((size_t)F * VP_NCLS * VP_NCLS * sizeof(unsigned)); }
+// One workspace serves both metric calls: [contingency tables of the mask metrics | tile partials of the image metrics]
+constexpr size_t VP_WS_SLACK = 256;
+inline unsigned* vp_take_tables(SfArena& a, int F) { return a.take<unsigned>((size_t)F * VP_NCLS * VP_NCLS); }
+inline double* vp_take_partial(SfArena& a, int F, int H, int W) { return a.take<double>((size_t)F * 3 * vp_tiles_x(W) * vp_tiles_y(H) * 2); }
 
 }  // namespace
 
@@ -391,7 +394,10 @@ extern "C" {
 
 size_t sf_vp_metrics_workspace_bytes(int F, int H, int W) {
   if (F < 0 || H < 2 * VP_R + 1 || W < 2 * VP_R + 1) return 0;
-  return vp_table_bytes(F) + vp_align((size_t)F * 3 * vp_tiles_x(W) * vp_tiles_y(H) * 2 * sizeof(double)) + 256;
+  SfArena a(nullptr);
+  vp_take_tables(a, F);
+  vp_take_partial(a, F, H, W);
+  return a.bytes() + VP_WS_SLACK;
 }
 
 int sf_vp_image_metrics_f32(const float* gt, const float* pred, double* mse, double* psnr, double* ssim, int F, int H, int W, int to_rgb,
@@ -409,7 +415,9 @@ int sf_vp_image_metrics_f32(const float* gt, const float* pred, double* mse, dou
   }
   for (int k = 0; k <= VP_R; ++k) taps.w[k] = (float)(w[k] / sum);
   const int txn = vp_tiles_x(W), tyn = vp_tiles_y(H);
-  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + vp_table_bytes(F));
+  SfArena a(workspace);
+  vp_take_tables(a, F);
+  double* partial = vp_take_partial(a, F, H, W);
   hipStream_t st = (hipStream_t)stream;
   // (frame, channel) planes on grid.y (at most 65535 per launch)
   for (long long p0 = 0; p0 < (long long)F * 3; p0 += 65535) {
@@ -429,12 +437,14 @@ int sf_vp_mask_metrics(const long long* gt_mask, const void* pred_mask, int pred
   SF_REQUIRE(gt_mask && pred_mask && ari && fari && miou && flag, "null pointer");
   SF_REQUIRE(num_classes >= 1 && num_classes <= VP_NCLS, "at most 16 classes");
   SF_REQUIRE(F >= 0 && H >= 1 && W >= 1 && (long long)H * W < (1ll << 31) - 256, "bad mask-metric shape");
-  SF_REQUIRE(tables || (workspace && workspace_bytes >= vp_table_bytes(F)), "workspace too small (sf_vp_metrics_workspace_bytes)");
+  SfArena a(workspace, workspace_bytes);
+  unsigned* ws_tab = F > 0 ? vp_take_tables(a, F) : nullptr;
+  SF_REQUIRE(tables || (workspace && a.ok), "workspace too small (sf_vp_metrics_workspace_bytes)");
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(flag, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return sf_set_err((int)e, hipGetErrorString(e), __FILE__, __LINE__);
   if (F == 0) return 0;
-  unsigned* tab = tables ? tables : static_cast<unsigned*>(workspace);
+  unsigned* tab = tables ? tables : ws_tab;
   if (pred_is_u8)
     hipLaunchKernelGGL(vp_mask_count_kernel<unsigned char>, dim3(F), dim3(256), 0, st, gt_mask, static_cast<const unsigned char*>(pred_mask), tab,
                        pred_boxes, flag, H * W, W, num_classes, VP_NCLS);

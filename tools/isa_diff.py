@@ -3,7 +3,8 @@
     python tools/isa_diff.py <tree A> <tree B> [source.hip ...]      # default: every entry of build.SOURCES
 Every source is compiled in both trees with build.FLAGS + build.FILE_FLAGS of tree B.  Comment lines, trailing comments and the
 .file / .ident / .loc / .section-style directives are dropped; every instruction line, the .amdhsa_* descriptor fields and the
-kernel's metadata entry (registers, scratch, LDS, arguments) are kept.  Prints one markdown table row per function symbol."""
+kernel's metadata entry (registers, scratch, LDS, arguments) are kept.  A function is matched by its symbol across sources: one that moved is
+compared in the source tree B has it in ("moved here") against wherever tree A had it.  Prints one markdown table row per source."""
 import importlib.util
 import os
 import re
@@ -32,6 +33,8 @@ def functions(asm):
         elif s.startswith('.name:') and cur is meta:
             cur = out.setdefault(s.split()[1], [])
             cur += meta
+        elif raw.startswith('amdhsa.'):                      # a top-level metadata key: the file's last kernel entry ends here, not at the file's end
+            cur = None
         if not s or DROP.match(s) or cur is None:
             continue
         cur.append(LABEL.sub(r'.L\1', s))
@@ -63,13 +66,18 @@ def main(a, b, *sources):
     sources = list(sources) or build.SOURCES
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         fa, fb = assemble(a, build, sources, ta), assemble(b, build, sources, tb)
-    print('| source | functions | instruction lines | differing |\n|---|---|---|---|')
+    # a function that moved between sources is matched by its symbol: compared where tree B has it, against wherever tree A had it
+    home_a = {k: s for s in sources for k in fa[s]}
+    home_b = {k: s for s in sources for k in fb[s]}
+    print('| source | functions | instruction lines | moved here | differing |\n|---|---|---|---|---|')
     bad = 0
     for s in sources:
-        diff = sorted(k for k in fa[s].keys() | fb[s].keys() if fa[s].get(k) != fb[s].get(k))
+        moved = sorted(k for k in fb[s] if k not in fa[s] and k in home_a)
+        gone = {k for k in fa[s] if k not in fb[s] and k in home_b}
+        diff = sorted(k for k in (fa[s].keys() | fb[s].keys()) - gone if (fa[s] if k in fa[s] else fa[home_a.get(k, s)]).get(k) != fb[s].get(k))
         bad += len(diff)
         n = sum(1 for v in fb[s].values() for l in v if l[0].isalpha() and not l.endswith(':'))
-        print(f"| {s} | {len(fb[s])} | {n} | {', '.join(diff) or 'none'} |")
+        print(f"| {s} | {len(fb[s])} | {n} | {', '.join(f'{k} ({home_a[k]})' for k in moved) or 'none'} | {', '.join(diff) or 'none'} |")
     print(f'\n{bad} differing function(s) in {len(sources)} source(s)')
     return 1 if bad else 0
 
