@@ -12,6 +12,7 @@ from torch import nn
 
 from ...nerv_compat import BaseModel
 from ... import ops, plans
+from ..._call import require_device
 
 
 def conv2d(in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, weight_init='xavier'):
@@ -218,8 +219,7 @@ class dVAE(BaseModel):
             return self.tokenize(data_dict['img'], one_hot=False)
         from ... import train
         x = data_dict['img']
-        if not x.is_cuda:
-            raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
+        require_device(x)
         tau = data_dict.get('gumbel_tau', self.tau)
         hard = data_dict.get('hard', False)
         B = x.shape[0]

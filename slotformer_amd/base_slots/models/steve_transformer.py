@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from ... import ops, plans
+from ..._call import ptr, scratch, stream
 
 
 def linear(in_features, out_features, bias=True, weight_init='xavier', gain=1.):
@@ -193,10 +194,9 @@ class STEVETransformerDecoder(nn.Module):
         m = self._slate_plan().struct
         tokens = torch.empty(B, steps, dtype=torch.int64, device=slots.device)
         logits = torch.empty(B, steps, self.vocab_size, dtype=torch.float32, device=slots.device)
-        nb = lib().sf_slate_generate_workspace_bytes(C.byref(m), B, steps)
-        ws = torch.empty(nb, dtype=torch.uint8, device=slots.device)
+        ws = scratch(lib().sf_slate_generate_workspace_bytes, C.byref(m), B, steps, device=slots.device)
         check(lib().sf_slate_generate_f32(C.byref(m), slots.data_ptr(), B, steps, tokens.data_ptr(), logits.data_ptr(),
-                                          ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream))
+                                          ws.data_ptr(), ws.numel(), stream()))
         return tokens, logits.cpu()
 
     def generate_tokens(self, slots, steps, return_logits=False, frames_per_wg=0):
@@ -219,12 +219,10 @@ class STEVETransformerDecoder(nn.Module):
         m = self._slate_plan().struct
         tokens = torch.empty(B, steps, dtype=torch.int64, device=slots.device)
         logits = torch.empty(B, steps, self.vocab_size, dtype=torch.float32, device=slots.device) if return_logits else None
-        nb = lib().sf_slate_generate_tok_workspace_bytes(C.byref(m), B, steps)
-        ws = torch.empty(nb, dtype=torch.uint8, device=slots.device)
+        ws = scratch(lib().sf_slate_generate_tok_workspace_bytes, C.byref(m), B, steps, device=slots.device)
         ran = C.c_int(-1)
-        check(lib().sf_slate_generate_tok_f32(C.byref(m), slots.data_ptr(), B, steps, tokens.data_ptr(),
-                                              None if logits is None else logits.data_ptr(), int(frames_per_wg), ws.data_ptr(), nb,
-                                              torch.cuda.current_stream().cuda_stream, C.byref(ran)))
+        check(lib().sf_slate_generate_tok_f32(C.byref(m), slots.data_ptr(), B, steps, tokens.data_ptr(), ptr(logits), int(frames_per_wg),
+                                              ws.data_ptr(), ws.numel(), stream(), C.byref(ran)))
         self.last_generate_form = ran.value
         return tokens, logits
 

@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from ._call import ptr, stream
 
 TRUNC, NEAREST_EVEN = 0, 1
 _ROUNDING = {'trunc': TRUNC, 'nearest': NEAREST_EVEN, 'nearest_even': NEAREST_EVEN}
@@ -58,10 +59,6 @@ def to_rgb(x):
     return (x * 0.5 + 0.5).clamp(0, 1)
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 # ---- (a) frames ------------------------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def frames_to_uint8(x, to_rgb=True, layout='hwc', rounding='trunc', out=None):
@@ -84,7 +81,7 @@ def frames_to_uint8(x, to_rgb=True, layout='hwc', rounding='trunc', out=None):
         return out
     if x.is_cuda:
         L.check(L.lib().sf_egress_frames_u8(x.data_ptr(), out.data_ptr(), F, H, W, int(layout == 'hwc'), int(bool(to_rgb)), _ROUNDING[rounding],
-                                            _stream(x)))
+                                            stream(x)))
         return out
     v = (x * 0.5 + 0.5).clamp(0, 1) if to_rgb else x
     s = (v * 255.).clamp(0, 255)
@@ -225,7 +222,7 @@ def video_grid(tiles, nrow=None, padding=2, pad_value=0., dtype=torch.float32, l
             e.history_len = t.border[1] if t.border is not None else 0
             arr[i] = e
         L.check(L.lib().sf_egress_grid(arr, len(tiles), out.data_ptr(), _GRID_MODE[(dtype, layout)], T, H, W, K if nrow is None else int(nrow),
-                                       int(padding), float(pad_value), border, _stream(out)))
+                                       int(padding), float(pad_value), border, stream(out)))
         return out
     # the CPU home: the same float32 operations, tile by tile
     TH, TW = H + 2 * border, W + 2 * border
@@ -278,8 +275,8 @@ def draw_boxes_(frames_u8, boxes, pres_mask=None, palette=None, width=2):
     if F == 0 or M == 0 or H == 0 or W == 0:
         return frames_u8
     if frames_u8.is_cuda:
-        L.check(L.lib().sf_egress_draw_boxes(frames_u8.data_ptr(), boxes.data_ptr(), None if pres_mask is None else pres_mask.data_ptr(),
-                                             pal.data_ptr(), pal.shape[0], F, M, H, W, int(width), _stream(frames_u8)))
+        L.check(L.lib().sf_egress_draw_boxes(frames_u8.data_ptr(), boxes.data_ptr(), ptr(pres_mask),
+                                             pal.data_ptr(), pal.shape[0], F, M, H, W, int(width), stream(frames_u8)))
         return frames_u8
     ys = torch.arange(H).view(H, 1)
     xs = torch.arange(W).view(1, W)

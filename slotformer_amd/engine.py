@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import _lib
+from ._call import ptr, require_device, scratch, stream
 from ._lib import lib, check, sf_tfm_layer, sf_rollouter, sf_savi_encoder, sf_savi_decoder
 from . import ops, plans
 
@@ -26,6 +27,13 @@ def workspace(device, nbytes, slot=0):
         cur = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
         _WORKSPACES[key] = cur
     return cur
+
+
+def workspace_for(device, slot, query, *args, at_least=0):
+    """`workspace` of the size query(*args) asks for: `scratch` (and its error for a query that returns 0) with the cached buffer to reuse."""
+    key = (device.type, device.index, slot)
+    ws = _WORKSPACES[key] = scratch(query, *args, device=device, reuse=_WORKSPACES.get(key), at_least=at_least)
+    return ws
 
 
 def release_workspaces(prefix):
@@ -53,9 +61,7 @@ def _require_inference(module, *tensors):
         raise NotImplementedError(
             'slotformer_amd: this call is inference-only on the HIP path (the training nodes of row N1 live in train.py); '
             'wrap the call in torch.no_grad()')
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
+    require_device(*tensors)
 
 
 # the plan cache (plans.py): one signature, one cache per module, one `invalidate`.  The caches are keyed on (data_ptr, _version) of the
@@ -76,14 +82,14 @@ def _tfm_layers(plan, encoder, pack_ffn=False):
             p1 = torch.empty(nb, dtype=torch.uint8, device=l.linear1.weight.device)
             p2 = torch.empty(nb, dtype=torch.uint8, device=l.linear1.weight.device)
             check(lib().sf_pack_ffn_weights(plan.dp(l.linear1.weight), plan.dp(l.linear2.weight), p1.data_ptr(),
-                                            p2.data_ptr(), d, ffn, torch.cuda.current_stream().cuda_stream))
+                                            p2.data_ptr(), d, ffn, stream()))
             plan.keep += [p1, p2]
             a.lin1_packed, a.lin2_packed = p1.data_ptr(), p2.data_ptr()
             if l.self_attn.num_heads == 8:
                 q1 = torch.empty(lib().sf_attn_packed_bytes(d, 0), dtype=torch.uint8, device=p1.device)
                 q2 = torch.empty(lib().sf_attn_packed_bytes(d, 1), dtype=torch.uint8, device=p1.device)
                 check(lib().sf_pack_attn_weights(plan.dp(l.self_attn.in_proj_weight), plan.dp(l.self_attn.out_proj.weight),
-                                                 q1.data_ptr(), q2.data_ptr(), d, 8, torch.cuda.current_stream().cuda_stream))
+                                                 q1.data_ptr(), q2.data_ptr(), d, 8, stream()))
                 plan.keep += [q1, q2]
                 a.attn_in_packed, a.attn_out_packed = q1.data_ptr(), q2.data_ptr()
         a.norm1_g, a.norm1_b = plan.dp(l.norm1.weight), plan.dp(l.norm1.bias)
@@ -97,7 +103,7 @@ def _tfm_layers(plan, encoder, pack_ffn=False):
             # all four matrices as the fragment stream of the token-stationary layer launch + the layer's vectors (layer_tok.hip; layer_tok128.hip
             # for the OBJ3D shape, which has no other packed copy)
             tp = torch.empty(lib().sf_layer_tok_packed_bytes_ex(d, heads, ffn), dtype=torch.uint8, device=l.linear1.weight.device)
-            check(lib().sf_pack_layer_tok_weights(C.byref(a), tp.data_ptr(), d, heads, ffn, torch.cuda.current_stream().cuda_stream))
+            check(lib().sf_pack_layer_tok_weights(C.byref(a), tp.data_ptr(), d, heads, ffn, stream()))
             plan.keep.append(tp)
             a.tok_packed = tp.data_ptr()
     plan.keep.append(arr)
@@ -213,11 +219,10 @@ def rollout(r, slots_all, n_in, pred_len, ws_slot=0, opts=None):
                            '(history_len; 1 for SingleStepSlotRollouter)')
     plan = rollouter_plan(r)
     B, T_total = slots_all.shape[:2]
-    need = lib().sf_rollout_workspace_bytes(C.byref(plan.struct), B)
-    ws = workspace(slots_all.device, need, ('roll', ws_slot))
+    ws = workspace_for(slots_all.device, ('roll', ws_slot), lib().sf_rollout_workspace_bytes, C.byref(plan.struct), B)
     o = rollout_opts(opts)
     check(lib().sf_rollout_opts_f32(C.byref(plan.struct), slots_all.data_ptr(), B, T_total, pred_len, ws.data_ptr(),
-                                    ws.numel(), torch.cuda.current_stream().cuda_stream, None if o is None else C.byref(o)))
+                                    ws.numel(), stream(), None if o is None else C.byref(o)))
     return slots_all
 
 
@@ -247,11 +252,10 @@ def rollout_phases(r, slots_all, obs, pred_len, frame_offset, ws_slot=0, opts=No
     _require_inference(r, slots_all)
     ops._chk(slots_all)
     plan = rollouter_plan(r)
-    need = lib().sf_rollout_phases_workspace_bytes(C.byref(plan.struct), B, f)
-    ws = workspace(slots_all.device, need, ('roll', ws_slot))
+    ws = workspace_for(slots_all.device, ('roll', ws_slot), lib().sf_rollout_phases_workspace_bytes, C.byref(plan.struct), B, f)
     o = rollout_opts(opts)
     check(lib().sf_rollout_phases_f32(C.byref(plan.struct), slots_all.data_ptr(), B, T_total, obs, f, pred_len, ws.data_ptr(), ws.numel(),
-                                      torch.cuda.current_stream().cuda_stream, None if o is None else C.byref(o)))
+                                      stream(), None if o is None else C.byref(o)))
     return slots_all
 
 
@@ -435,23 +439,22 @@ def savi_encode(m, img, prev_slots=None, noise=None, want_attn=False, ws_slot=0,
     if isinstance(side_stream, str):
         side_stream = _auto_side_stream(dev) if side_stream == 'auto' else None
     if side_stream is not None:
-        need = lib().sf_savi_encode_fork_workspace_bytes(C.byref(plan.struct), B, T)
+        query = (lib().sf_savi_encode_fork_workspace_bytes, C.byref(plan.struct), B, T)
     elif feat_pre is None:
         # (room for the convolutions of all T steps as one launch per layer: csrc/engine.hip, batched form)
-        need = lib().sf_savi_encode_batched_workspace_bytes(C.byref(plan.struct), B, T)
+        query = (lib().sf_savi_encode_batched_workspace_bytes, C.byref(plan.struct), B, T)
     else:
-        need = lib().sf_savi_encode_workspace_bytes(C.byref(plan.struct), B)
-    ws = workspace(dev, need, ('enc', ws_slot))
-    P = ops._p
+        query = (lib().sf_savi_encode_workspace_bytes, C.byref(plan.struct), B)
+    ws = workspace_for(dev, ('enc', ws_slot), *query)
     n_pre = 0
     if feat_pre is not None:
         ops._chk(feat_pre)
         n_pre = feat_pre.shape[0]
         if feat_pre.shape[1] != B or feat_pre.shape[2] != 64 * 64:
             raise RuntimeError(f'feat_pre must be [n_pre,{B},4096,C], got {tuple(feat_pre.shape)}')
-    check(lib().sf_savi_encode_fork_f32(C.byref(plan.struct), img.data_ptr(), P(feat_pre), n_pre, P(noise), P(prev_slots), P(h),
-                                        P(c), valid, post.data_ptr(), P(kdist), P(attn), B, T, ws.data_ptr(), ws.numel(),
-                                        torch.cuda.current_stream().cuda_stream, None if side_stream is None else side_stream.cuda_stream))
+    check(lib().sf_savi_encode_fork_f32(C.byref(plan.struct), img.data_ptr(), ptr(feat_pre), n_pre, ptr(noise), ptr(prev_slots), ptr(h),
+                                        ptr(c), valid, post.data_ptr(), ptr(kdist), ptr(attn), B, T, ws.data_ptr(), ws.numel(),
+                                        stream(), None if side_stream is None else side_stream.cuda_stream))
     return post, kdist, attn
 
 
@@ -473,10 +476,9 @@ def savi_features(m, img, out, ws_slot=0):
     ops._chk(img)
     plan = encoder_plan(m)
     B, T = img.shape[:2]
-    need = lib().sf_savi_features_workspace_bytes(C.byref(plan.struct), B, T)
-    ws = workspace(img.device, need, ('encf', ws_slot))
+    ws = workspace_for(img.device, ('encf', ws_slot), lib().sf_savi_features_workspace_bytes, C.byref(plan.struct), B, T)
     check(lib().sf_savi_features_planes_f32(C.byref(plan.struct), img.data_ptr(), B, T, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            torch.cuda.current_stream().cuda_stream))
+                                            stream()))
     return out
 
 
@@ -490,11 +492,9 @@ def savi_slots_chain(m, planes, nb, B, T, post, noise=None, prev_slots=None, kdi
     V = int(nb) * int(B)
     if post.shape[0] != V or post.shape[1] < T or post.stride(0) < T * s.num_slots * s.slot_size or post.stride(1) != s.num_slots * s.slot_size:
         raise RuntimeError(f'post must be [{V}, >= {T}, N, D] float32 with contiguous steps, got {tuple(post.shape)} strides {post.stride()}')
-    need = lib().sf_savi_slots_chain_workspace_bytes(C.byref(plan.struct), V)
-    ws = workspace(post.device, need, ('encs', ws_slot))
-    P = ops._p
-    check(lib().sf_savi_slots_chain_f32(C.byref(plan.struct), planes.data_ptr(), P(noise), P(prev_slots), post.data_ptr(), post.stride(0), P(kdist), P(attn),
-                                        int(nb), int(B), int(T), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+    ws = workspace_for(post.device, ('encs', ws_slot), lib().sf_savi_slots_chain_workspace_bytes, C.byref(plan.struct), V)
+    check(lib().sf_savi_slots_chain_f32(C.byref(plan.struct), planes.data_ptr(), ptr(noise), ptr(prev_slots), post.data_ptr(), post.stride(0), ptr(kdist),
+                                        ptr(attn), int(nb), int(B), int(T), ws.data_ptr(), ws.numel(), stream()))
     return post
 
 
@@ -509,10 +509,9 @@ def savi_cnn(m, img, t0, t1, out=None, ws_slot=0):
     cl = s.enc_channels[s.enc_layers]
     if out is None:
         out = torch.empty(t1 - t0, B, 64 * 64, cl, device=img.device, dtype=torch.float32)
-    need = lib().sf_savi_cnn_workspace_bytes(C.byref(plan.struct), B)
-    ws = workspace(img.device, need, ('cnn', ws_slot))
+    ws = workspace_for(img.device, ('cnn', ws_slot), lib().sf_savi_cnn_workspace_bytes, C.byref(plan.struct), B)
     check(lib().sf_savi_cnn_f32(C.byref(plan.struct), img.data_ptr(), B, T, t0, t1, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                torch.cuda.current_stream().cuda_stream))
+                                stream()))
     return out
 
 
@@ -591,8 +590,7 @@ def savi_decode(m, slots, ws_slot=0, want=('recons', 'masks'), seg_dtype=torch.i
     if torch.is_grad_enabled() and (slots.requires_grad or any(p.requires_grad for p in m.decoder.parameters())):
         from . import train
         return train.decode_with_grad(m, slots)   # one autograd node, data gradient only (row N1)
-    if not slots.is_cuda:
-        raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
+    require_device(slots)
     slots = slots.detach().float().contiguous()
     plan = decoder_plan(m)
     F_, N, D = slots.shape
@@ -613,12 +611,10 @@ def savi_decode(m, slots, ws_slot=0, want=('recons', 'masks'), seg_dtype=torch.i
         seg = torch.empty(F_, H, H, device=dev, dtype=seg_dtype) if out_seg is None else out_seg
         if out_seg is not None and (tuple(seg.shape) != (F_, H, H) or seg.dtype != seg_dtype or not seg.is_contiguous() or seg.device != dev):
             raise RuntimeError(f'out_seg must be a contiguous {seg_dtype} [{F_},{H},{H}] tensor on {dev}')
-    need = lib().sf_savi_decode_workspace_bytes(C.byref(plan.struct), F_)
-    ws = workspace(dev, need, ('dec', ws_slot))
-    P = ops._p
-    check(lib().sf_savi_decode_seg_f32(C.byref(plan.struct), slots.data_ptr(), recon.data_ptr(), P(recons), P(masks),
-                                       P(seg) if seg_dtype == torch.int64 else None, P(seg) if seg_dtype == torch.uint8 else None,
-                                       float(fg_thre), F_, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+    ws = workspace_for(dev, ('dec', ws_slot), lib().sf_savi_decode_workspace_bytes, C.byref(plan.struct), F_)
+    check(lib().sf_savi_decode_seg_f32(C.byref(plan.struct), slots.data_ptr(), recon.data_ptr(), ptr(recons), ptr(masks),
+                                       ptr(seg) if seg_dtype == torch.int64 else None, ptr(seg) if seg_dtype == torch.uint8 else None,
+                                       float(fg_thre), F_, ws.data_ptr(), ws.numel(), stream()))
     if 'seg' in want:
         return recon, recons, masks, seg
     return recon, recons, masks

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._call import stream
 
 BILINEAR, ANTIALIAS, NEAREST = 0, 1, 2
 
@@ -158,7 +159,7 @@ class FrameIngest:
                     self._consts[dkey] = self.palette.to(frames.device)
                 pal, K = self._consts[dkey].data_ptr(), self.palette.shape[0]
             L.check(L.lib().sf_ingest_frames_u8(frames.data_ptr(), pal, K, tab.data_ptr(), self._mean3, self._std3, out.data_ptr(), F, H0, W0, H, W,
-                                                mode, int(self.max_blocks), torch.cuda.current_stream(frames.device).cuda_stream))
+                                                mode, int(self.max_blocks), stream(frames)))
             return out
         t, _, _ = self._tab(H0, W0, mode)
         if 'wy' not in t:
@@ -202,7 +203,7 @@ class FrameIngest:
             if F:
                 L.check(L.lib().sf_resize_masks_nearest(mask.data_ptr(), int(mask.dtype == torch.uint8), tab.data_ptr(),
                                                         out.data_ptr() if dtype == torch.int64 else None, out.data_ptr() if dtype == torch.uint8 else None,
-                                                        F, H0, W0, H, W, torch.cuda.current_stream(mask.device).cuda_stream))
+                                                        F, H0, W0, H, W, stream(mask)))
             return out
         t, H, W = self._tab(H0, W0, NEAREST)
         ry = torch.from_numpy(t['ry_first'].astype(np.int64))

@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from . import engine, plans
+from ._call import stream
 from ._lib import lib, check, sf_lpips_model
 
 # (slice, index inside torchvision's vgg16().features, Cin, Cout) of the thirteen convolutions, in order: THE table of state-dict names --
@@ -131,7 +132,7 @@ class LPIPS(nn.Module):
         ws = engine.workspace(dev, need, ('lpips', ))
         x, y = in0.contiguous(), in1.contiguous()
         check(lib().sf_lpips_f32(C.byref(plan.struct), x.data_ptr(), y.data_ptr(), out.data_ptr(), F, H, W, chunk, int(bool(normalize)),
-                                 ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+                                 ws.data_ptr(), ws.numel(), stream(x)))
         return out
 
     def forward(self, in0, in1, retPerLayer=False, normalize=False):

@@ -5,15 +5,8 @@ current stream.  There is no CPU path.
 """
 import torch
 
+from ._call import ptr, scratch, stream
 from ._lib import lib, check
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _chk(*ts):
@@ -34,8 +27,8 @@ def linear(x, weight, bias=None, ln=None, residual=None, relu=False, ln_eps=1e-5
     M = x.numel() // K
     out = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
     g, b = (ln if ln is not None else (None, None))
-    check(lib().sf_linear_f32(_p(x), K, _p(weight), _p(bias), _p(g), _p(b), ln_eps, _p(residual), N, _p(out), N,
-                              M, N, K, int(relu), _stream()))
+    check(lib().sf_linear_f32(ptr(x), K, ptr(weight), ptr(bias), ptr(g), ptr(b), ln_eps, ptr(residual), N, ptr(out), N,
+                              M, N, K, int(relu), stream()))
     return out
 
 
@@ -43,7 +36,7 @@ def layernorm(x, gamma, beta, eps=1e-5):
     _chk(x, gamma, beta)
     out = torch.empty_like(x)
     D = x.shape[-1]
-    check(lib().sf_layernorm_f32(_p(x), _p(gamma), _p(beta), _p(out), x.numel() // D, D, eps, _stream()))
+    check(lib().sf_layernorm_f32(ptr(x), ptr(gamma), ptr(beta), ptr(out), x.numel() // D, D, eps, stream()))
     return out
 
 
@@ -51,7 +44,7 @@ def pack_conv_weight(w):
     """[Cout,Cin,k,k] -> [Cout,k,k,Cin]."""
     _chk(w)
     out = torch.empty(w.shape[0], w.shape[2], w.shape[3], w.shape[1], device=w.device, dtype=torch.float32)
-    check(lib().sf_pack_conv_weight_f32(_p(w), _p(out), w.shape[0], w.shape[1], w.shape[2], _stream()))
+    check(lib().sf_pack_conv_weight_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], w.shape[2], stream()))
     return out
 
 
@@ -60,7 +53,7 @@ def pack_conv_frag(w_packed):
     _chk(w_packed)
     Cout, ks, _, Cin = w_packed.shape
     out = torch.empty(lib().sf_conv_frag_bytes(Cout, Cin, ks), device=w_packed.device, dtype=torch.uint8)
-    check(lib().sf_pack_conv_frag_weights(_p(w_packed), out.data_ptr(), Cout, Cin, ks, _stream()))
+    check(lib().sf_pack_conv_frag_weights(ptr(w_packed), out.data_ptr(), Cout, Cin, ks, stream()))
     return out
 
 
@@ -70,7 +63,7 @@ def pack_deconv_frag(w_packed):
     _chk(w_packed)
     Cout, ks, _, Cin = w_packed.shape
     out = torch.empty(lib().sf_deconv_frag_bytes(Cout, Cin, ks, 2), device=w_packed.device, dtype=torch.uint8)
-    check(lib().sf_pack_deconv_frag_weights(_p(w_packed), out.data_ptr(), Cout, Cin, ks, 2, _stream()))
+    check(lib().sf_pack_deconv_frag_weights(ptr(w_packed), out.data_ptr(), Cout, Cin, ks, 2, stream()))
     return out
 
 
@@ -79,7 +72,7 @@ def deconv5x5s2_frag(x, w_frag, bias, relu=True):
     _chk(x, bias)
     R, H, W, _ = x.shape
     out = torch.empty(R, 2 * H, 2 * W, 64, device=x.device, dtype=torch.float32)
-    check(lib().sf_deconv5x5s2_frag_f32(_p(x), w_frag.data_ptr(), _p(bias), _p(out), R, H, W, int(relu), _stream()))
+    check(lib().sf_deconv5x5s2_frag_f32(ptr(x), w_frag.data_ptr(), ptr(bias), ptr(out), R, H, W, int(relu), stream()))
     return out
 
 
@@ -89,7 +82,7 @@ def deconv5x5s2_head(x, w_frag, bias, head_w, head_b):
     _chk(x, bias, head_w, head_b)
     R, H, W, _ = x.shape
     dec = torch.empty(R, 4 * H * W, 4, device=x.device, dtype=torch.float32)
-    check(lib().sf_deconv5x5s2_head_frag_f32(_p(x), w_frag.data_ptr(), _p(bias), _p(head_w), _p(head_b), _p(dec), R, H, W, _stream()))
+    check(lib().sf_deconv5x5s2_head_frag_f32(ptr(x), w_frag.data_ptr(), ptr(bias), ptr(head_w), ptr(head_b), ptr(dec), R, H, W, stream()))
     return dec
 
 
@@ -98,7 +91,7 @@ def conv5x5_frag(x, w_frag, bias, relu=True, add=None):
     _chk(x, bias, add)
     F_, H, W, Cin = x.shape
     out = torch.empty(F_, H, W, 64, device=x.device, dtype=torch.float32)
-    check(lib().sf_conv5x5_frag_f32(_p(x), w_frag.data_ptr(), _p(bias), _p(add), _p(out), F_, H, W, int(relu), _stream()))
+    check(lib().sf_conv5x5_frag_f32(ptr(x), w_frag.data_ptr(), ptr(bias), ptr(add), ptr(out), F_, H, W, int(relu), stream()))
     return out
 
 
@@ -107,7 +100,7 @@ def conv5x5_ws(x, w_frag, bias, relu=True, add=None, n_workgroups=0):
     _chk(x, bias, add)
     F_, H, W, Cin = x.shape
     out = torch.empty(F_, H, W, 64, device=x.device, dtype=torch.float32)
-    check(lib().sf_conv5x5_ws_f32(_p(x), w_frag.data_ptr(), _p(bias), _p(add), _p(out), F_, H, W, int(relu), int(n_workgroups), _stream()))
+    check(lib().sf_conv5x5_ws_f32(ptr(x), w_frag.data_ptr(), ptr(bias), ptr(add), ptr(out), F_, H, W, int(relu), int(n_workgroups), stream()))
     return out
 
 
@@ -115,7 +108,7 @@ def pack_deconv_weight(w):
     """ConvTranspose2d weight [Cin,Cout,k,k] -> [Cout,k,k,Cin]."""
     _chk(w)
     out = torch.empty(w.shape[1], w.shape[2], w.shape[3], w.shape[0], device=w.device, dtype=torch.float32)
-    check(lib().sf_pack_deconv_weight_f32(_p(w), _p(out), w.shape[0], w.shape[1], w.shape[2], _stream()))
+    check(lib().sf_pack_deconv_weight_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], w.shape[2], stream()))
     return out
 
 
@@ -125,8 +118,8 @@ def conv_transpose2d_nhwc(x, w_packed, bias, stride, relu=True):
     F_, H, W, Cin = x.shape
     Cout, ks = w_packed.shape[0], w_packed.shape[1]
     out = torch.empty(F_, H * stride, W * stride, Cout, device=x.device, dtype=torch.float32)
-    check(lib().sf_conv_transpose2d_nhwc_f32(_p(x), _p(w_packed), _p(bias), _p(out), F_, H, W, Cin, Cout, ks, stride,
-                                             int(relu), _stream()))
+    check(lib().sf_conv_transpose2d_nhwc_f32(ptr(x), ptr(w_packed), ptr(bias), ptr(out), F_, H, W, Cin, Cout, ks, stride,
+                                             int(relu), stream()))
     return out
 
 
@@ -135,8 +128,8 @@ def pos_embed_table(grid, dense_w, dense_b):
     grid = grid.reshape(-1, 4).contiguous()
     _chk(grid, dense_w, dense_b)
     out = torch.empty(grid.shape[0], dense_w.shape[0], device=grid.device, dtype=torch.float32)
-    check(lib().sf_pos_embed_table_f32(_p(grid), _p(dense_w), _p(dense_b), _p(out), grid.shape[0],
-                                       dense_w.shape[0], _stream()))
+    check(lib().sf_pos_embed_table_f32(ptr(grid), ptr(dense_w), ptr(dense_b), ptr(out), grid.shape[0],
+                                       dense_w.shape[0], stream()))
     return out
 
 
@@ -148,8 +141,8 @@ def conv2d_first(img, weight, bias, stride, relu=True, add=None):
     Ho = (H + 2 * (ks // 2) - ks) // stride + 1
     Wo = (W + 2 * (ks // 2) - ks) // stride + 1
     out = torch.empty(F_, Ho, Wo, Cout, device=img.device, dtype=torch.float32)
-    check(lib().sf_conv2d_nchw_in_f32(_p(img), Cin * H * W, _p(weight), _p(bias), _p(add), _p(out), F_, Cin, H, W,
-                                      Cout, ks, stride, int(relu), _stream()))
+    check(lib().sf_conv2d_nchw_in_f32(ptr(img), Cin * H * W, ptr(weight), ptr(bias), ptr(add), ptr(out), F_, Cin, H, W,
+                                      Cout, ks, stride, int(relu), stream()))
     return out
 
 
@@ -161,8 +154,8 @@ def conv2d_first_clip(clip, weight, bias, stride, relu=True, add=None):
     Ho = (H + 2 * (ks // 2) - ks) // stride + 1
     Wo = (W + 2 * (ks // 2) - ks) // stride + 1
     out = torch.empty(T * B, Ho, Wo, Cout, device=clip.device, dtype=torch.float32)
-    check(lib().sf_conv2d_nchw_in_grouped_f32(_p(clip), T * Cin * H * W, B, Cin * H * W, _p(weight), _p(bias), _p(add), _p(out), T * B, Cin,
-                                              H, W, Cout, ks, stride, int(relu), _stream()))
+    check(lib().sf_conv2d_nchw_in_grouped_f32(ptr(clip), T * Cin * H * W, B, Cin * H * W, ptr(weight), ptr(bias), ptr(add), ptr(out), T * B, Cin,
+                                              H, W, Cout, ks, stride, int(relu), stream()))
     return out
 
 
@@ -172,8 +165,8 @@ def pixel_feat(x, ln0, fc1, fc2, ln1, form=3, eps=1e-5):
     _chk(x, *ln0, *fc1, *fc2, *ln1)
     M = x.shape[0]
     out = torch.empty(M, 256, device=x.device, dtype=torch.bfloat16) if form == 4 else torch.empty(M, 128, device=x.device, dtype=torch.float32)
-    check(lib().sf_pixel_feat_f32(_p(x), _p(ln0[0]), _p(ln0[1]), _p(fc1[0]), _p(fc1[1]), _p(fc2[0]), _p(fc2[1]), _p(ln1[0]), _p(ln1[1]),
-                                  out.data_ptr(), M, eps, form, _stream()))
+    check(lib().sf_pixel_feat_f32(ptr(x), ptr(ln0[0]), ptr(ln0[1]), ptr(fc1[0]), ptr(fc1[1]), ptr(fc2[0]), ptr(fc2[1]), ptr(ln1[0]), ptr(ln1[1]),
+                                  out.data_ptr(), M, eps, form, stream()))
     return out
 
 
@@ -183,8 +176,8 @@ def conv2d_nhwc(x, w_packed, bias, relu=True, add=None):
     F_, H, W, Cin = x.shape
     Cout, ks = w_packed.shape[0], w_packed.shape[1]
     out = torch.empty(F_, H, W, Cout, device=x.device, dtype=torch.float32)
-    check(lib().sf_conv2d_nhwc_f32(_p(x), _p(w_packed), _p(bias), _p(add), _p(out), F_, H, W, Cin, Cout, ks,
-                                   int(relu), _stream()))
+    check(lib().sf_conv2d_nhwc_f32(ptr(x), ptr(w_packed), ptr(bias), ptr(add), ptr(out), F_, H, W, Cin, Cout, ks,
+                                   int(relu), stream()))
     return out
 
 
@@ -197,7 +190,7 @@ def conv_wgrad(a, x, stride=1, partial=None):
     if partial is None:
         partial = torch.empty(lib().sf_conv_wgrad_partial_floats(CA, 5), device=a.device, dtype=torch.float32)
     out = torch.empty(CA, 64, 5, 5, device=a.device, dtype=torch.float32)
-    check(lib().sf_conv_wgrad_f32(_p(a), CA, F_, H, W, _p(x), Hx, Wx, int(stride), 5, F_ * H * W, _p(out), _p(partial), partial.numel(), _stream()))
+    check(lib().sf_conv_wgrad_f32(ptr(a), CA, F_, H, W, ptr(x), Hx, Wx, int(stride), 5, F_ * H * W, ptr(out), ptr(partial), partial.numel(), stream()))
     return out
 
 
@@ -205,7 +198,7 @@ def pack_conv_bwd_weight(w):
     """Conv2d weight [Cout,Cin,k,k] -> [Cin,k,k,Cout], flipped: the packed weight of its backward-data convolution."""
     _chk(w)
     out = torch.empty(w.shape[1], w.shape[2], w.shape[3], w.shape[0], device=w.device, dtype=torch.float32)
-    check(lib().sf_pack_conv_bwd_weight_f32(_p(w), _p(out), w.shape[0], w.shape[1], w.shape[2], _stream()))
+    check(lib().sf_pack_conv_bwd_weight_f32(ptr(w), ptr(out), w.shape[0], w.shape[1], w.shape[2], stream()))
     return out
 
 
@@ -215,7 +208,7 @@ def conv2d_nhwc_bwd_data(g, w_packed, stride=1, relu_mask=None):
     F_, H, W, Cin = g.shape
     Cout, ks = w_packed.shape[0], w_packed.shape[1]
     out = torch.empty(F_, H // stride, W // stride, Cout, device=g.device, dtype=torch.float32)
-    check(lib().sf_conv2d_nhwc_bwd_data_f32(_p(g), _p(w_packed), _p(relu_mask), _p(out), F_, H, W, Cin, Cout, ks, int(stride), _stream()))
+    check(lib().sf_conv2d_nhwc_bwd_data_f32(ptr(g), ptr(w_packed), ptr(relu_mask), ptr(out), F_, H, W, Cin, Cout, ks, int(stride), stream()))
     return out
 
 
@@ -223,10 +216,10 @@ def conv_first_wgrad(img, dy, frame_stride=None):
     """img [F,3,R,R] NCHW (R 64 or 128), dy [F*4096,64] -> dW [64,3,5,5] of the encoder's first convolution."""
     _chk(img, dy)
     F_, res = img.shape[0], img.shape[-1]
-    nb = lib().sf_conv_first_wgrad_workspace_bytes(F_)
-    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=img.device)
+    ws = scratch(lib().sf_conv_first_wgrad_workspace_bytes, F_, device=img.device, at_least=16)
     out = torch.empty(64, 3, 5, 5, device=img.device, dtype=torch.float32)
-    check(lib().sf_conv_first_wgrad_f32(_p(img), int(frame_stride or 3 * res * res), res, _p(dy), F_, _p(out), ws.data_ptr(), nb, _stream()))
+    check(lib().sf_conv_first_wgrad_f32(ptr(img), int(frame_stride or 3 * res * res), res, ptr(dy), F_, ptr(out), ws.data_ptr(), ws.numel(),
+                                        stream()))
     return out
 
 
@@ -236,7 +229,7 @@ def pos_dense_grad(d, grid):
     F_, HW, C_ = d.shape
     dw, db = torch.empty(C_, 4, device=d.device), torch.empty(C_, device=d.device)
     dtab = torch.empty(HW, C_, device=d.device)
-    check(lib().sf_pos_dense_grad_f32(_p(d), F_, HW, C_, _p(grid), _p(dw), _p(db), _p(dtab), _stream()))
+    check(lib().sf_pos_dense_grad_f32(ptr(d), F_, HW, C_, ptr(grid), ptr(dw), ptr(db), ptr(dtab), stream()))
     return dw, db, dtab
 
 
@@ -248,10 +241,9 @@ def savi_decode_head_bwd(dec, d_recon, act, out_w, want_param_grads=True):
     d_dec, d_act = torch.empty_like(dec), torch.empty_like(act)
     gw = torch.empty(4, Cl, device=dec.device) if want_param_grads else None
     gb = torch.empty(4, device=dec.device) if want_param_grads else None
-    nb = lib().sf_savi_decode_head_bwd_workspace_bytes(Cl)
-    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dec.device)
-    check(lib().sf_savi_decode_head_bwd_f32(_p(dec), _p(d_recon), _p(act), _p(out_w), _p(d_dec), _p(d_act), _p(gw), _p(gb), F_, N, HW, Cl,
-                                            ws.data_ptr(), nb, _stream()))
+    ws = scratch(lib().sf_savi_decode_head_bwd_workspace_bytes, Cl, device=dec.device, at_least=16)
+    check(lib().sf_savi_decode_head_bwd_f32(ptr(dec), ptr(d_recon), ptr(act), ptr(out_w), ptr(d_dec), ptr(d_act), ptr(gw), ptr(gb), F_, N, HW, Cl,
+                                            ws.data_ptr(), ws.numel(), stream()))
     return d_dec, d_act, gw, gb
 
 
@@ -264,8 +256,8 @@ def slot_attn_iter(k, v, q, eps=1e-6, want_attn=False):
     pn = torch.empty(B, P, N, D, device=k.device, dtype=torch.float32)
     pd = torch.empty(B, P, N, device=k.device, dtype=torch.float32)
     attn = torch.empty(B, N, HW, device=k.device, dtype=torch.float32) if want_attn else None
-    check(lib().sf_slot_attn_iter_f32(_p(k), _p(v), D, HW * D, _p(q), _p(pn), _p(pd), _p(attn), B, HW, N, D,
-                                      float(D)**-0.5, eps, _stream()))
+    check(lib().sf_slot_attn_iter_f32(ptr(k), ptr(v), D, HW * D, ptr(q), ptr(pn), ptr(pd), ptr(attn), B, HW, N, D,
+                                      float(D)**-0.5, eps, stream()))
     return pn, pd, attn
 
 
@@ -279,8 +271,8 @@ def slot_attn_iter_planes(planes, q, eps=1e-6, want_attn=False):
     pn = torch.empty(B, P, N, 128, device=q.device, dtype=torch.float32)
     pd = torch.empty(B, P, N, device=q.device, dtype=torch.float32)
     attn = torch.empty(B, N, HW, device=q.device, dtype=torch.float32) if want_attn else None
-    check(lib().sf_slot_attn_iter_planes_f32(planes.data_ptr(), HW, _p(q), _p(pn), _p(pd), _p(attn), N * HW, B, HW, N, 128.0**-0.5, eps,
-                                             _stream()))
+    check(lib().sf_slot_attn_iter_planes_f32(planes.data_ptr(), HW, ptr(q), ptr(pn), ptr(pd), ptr(attn), N * HW, B, HW, N, 128.0**-0.5, eps,
+                                             stream()))
     return pn, pd, attn
 
 
@@ -296,9 +288,9 @@ def slot_prologue(prev, init, pm, kd, q, noise=None, norm_first=True, want_kdist
     w0_t, w2_t, kd_t, q_t = t(pm[2]), t(pm[4]), t(kd[0]), t(q[2])
     slots, q_out = torch.empty(B, N, D, device=init.device), torch.empty(B, N, D, device=init.device)
     kdist = torch.empty(B, N, 2 * D, device=init.device) if want_kdist else None
-    check(lib().sf_slot_prologue_f32(_p(prev), _p(init), _p(pm[0]), _p(pm[1]), _p(w0_t), _p(pm[3]), _p(w2_t), _p(pm[5]), int(norm_first), _p(kd_t),
-                                     _p(kd[1]), _p(noise), N * D, _p(kdist), N * 2 * D, _p(q[0]), _p(q[1]), _p(q_t), _p(slots), _p(q_out), B, N, D,
-                                     ln_eps, _stream()))
+    check(lib().sf_slot_prologue_f32(ptr(prev), ptr(init), ptr(pm[0]), ptr(pm[1]), ptr(w0_t), ptr(pm[3]), ptr(w2_t), ptr(pm[5]), int(norm_first), ptr(kd_t),
+                                     ptr(kd[1]), ptr(noise), N * D, ptr(kdist), N * 2 * D, ptr(q[0]), ptr(q[1]), ptr(q_t), ptr(slots), ptr(q_out), B, N, D,
+                                     ln_eps, stream()))
     return slots, q_out, kdist
 
 
@@ -315,10 +307,9 @@ def slot_attn_iter_bwd(k, v, q, pn, pd, d_updates, dk=None, dv=None, eps=1e-6):
     # N <= 8: the 8-slot entry point; 9 .. 16 slots: the two-launch form behind its own entry point
     ws_bytes, bwd = ((lib().sf_slot_attn_iter_bwd_workspace_bytes, lib().sf_slot_attn_iter_bwd_f32) if N <= 8 else
                      (lib().sf_slot_attn_iter_bwd16_workspace_bytes, lib().sf_slot_attn_iter_bwd16_f32))
-    nb = ws_bytes(B, HW, N, D)
-    ws = torch.empty(nb, dtype=torch.uint8, device=k.device)
-    check(bwd(_p(k), _p(v), D, HW * D, _p(q), _p(pn), _p(pd), P, _p(d_updates), _p(dk), _p(dv),
-              int(acc), _p(dq), B, HW, N, D, float(D)**-0.5, eps, ws.data_ptr(), nb, _stream()))
+    ws = scratch(ws_bytes, B, HW, N, D, device=k.device)
+    check(bwd(ptr(k), ptr(v), D, HW * D, ptr(q), ptr(pn), ptr(pd), P, ptr(d_updates), ptr(dk), ptr(dv),
+              int(acc), ptr(dq), B, HW, N, D, float(D)**-0.5, eps, ws.data_ptr(), ws.numel(), stream()))
     return dq, dk, dv
 
 
@@ -328,9 +319,9 @@ def slot_update(pn, pd, slots_prev, gru, ln_g, ln_b, w1, b1, w2, b2, ln_eps=1e-5
     B, P, N, D = pn.shape
     out = torch.empty_like(slots_prev)
     w_ih_t, w_hh_t, w1_t, w2_t = (w.t().contiguous() for w in (gru[0], gru[1], w1, w2))
-    check(lib().sf_slot_update_f32(_p(pn), _p(pd), P, _p(slots_prev), _p(w_ih_t), _p(w_hh_t), _p(gru[2]),
-                                   _p(gru[3]), _p(ln_g), _p(ln_b), _p(w1_t), _p(b1), _p(w2_t), _p(b2), _p(out),
-                                   B, N, D, w1.shape[0], ln_eps, _stream()))
+    check(lib().sf_slot_update_f32(ptr(pn), ptr(pd), P, ptr(slots_prev), ptr(w_ih_t), ptr(w_hh_t), ptr(gru[2]),
+                                   ptr(gru[3]), ptr(ln_g), ptr(ln_b), ptr(w1_t), ptr(b1), ptr(w2_t), ptr(b2), ptr(out),
+                                   B, N, D, w1.shape[0], ln_eps, stream()))
     return out
 
 
@@ -339,7 +330,7 @@ def pack_linear(w):
     _chk(w)
     n, k = w.shape
     buf = torch.empty(lib().sf_packed_linear_bytes(n, k), dtype=torch.uint8, device=w.device)
-    check(lib().sf_pack_linear_weights(_p(w.contiguous()), buf.data_ptr(), n, k, _stream()))
+    check(lib().sf_pack_linear_weights(ptr(w.contiguous()), buf.data_ptr(), n, k, stream()))
     return buf
 
 
@@ -351,10 +342,10 @@ def slot_update_packed(pn, pd, slots_prev, gru, ln_g, ln_b, w1, b1, w2, b2, q=No
     packed = [pack_linear(w) for w in (gru[0], gru[1], w1, w2)]
     q_out = torch.empty_like(slots_prev) if q is not None else None
     qp = pack_linear(q[2]) if q is not None else None
-    check(lib().sf_slot_update_packed_f32(_p(pn), _p(pd), P, _p(slots_prev), packed[0].data_ptr(), packed[1].data_ptr(), _p(gru[2]),
-                                          _p(gru[3]), _p(ln_g), _p(ln_b), packed[2].data_ptr(), _p(b1), packed[3].data_ptr(), _p(b2),
-                                          _p(out), _p(q[0]) if q is not None else None, _p(q[1]) if q is not None else None,
-                                          qp.data_ptr() if qp is not None else None, _p(q_out), B, N, D, w1.shape[0], ln_eps, _stream()))
+    check(lib().sf_slot_update_packed_f32(ptr(pn), ptr(pd), P, ptr(slots_prev), packed[0].data_ptr(), packed[1].data_ptr(), ptr(gru[2]),
+                                          ptr(gru[3]), ptr(ln_g), ptr(ln_b), packed[2].data_ptr(), ptr(b1), packed[3].data_ptr(), ptr(b2),
+                                          ptr(out), ptr(q[0]) if q is not None else None, ptr(q[1]) if q is not None else None,
+                                          ptr(qp), ptr(q_out), B, N, D, w1.shape[0], ln_eps, stream()))
     return (out, q_out) if q is not None else out
 
 
@@ -367,11 +358,11 @@ def slot_update_packed_next(pn, pd, slots_prev, gru, ln_g, ln_b, w1, b1, w2, b2,
     out, nxt, q_out = torch.empty_like(slots_prev), torch.empty_like(slots_prev), torch.empty_like(slots_prev)
     kdist = torch.empty(B, N, 2 * D, device=pn.device) if want_kdist else None
     pk = [pack_linear(w) for w in (gru[0], gru[1], w1, w2, q[2], pm[2], pm[4], kd[0])]
-    check(lib().sf_slot_update_packed_next_f32(_p(pn), _p(pd), P, _p(slots_prev), pk[0].data_ptr(), pk[1].data_ptr(), _p(gru[2]), _p(gru[3]), _p(ln_g),
-                                               _p(ln_b), pk[2].data_ptr(), _p(b1), pk[3].data_ptr(), _p(b2), _p(out), _p(q[0]), _p(q[1]),
-                                               pk[4].data_ptr(), _p(q_out), B, N, D, w1.shape[0], ln_eps, None, 0, p_step, _p(pm[0]), _p(pm[1]),
-                                               pk[5].data_ptr(), _p(pm[3]), pk[6].data_ptr(), _p(pm[5]), int(norm_first), pk[7].data_ptr(),
-                                               _p(kd[1]), _p(noise), N * D, _p(kdist), N * 2 * D, _p(nxt), _stream()))
+    check(lib().sf_slot_update_packed_next_f32(ptr(pn), ptr(pd), P, ptr(slots_prev), pk[0].data_ptr(), pk[1].data_ptr(), ptr(gru[2]), ptr(gru[3]), ptr(ln_g),
+                                               ptr(ln_b), pk[2].data_ptr(), ptr(b1), pk[3].data_ptr(), ptr(b2), ptr(out), ptr(q[0]), ptr(q[1]),
+                                               pk[4].data_ptr(), ptr(q_out), B, N, D, w1.shape[0], ln_eps, None, 0, p_step, ptr(pm[0]), ptr(pm[1]),
+                                               pk[5].data_ptr(), ptr(pm[3]), pk[6].data_ptr(), ptr(pm[5]), int(norm_first), pk[7].data_ptr(),
+                                               ptr(kd[1]), ptr(noise), N * D, ptr(kdist), N * 2 * D, ptr(nxt), stream()))
     return out, nxt, q_out, kdist
 
 
@@ -380,7 +371,7 @@ def mha(qkv, B, L, d_model, num_heads, Lq=None):
     _chk(qkv)
     Lq = L if Lq is None else Lq
     out = torch.empty(B * Lq, d_model, device=qkv.device, dtype=torch.float32)
-    check(lib().sf_mha_f32(_p(qkv), _p(out), B, L, Lq, d_model, num_heads, _stream()))
+    check(lib().sf_mha_f32(ptr(qkv), ptr(out), B, L, Lq, d_model, num_heads, stream()))
     return out
 
 
@@ -391,8 +382,8 @@ def qkv_attention(x, in_proj_w, in_proj_b, B, L, num_heads, ln=None, Lq=None, ln
     Lq = L if Lq is None else Lq
     out = torch.empty(B * Lq, d, device=x.device, dtype=torch.float32)
     g, b = ln if ln is not None else (None, None)
-    check(lib().sf_qkv_attention_f32(_p(x), _p(g), _p(b), ln_eps, _p(in_proj_w), _p(in_proj_b), _p(out), B, L, Lq, d,
-                                     num_heads, _stream()))
+    check(lib().sf_qkv_attention_f32(ptr(x), ptr(g), ptr(b), ln_eps, ptr(in_proj_w), ptr(in_proj_b), ptr(out), B, L, Lq, d,
+                                     num_heads, stream()))
     return out
 
 
@@ -401,7 +392,7 @@ def lstm_pointwise(gates, c_prev):
     R, H4 = gates.shape
     h = torch.empty(R, H4 // 4, device=gates.device, dtype=torch.float32)
     c = torch.empty_like(h)
-    check(lib().sf_lstm_pointwise_f32(_p(gates), _p(c_prev), _p(h), _p(c), R, H4 // 4, _stream()))
+    check(lib().sf_lstm_pointwise_f32(ptr(gates), ptr(c_prev), ptr(h), ptr(c), R, H4 // 4, stream()))
     return h, c
 
 
@@ -409,7 +400,7 @@ def sample_dist(dist, noise=None):
     _chk(dist, noise)
     D = dist.shape[-1] // 2
     out = torch.empty(*dist.shape[:-1], D, device=dist.device, dtype=torch.float32)
-    check(lib().sf_sample_dist_f32(_p(dist), _p(noise), _p(out), dist.numel() // (2 * D), D, _stream()))
+    check(lib().sf_sample_dist_f32(ptr(dist), ptr(noise), ptr(out), dist.numel() // (2 * D), D, stream()))
     return out
 
 
@@ -418,8 +409,8 @@ def bilinear_resize(x, size):
     _chk(x)
     Hi, Wi = x.shape[-2:]
     out = torch.empty(*x.shape[:-2], size[0], size[1], device=x.device, dtype=torch.float32)
-    check(lib().sf_bilinear_resize_f32(_p(x), _p(out), x.numel() // (Hi * Wi), Hi, Wi, size[0], size[1],
-                                       _stream()))
+    check(lib().sf_bilinear_resize_f32(ptr(x), ptr(out), x.numel() // (Hi * Wi), Hi, Wi, size[0], size[1],
+                                       stream()))
     return out
 
 
@@ -430,10 +421,9 @@ def groupnorm1_nhwc(x, gamma, beta, eps=1e-5, relu=True, pixel_shuffle=1):
     F_, H, W, C_ = x.shape
     r = pixel_shuffle
     out = torch.empty(F_, H * r, W * r, C_ // (r * r), device=x.device, dtype=torch.float32)
-    nb = lib().sf_groupnorm1_workspace_bytes(F_)
-    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=x.device)
-    check(lib().sf_groupnorm1_nhwc_f32(_p(x), _p(gamma), _p(beta), _p(out), F_, H, W, C_, eps, int(relu), r, ws.data_ptr(), nb,
-                                       _stream()))
+    ws = scratch(lib().sf_groupnorm1_workspace_bytes, F_, device=x.device, empty_ok=F_ == 0, at_least=8)   # (no frames: an empty batch, which is taken)
+    check(lib().sf_groupnorm1_nhwc_f32(ptr(x), ptr(gamma), ptr(beta), ptr(out), F_, H, W, C_, eps, int(relu), r, ws.data_ptr(), ws.numel(),
+                                       stream()))
     return out
 
 
@@ -445,8 +435,8 @@ def slate_attention(q, k, v, num_heads, causal, q_off=0, k_off=0, v_off=0, d_mod
     Lk, ldk, ldv = k.shape[1], k.shape[2], v.shape[2]
     d = d_model if d_model is not None else ldq
     out = torch.empty(B, Lq, d, device=q.device, dtype=torch.float32)
-    check(lib().sf_slate_attention_f32(q.data_ptr() + 4 * q_off, k.data_ptr() + 4 * k_off, v.data_ptr() + 4 * v_off, _p(out),
-                                       ldq, ldk, ldv, d, B, Lq, Lk, num_heads, d // num_heads, int(causal), _stream()))
+    check(lib().sf_slate_attention_f32(q.data_ptr() + 4 * q_off, k.data_ptr() + 4 * k_off, v.data_ptr() + 4 * v_off, ptr(out),
+                                       ldq, ldk, ldv, d, B, Lq, Lk, num_heads, d // num_heads, int(causal), stream()))
     return out
 
 
@@ -456,10 +446,9 @@ def slate_attention_bwd(q, k, v, out, d_out, num_heads, causal):
     B, Lq, d = q.shape
     Lk = k.shape[1]
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    nb = lib().sf_slate_attention_bwd_workspace_bytes(B, Lq, num_heads)
-    ws = torch.empty(nb, dtype=torch.uint8, device=q.device)
-    check(lib().sf_slate_attention_bwd_f32(_p(q), _p(k), _p(v), _p(out), _p(d_out), _p(dq), _p(dk), _p(dv), d, d, d, d, Lq * d, Lk * d,
-                                           Lk * d, Lq * d, B, Lq, Lk, num_heads, d // num_heads, int(causal), ws.data_ptr(), nb, _stream()))
+    ws = scratch(lib().sf_slate_attention_bwd_workspace_bytes, B, Lq, num_heads, device=q.device)
+    check(lib().sf_slate_attention_bwd_f32(ptr(q), ptr(k), ptr(v), ptr(out), ptr(d_out), ptr(dq), ptr(dk), ptr(dv), d, d, d, d, Lq * d, Lk * d,
+                                           Lk * d, Lq * d, B, Lq, Lk, num_heads, d // num_heads, int(causal), ws.data_ptr(), ws.numel(), stream()))
     return dq, dk, dv
 
 
@@ -471,7 +460,7 @@ def embed_tokens(idx, tok_emb, pos):
     B, L = idx.shape
     d = tok_emb.shape[1]
     out = torch.empty(B, L, d, device=tok_emb.device, dtype=torch.float32)
-    check(lib().sf_embed_tokens_f32(idx.data_ptr(), _p(tok_emb), _p(pos), _p(out), B, L, d, _stream()))
+    check(lib().sf_embed_tokens_f32(idx.data_ptr(), ptr(tok_emb), ptr(pos), ptr(out), B, L, d, stream()))
     return out
 
 
@@ -481,7 +470,7 @@ def argmax_rows(x):
     V = x.shape[-1]
     R = x.numel() // V
     out = torch.empty(x.shape[:-1], device=x.device, dtype=torch.int64)
-    check(lib().sf_argmax_rows_f32(_p(x), V, out.data_ptr(), R, V, _stream()))
+    check(lib().sf_argmax_rows_f32(ptr(x), V, out.data_ptr(), R, V, stream()))
     return out
 
 
@@ -496,7 +485,7 @@ def patch_embed(imgs, weight):
     _chk(imgs, weight)
     F_, C_, H, W = imgs.shape
     out = torch.empty(F_, H // 4, W // 4, 64, device=imgs.device, dtype=torch.float32)
-    check(lib().sf_dvae_patch_embed_f32(_p(imgs), _p(weight), _p(out), F_, C_, H, W, _stream()))
+    check(lib().sf_dvae_patch_embed_f32(ptr(imgs), ptr(weight), ptr(out), F_, C_, H, W, stream()))
     return out
 
 
@@ -508,7 +497,7 @@ def pack_head_weight(w):
     if nb == 0:
         raise RuntimeError(f'slotformer_amd pack_head_weight: K must be 64 and V a multiple of 32, got [{V}, {K}]')
     out = torch.empty(nb, device=w.device, dtype=torch.uint8)
-    check(lib().sf_dvae_pack_head_weights(_p(w), out.data_ptr(), V, K, _stream()))
+    check(lib().sf_dvae_pack_head_weights(ptr(w), out.data_ptr(), V, K, stream()))
     return out
 
 
@@ -530,7 +519,7 @@ def linear_argmax(x, w_packed, bias, V, out=None, out_i16=None):
     for t, dt in ((out, torch.int64), (out_i16, torch.int16)):
         if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == R):
             raise TypeError(f'linear_argmax: outputs must be contiguous {dt} device tensors of {R} elements')
-    check(lib().sf_dvae_head_argmax_f32(x.data_ptr(), ld, w_packed.data_ptr(), _p(bias), _p(out), _p(out_i16), R, int(V), K, _stream()))
+    check(lib().sf_dvae_head_argmax_f32(x.data_ptr(), ld, w_packed.data_ptr(), ptr(bias), ptr(out), ptr(out_i16), R, int(V), K, stream()))
     return out if out_i16 is None else out_i16 if out is None else (out, out_i16)
 
 
@@ -541,7 +530,7 @@ def gather_rows(table, ids):
         raise TypeError('gather_rows: ids must be a contiguous int64 device tensor')
     rows, d = table.shape
     out = torch.empty(tuple(ids.shape) + (d, ), device=table.device, dtype=torch.float32)
-    check(lib().sf_gather_rows_f32(_p(table), ids.data_ptr(), _p(out), ids.numel(), d, rows, _stream()))
+    check(lib().sf_gather_rows_f32(ptr(table), ids.data_ptr(), ptr(out), ids.numel(), d, rows, stream()))
     return out
 
 
@@ -553,7 +542,7 @@ def pack_head_ce_weight(w):
     if nb == 0:
         raise RuntimeError(f'slotformer_amd pack_head_ce_weight: K a multiple of 32 in [32, 256] and V a multiple of 32 in [32, 2^20], got [{V}, {K}]')
     out = torch.empty(nb, device=w.device, dtype=torch.uint8)
-    check(lib().sf_head_ce_pack_weights(_p(w), out.data_ptr(), V, K, _stream()))
+    check(lib().sf_head_ce_pack_weights(ptr(w), out.data_ptr(), V, K, stream()))
     return out
 
 
@@ -591,9 +580,9 @@ def head_ce_forward(x, w_packed, target, V, group_w=None, group=1, stats=None, w
     if stats is not None:
         if not (stats.is_cuda and stats.dtype == torch.float64 and stats.numel() == 2 and stats.is_contiguous()):
             raise TypeError('slotformer_amd head_ce: stats is a contiguous float64 [2] device tensor')
-        ws = torch.empty(lib().sf_head_ce_workspace_bytes(R) // 8, device=x.device, dtype=torch.float64)
-    check(lib().sf_head_ce_fwd_f32(x.data_ptr(), ld, w_packed.data_ptr(), t64, t16, _p(group_w), int(group), _p(lse), _p(rows), _p(stats), R, int(V), K,
-                                   _p(ws), 0 if ws is None else ws.numel() * 8, _stream()))
+        ws = scratch(lib().sf_head_ce_workspace_bytes, R, device=x.device)
+    check(lib().sf_head_ce_fwd_f32(x.data_ptr(), ld, w_packed.data_ptr(), t64, t16, ptr(group_w), int(group), ptr(lse), ptr(rows), ptr(stats), R, int(V), K,
+                                   ptr(ws), 0 if ws is None else ws.numel(), stream()))
     return lse, rows
 
 
@@ -608,8 +597,8 @@ def head_ce_backward(x, w_packed, target, V, lse, g, group_w=None, group=1, out=
         out = torch.empty(R, K, device=x.device, dtype=torch.float32)
     elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (R, K) and out.stride(1) == 1 and out.stride(0) >= K):
         raise TypeError(f'slotformer_amd head_ce: out is a float32 [{R}, {K}] device tensor with unit column stride')
-    check(lib().sf_head_ce_bwd_f32(x.data_ptr(), ld, w_packed.data_ptr(), t64, t16, _p(group_w), int(group), _p(lse), _p(g), out.data_ptr(),
-                                   out.stride(0), R, int(V), K, _stream()))
+    check(lib().sf_head_ce_bwd_f32(x.data_ptr(), ld, w_packed.data_ptr(), t64, t16, ptr(group_w), int(group), ptr(lse), ptr(g), out.data_ptr(),
+                                   out.stride(0), R, int(V), K, stream()))
     return out
 
 
@@ -621,7 +610,7 @@ def cross_entropy(logits, target):
     R, V = logits.shape
     rows = torch.empty(R, device=logits.device, dtype=torch.float32)
     mean = torch.empty(1, device=logits.device, dtype=torch.float32)
-    check(lib().sf_cross_entropy_f32(_p(logits), target.data_ptr(), _p(rows), _p(mean), R, V, _stream()))
+    check(lib().sf_cross_entropy_f32(ptr(logits), target.data_ptr(), ptr(rows), ptr(mean), R, V, stream()))
     return mean[0]
 
 
@@ -630,7 +619,7 @@ def softmax_rows(x, add=None, scale=1.0):
     _chk(x, add)
     V = x.shape[-1]
     out = torch.empty_like(x)
-    check(lib().sf_softmax_rows_f32(_p(x), _p(add), float(scale), _p(out), x.numel() // V, V, _stream()))
+    check(lib().sf_softmax_rows_f32(ptr(x), ptr(add), float(scale), ptr(out), x.numel() // V, V, stream()))
     return out
 
 
@@ -639,7 +628,7 @@ def log_softmax_rows(x):
     _chk(x)
     V = x.shape[-1]
     out = torch.empty_like(x)
-    check(lib().sf_log_softmax_rows_f32(_p(x), _p(out), x.numel() // V, V, _stream()))
+    check(lib().sf_log_softmax_rows_f32(ptr(x), ptr(out), x.numel() // V, V, stream()))
     return out
 
 
@@ -649,7 +638,7 @@ def gumbel_softmax_rows(x, seed, scale=1.0):
     _chk(x)
     V = x.shape[-1]
     out = torch.empty_like(x)
-    check(lib().sf_gumbel_softmax_rows_f32(_p(x), int(seed) & 0xffffffffffffffff, float(scale), _p(out), x.numel() // V, V, _stream()))
+    check(lib().sf_gumbel_softmax_rows_f32(ptr(x), int(seed) & 0xffffffffffffffff, float(scale), ptr(out), x.numel() // V, V, stream()))
     return out
 
 
@@ -661,8 +650,8 @@ def slate_attention_cached(q, kv_cache, Lk, num_heads, d_model, k_off, v_off):
     Lmax, ld = kv_cache.shape[1], kv_cache.shape[2]
     out = torch.empty(B, Lq, d_model, device=q.device, dtype=torch.float32)
     check(lib().sf_slate_attention_strided_f32(q.data_ptr(), kv_cache.data_ptr() + 4 * k_off, kv_cache.data_ptr() + 4 * v_off,
-                                               _p(out), ldq, ld, ld, d_model, Lq * ldq, Lmax * ld, Lmax * ld, Lq * d_model, B, Lq,
-                                               Lk, num_heads, d_model // num_heads, 0, _stream()))
+                                               ptr(out), ldq, ld, ld, d_model, Lq * ldq, Lmax * ld, Lmax * ld, Lq * d_model, B, Lq,
+                                               Lk, num_heads, d_model // num_heads, 0, stream()))
     return out
 
 
@@ -725,8 +714,8 @@ def physion_readout_fwd(slots, W1, b1, w2, b2, agg, video_index=None, video_len=
     t_star = torch.empty(K, B, dtype=torch.int32, device=dev)
     steps = torch.empty(K, B, T, dtype=torch.float32, device=dev) if want_steps else None
     pairs = torch.empty(K, B, F, dtype=torch.uint8, device=dev) if want_pairs else None
-    check(lib().sf_physion_readout_fwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, _p(video_index), _p(W1), _p(b1), _p(w2), _p(b2),
-                                           _p(logits), _p(t_star), _p(steps), _p(pairs), K, B, T, N, C, F, READOUT_AGG[agg], _stream()))
+    check(lib().sf_physion_readout_fwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, ptr(video_index), ptr(W1), ptr(b1), ptr(w2), ptr(b2),
+                                           ptr(logits), ptr(t_star), ptr(steps), ptr(pairs), K, B, T, N, C, F, READOUT_AGG[agg], stream()))
     return logits, t_star, steps, pairs
 
 
@@ -750,11 +739,10 @@ def physion_readout_bwd(slots, W1, b1, w2, g, t_star, agg, pair_star=None, video
     if flat.numel() != n or flat.dtype != torch.float32 or not flat.is_contiguous():
         raise ValueError(f'slotformer_amd: the readout gradient buffer holds {n} contiguous float32 elements')
     dW1, db1, dw2, db2 = flat[:F * 2 * C].view(F, 2 * C), flat[F * 2 * C:F * 2 * C + F], flat[F * 2 * C + F:F * 2 * C + 2 * F], flat[n - 1:]
-    nbytes = int(lib().sf_physion_readout_bwd_workspace_bytes(B, N, F))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=slots.device)
-    check(lib().sf_physion_readout_bwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, _p(video_index), _p(W1), _p(b1), _p(w2), _p(g),
-                                           _p(t_star), _p(pair_star), _p(dW1), _p(db1), _p(dw2), _p(db2), B, T, N, C, F, READOUT_AGG[agg],
-                                           ws.data_ptr(), ws.numel(), _stream()))
+    ws = scratch(lib().sf_physion_readout_bwd_workspace_bytes, B, N, F, device=slots.device, at_least=16)
+    check(lib().sf_physion_readout_bwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, ptr(video_index), ptr(W1), ptr(b1), ptr(w2), ptr(g),
+                                           ptr(t_star), ptr(pair_star), ptr(dW1), ptr(db1), ptr(dw2), ptr(db2), B, T, N, C, F, READOUT_AGG[agg],
+                                           ws.data_ptr(), ws.numel(), stream()))
     return dW1, db1, dw2, db2
 
 
@@ -782,8 +770,8 @@ def physion_readout_score(logits, labels, threshs=(), task_idx=None, n_tasks=0, 
     if threshs and n_tasks and task_counts is None:
         task_counts = torch.zeros(K, n_tasks, len(threshs), dtype=torch.int32, device=dev)
     th = (C.c_float * max(len(threshs), 1))(*threshs)
-    check(lib().sf_physion_readout_score_f32(_p(logits), _p(labels), _p(task_idx), th, len(threshs), n_tasks, _p(loss), _p(g), _p(counts),
-                                             _p(task_counts), K, B, _stream()))
+    check(lib().sf_physion_readout_score_f32(ptr(logits), ptr(labels), ptr(task_idx), th, len(threshs), n_tasks, ptr(loss), ptr(g), ptr(counts),
+                                             ptr(task_counts), K, B, stream()))
     return loss, g, counts, task_counts
 
 
@@ -818,13 +806,12 @@ def phyre_readout_fwd(slots, sel, in_proj_w, in_proj_b, enc_t_pe, cls, layers, n
         raise ValueError(f'slotformer_amd: a scatter table needs one scatter_index entry per batch entry ({B})')
     logits = torch.empty(B, dtype=torch.float32, device=dev)
     conf = torch.empty(B, dtype=torch.float32, device=dev) if want_conf else None
-    nbytes = int(lib().sf_phyre_readout_workspace_bytes(B, N, T))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    check(lib().sf_phyre_readout_fwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), (C.c_int * max(T, 1))(*sel),
-                                         _p(in_proj_w), _p(in_proj_b), _p(enc_t_pe), _p(cls), layers, int(num_layers), int(d_model), int(num_heads),
-                                         int(ffn), _p(mlp_w1), _p(mlp_b1), _p(mlp_w2), _p(mlp_b2), _p(logits), _p(conf), _p(scatter_index),
-                                         _p(scatter_table), 0 if scatter_table is None else scatter_table.numel(), B, T, N, Cs, ws.data_ptr(),
-                                         ws.numel(), _stream()))
+    ws = scratch(lib().sf_phyre_readout_workspace_bytes, B, N, T, device=dev, at_least=16)
+    check(lib().sf_phyre_readout_fwd_f32(slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, ptr(video_index), (C.c_int * max(T, 1))(*sel),
+                                         ptr(in_proj_w), ptr(in_proj_b), ptr(enc_t_pe), ptr(cls), layers, int(num_layers), int(d_model), int(num_heads),
+                                         int(ffn), ptr(mlp_w1), ptr(mlp_b1), ptr(mlp_w2), ptr(mlp_b2), ptr(logits), ptr(conf), ptr(scatter_index),
+                                         ptr(scatter_table), 0 if scatter_table is None else scatter_table.numel(), B, T, N, Cs, ws.data_ptr(),
+                                         ws.numel(), stream()))
     return logits, conf
 
 
@@ -873,17 +860,15 @@ def phyre_readout_train_fwd(model, slots, sel, video_index=None, p=0., seed=0, w
     import ctypes as C
     slots, T_all, V, sel, sel_c, video_index, B = _phyre_train_args(model, slots, sel, video_index)
     dev, T = slots.device, len(sel)
-    nbytes = phyre_readout_train_workspace_bytes(model, B, T)
-    if nbytes == 0:
+    if phyre_readout_train_workspace_bytes(model, B, T) == 0:
         raise NotImplementedError(f'slotformer_amd: the PHYRE readout has no training kernel for these shapes: {PHYRE_LIMITS}')
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = scratch(lib().sf_phyre_readout_train_workspace_bytes, C.byref(model), B, T, device=dev, reuse=ws)
     L = 1 + T * model.num_slots
     logits = torch.empty(B, dtype=torch.float32, device=dev)
     gates = torch.empty(model.num_layers, B * L, model.ffn_dim, dtype=torch.uint8, device=dev) if want_gates else None
     head_gates = torch.empty(B, model.d_model, dtype=torch.uint8, device=dev) if want_gates else None
-    check(lib().sf_phyre_readout_train_fwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), sel_c, B, T,
-                                               float(p), int(seed), _p(logits), _p(gates), _p(head_gates), ws.data_ptr(), ws.numel(), _stream()))
+    check(lib().sf_phyre_readout_train_fwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, ptr(video_index), sel_c, B, T,
+                                               float(p), int(seed), ptr(logits), ptr(gates), ptr(head_gates), ws.data_ptr(), ws.numel(), stream()))
     return logits, ws, gates, head_gates
 
 
@@ -906,16 +891,16 @@ def phyre_readout_train_bwd(model, slots, sel, g, ws, video_index=None, p=0., se
     arr = (sf_tfm_layer_grads * model.num_layers)()
     off = 0
     for name, k in layout:
-        ptr = flat.data_ptr() + 4 * off
+        addr = flat.data_ptr() + 4 * off
         if name.startswith('layers.'):
             _, i, field = name.split('.')
-            setattr(arr[int(i)], field, ptr)
+            setattr(arr[int(i)], field, addr)
         else:
-            setattr(gs, name, ptr)
+            setattr(gs, name, addr)
         off += k
     gs.layers = C.cast(arr, C.POINTER(sf_tfm_layer_grads))
-    check(lib().sf_phyre_readout_train_bwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), sel_c, B, T,
-                                               _p(g), C.byref(gs), float(p), int(seed), ws.data_ptr(), ws.numel(), _stream()))
+    check(lib().sf_phyre_readout_train_bwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, ptr(video_index), sel_c, B, T,
+                                               ptr(g), C.byref(gs), float(p), int(seed), ws.data_ptr(), ws.numel(), stream()))
     return flat
 
 
@@ -931,7 +916,7 @@ def phyre_auccess_ranks(conf, status):
     status = status.to(torch.int32).contiguous()
     tasks, actions = conf.shape
     ranks = torch.empty(tasks, dtype=torch.int32, device=conf.device)
-    check(lib().sf_phyre_auccess_f32(_p(conf), _p(status), _p(ranks), tasks, actions, _stream()))
+    check(lib().sf_phyre_auccess_f32(ptr(conf), ptr(status), ptr(ranks), tasks, actions, stream()))
     return ranks
 
 
@@ -955,7 +940,7 @@ def aloe_text_table(q_embedding, q_in_proj_w, q_in_proj_b):
     if q_in_proj_w.shape[1] != E + 4:
         raise ValueError(f'slotformer_amd: q_in_proj takes {q_in_proj_w.shape[1]} inputs, an embedding with its two id pairs has {E + 4}')
     table = torch.empty(vocab, d, dtype=torch.float32, device=q_embedding.device)
-    check(lib().sf_aloe_text_table_f32(_p(q_embedding), _p(q_in_proj_w), _p(q_in_proj_b), _p(table), vocab, E, d, _stream()))
+    check(lib().sf_aloe_text_table_f32(ptr(q_embedding), ptr(q_in_proj_w), ptr(q_in_proj_b), ptr(table), vocab, E, d, stream()))
     return table
 
 
@@ -984,11 +969,10 @@ def aloe_fwd(model_struct, slots, tokens, pad_mask, head, multiple_choice, video
     H, A = W1.shape[0], W2.shape[0]
     logits = torch.empty(B, A, dtype=torch.float32, device=dev)
     answers = torch.empty(B, dtype=torch.int32, device=dev) if want_answers else None
-    nbytes = int(lib().sf_aloe_workspace_bytes(B, m.num_slots, m.T, m.text_len, m.d_model, m.ffn_dim))
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    check(lib().sf_aloe_fwd_f32(C.byref(m), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, _p(video_index), _p(start), int(frame_offset),
-                                _p(tokens), _p(pad_mask), int(bool(multiple_choice)), _p(W1), _p(b1), _p(W2), _p(b2), H, A, _p(logits), _p(answers), B,
-                                ws.data_ptr(), ws.numel(), _stream()))
+    ws = scratch(lib().sf_aloe_workspace_bytes, B, m.num_slots, m.T, m.text_len, m.d_model, m.ffn_dim, device=dev, at_least=16)
+    check(lib().sf_aloe_fwd_f32(C.byref(m), slots.data_ptr(), slots.stride(0), slots.stride(1), V, T_all, ptr(video_index), ptr(start), int(frame_offset),
+                                ptr(tokens), ptr(pad_mask), int(bool(multiple_choice)), ptr(W1), ptr(b1), ptr(W2), ptr(b2), H, A, ptr(logits), ptr(answers), B,
+                                ws.data_ptr(), ws.numel(), stream()))
     return logits, answers
 
 
@@ -1020,6 +1004,6 @@ def aloe_score(cls_logits=None, cls_labels=None, mc_logits=None, mc_labels=None,
     ques = torch.empty(Q, dtype=torch.int32, device=dev)
     if counts is None:
         counts = torch.zeros(10, dtype=torch.int32, device=dev)
-    check(lib().sf_aloe_score_f32(_p(cls_logits), _p(cls_labels), B1, A, _p(mc_logits), _p(mc_labels), _p(mc_flag), Bn, _p(mc_subtype), Q, _p(losses),
-                                  ques.data_ptr() if Q else None, _p(counts), _stream()))
+    check(lib().sf_aloe_score_f32(ptr(cls_logits), ptr(cls_labels), B1, A, ptr(mc_logits), ptr(mc_labels), ptr(mc_flag), Bn, ptr(mc_subtype), Q, ptr(losses),
+                                  ques.data_ptr() if Q else None, ptr(counts), stream()))
     return losses, ques, counts

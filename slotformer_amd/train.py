@@ -18,6 +18,7 @@ import ctypes as C
 import torch
 import torch.nn.functional as tnf
 
+from ._call import ptr, require_device, scratch, stream
 from ._lib import sf_savi_features, sf_savi_features_grads, sf_savi_decoder_grads
 from ._lib import sf_adam_group
 from ._lib import lib, check, sf_rollouter_grads, sf_tfm_layer_grads, sf_slot_attention, sf_slot_attention_grads, _SA_LEAVES
@@ -81,17 +82,13 @@ class _Rollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, x, pred_len, p_drop, seed, *params):
         x = x.detach().float().contiguous()
-        if not x.is_cuda:
-            raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
+        require_device(x)
         plan = engine.rollouter_plan(r, packed=False)
         B = x.shape[0]
-        nbytes = lib().sf_rollout_train_workspace_bytes(C.byref(plan.struct), B, pred_len)
-        if nbytes == 0:
-            check(-1)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+        ws = scratch(lib().sf_rollout_train_workspace_bytes, C.byref(plan.struct), B, pred_len, device=x.device)
         pred = torch.empty(B, pred_len, *x.shape[2:], dtype=torch.float32, device=x.device)
         check(lib().sf_rollout_train_fwd_f32(C.byref(plan.struct), x.data_ptr(), pred.data_ptr(), B, pred_len, float(p_drop),
-                                             int(seed), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+                                             int(seed), ws.data_ptr(), ws.numel(), stream()))
         ctx.r, ctx.plan, ctx.ws, ctx.args = r, plan, ws, (B, pred_len, float(p_drop), int(seed), tuple(x.shape))
         ctx.params = params
         return pred
@@ -126,9 +123,9 @@ def _rollout_backward(ctx, d_pred, xshape=None, grad_out=None):
     g, keep = _grad_descriptor(flat, params, len(r.transformer_encoder.layers), None)
     g.pe_tok = pe.data_ptr() if tables else None
     d_x = torch.empty(xshape, dtype=torch.float32, device=d_pred.device) if xshape is not None else None
-    check(lib().sf_rollout_train_bwd_f32(C.byref(plan.struct), d_pred.data_ptr(), d_x.data_ptr() if d_x is not None else None,
+    check(lib().sf_rollout_train_bwd_f32(C.byref(plan.struct), d_pred.data_ptr(), ptr(d_x),
                                          C.byref(g), B, pred_len, p_drop, seed, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                         torch.cuda.current_stream().cuda_stream))
+                                         stream()))
     del keep
     ctx.ws = None
     if grad_out is None:
@@ -198,15 +195,11 @@ def _clips_forward(r, table, clip_video, clip_start, frame_offset, pred_len, p_d
     B = clip_video.numel() if torch.is_tensor(clip_video) else 0
     _index_i32(clip_video, B, 'clip_video')
     _index_i32(clip_start, B, 'clip_start')
-    nbytes = lib().sf_rollout_train_workspace_bytes(C.byref(plan.struct), B, pred_len)
-    if nbytes == 0:
-        check(-1)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=table.device)
+    ws = scratch(lib().sf_rollout_train_workspace_bytes, C.byref(plan.struct), B, pred_len, device=table.device, reuse=ws)
     pred = torch.empty(B, pred_len, N, Cs, dtype=torch.float32, device=table.device)
     check(lib().sf_rollout_train_clips_fwd_f32(C.byref(plan.struct), table.data_ptr(), table.shape[1], clip_video.data_ptr(), clip_start.data_ptr(),
                                                int(frame_offset), pred.data_ptr(), B, pred_len, float(p_drop), int(seed), ws.data_ptr(), ws.numel(),
-                                               torch.cuda.current_stream().cuda_stream))
+                                               stream()))
     return pred, plan, ws
 
 
@@ -235,8 +228,7 @@ def rollout_clips_with_grad(r, table, clip_video, clip_start, frame_offset, pred
     (default: r.dropout_seed_override, else a fresh one from torch's CPU generator).
     grad_out: a flat fp32 buffer laid out as FlatAdam's bucket over rollouter_parameters(r) + learnable_tables(r) (`FlatAdam.grad`): the backward
     writes the gradients there -- then step with `FlatAdam.step(gathered=True)` -- and the parameters' `.grad` are left alone."""
-    if not (torch.is_tensor(table) and table.is_cuda):
-        raise RuntimeError('slotformer_amd: the slot table must live on a HIP device; there is no CPU fallback')
+    require_device(table, what='the slot table')
     layer0 = r.transformer_encoder.layers[0]
     p_drop = float(layer0.dropout.p) if r.training else 0.0
     if seed is None:
@@ -249,12 +241,13 @@ def rollout_clips_with_grad(r, table, clip_video, clip_start, frame_offset, pred
 _CLIP_MSE_WS = {}
 
 
-def _clip_mse_ws(device, nbytes):
+def _clip_mse_ws(device, B, S, E):
     """The loss launch's workspace, one per device: zero-filled once; every launch leaves its arrival counter at zero.  Launches that share it must
     be ordered (one stream at a time), as everything in this module is."""
-    ws = _CLIP_MSE_WS.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = _CLIP_MSE_WS[device] = torch.zeros(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=device)
+    old = _CLIP_MSE_WS.get(device)
+    ws = scratch(lib().sf_clip_mse_workspace_bytes, B, S, E, device=device, reuse=old, at_least=1 << 16)
+    if ws is not old:
+        _CLIP_MSE_WS[device] = ws.zero_()
     return ws
 
 
@@ -284,14 +277,11 @@ def clip_mse_launch(pred, target, clip_video, clip_start, frame_offset, hist, st
         _index_i32(clip_len, B, 'clip_len')
     if stats.dtype != torch.float64 or stats.numel() != 1 + 2 * S or not stats.is_contiguous():
         raise ValueError(f'slotformer_amd: stats is a contiguous float64 [{1 + 2 * S}] device tensor')
-    nbytes = lib().sf_clip_mse_workspace_bytes(B, S, E)
-    if nbytes == 0:
+    if lib().sf_clip_mse_workspace_bytes(B, S, E) == 0:
         raise NotImplementedError(f'slotformer_amd: clip_mse takes 1 to 64 steps and rows of a multiple of 4 elements, got S {S}, E {E}')
-    ws = _clip_mse_ws(pred.device, nbytes)
-    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    check(lib().sf_clip_mse_f32(pred.data_ptr(), target.data_ptr(), p(clip_video), p(clip_start), T_total, first, fstep, p(step_w), p(clip_len),
-                                int(hist), float(scale), p(d_pred), stats.data_ptr(), B, S, E, ws.data_ptr(), ws.numel(),
-                                torch.cuda.current_stream().cuda_stream))
+    ws = _clip_mse_ws(pred.device, B, S, E)
+    check(lib().sf_clip_mse_f32(pred.data_ptr(), target.data_ptr(), ptr(clip_video), ptr(clip_start), T_total, first, fstep, ptr(step_w),
+                                ptr(clip_len), int(hist), float(scale), ptr(d_pred), stats.data_ptr(), B, S, E, ws.data_ptr(), ws.numel(), stream()))
 
 
 class _ClipMse(torch.autograd.Function):
@@ -324,8 +314,7 @@ def clip_mse(pred, target, clip_video=None, clip_start=None, frame_offset=1, his
 def clip_frames(frames, clip_video, clip_start, frame_offset, hist, S, mean=0.5, std=0.5):
     """sf_clip_frames_f32: the S target frames of every clip from a uint8 table [V, T, H, W, 3] (already at the model's resolution) ->
     float32 [B, S, 3, H, W] = (x / 255 - mean) / std, the bits `FrameIngest` gives at equal source and output size.  mean / std: a float or three."""
-    if not (torch.is_tensor(frames) and frames.is_cuda):
-        raise RuntimeError('slotformer_amd: the frame table must live on a HIP device; there is no CPU fallback')
+    require_device(frames, what='the frame table')
     if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or not frames.is_contiguous():
         raise ValueError(f'slotformer_amd: the frame table is a contiguous uint8 [V, T, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)}')
     B = clip_video.numel() if torch.is_tensor(clip_video) else 0
@@ -336,7 +325,7 @@ def clip_frames(frames, clip_video, clip_start, frame_offset, hist, S, mean=0.5,
     out = torch.empty(B, int(S), 3, H, W, dtype=torch.float32, device=frames.device)
     check(lib().sf_clip_frames_f32(frames.data_ptr(), frames.shape[1], clip_video.data_ptr(), clip_start.data_ptr(), int(hist) * int(frame_offset),
                                    int(frame_offset), three(mean), three(std), out.data_ptr(), B, int(S), H, W,
-                                   torch.cuda.current_stream().cuda_stream))
+                                   stream()))
     return out
 
 
@@ -356,8 +345,7 @@ class _SlotAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sa, inputs, slots, *params):
         inputs, slots = inputs.detach().float().contiguous(), slots.detach().float().contiguous()
-        if not inputs.is_cuda:
-            raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
+        require_device(inputs)
         keep = [p.detach().float().contiguous() for p in params]
         m = sf_slot_attention()
         m.in_features, m.slot_size, m.mlp_hidden, m.num_slots = sa.in_features, sa.slot_size, sa.mlp_hidden_size, slots.shape[1]
@@ -365,13 +353,10 @@ class _SlotAttention(torch.autograd.Function):
         for name, t in zip(_SA_LEAVES, keep):
             setattr(m, name, t.data_ptr())
         B, HW = inputs.shape[:2]
-        nbytes = lib().sf_slot_attention_train_workspace_bytes(C.byref(m), B, HW, sa.num_iterations)
-        if nbytes == 0:
-            check(-1)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=inputs.device)
+        ws = scratch(lib().sf_slot_attention_train_workspace_bytes, C.byref(m), B, HW, sa.num_iterations, device=inputs.device)
         out = torch.empty_like(slots)
         check(lib().sf_slot_attention_train_fwd_f32(C.byref(m), inputs.data_ptr(), slots.data_ptr(), B, HW, sa.num_iterations,
-                                                    out.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+                                                    out.data_ptr(), ws.data_ptr(), ws.numel(), stream()))
         ctx.sa, ctx.m, ctx.keep, ctx.ws, ctx.inputs, ctx.params = sa, m, keep, ws, inputs, params
         return out
 
@@ -388,9 +373,9 @@ class _SlotAttention(torch.autograd.Function):
         d_in = torch.empty_like(inputs) if ctx.needs_input_grad[1] else None
         d_slots = torch.empty_like(d_out)
         check(lib().sf_slot_attention_train_bwd_f32(C.byref(m), inputs.data_ptr(), d_out.data_ptr(),
-                                                    d_in.data_ptr() if d_in is not None else None, d_slots.data_ptr(), C.byref(g), B, HW,
+                                                    ptr(d_in), d_slots.data_ptr(), C.byref(g), B, HW,
                                                     sa.num_iterations, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                                    torch.cuda.current_stream().cuda_stream))
+                                                    stream()))
         ctx.ws = None
         grads = _split(flat, params)
         return (None, d_in, d_slots if ctx.needs_input_grad[2] else None) + tuple(
@@ -423,8 +408,7 @@ class _Decode(torch.autograd.Function):
     def forward(ctx, m, slots, *params):
         from . import ops
         slots = slots.detach().float().contiguous()
-        if not slots.is_cuda:
-            raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
+        require_device(slots)
         plan = engine.decoder_plan(m, inference=False)
         if not hasattr(plan, 'bwd_w'):
             n = plan.struct.dec_layers
@@ -432,15 +416,12 @@ class _Decode(torch.autograd.Function):
             plan.bwd_w = (C.c_void_p * n)(*[t.data_ptr() for t in plan.bwd_keep])
         F_, N, D = slots.shape
         H = plan.struct.resolution
-        nbytes = lib().sf_savi_decode_train_workspace_bytes(C.byref(plan.struct), F_)
-        if nbytes == 0:
-            check(-1)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=slots.device)
+        ws = scratch(lib().sf_savi_decode_train_workspace_bytes, C.byref(plan.struct), F_, device=slots.device)
         recon = torch.empty(F_, 3, H, H, device=slots.device, dtype=torch.float32)
         recons = torch.empty(F_, N, 3, H, H, device=slots.device, dtype=torch.float32)
         masks = torch.empty(F_, N, 1, H, H, device=slots.device, dtype=torch.float32)
         check(lib().sf_savi_decode_train_fwd_f32(C.byref(plan.struct), slots.data_ptr(), recon.data_ptr(), recons.data_ptr(),
-                                                 masks.data_ptr(), F_, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+                                                 masks.data_ptr(), F_, ws.data_ptr(), ws.numel(), stream()))
         ctx.m, ctx.plan, ctx.ws, ctx.shape, ctx.params = m, plan, ws, (F_, N, D), params
         ctx.mark_non_differentiable(recons, masks)
         return recon, recons, masks
@@ -465,8 +446,8 @@ class _Decode(torch.autograd.Function):
             g.out_w, g.out_b, g.pos_w, g.pos_b = ptrs[2 * n:2 * n + 4]
             grid = m.decoder_pos_embedding.grid.detach().float().reshape(-1, 4).contiguous()
         check(lib().sf_savi_decode_train_bwd_f32(C.byref(ctx.plan.struct), ctx.plan.bwd_w, d_recon.data_ptr(), d_slots.data_ptr(),
-                                                 grid.data_ptr() if grid is not None else None, C.byref(g) if g is not None else None,
-                                                 F_, ctx.ws.data_ptr(), ctx.ws.numel(), torch.cuda.current_stream().cuda_stream))
+                                                 ptr(grid), C.byref(g) if g is not None else None,
+                                                 F_, ctx.ws.data_ptr(), ctx.ws.numel(), stream()))
         ctx.ws = None
         grads = ()
         if params:
@@ -501,8 +482,7 @@ class _Features(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, img, *params):
         img = img.detach().float().contiguous()
-        if not img.is_cuda:
-            raise RuntimeError('slotformer_amd: inputs must live on a HIP device; there is no CPU fallback')
+        require_device(img)
         keep = [p.detach().float().contiguous() for p in params]
         n = len(m.enc_channels) - 1
         s = sf_savi_features()
@@ -518,13 +498,10 @@ class _Features(torch.autograd.Function):
         for name, t in zip(('pos_w', 'pos_b', 'ln_g', 'ln_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b'), keep[2 * n:2 * n + 8]):
             setattr(s, name, t.data_ptr())
         F_ = img.shape[0]
-        nbytes = lib().sf_savi_features_train_workspace_bytes(C.byref(s), F_)
-        if nbytes == 0:
-            check(-1)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=img.device)
+        ws = scratch(lib().sf_savi_features_train_workspace_bytes, C.byref(s), F_, device=img.device)
         out = torch.empty(F_, 64 * 64, s.out_channels, dtype=torch.float32, device=img.device)
         check(lib().sf_savi_features_train_fwd_f32(C.byref(s), img.data_ptr(), img[0].numel(), F_, out.data_ptr(), ws.data_ptr(),
-                                                   ws.numel(), torch.cuda.current_stream().cuda_stream))
+                                                   ws.numel(), stream()))
         ctx.m, ctx.s, ctx.keep, ctx.ws, ctx.img, ctx.params = m, s, keep, ws, img, params
         return out
 
@@ -541,10 +518,10 @@ class _Features(torch.autograd.Function):
         n = s.layers
         for i in range(n):
             g.conv_w[i], g.conv_b[i] = ptrs[2 * i], ptrs[2 * i + 1]
-        for name, ptr in zip(('pos_w', 'pos_b', 'ln_g', 'ln_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b'), ptrs[2 * n:]):
-            setattr(g, name, ptr)
+        for name, at in zip(('pos_w', 'pos_b', 'ln_g', 'ln_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b'), ptrs[2 * n:]):
+            setattr(g, name, at)
         check(lib().sf_savi_features_train_bwd_f32(C.byref(s), img.data_ptr(), img[0].numel(), d_out.data_ptr(), C.byref(g), img.shape[0],
-                                                   ctx.ws.data_ptr(), ctx.ws.numel(), torch.cuda.current_stream().cuda_stream))
+                                                   ctx.ws.data_ptr(), ctx.ws.numel(), stream()))
         ctx.ws = None
         grads = _split(flat, params)
         return (None, None) + tuple(g_ if ctx.needs_input_grad[2 + i] else None for i, g_ in enumerate(grads))
@@ -579,11 +556,9 @@ class _Linear(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w)
         db = torch.empty(N, dtype=torch.float32, device=w.device) if ctx.has_bias else None
-        nb = lib().sf_linear_bwd_workspace_bytes(M, N, K)
-        ws = torch.empty(nb, dtype=torch.uint8, device=w.device)
-        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        check(lib().sf_linear_bwd_f32(p(x), p(w), p(y), p(dy), p(dx), p(dw), p(db), M, N, K, int(ctx.relu), ws.data_ptr(), nb,
-                                      torch.cuda.current_stream().cuda_stream))
+        ws = scratch(lib().sf_linear_bwd_workspace_bytes, M, N, K, device=w.device)
+        check(lib().sf_linear_bwd_f32(ptr(x), ptr(w), ptr(y), ptr(dy), ptr(dx), ptr(dw), ptr(db), M, N, K, int(ctx.relu), ws.data_ptr(), ws.numel(),
+                                      stream()))
         return dx, dw, db, None
 
 
@@ -602,10 +577,9 @@ class _LayerNorm(torch.autograd.Function):
         dy = dy.float().contiguous()
         D = x.shape[-1]
         dx, dg, db = torch.empty_like(x), torch.empty_like(g), torch.empty_like(g)
-        nb = lib().sf_layernorm_bwd_workspace_bytes(D)
-        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        ws = scratch(lib().sf_layernorm_bwd_workspace_bytes, D, device=x.device)
         check(lib().sf_layernorm_bwd_f32(x.data_ptr(), dy.data_ptr(), g.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                         x.numel() // D, D, ctx.eps, ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream))
+                                         x.numel() // D, D, ctx.eps, ws.data_ptr(), ws.numel(), stream()))
         return dx, dg, db, None
 
 
@@ -617,7 +591,7 @@ class _MHA(torch.autograd.Function):
         qkv = qkv.detach().float().contiguous()
         out = torch.empty(B * L, d, dtype=torch.float32, device=qkv.device)
         check(lib().sf_mha_train_fwd_f32(qkv.data_ptr(), out.data_ptr(), B, L, d, heads, float(p), int(seed),
-                                         torch.cuda.current_stream().cuda_stream))
+                                         stream()))
         ctx.save_for_backward(qkv)
         ctx.args = (B, L, d, heads, float(p), int(seed))
         return out
@@ -629,7 +603,7 @@ class _MHA(torch.autograd.Function):
         d_out = d_out.float().contiguous()
         dqkv = torch.empty_like(qkv)
         check(lib().sf_mha_train_bwd_f32(qkv.data_ptr(), d_out.data_ptr(), dqkv.data_ptr(), B, L, d, heads, p, seed,
-                                         torch.cuda.current_stream().cuda_stream))
+                                         stream()))
         return dqkv, None, None, None, None, None, None
 
 
@@ -640,7 +614,7 @@ class _Dropout(torch.autograd.Function):
     def forward(ctx, x, p, seed):
         x = x.detach().float().contiguous()
         y = torch.empty_like(x)
-        check(lib().sf_dropout_f32(x.data_ptr(), None, y.data_ptr(), x.numel(), float(p), int(seed), torch.cuda.current_stream().cuda_stream))
+        check(lib().sf_dropout_f32(x.data_ptr(), None, y.data_ptr(), x.numel(), float(p), int(seed), stream()))
         ctx.args = (float(p), int(seed))
         return y
 
@@ -648,7 +622,7 @@ class _Dropout(torch.autograd.Function):
     def backward(ctx, dy):
         dy = dy.float().contiguous()
         dx = torch.empty_like(dy)
-        check(lib().sf_dropout_f32(dy.data_ptr(), None, dx.data_ptr(), dy.numel(), ctx.args[0], ctx.args[1], torch.cuda.current_stream().cuda_stream))
+        check(lib().sf_dropout_f32(dy.data_ptr(), None, dx.data_ptr(), dy.numel(), ctx.args[0], ctx.args[1], stream()))
         return dx, None, None
 
 
@@ -711,7 +685,7 @@ class _SlateAttention(torch.autograd.Function):
             lse = torch.empty(B, heads, Lq, dtype=torch.float32, device=q.device)
             check(lib().sf_slate_attention_train_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), d, d, d, d,
                                                          Lq * d, Lk * d, Lk * d, Lq * d, B, Lq, Lk, heads, d // heads, int(causal), float(p),
-                                                         int(seed), torch.cuda.current_stream().cuda_stream))
+                                                         int(seed), stream()))
         else:
             out = ops.slate_attention(q, k, v, heads, causal)
         ctx.save_for_backward(q, k, v, out, lse)
@@ -726,12 +700,10 @@ class _SlateAttention(torch.autograd.Function):
         Lk = k.shape[1]
         d_out = d_out.float().contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        nb = lib().sf_slate_attention_bwd_workspace_bytes(B, Lq, heads)
-        ws = torch.empty(nb, dtype=torch.uint8, device=q.device)
-        check(lib().sf_slate_attention_train_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), d_out.data_ptr(),
-                                                     lse.data_ptr() if lse is not None else None, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                                                     d, d, d, d, Lq * d, Lk * d, Lk * d, Lq * d, B, Lq, Lk, heads, d // heads, int(causal), p,
-                                                     seed, ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream))
+        ws = scratch(lib().sf_slate_attention_bwd_workspace_bytes, B, Lq, heads, device=q.device)
+        check(lib().sf_slate_attention_train_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), d_out.data_ptr(), ptr(lse),
+                                                     dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), d, d, d, d, Lq * d, Lk * d, Lk * d, Lq * d,
+                                                     B, Lq, Lk, heads, d // heads, int(causal), p, seed, ws.data_ptr(), ws.numel(), stream()))
         return dq, dk, dv, None, None, None, None
 
 
@@ -754,7 +726,7 @@ class _SelfAttention(torch.autograd.Function):
             base = qkv.data_ptr()
             check(lib().sf_slate_attention_train_fwd_f32(base, base + 4 * d, base + 8 * d, out.data_ptr(), lse.data_ptr(), 3 * d, 3 * d,
                                                          3 * d, d, L * 3 * d, L * 3 * d, L * 3 * d, L * d, B, L, L, heads, d // heads,
-                                                         int(causal), float(p), int(seed), torch.cuda.current_stream().cuda_stream))
+                                                         int(causal), float(p), int(seed), stream()))
         else:
             out = ops.slate_attention(qkv, qkv, qkv, heads, causal, 0, d, 2 * d, d_model=d)
         ctx.save_for_backward(x, wcat, qkv, out, lse)
@@ -768,21 +740,18 @@ class _SelfAttention(torch.autograd.Function):
         B, L, d = x.shape
         d_out = d_out.float().contiguous()
         dqkv = torch.empty_like(qkv)
-        st = torch.cuda.current_stream().cuda_stream
-        nb = lib().sf_slate_attention_bwd_workspace_bytes(B, L, heads)
-        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        st = stream()
+        ws = scratch(lib().sf_slate_attention_bwd_workspace_bytes, B, L, heads, device=x.device)
         b0, g0 = qkv.data_ptr(), dqkv.data_ptr()
-        check(lib().sf_slate_attention_train_bwd_f32(b0, b0 + 4 * d, b0 + 8 * d, out.data_ptr(), d_out.data_ptr(),
-                                                     lse.data_ptr() if lse is not None else None, g0, g0 + 4 * d, g0 + 8 * d, 3 * d, 3 * d,
-                                                     3 * d, d, L * 3 * d, L * 3 * d, L * 3 * d, L * d, B, L, L, heads, d // heads,
-                                                     int(causal), p, seed, ws.data_ptr(), nb, st))
+        check(lib().sf_slate_attention_train_bwd_f32(b0, b0 + 4 * d, b0 + 8 * d, out.data_ptr(), d_out.data_ptr(), ptr(lse), g0, g0 + 4 * d,
+                                                     g0 + 8 * d, 3 * d, 3 * d, 3 * d, d, L * 3 * d, L * 3 * d, L * 3 * d, L * d, B, L, L, heads,
+                                                     d // heads, int(causal), p, seed, ws.data_ptr(), ws.numel(), st))
         dx = torch.empty_like(x)
         dw = torch.empty_like(wcat)
         M = B * L
-        nb = lib().sf_linear_bwd_workspace_bytes(M, 3 * d, d)
-        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        ws = scratch(lib().sf_linear_bwd_workspace_bytes, M, 3 * d, d, device=x.device)
         check(lib().sf_linear_bwd_f32(x.data_ptr(), wcat.data_ptr(), None, dqkv.data_ptr(), dx.data_ptr(), dw.data_ptr(), None, M, 3 * d, d,
-                                      0, ws.data_ptr(), nb, st))
+                                      0, ws.data_ptr(), ws.numel(), st))
         return (dx, ) + tuple(dw.split(d, 0)) + (None, None, None, None)
 
 
@@ -831,7 +800,7 @@ class _TokenCrossEntropy(torch.autograd.Function):
         dx = torch.empty_like(logits)
         gs = g.detach().float().reshape(1).contiguous()
         check(lib().sf_cross_entropy_bwd_f32(logits.data_ptr(), target.data_ptr(), gs.data_ptr(), dx.data_ptr(), R, V,
-                                             torch.cuda.current_stream().cuda_stream))
+                                             stream()))
         return dx, None
 
 
@@ -955,10 +924,9 @@ class _LinearCat(torch.autograd.Function):
         M = x.numel() // K
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w)
-        nb = lib().sf_linear_bwd_workspace_bytes(M, N, K)
-        ws = torch.empty(nb, dtype=torch.uint8, device=w.device)
-        check(lib().sf_linear_bwd_f32(x.data_ptr(), w.data_ptr(), None, dy.data_ptr(), dx.data_ptr() if dx is not None else None,
-                                      dw.data_ptr(), None, M, N, K, 0, ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream))
+        ws = scratch(lib().sf_linear_bwd_workspace_bytes, M, N, K, device=w.device)
+        check(lib().sf_linear_bwd_f32(x.data_ptr(), w.data_ptr(), None, dy.data_ptr(), ptr(dx), dw.data_ptr(), None, M, N, K, 0, ws.data_ptr(),
+                                      ws.numel(), stream()))
         return (dx, ) + tuple(dw.split(ctx.sizes, 0))
 
 
@@ -997,11 +965,9 @@ class _GroupNorm1(torch.autograd.Function):
         dy = dy.float().contiguous()
         F_, H, W, C_ = x.shape
         dx, dg, db = torch.empty_like(x), torch.empty_like(g), torch.empty_like(b)
-        nb = lib().sf_groupnorm1_bwd_workspace_bytes(F_, H, W, C_)
-        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        ws = scratch(lib().sf_groupnorm1_bwd_workspace_bytes, F_, H, W, C_, device=x.device)
         check(lib().sf_groupnorm1_nhwc_bwd_f32(x.data_ptr(), g.data_ptr(), b.data_ptr(), dy.data_ptr(), dx.data_ptr(), dg.data_ptr(),
-                                               db.data_ptr(), F_, H, W, C_, eps, relu, r, ws.data_ptr(), nb,
-                                               torch.cuda.current_stream().cuda_stream))
+                                               db.data_ptr(), F_, H, W, C_, eps, relu, r, ws.data_ptr(), ws.numel(), stream()))
         return dx, dg, db, None, None, None
 
 
@@ -1034,7 +1000,7 @@ class _SoftmaxRows(torch.autograd.Function):
         V = y.shape[-1]
         dx = torch.empty_like(y)
         check(lib().sf_softmax_rows_bwd_f32(y.data_ptr(), dy.data_ptr(), ctx.scale, dx.data_ptr(), y.numel() // V, V,
-                                            torch.cuda.current_stream().cuda_stream))
+                                            stream()))
         return dx, None, None, None
 
 
@@ -1173,7 +1139,7 @@ class FlatAdam:
         if self.clip_grad:
             # norm, coefficient, non-finite flag; the workspace's arrival counter starts at zero and every call leaves it there
             self._clip_out = torch.zeros(3, dtype=torch.float32, device=dev)
-            self._clip_ws = torch.zeros(int(lib().sf_grad_norm_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+            self._clip_ws = scratch(lib().sf_grad_norm_workspace_bytes, n, device=dev).zero_()
             self.grad_norm, self.grad_nonfinite = self._clip_out[0:1], self._clip_out[2:3]
 
     @property
@@ -1202,7 +1168,7 @@ class FlatAdam:
         if self.allreduce:
             parallel.allreduce_flat(self.grad)
         self.steps += 1
-        st = torch.cuda.current_stream().cuda_stream
+        st = stream()
         scale = None
         if self.clip_grad:
             check(lib().sf_grad_clip_coef_f32(self.grad.data_ptr(), self.grad.numel(), self.clip_grad, self._clip_out.data_ptr(),
@@ -1489,8 +1455,7 @@ def phyre_readout_with_grad(readout, slots, sel=None, video_index=None, p=None, 
     picks the batch out of the slots without a gather.  p: the dropout rate -- default the layers' own when readout.training, else 0; seed: the
     seed of the masks (default a fresh one).  grad_out: a flat fp32 buffer laid out as FlatAdam's bucket over phyre_readout_parameters(readout)
     (`FlatAdam.grad`): the backward writes the gradients there -- then step with `FlatAdam.step(gathered=True)` -- and leaves `.grad` alone."""
-    if not (torch.is_tensor(slots) and slots.is_cuda):
-        raise RuntimeError('slotformer_amd: the slots must live on a HIP device; there is no CPU fallback')
+    require_device(slots, what='the slots')
     if p is None:
         p = float(readout.transformer_encoder.layers[0].dropout.p) if readout.training else 0.0
     if seed is None:

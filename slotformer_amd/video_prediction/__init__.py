@@ -6,6 +6,7 @@ from types import SimpleNamespace
 
 import torch
 
+from .._call import require_device
 from .models import build_model
 
 MIN_FRAMES = 3   # datasets/clevrer.py:240: an object entering fewer than this many frames into the burn-in does not spoil a clip
@@ -113,8 +114,7 @@ def _check_clips(clips, table_shape, n_frames, frame_offset):
 
 
 def _device_table(table):
-    if not (torch.is_tensor(table) and table.is_cuda):
-        raise RuntimeError('slotformer_amd: the slot table must live on a HIP device; there is no CPU fallback')
+    require_device(table, what='the slot table')
     return table
 
 
@@ -147,8 +147,7 @@ def _token_table(tokens, table, model, who):
             tuple(tokens.shape[:2]) != tuple(table.shape[:2]) or tokens.shape[2] != hw or not tokens.is_contiguous():
         raise ValueError(f'slotformer_amd.video_prediction.{who}: tokens are contiguous int16 or int64 ids [{table.shape[0]}, {table.shape[1]}, {hw}], '
                          f'got {getattr(tokens, "dtype", type(tokens).__name__)} {tuple(getattr(tokens, "shape", ()))}')
-    if not tokens.is_cuda:
-        raise RuntimeError('slotformer_amd: the token table must live on a HIP device; there is no CPU fallback')
+    require_device(tokens, what='the token table')
     return tokens
 
 

@@ -12,6 +12,8 @@ import colorsys
 import numpy as np
 import torch
 
+from slotformer_amd._call import scratch, stream   # (absolute: this file is also loaded under the reference's package name)
+
 FG_THRE = 0.5
 # the colours of the slots in visualisations (test_vp.py:137): 16 hues, a golden-ratio walk round the colour circle
 PALETTE = [tuple(int(round(255 * c)) for c in colorsys.hsv_to_rgb((0.33 + 0.618034 * i) % 1., 0.85 if i % 2 == 0 else 0.55, 1. if i % 3 else 0.8))
@@ -33,9 +35,9 @@ def postproc_mask(batch_masks):
         B, T, N, _, H, W = batch_masks.shape
         mk = batch_masks.detach().contiguous()
         out = torch.empty(B, T, H, W, dtype=torch.int64, device=mk.device)
-        scratch = torch.empty(B * T * N, dtype=torch.int32, device=mk.device)
-        _lib.check(_lib.lib().sf_postproc_mask_f32(mk.data_ptr(), out.data_ptr(), None, float(FG_THRE), scratch.data_ptr(), B * T, N, H * W,
-                                                   torch.cuda.current_stream(mk.device).cuda_stream))
+        maxima = torch.empty(B * T * N, dtype=torch.int32, device=mk.device)
+        _lib.check(_lib.lib().sf_postproc_mask_f32(mk.data_ptr(), out.data_ptr(), None, float(FG_THRE), maxima.data_ptr(), B * T, N, H * W,
+                                                   stream(mk)))
         return out
     m = batch_masks.clone()
     B, T, N, _, H, W = m.shape
@@ -55,10 +57,6 @@ def _lib():
     return L
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _is_dev_f32(*ts):
     return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in ts)
 
@@ -69,8 +67,7 @@ def _is_dev_ids(*ts):
 
 def _ws(dev, F, H, W, slot='vp'):
     from slotformer_amd import engine
-    need = _lib().lib().sf_vp_metrics_workspace_bytes(F, H, W)
-    return engine.workspace(dev, max(need, 256), (slot, ))
+    return engine.workspace_for(dev, (slot, ), _lib().lib().sf_vp_metrics_workspace_bytes, F, H, W, at_least=256)
 
 
 def _dev_image_scores(x, y, to_rgb):
@@ -81,7 +78,7 @@ def _dev_image_scores(x, y, to_rgb):
     out = torch.empty(3, F, dtype=torch.float64, device=x.device)
     ws = _ws(x.device, F, H, W)
     L.check(L.lib().sf_vp_image_metrics_f32(x.data_ptr(), y.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), F, H, W,
-                                            int(to_rgb), ws.data_ptr(), ws.numel(), _stream(x)))
+                                            int(to_rgb), ws.data_ptr(), ws.numel(), stream(x)))
     return out
 
 
@@ -96,7 +93,7 @@ def _dev_mask_scores(gt, pm, H, W):
     flag = torch.empty(1, dtype=torch.int32, device=gt.device)
     tables = torch.empty(F, NUM_CLASSES, NUM_CLASSES, dtype=torch.int32, device=gt.device)
     L.check(L.lib().sf_vp_mask_metrics(gt.data_ptr(), pm.data_ptr(), int(pm.dtype == torch.uint8), tables.data_ptr(), None, out[0].data_ptr(),
-                                       out[1].data_ptr(), out[2].data_ptr(), flag.data_ptr(), F, H, W, NUM_CLASSES, None, 0, _stream(gt)))
+                                       out[1].data_ptr(), out[2].data_ptr(), flag.data_ptr(), F, H, W, NUM_CLASSES, None, 0, stream(gt)))
     return out, flag, tables
 
 
@@ -108,7 +105,7 @@ def _dev_bbox_scores(pres, gtb, pb, ovthresh=0.5):
     F, N = pres.shape
     out = torch.empty(2, F, dtype=torch.float64, device=gtb.device)
     L.check(L.lib().sf_vp_bbox_pr_f32(gtb.data_ptr(), pres.data_ptr(), pb.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), F, N, pb.shape[1],
-                                      float(ovthresh), _stream(gtb)))
+                                      float(ovthresh), stream(gtb)))
     return out
 
 
@@ -116,7 +113,7 @@ def _dev_boxes(masks, F, H, W, num_boxes):
     L = _lib()
     masks = masks.contiguous()
     boxes = torch.empty(F, num_boxes, 4, dtype=torch.float32, device=masks.device)
-    L.check(L.lib().sf_masks_to_boxes(masks.data_ptr(), int(masks.dtype == torch.uint8), boxes.data_ptr(), None, F, H, W, num_boxes, _stream(masks)))
+    L.check(L.lib().sf_masks_to_boxes(masks.data_ptr(), int(masks.dtype == torch.uint8), boxes.data_ptr(), None, F, H, W, num_boxes, stream(masks)))
     return boxes
 
 
@@ -427,14 +424,14 @@ def _step_on_device(gt, pred, gt_mask, pred_mask, gt_pres_mask, gt_bbox, pred_bb
         buf = {'raw': raw, 'head': head, 'mean': head[:K * T * 8].view(torch.float64).view(K, T),
                'flag': head[K * T * 8:(K * T + 1) * 8].view(torch.int32)[:1],
                'per': raw[(K * T + 1 + P) * 8:(K * T + 1 + P + K * F) * 8].view(torch.float64).view(K, B, T),
-               'ws': torch.empty(max(int(lib.sf_vp_metrics_workspace_bytes(F, H, W)), 256), dtype=torch.uint8, device=dev)}
+               'ws': scratch(lib.sf_vp_metrics_workspace_bytes, F, H, W, device=dev, at_least=256)}
         if lpips is not None:
             tail = raw[(K * T + 1 + P + K * F) * 8:]
             buf['lp_mean'] = head[(K * T + 1) * 8:].view(torch.float64)
             buf['lp_per'] = tail[:F * 8].view(torch.float64).view(B, T)
             buf['lp_scores'] = tail[F * 8:].view(torch.float32)
         _STEP_BUFFERS[key] = buf
-    per, ws, st = buf['per'], buf['ws'], _stream(gt)
+    per, ws, st = buf['per'], buf['ws'], stream(gt)
     gt, pred = gt.contiguous(), pred.contiguous()
     L.check(lib.sf_vp_image_metrics_f32(gt.data_ptr(), pred.data_ptr(), per[0].data_ptr(), per[1].data_ptr(), per[2].data_ptr(), F, H, W, 1,
                                         ws.data_ptr(), ws.numel(), st))

@@ -331,6 +331,18 @@ def test_head_bwd_single_pass_bf16(dev, name):
         head_check(dev, name, sc.BOUNDS['head_act'][what], what)
 
 
+def test_head_bwd_wrapper_is_the_direct_call(dev):
+    """ops.savi_decode_head_bwd, whose workspace comes from _call.scratch, on the smallest case: bit for bit what the entry point gives when it is
+    called directly with a workspace of the queried size.  The same library and no atomics in it, so equality is the bar."""
+    from slotformer_amd import ops
+    dec, d_recon, act, out_w = (t.to(dev).contiguous() for t in sc.head_inputs('n1'))
+    for params in (True, False):
+        got = ops.savi_decode_head_bwd(dec, d_recon, act, out_w, want_param_grads=params)
+        want = head_run(dev, 'n1', params)[:4 if params else 2]
+        assert all(torch.equal(bits(g), bits(w)) for g, w in zip(got, want))
+        assert params or got[2:] == (None, None)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # module wiring: StoSAVi.decode under autograd on decode_cases.TRAIN_CASE (split-bf16 and f32: the margin that keeps the ReLUs off their kinks is
 # sized for those, not for the 2^-8 of mode 2)
