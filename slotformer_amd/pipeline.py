@@ -43,15 +43,14 @@ import ctypes as C
 import math
 import os
 import threading
-import time
 
 import torch
 
 from . import _lib, engine
 
 _STREAMS = {}                      # process-wide stream pool (EncodeRolloutPipeline._masked_stream / _pool_stream)
+                                   # (ONE pool: private streams per pipeline object share hardware queues: 405 vs 455 k frames/s)
 _STREAMS_LOCK = threading.Lock()
-_POOL = True                        # one process-wide pool of streams (private streams per pipeline object share hardware queues: 405 vs 455 k frames/s)
 
 
 def encode_mask_words(spec):
@@ -235,6 +234,161 @@ def unit_sizes_for(n, group, rows_per_batch, ramp=False, spread=True):
     return sizes, len(tail)
 
 
+def encode_lane_for(j, n, n_fill, hybrid, hybrid_tail, free_streams, fill_par):
+    """Where batch j of a run over n batches is encoded (a pure function of the counts: tests/test_pipeline_plan.py): 'fill' = one of the first
+    n_fill batches, on the whole chip; 'hybrid' = every `hybrid`-th batch behind the fill -- none among the last `hybrid_tail` of the run, and
+    only with an unmasked stream to take it (free_streams: how many there are) and a second fill graph (fill_par > 1) -- on an unmasked stream
+    beside the CU-masked lanes; 'lane' = every other batch, on the masked lanes."""
+    if (hybrid > 0 and j >= n_fill and n_fill > 0 and (j - n_fill) % hybrid == hybrid - 1
+            and j + hybrid_tail < n and free_streams > 0 and fill_par > 1):
+        return 'hybrid'
+    return 'fill' if j < n_fill else 'lane'
+
+
+def _pool_stream(dev, kind, k=0, priority=0):
+    """an unmasked torch stream from the process-wide pool (kind: 'out', 'copy', 'dec', 'roll', 'lane')"""
+    key = ('torch', dev.index, kind, k, priority)
+    with _STREAMS_LOCK:
+        st = _STREAMS.get(key)
+        if st is None:
+            st = _STREAMS[key] = torch.cuda.Stream(device=dev, priority=priority)
+    return st
+
+
+class _InputRing:
+    """The input side of run(): device-resident float32 batches pass through untouched; host-resident and / or ingested ones go through rings
+    of `slots` staging buffers, filled by an upload stage on a copy stream of its own.  The buffers live as long as the pipeline (one set per
+    input shape); begin() prepares the ring for a run, frames() hands out a batch."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self._stage, self._pin, self._s_copy = None, None, None   # staging ring + copy stream for host-resident inputs
+        self._stage_u8, self._pin_u8 = None, None                 # ingest=: the device / page-locked rings of uint8 frames at source size
+        self.staged = False
+
+    def begin(self, imgs, ingest, host_in, slots, cur, ev_enc):
+        """Prepare for a run over `imgs` (ingest: None or an ingest.FrameIngest; host_in: the batches are in host memory; cur: the calling
+        stream; ev_enc[j]: the events of batch j's encode)."""
+        self.imgs, self.ingest, self.host_in, self.NS, self.ev_enc = imgs, ingest, host_in, slots, ev_enc
+        n = len(imgs)
+        NS = slots
+        self.ev_up, self.up_next = [], 0
+        self.pinned_in = pinned_in = host_in and all(im.is_pinned() for im in imgs)
+        self.staged = host_in or ingest is not None
+        self.pin = None
+        if self.staged:
+            fshape = imgs[0].shape if ingest is None else ingest.output_shape(imgs[0])
+            if self._stage is None or self._stage[0].shape != fshape:
+                self._stage = [torch.empty(fshape, device=self.dev) for _ in range(NS)]
+                self._s_copy = _pool_stream(self.dev, 'copy')
+                self._pin = None
+            if ingest is None:
+                if not pinned_in and self._pin is None:
+                    # pageable input: batches pass through a ring of NS page-locked staging buffers (never the whole set page-locked at once;
+                    # the host pays one memcpy per batch -- pre-pinned input skips it)
+                    self._pin = [torch.empty(imgs[0].shape, pin_memory=True) for _ in range(NS)]
+                self.pin = self._pin
+            elif host_in:
+                # ingest=: both rings hold the decoder's uint8 frames at source size; self._stage is what the ingest kernel writes
+                if self._stage_u8 is None or self._stage_u8[0].shape != imgs[0].shape:
+                    self._stage_u8 = [torch.empty(imgs[0].shape, dtype=torch.uint8, device=self.dev) for _ in range(NS)]
+                    self._pin_u8 = None
+                if not pinned_in and self._pin_u8 is None:
+                    self._pin_u8 = [torch.empty(imgs[0].shape, dtype=torch.uint8, pin_memory=True) for _ in range(NS)]
+                self.pin = self._pin_u8
+            self._s_copy.wait_stream(cur)
+            self.ev_up = [torch.cuda.Event() for _ in range(n)]
+
+    def frames(self, j, stream):
+        """the frames of batch j as a device tensor `stream` may read"""
+        imgs, ingest, host_in, pinned_in, pin, NS = self.imgs, self.ingest, self.host_in, self.pinned_in, self.pin, self.NS
+        if not self.staged:
+            return imgs[j]
+        while self.up_next <= min(j, len(imgs) - 1):
+            k = self.up_next
+            with torch.cuda.stream(self._s_copy):
+                if k >= NS:
+                    # the staging slot's previous batch has been encoded (issued NS batches ago).  The HOST waits, not the copy
+                    # stream: a queue parked in a cross-queue wait slows the queues that are running on this platform (the
+                    # masked encode lane ran at 5.8 instead of 4.05 ms per batch with the wait on the stream)
+                    for e in self.ev_enc[k - NS]:
+                        e.synchronize()
+                src = imgs[k]
+                if host_in and not pinned_in:
+                    if k >= NS:
+                        self.ev_up[k - NS].synchronize()   # the upload out of this page-locked slot is done
+                    pin[k % NS].copy_(src)
+                    src = pin[k % NS]
+                if ingest is None:
+                    self._stage[k % NS].copy_(src, non_blocking=True)
+                else:
+                    if host_in:
+                        # (the slot's previous frames were read by the ingest launch of batch k - NS, earlier on this stream)
+                        self._stage_u8[k % NS].copy_(src, non_blocking=True)
+                        src = self._stage_u8[k % NS]
+                    ingest(src, out=self._stage[k % NS])   # on the copy stream, behind the upload
+                self.ev_up[k].record(self._s_copy)
+            self.up_next += 1
+        stream.wait_event(self.ev_up[j])
+        return self._stage[j % NS]
+
+    def end(self):
+        """the run is over: drop what belongs to it (the caller's batches, its events); the buffers stay"""
+        self.imgs = self.ingest = self.ev_enc = self.pin = None
+        self.ev_up = []
+
+
+class _Downloads:
+    """Host-resident output of a run: units rolled out whose slots are not yet on their way to the host."""
+
+    def __init__(self, out, B, s_out, ev_roll):
+        self.out, self.B, self.s_out, self.ev_roll = out, B, s_out, ev_roll
+        self.pending = []
+
+    def add(self, ui, u0, nb, u, done):
+        self.pending.append((ui, u0, nb, u, done))
+
+    def ready(self, for_unit=None, everything=False):
+        """enqueue the downloads of the units whose rollout is done (for_unit: WAIT for that unit buffer's rollout -- the buffer is
+        about to be encoded into again; everything: wait for all of them)"""
+        B = self.B
+        for d in list(self.pending):
+            dui, du0, dnb, du, done = d
+            if everything or du is for_unit:
+                done.synchronize()
+            if done.query():
+                with torch.cuda.stream(self.s_out):
+                    for h in range(dnb):
+                        self.out[du0 + h].copy_(du.buf[h * B:(h + 1) * B], non_blocking=True)
+                    self.ev_roll[dui].record(self.s_out)
+                self.pending.remove(d)
+
+
+class _Run:
+    """What the stages of one run() share: the arguments, the unit plan, and -- pipelined schedule only -- the events that order the streams."""
+
+    def __init__(self, imgs, noises, out, ingest, host_in, decoded, units, cur):
+        self.imgs, self.noises, self.out, self.ingest, self.host_in = imgs, noises, out, ingest, host_in
+        self.n = len(imgs)
+        self.rc_all, self.sg_all, self.u8_all = decoded if decoded is not None else (None, None, None)
+        self.decoded = decoded is not None
+        self.units, self.cur = units, cur     # [(first batch, number of batches, _Unit, drain?)]; the calling stream
+        self.n_fill = 0          # batches of the whole-chip fill
+        self.NF = 0              # feature buffers per lane (slot of batch j: j % NF)
+        self.ev_enc = []         # [batch][lane] end of the encode
+        self.ev_roll = []        # [unit] end of rollout + copy-out; also: completion time of every unit
+        self.ev_pre = []         # [batch] its stolen features are computed
+        self.stolen = []         # time steps of precomputed features batch j will find in its feature buffer
+        self.fill_last = {}      # fill graph index -> the last batch encoded through it
+        self.n_free = 0          # drain units sent to unmasked streams so far
+        self.ev_rstart = None    # SF_PIPE_TRACE: [unit] start of the rollout
+        self.ev_dec = None       # decode stage: end of the last decode issued
+        self.downloads = None    # _Downloads
+
+    def noise(self, j):
+        return None if self.noises is None else self.noises[j]
+
+
 class EncodeRolloutPipeline:
     """savi: StoSAVi / STEVE container (eval, testing=True); rollouter: SlotRollouter / SingleStepSlotRollouter container.
 
@@ -272,7 +426,7 @@ class EncodeRolloutPipeline:
 
     def __init__(self, savi, rollouter, batch, burn_in, pred_len, encode_cu_word=0xff, steal_steps=None, use_graph=True,
                  partition='pair', group=None, rollout_opts=None, encode_graph=None, hybrid=None, decoder=None, seg_dtype=torch.uint8,
-                 encode_fork=None, tok=None, split=None, chain_on='enc', roll_streams=2):
+                 tok=None, split=None, chain_on='enc', roll_streams=2):
         self.savi, self.roll = savi, rollouter
         # optional third stage (row N2; video_prediction/test_vp.py:55-63,145-146 -> slotformer.py:244-259 -> savi.py:504-525 ->
         # vp_utils.py:20-41): the predicted frames of every batch are decoded behind its rollout -- spatial-broadcast decoder, softmax
@@ -328,9 +482,7 @@ class EncodeRolloutPipeline:
         if steal_steps is None:
             steal_steps = float({'pair': 0, 'two': 1, 'three': 0}.get(partition, 1))
         self.steal = max(0.0, min(float(steal_steps), float(self.T)))   # may be fractional: see _steal_of
-        self._steal_arg = self.steal
         self._masked_taken = {}
-        self._lib = _lib.lib()
         # 'pair': the encode partition's CU mask (the rollout streams get the complement)
         self._enc_words_pair = ENC_WORDS_P
         if partition == 'pair':
@@ -340,6 +492,7 @@ class EncodeRolloutPipeline:
                 self._enc_words_pair = encode_mask_words(os.environ['SF_PIPE_CU_SPLIT'])
             elif self._encode_rows() != 4:
                 self._enc_words_pair = encode_mask_words(f'rows{self._encode_rows()}')
+        self._row_tiles = False
         if rollout_opts is None and partition == 'pair':
             roll_cus = 256 - sum(bin(w).count('1') for w in self._enc_words_pair)
             rollout_opts = pair_unit_options(self.roll, self.B, self.G, roll_cus, self.tok, self.T)
@@ -357,7 +510,7 @@ class EncodeRolloutPipeline:
         if self.tok:
             o = self.rollout_opts
             self.row_opts = _lib.sf_rollout_opts(o.precision, o.seam_fused, o.ffn_rows, o.attn_heads_per_wg, o.attn_qkv_rows, o.ffn_tile, o.cus_available, -1)
-        # units of fewer batches (the ramp at both ends of a run) are on the critical path of fill and drain: the latency forms
+        # units of fewer batches are on the critical path of fill and drain: the latency forms
         # of the kernels (head-pair attention workgroups, narrower FFN workgroups: more, shorter workgroups per launch) -- the
         # same bits
         self.tail_opts = self.rollout_opts
@@ -370,8 +523,6 @@ class EncodeRolloutPipeline:
         # batches, 399.5 vs 398.2 at 40) at the price of a 38 MB device copy of the frames into the fixed input buffer per batch
         self.encode_graph = bool(int(os.environ.get('SF_PIPE_ENCODE_GRAPH', '1'))) if encode_graph is None else bool(encode_graph)
         self._enc_graphs = {}
-        # (encode_fork=True: every encode graph with two branches; measured slower inside the pipeline -- the kwarg stays for measurements)
-        self.encode_fork = bool(encode_fork)
         # the last unit of a run rolls out alone on an unmasked stream: in the kernels' latency forms (head-pair attention, 64-row FFN
         # workgroups) while a unit is small -- C4, 64 videos: 172 vs 165 k frames/s -- but a large unit fills the chip with its row tiles and
         # four times the workgroups only queue: C5, 256 videos: 392 -> 435 k; C2, 128 videos: 436 / 440 k
@@ -393,7 +544,6 @@ class EncodeRolloutPipeline:
             self.steal = 0.0   # (no stolen convolutions: the feature half IS the lane's work)
         self._plan = None
         self.units = []
-        self.spread_remainder = True
         hist_ = getattr(rollouter, 'cond_len', None) or getattr(rollouter, 'history_len', None) or self.T
         self._rows_per_batch = self.B * int(rollouter.num_slots) * int(hist_)
         self._tails = {}
@@ -428,7 +578,6 @@ class EncodeRolloutPipeline:
                 self.cu_split = True
                 self.partition = partition
             except RuntimeError:      # CU masking unavailable on this runtime: keep the pipeline, on shared CUs
-                self._close_streams()
                 self.s_roll, self.lanes, self.roll_streams = None, [], []
         if self.s_roll is None:
             self.s_roll = self._pool_stream('roll', priority=-1)
@@ -444,10 +593,6 @@ class EncodeRolloutPipeline:
         self.fill_whole_chip = True      # the first encode(s) of a run on the calling stream (all CUs)
         # (group 1: a second whole-chip encode was measured worse, 311 vs 323 k frames/s at 20 steps; with group 2 the first
         #  rollout cannot start before both batches of its unit are encoded)
-        # smaller units at the end of a run (_unit_plan): measured WORSE with group 4 (unmasked drain units take CUs from the
-        # encode and the full units: 322 vs 376 k frames/s at 20 batches) -- off
-        self.ramp = False
-        self._hybrid_arg = hybrid
         self.fill_par = 2   # whole-chip encodes side by side during the fill (3: 495 vs 552 k frames/s)
         # batches encoded on the WHOLE chip (unmasked streams, fill_par at a time) at the start of a run.  The first unit's had to be
         # (nothing else runs yet); since the row-tile kernels the rollout streams have slack, and the unmasked encodes of the NEXT
@@ -455,15 +600,15 @@ class EncodeRolloutPipeline:
         # then works from: two units by default (C4 172 -> 175 k, C5 381 -> 390 k frames/s at 20 batches), three where the encode lane is
         # the bound of a balanced pair running row tiles (C2: 427 -> 445-447 k at 20 batches, 441 -> 460 k at 40; four or more units
         # starve the rollouts: 432 / 410 k).  SF_PIPE_FILL overrides (batches)
-        balanced = getattr(self, '_row_tiles', False) and partition == 'pair' and self._encode_rows() == 4
+        balanced = self._row_tiles and partition == 'pair' and self._encode_rows() == 4
         fill_units = 3 if balanced else 2
         # hybrid lane: behind the fill every `hybrid`-th batch is encoded on an UNMASKED stream (the second fill graph) beside the CU-masked
         # lane.  With the encode lane the bound (3.9 ms per batch against ~3.0-3.3 of rollout capacity) the rollout partition has slack to
         # lend: C2 at 40 / 100 / 200 batches 484 / 489 / 487 -> 501 / 511 / 526 k frames/s with every 5th (4: 496 / 510, 6: 497 / 507), nothing
         # at 20 (one such batch); C4 209 -> 212 k at 60; the rollout-bound C5 (one CU row for the encode) keeps the lane alone.  None
         # among the last three batches of a run: the lane is about to fall idle there (C2 487.5 vs 480.5 at 20, 517.8 vs 513.2 at 100 against none among the last five).  Same bits (tests/test_pipeline_gpu.py).
-        if self._hybrid_arg is not None:
-            self.hybrid = int(self._hybrid_arg)
+        if hybrid is not None:
+            self.hybrid = int(hybrid)
         else:
             # (units of more than 4 batches -- unit_batches_for: long runs of small batches -- make the rollouts cheaper per batch and the encode the
             #  bound by more: C4 with units of 7 at 84 batches, every 5th / 4th / 3rd / 2nd batch: 236.0 / 242.9 / 250.6 / 250.9 k)
@@ -472,17 +617,9 @@ class EncodeRolloutPipeline:
             self.hybrid = int(os.environ.get('SF_PIPE_HYBRID', ('8' if self.tok else '3' if self.G > 4 else '5') if balanced else '0'))
         self.hybrid_tail = min(self.hybrid, 3)
         self.fill_batches = int(os.environ.get('SF_PIPE_FILL', '0')) or (fill_units * self.G if partition == 'pair' else 0)
-        self.fill_steal = 0
-        # pre_steal[h]: time steps of convolutions of batch h of the NEXT unit computed on a rollout stream right before a unit
-        # rolls out (group >= 2 only; batch 0 of the next unit starts encoding at once and cannot wait)
-        ps = ''
-        self.pre_steal = [int(x) for x in ps.split(',')] if ps else []   # (measured neutral at 20 batches: 381-383 k frames/s with [0,0,1,1] .. [0,1,1,1] and off)
-        self.pre_steal = [min(k, self.T) for k in self.pre_steal]
-        if not any(self.pre_steal):
-            self.pre_steal = []
         self.feat_bufs = None
-        self._stage, self._s_copy, self._s_out = None, None, None   # staging ring + copy streams for host-resident inputs / outputs
-        self._stage_u8, self._pin_u8 = None, None                   # ingest=: the device / page-locked rings of uint8 frames at source size
+        self._ring = _InputRing(self.dev)   # staging rings + copy stream for host-resident / ingested inputs
+        self._s_out = None                  # copy stream for host-resident outputs
         self.completion_events = []      # one event per unit of the last run() ...
         self.completion_batches = []     # ... and the number of batches it completed
         # the encode graphs hold raw pointers into the SAVi encoder's plan (packed conv weights, folded Slot-Attention matrices,
@@ -500,7 +637,7 @@ class EncodeRolloutPipeline:
                 for st in list(self.s_free):
                     self._lib.sf_stream_set_cus(C.c_void_p(st.cuda_stream), int(self._lib.sf_stream_cus(None)))
             return
-        if self.encode_graph and self.steal == 0 and not self.fill_steal and not self.pre_steal:
+        if self.encode_graph and self.steal == 0:
             res = getattr(self.savi, 'resolution', (128, 128))[0]
             with_noise = engine.kernel_noise(self.savi, torch.empty(0), 1, self.T, self.dev) is not None   # (no draw: the gate only)
             with torch.no_grad():
@@ -549,7 +686,7 @@ class EncodeRolloutPipeline:
         k = self._masked_taken.get(key, 0)
         self._masked_taken[key] = k + 1
         with _STREAMS_LOCK:
-            st = _STREAMS.get(('masked', ) + key + (k, )) if _POOL else None
+            st = _STREAMS.get(('masked', ) + key + (k, ))
             if st is None:
                 arr = (C.c_uint * 8)(*words)
                 h = C.c_void_p()
@@ -560,12 +697,7 @@ class EncodeRolloutPipeline:
 
     def _pool_stream(self, kind, k=0, priority=0):
         """an unmasked torch stream from the same pool (kind: 'out', 'copy', 'roll', 'lane')"""
-        key = ('torch', self.dev.index, kind, k, priority)
-        with _STREAMS_LOCK:
-            st = _STREAMS.get(key) if _POOL else None
-            if st is None:
-                st = _STREAMS[key] = torch.cuda.Stream(device=self.dev, priority=priority)
-        return st
+        return _pool_stream(self.dev, kind, k, priority)
 
     def _pick_free_streams(self, n):
         """n unmasked streams from the process-wide pool for the whole-chip fill encodes and the drain units.
@@ -629,11 +761,8 @@ class EncodeRolloutPipeline:
         which reads the frames of a batch lead * G + G batches before its encode."""
         return self.lead * self.G + self.G + 2
 
-    def _close_streams(self):
-        pass   # (the streams belong to the process-wide pool and live as long as the process)
-
     def close(self):
-        self._close_streams()
+        # (the streams belong to the process-wide pool and live as long as the process)
         self.units, self._tails, self._enc_graphs, self._egress = [], {}, {}, {}
         engine.release_workspaces(self._key)
 
@@ -673,7 +802,7 @@ class EncodeRolloutPipeline:
         self._plan = engine.rollouter_plan(self.roll)   # keeps the packed weight copies the graphs point to alive
 
     def _tail_unit(self, nb, k=0, row_form=False):
-        """a unit of fewer than `group` batches (the ramp at both ends of a run, a ragged remainder); k: which of the two; row_form: the last unit of a
+        """a unit of fewer than `group` batches (a ragged remainder); k: which of the two; row_form: the last unit of a
         run of token-stationary units"""
         key = (nb, k, bool(row_form))
         if key not in self._tails:
@@ -758,26 +887,9 @@ class EncodeRolloutPipeline:
             eg['graph'].replay()
             dst[lo:hi, :self.T].copy_(eg['post'])
             return
-        side = None   # (one stream: see engine.savi_encode)
-        if self.encode_fork:
-            # (probe) eager two-branch encode: the slot branch on a second stream with the lane's own CU mask (an unmasked one for the fill lanes)
-            cache = self.__dict__.setdefault('_fork_side', {})
-            side = cache.get(lane)
-            if side is None:
-                if isinstance(lane, int) and self.cu_split:
-                    side = self._masked_stream(self._lane_words(lane))
-                else:
-                    side = self._pool_stream('fork', k=len(cache))
-                cache[lane] = side
-        post, _, _ = engine.savi_encode(self.savi, img, noise=noise, feat_pre=feat_pre, ws_slot=self._key + ('enc', lane), side_stream=side)
+        # (one stream: see engine.savi_encode)
+        post, _, _ = engine.savi_encode(self.savi, img, noise=noise, feat_pre=feat_pre, ws_slot=self._key + ('enc', lane), side_stream=None)
         dst[lo:hi, :self.T].copy_(post)
-
-    def _lane_words(self, lane):
-        if self.partition == 'pair':
-            return self._enc_words_pair
-        if self.partition == 'three':
-            return LANE0_WORDS_3 if lane == 0 else LANE1_WORDS_3
-        return [0xffffffff] * 8
 
     def _encode_graph_for(self, lane, nv, k, res, with_noise):
         key = (lane, nv, k, res, with_noise)
@@ -793,10 +905,6 @@ class EncodeRolloutPipeline:
             # on one pooled stream the same run took 93 instead of 78 ms (tools/two_pipes_probe.py)
             side = torch.cuda.Stream(device=self.dev)
             side.wait_stream(cur)
-            # encode_fork: the graph gets two parallel branches -- the image features of all time steps, and one step behind them the slot
-            # branches (engine.savi_encode side_stream=; the seven-workgroup launches of the slot branch no longer hold up the convolutions)
-            fork_here = self.encode_fork
-            side2 = torch.cuda.Stream(device=self.dev) if fork_here else None
             # the graph of a CU-masked lane replays on that lane's CUs: the persistent kernels inside it (csrc/conv_ws.hip: one workgroup per CU)
             # size their grids for those, not for the capture stream's whole chip
             lane_cus = int(self.encode_cus // max(len(self.lanes), 1)) if (isinstance(lane, int) and self.cu_split) else 0
@@ -809,11 +917,11 @@ class EncodeRolloutPipeline:
                 self._lib.sf_stream_set_cus(C.c_void_p(side.cuda_stream), lane_cus)
             try:
                 with torch.cuda.stream(side):
-                    engine.savi_encode(self.savi, eg['img'], noise=eg['noise'], feat_pre=eg['feat'], ws_slot=ws, side_stream=side2)   # workspace, plans
+                    engine.savi_encode(self.savi, eg['img'], noise=eg['noise'], feat_pre=eg['feat'], ws_slot=ws, side_stream=None)   # workspace, plans
                     side.synchronize()
                     g = torch.cuda.CUDAGraph()
                     with _lib.CAPTURE_GATE, torch.cuda.graph(g, stream=side, capture_error_mode='thread_local'):
-                        post, _, _ = engine.savi_encode(self.savi, eg['img'], noise=eg['noise'], feat_pre=eg['feat'], ws_slot=ws, side_stream=side2)
+                        post, _, _ = engine.savi_encode(self.savi, eg['img'], noise=eg['noise'], feat_pre=eg['feat'], ws_slot=ws, side_stream=None)
                 cur.wait_stream(side)
             finally:
                 # (a failed capture must not leave a CU count keyed by a stream handle torch hands out again)
@@ -824,23 +932,19 @@ class EncodeRolloutPipeline:
         return eg
 
     def _unit_plan(self, n):
-        """[(first batch, number of batches, _Unit, drain?)] of a run over n batches.  With `ramp` the LAST batches of a run
-        go into ever smaller units (group 4: .., 4, 2, 1, 1): the drain -- the rollouts still running once the last encode
-        is done, which nothing overlaps -- then ends with short units in the kernels' latency forms, and those units run on
-        unmasked streams (the encode partition is about to fall idle)."""
+        """[(first batch, number of batches, _Unit, drain?)] of a run over n batches.  The drain -- the rollouts still running once the
+        last encode is done, which nothing overlaps -- runs on unmasked streams (the encode partition is about to fall idle): the last
+        unit of a run, or its last two."""
         G = self.G
-        sizes, n_tail = unit_sizes_for(n, G, self._rows_per_batch, ramp=self.ramp, spread=self.spread_remainder)
-        probe = getattr(self, 'unit_sizes_override', None)   # (tools: an explicit unit plan, e.g. "4,4,6,6"; at most two units of a size other than `group` in a row)
-        if probe and sum(int(x) for x in probe.split(',')) == n:
-            sizes = [int(x) for x in probe.split(',')]
+        sizes, _ = unit_sizes_for(n, G, self._rows_per_batch)
         plan, u0, nfull, ntail = [], 0, 0, {}
-        n_drain = n_tail
-        if self.tok and len(sizes) >= 3 and sizes[-1] <= getattr(self, 'hybrid_tail', 2):
+        n_drain = 1
+        if self.tok and len(sizes) >= 3 and sizes[-1] <= self.hybrid_tail:
             # token-stationary units take 22.7 ms each whatever runs beside them: when the run ends in a SHORT unit, the last TWO units go to unmasked
             # streams -- the third unit of the driver's 20 batches (6, 6, 6, 2) would otherwise wait 15 ms for a rollout stream (488 -> 550 k frames/s).
             # Only when no hybrid-lane encode follows (the last unit's batches all take the masked lane): the first drain unit sits on that lane's
             # stream (24 batches as 6, 6, 6, 6 with two drain units: 506 k; 60 batches: 538 against 580 k)
-            n_drain = max(n_drain, 2)
+            n_drain = 2
         for i, nb in enumerate(sizes):
             if nb == G:
                 u = self.units[nfull % self.NU]
@@ -848,7 +952,7 @@ class EncodeRolloutPipeline:
             else:
                 u = self._tail_unit(nb, ntail.get(nb, 0) % 2, row_form=self.tok and i == len(sizes) - 1)
                 ntail[nb] = ntail.get(nb, 0) + 1
-            drain = i >= len(sizes) - max(n_drain, 1)
+            drain = i >= len(sizes) - n_drain
             if drain and nb == G and len(sizes) > 1 and self.tail_opts is not self.rollout_opts and self.drain_latency_form:
                 # the last unit of a run rolls out alone on the whole chip (unmasked stream): a graph of the same buffer size
                 # captured with the kernels' LATENCY forms (many short workgroups: 12.1 instead of 15.5 ms for 4 batches)
@@ -950,11 +1054,97 @@ class EncodeRolloutPipeline:
         float32 bytes at equal size), and the ingest kernel runs on the copy stream behind each upload, writing the float32 stage buffer the encodes
         read.  Device-resident batches take the same ring without the copy."""
         n = len(imgs)
-        B = self.B
-        rc_all, sg_all, u8_all = self._decoded_buffers(decoded, n) if decoded is not None else (None, None, None)
+        bufs = self._decoded_buffers(decoded, n) if decoded is not None else None
         if decoded is not None and out is not None and not out.is_cuda:
             raise RuntimeError('slotformer_amd: the decode stage reads the slots from a device-resident `out`')
-        host_in = n > 0 and not imgs[0].is_cuda
+        host_in = self._check_inputs(imgs, ingest)
+        if out is None:
+            out = torch.empty(n, self.B, self.T + self.H, self.N, self.D, device=self.dev)
+        self._check_plan()
+        cur = torch.cuda.current_stream(self.dev)
+        r = _Run(imgs, noises, out, ingest, host_in, bufs, self._unit_plan(n), cur)
+        if serial or n == 0:
+            return self._run_serial(r)
+        units, lanes, rolls = r.units, self.lanes, self.roll_streams
+        nl, nu = len(lanes), len(units)
+        # work stealing: the features of the batches of unit u are computed behind the rollout of unit u - lead, on its stream
+        r.NF = self.lead * self.G + self.G                # feature buffers per lane (slot of batch j: j % NF)
+        kmax = int(math.ceil(self.steal))
+        if kmax and self.feat_bufs is None:
+            cl = list(self.savi.enc_channels)[-1]
+            self.feat_bufs = [[torch.empty(kmax, hi - lo, 64 * 64, cl, device=self.dev) for _ in range(r.NF)] for _, lo, hi in lanes]
+        for st, _, _ in lanes:
+            st.wait_stream(cur)
+        for st in rolls + list(self.s_free):
+            st.wait_stream(cur)
+        if not out.is_cuda:
+            if self._s_out is None:
+                self._s_out = self._pool_stream('out')
+            self._s_out.wait_stream(cur)
+        if decoded is not None:
+            if self._s_dec is None:
+                self._s_dec = self._pool_stream('dec')
+            self._s_dec.wait_stream(cur)
+            r.ev_dec = torch.cuda.Event()
+        trace = bool(int(os.environ.get('SF_PIPE_TRACE', '0')))   # timeline of a run (tools/pipe_timeline.py): timing events everywhere
+        r.ev_enc = [[torch.cuda.Event(enable_timing=trace) for _ in range(nl)] for _ in range(n)]
+        r.ev_roll = [torch.cuda.Event(enable_timing=True) for _ in range(nu)]   # also: completion time of every unit
+        r.ev_pre = [torch.cuda.Event() for _ in range(n)]
+        r.stolen = [0] * n                 # time steps of precomputed features batch j will find in its feature buffer
+        # host-resident inputs (pinned): an upload stage on its own stream runs ahead of the consumers -- far enough for the
+        # work stealing, which reads the frames of a batch lead * G + G batches before its encode (extract_slots.py:19-38 reads
+        # its videos from a DataLoader; this is the device side of that hand-over)
+        assert self.stage_slots == r.NF + 2
+        self._ring.begin(imgs, ingest, host_in, self.stage_slots, cur, r.ev_enc)
+        r.n_fill = min(self.fill_batches or units[0][1], n) if (self.cu_split and self.fill_whole_chip) else 0
+        for _, _, u, _ in units:
+            u.busy = None
+        ev_t0 = torch.cuda.Event(enable_timing=True)
+        ev_t0.record(cur)
+        r.ev_rstart = [torch.cuda.Event(enable_timing=True) for _ in range(nu)] if trace else None
+        r.downloads = _Downloads(out, self.B, self._s_out, r.ev_roll)
+        for ui, (u0, nb, u, drain) in enumerate(units):
+            r.downloads.ready(for_unit=u)
+            ev_wait = []
+            for h in range(nb):
+                where = encode_lane_for(u0 + h, n, r.n_fill, self.hybrid, self.hybrid_tail, len(self.s_free), self.fill_par)
+                encode = {'hybrid': self._encode_hybrid, 'fill': self._encode_fill, 'lane': self._encode_lanes}[where]
+                last_stream, ev_wait_j = encode(r, u0 + h, u, h)
+                ev_wait = ev_wait + list(ev_wait_j)
+            if self.split and self.chain_on != 'roll':
+                ev_wait = self._chain_unit(u, last_stream, ev_wait)
+            self._rollout_unit(r, ui, ev_wait)
+        # The host waits for the last units HERE, before the calling stream is made to wait for the pipeline's streams: a
+        # wait that sits pending on the calling stream (PyTorch's default stream is the legacy null stream) for the whole
+        # run was measured to slow the kernels of the masked encode lane that shares shader engines with the rollout by
+        # 30 % (7.7 instead of 6.4 ms per batch, tools/lane_probe.py COPY=1) -- so run() returns when the results are done.
+        r.downloads.ready(everything=True)
+        for e in r.ev_roll[-(len(rolls) + 4):]:   # (the drain units on the unmasked streams may overtake the units before them)
+            e.synchronize()
+        if decoded is not None:
+            r.ev_dec.synchronize()   # (the last decode: the stage runs in order on one stream)
+            cur.wait_stream(self._s_dec)
+        for st, _, _ in lanes:
+            cur.wait_stream(st)
+        for st in rolls + list(self.s_free) + ([self._ring._s_copy] if self._ring.staged else []) + ([self._s_out] if not out.is_cuda else []):
+            cur.wait_stream(st)
+        self._ring.end()
+        self.completion_events = r.ev_roll
+        self.completion_batches = [nb for _, nb, _, _ in units]
+        if trace:
+            torch.cuda.synchronize(self.dev)
+            self.timeline = {'encode_end_ms': [max(ev_t0.elapsed_time(e) for e in r.ev_enc[j][:1 if j < r.n_fill else nl]) for j in range(n)],
+                             'rollout_start_ms': [ev_t0.elapsed_time(e) for e in r.ev_rstart],
+                             'rollout_end_ms': [ev_t0.elapsed_time(e) for e in r.ev_roll],
+                             'units': [(u0, nb) for u0, nb, _, _ in units]}
+        self._check_seam()
+        return out
+
+    def _check_inputs(self, imgs, ingest):
+        """Every batch of a run against the pipeline's shape (ingest: against what the FrameIngest takes).  Returns whether the batches are
+        in host memory."""
+        B = self.B
+        host_in = len(imgs) > 0 and not imgs[0].is_cuda
         for im in imgs:
             if ingest is not None:
                 fshape = ingest.output_shape(im)   # (ValueError for anything but contiguous uint8 frames)
@@ -964,324 +1154,168 @@ class EncodeRolloutPipeline:
             elif tuple(im.shape[:2]) != (B, self.T) or im.is_cuda == host_in or im.dtype != torch.float32:
                 raise RuntimeError(f'every batch must be a float32 tensor [{B},{self.T},3,H,W], all on the device or all in (pinned) host '
                                    f'memory, got {tuple(im.shape)} {im.dtype} on {im.device}')
-        if out is None:
-            out = torch.empty(n, B, self.T + self.H, self.N, self.D, device=self.dev)
-        self._check_plan()
-        nz = (lambda j: None) if noises is None else (lambda j: noises[j])
-        cur = torch.cuda.current_stream(self.dev)
-        units = self._unit_plan(n)
-        if serial or n == 0:
-            for u0, nb, u, _ in units:
-                for h in range(nb):
-                    im = imgs[u0 + h].to(self.dev, non_blocking=True) if host_in else imgs[u0 + h]
-                    if ingest is not None:
-                        im = ingest(im)
-                    # (on the calling stream the encode has the whole chip: the fill graph -- one persistent convolution workgroup per CU of the
-                    #  device -- not the lane's, which is sized for the encode partition)
-                    whole = ('fill', 0) if (self.encode_graph and self.cu_split and self.fill_whole_chip and self.s_free and self.fill_par > 1) else 0
-                    self._encode(im, nz(u0 + h), u.buf[h * B:(h + 1) * B], None, lane=whole, unit=(u, h))
-                if self.split and self.chain_on != 'roll':
-                    self._chain(u)
-                self._rollout(u)
-                for h in range(nb):
-                    out[u0 + h].copy_(u.buf[h * B:(h + 1) * B], non_blocking=True)
-                    if decoded is not None:
-                        self._decode_batch(u0 + h, out[u0 + h], rc_all, sg_all, u8_all)
-            if u8_all is not None and not (u8_all.is_cuda and sg_all.is_cuda):
-                cur.synchronize()   # (the copies into the caller's pinned tensors)
-            self._check_seam()
-            return out
-        G, NU, steal = self.G, self.NU, self.steal
-        lanes, rolls = self.lanes, self.roll_streams
-        nl, nu = len(lanes), len(units)
-        # work stealing: the features of the batches of unit u are computed behind the rollout of unit u - lead, on its stream
-        lead = self.lead
-        NF = lead * G + G                # feature buffers per lane (slot of batch j: j % NF)
-        # during the fill of a run the rollout partition is idle (the last rollout stream until the SECOND unit is encoded):
-        # it takes `fill_steal` whole time steps of convolutions off the encodes of the batches behind the fill
-        fill_k = min(self.fill_steal, self.T) if (len(rolls) > 1 and self.cu_split) else 0
-        kmax = max([int(math.ceil(steal)), fill_k] + list(self.pre_steal))
-        if kmax and self.feat_bufs is None:
-            cl = list(self.savi.enc_channels)[-1]
-            self.feat_bufs = [[torch.empty(kmax, hi - lo, 64 * 64, cl, device=self.dev) for _ in range(NF)] for _, lo, hi in lanes]
-        for st, _, _ in lanes:
-            st.wait_stream(cur)
-        for st in rolls + list(self.s_free):
-            st.wait_stream(cur)
-        if not out.is_cuda:
-            if self._s_out is None:
-                self._s_out = self._pool_stream('out')
-            self._s_out.wait_stream(cur)
-        ev_dec = None
-        if decoded is not None:
-            if self._s_dec is None:
-                self._s_dec = self._pool_stream('dec')
-            self._s_dec.wait_stream(cur)
-            ev_dec = torch.cuda.Event()
-        trace = bool(int(os.environ.get('SF_PIPE_TRACE', '0')))   # timeline of a run (tools/pipe_timeline.py): timing events everywhere
-        ev_enc = [[torch.cuda.Event(enable_timing=trace) for _ in range(nl)] for _ in range(n)]
-        ev_roll = [torch.cuda.Event(enable_timing=True) for _ in range(nu)]   # also: completion time of every unit
-        ev_pre = [torch.cuda.Event() for _ in range(n)]
-        stolen = [0] * n                 # time steps of precomputed features batch j will find in its feature buffer
-        # host-resident inputs (pinned): an upload stage on its own stream runs ahead of the consumers -- far enough for the
-        # work stealing, which reads the frames of a batch lead * G + G batches before its encode (extract_slots.py:19-38 reads
-        # its videos from a DataLoader; this is the device side of that hand-over)
-        NS = self.stage_slots
-        assert NS == NF + 2
-        ev_up, up_next = [], [0]
-        pinned_in = host_in and all(im.is_pinned() for im in imgs)
-        staged = host_in or ingest is not None
-        pin = None
-        if staged:
-            fshape = imgs[0].shape if ingest is None else ingest.output_shape(imgs[0])
-            if self._stage is None or self._stage[0].shape != fshape:
-                self._stage = [torch.empty(fshape, device=self.dev) for _ in range(NS)]
-                self._s_copy = self._pool_stream('copy')
-                self._pin = None
-            if ingest is None:
-                if not pinned_in and getattr(self, '_pin', None) is None:
-                    # pageable input: batches pass through a ring of NS page-locked staging buffers (never the whole set page-locked at once;
-                    # the host pays one memcpy per batch -- pre-pinned input skips it)
-                    self._pin = [torch.empty(imgs[0].shape, pin_memory=True) for _ in range(NS)]
-                pin = self._pin
-            elif host_in:
-                # ingest=: both rings hold the decoder's uint8 frames at source size; self._stage is what the ingest kernel writes
-                if self._stage_u8 is None or self._stage_u8[0].shape != imgs[0].shape:
-                    self._stage_u8 = [torch.empty(imgs[0].shape, dtype=torch.uint8, device=self.dev) for _ in range(NS)]
-                    self._pin_u8 = None
-                if not pinned_in and self._pin_u8 is None:
-                    self._pin_u8 = [torch.empty(imgs[0].shape, dtype=torch.uint8, pin_memory=True) for _ in range(NS)]
-                pin = self._pin_u8
-            self._s_copy.wait_stream(cur)
-            ev_up = [torch.cuda.Event() for _ in range(n)]
+        return host_in
 
-        def img_of(j, stream):
-            """the frames of batch j as a device tensor `stream` may read"""
-            if not staged:
-                return imgs[j]
-            while up_next[0] <= min(j, n - 1):
-                k = up_next[0]
-                with torch.cuda.stream(self._s_copy):
-                    if k >= NS:
-                        # the staging slot's previous batch has been encoded (issued NS batches ago).  The HOST waits, not the copy
-                        # stream: a queue parked in a cross-queue wait slows the queues that are running on this platform (the
-                        # masked encode lane ran at 5.8 instead of 4.05 ms per batch with the wait on the stream)
-                        for e in ev_enc[k - NS]:
-                            e.synchronize()
-                    src = imgs[k]
-                    if host_in and not pinned_in:
-                        if k >= NS:
-                            ev_up[k - NS].synchronize()   # the upload out of this page-locked slot is done
-                        pin[k % NS].copy_(src)
-                        src = pin[k % NS]
-                    if ingest is None:
-                        self._stage[k % NS].copy_(src, non_blocking=True)
-                    else:
-                        if host_in:
-                            # (the slot's previous frames were read by the ingest launch of batch k - NS, earlier on this stream)
-                            self._stage_u8[k % NS].copy_(src, non_blocking=True)
-                            src = self._stage_u8[k % NS]
-                        ingest(src, out=self._stage[k % NS])   # on the copy stream, behind the upload
-                    ev_up[k].record(self._s_copy)
-                up_next[0] += 1
-            stream.wait_event(ev_up[j])
-            return self._stage[j % NS]
-
-        def steal_for(jj, stream, tag, kj=None):
-            """features of the first steps of batch jj on `stream` (the current stream)"""
-            kj = self._steal_of(jj) if kj is None else kj
-            if kj:
-                im = img_of(jj, stream)
-                for li, (_, lo, hi) in enumerate(lanes):
-                    engine.savi_cnn(self.savi, im[lo:hi], 0, kj, out=self.feat_bufs[li][jj % NF][:kj],
-                                    ws_slot=self._key + ('steal', li, tag))
-            stolen[jj] = kj
-            ev_pre[jj].record(stream)
-
-        n_fill = min(self.fill_batches or units[0][1], n) if (self.cu_split and self.fill_whole_chip) else 0
-        for _, _, u, _ in units:
-            u.busy = None
-        ev_t0 = torch.cuda.Event(enable_timing=True)
-        ev_t0.record(cur)
-        ev_rstart = [torch.cuda.Event(enable_timing=True) for _ in range(nu)] if trace else None
-        n_free = 0
-        downloads = []   # host-resident output: units rolled out whose slots are not yet on their way to the host
-
-        def download_ready(for_unit=None, everything=False):
-            """enqueue the downloads of the units whose rollout is done (for_unit: WAIT for that unit buffer's rollout -- the buffer is
-            about to be encoded into again; everything: wait for all of them)"""
-            for d in list(downloads):
-                dui, du0, dnb, du, done = d
-                if everything or du is for_unit:
-                    done.synchronize()
-                if done.query():
-                    with torch.cuda.stream(self._s_out):
-                        for h in range(dnb):
-                            out[du0 + h].copy_(du.buf[h * B:(h + 1) * B], non_blocking=True)
-                        ev_roll[dui].record(self._s_out)
-                    downloads.remove(d)
-
-        fill_last = {}   # fill graph index -> the last batch encoded through it
-        for ui, (u0, nb, u, drain) in enumerate(units):
-            download_ready(for_unit=u)
+    def _run_serial(self, r):
+        """run(serial=True): the same calls back to back on the calling stream (reference schedule for the tests)"""
+        B, out = self.B, r.out
+        for u0, nb, u, _ in r.units:
             for h in range(nb):
-                j = u0 + h
-                dst = u.buf[h * B:(h + 1) * B]
-                hyb = (self.hybrid > 0 and j >= n_fill and n_fill > 0 and (j - n_fill) % self.hybrid == self.hybrid - 1
-                       and j + self.hybrid_tail < n and len(self.s_free) > 0 and self.fill_par > 1)
-                if hyb:
-                    # hybrid lane: every `hybrid`-th batch behind the fill is encoded on an UNMASKED stream (fill graph 1) beside the masked
-                    # lane -- the rollout partition has slack, the encode lane is the bound
-                    fs = self.s_free[0]
-                    if fill_last.get(1) is not None:
-                        fs.wait_event(ev_enc[fill_last[1]][0])
-                    if u.busy is not None:
-                        fs.wait_event(u.busy)
-                    with torch.cuda.stream(fs):
-                        self._encode(img_of(j, fs), nz(j), dst, None, lane=('fill', 1), unit=(u, h))
-                        ev_enc[j][0].record(fs)
-                    fill_last[1] = j
-                    last_stream = fs
-                    ev_wait_j = ev_enc[j][:1]
-                elif j < n_fill:
-                    # pipeline fill: the first encodes take the whole chip (unmasked streams); the masked lanes start after them.  One
-                    # encode alone cannot fill 256 CUs (2.7 ms for 470 CU-ms of work), so `fill_par` of them run side by side,
-                    # each from its own graph / buffers (380-382 vs 375-378 k frames/s at 20 batches).  The host waits: with the
-                    # other queues parked in a wait on this event the encode was measured at 4.8 instead of 3.05 ms (a queue stalled
-                    # in a cross-queue wait slows the queue that is running)
-                    fill_par = self.fill_par if self.s_free else 1
-                    fi = j % fill_par
-                    fs = cur if fi == 0 else self.s_free[(fi - 1) % len(self.s_free)]
-                    if (j >= units[0][1] or self.split) and self.s_free and fi == 0:
-                        # fill batches behind the first unit: a rollout is already enqueued, and the calling stream -- the legacy null
-                        # stream -- would wait for it.  Fill graph 0 (its fixed buffers) moves to an unmasked stream, behind its last use
-                        fs = self.s_free[-1]
-                    if j >= fill_par:
-                        fs.wait_event(ev_enc[j - fill_par][0])   # the previous batch through this fill graph / its buffers
-                    with torch.cuda.stream(fs):
-                        self._encode(img_of(j, fs), nz(j), dst, None, lane=('fill', fi) if fill_par > 1 else 0, unit=(u, h))
-                        ev_enc[j][0].record(fs)
-                    fill_last[fi] = j
-                    last_stream = fs
-                    if j == 0 and (steal or fill_k) and len(rolls) > 1:
-                        # the rollout streams idle until the first unit is encoded: they compute the stolen features of the
-                        # batches behind the fill now (round-robin), so that only the fill batches pay for their own convolutions
-                        # (all on the LAST rollout stream, whose first unit starts latest: on the first one they delayed the first
-                        #  rollout of a run by 3.3 ms, tools/pipe_timeline.py)
-                        first = max(n_fill, 1)
-                        fill_end = units[lead][0] if nu > lead else n      # (unit `lead` onwards: stolen behind the rollouts)
-                        if fill_k:   # only what the last rollout stream can finish before its first unit is ready: the second unit's batches
-                            fill_end = min(fill_end, units[2][0] if nu > 2 else n)
-                        for jj in range(first, fill_end):
-                            with torch.cuda.stream(rolls[-1]):
-                                steal_for(jj, rolls[-1], len(rolls) - 1, fill_k or None)
-                    if j == n_fill - 1:
-                        for jj in range(max(0, n_fill - fill_par), n_fill):
-                            ev_enc[jj][0].synchronize()
-                        for st, _, _ in lanes:
-                            for jj in range(max(0, n_fill - fill_par), n_fill):
-                                st.wait_event(ev_enc[jj][0])
-                    ev_wait_j = ev_enc[j][:1]
-                else:
-                    for li, (st, lo, hi) in enumerate(lanes):
-                        with torch.cuda.stream(st):
-                            if u.busy is not None:
-                                st.wait_event(u.busy)   # the unit buffer is free once its previous rollout + copy-out are done
-                            pre = None
-                            if stolen[j]:
-                                st.wait_event(ev_pre[j])
-                                pre = self.feat_bufs[li][j % NF][:stolen[j]]
-                            self._encode(img_of(j, st), nz(j), dst, pre, lo, hi, li, unit=(u, h))
-                            ev_enc[j][li].record(st)
-                    last_stream = lanes[0][0]
-                    ev_wait_j = ev_enc[j]
-                if h == 0:
-                    ev_wait = []
-                ev_wait = ev_wait + list(ev_wait_j)
+                im = r.imgs[u0 + h].to(self.dev, non_blocking=True) if r.host_in else r.imgs[u0 + h]
+                if r.ingest is not None:
+                    im = r.ingest(im)
+                # (on the calling stream the encode has the whole chip: the fill graph -- one persistent convolution workgroup per CU of the
+                #  device -- not the lane's, which is sized for the encode partition)
+                whole = ('fill', 0) if (self.encode_graph and self.cu_split and self.fill_whole_chip and self.s_free and self.fill_par > 1) else 0
+                self._encode(im, r.noise(u0 + h), u.buf[h * B:(h + 1) * B], None, lane=whole, unit=(u, h))
             if self.split and self.chain_on != 'roll':
-                # the slot branch of the unit on the stream that encoded its last batch, behind the features of all its batches
-                cst = last_stream
-                with torch.cuda.stream(cst):
-                    for e in ev_wait:
-                        cst.wait_event(e)
-                    self._chain(u)
-                    ev_c = torch.cuda.Event()
-                    ev_c.record(cst)
-                ev_wait = [ev_c]
-            s_roll = rolls[ui % len(rolls)]
-            if len(rolls) > 1 and drain and self.s_free:
-                # drain: the encode lane is (about to be) idle -- the last units take unmasked streams (all CUs) instead of queueing
-                # behind the full units on the rollout partition (their slot / feature buffers are ordered by events)
-                s_roll = self.s_free[n_free % len(self.s_free)]
-                n_free += 1
-            with torch.cuda.stream(s_roll):
-                for e in ev_wait:
-                    s_roll.wait_event(e)
-                if self.pre_steal and ui + 1 < nu and self.cu_split and not drain:
-                    # the rollout streams have a little slack per unit (the encode is the longer side): before this unit rolls
-                    # out, its stream takes pre_steal[h] time steps of convolutions off the LATER batches of the NEXT unit --
-                    # stealing behind a rollout is too late for units of several batches (the next unit is encoded meanwhile)
-                    nu0, nnb = units[ui + 1][:2]
-                    for h2 in range(nnb):
-                        k2 = self.pre_steal[min(h2, len(self.pre_steal) - 1)]
-                        if k2 and not stolen[nu0 + h2]:
-                            steal_for(nu0 + h2, s_roll, ui % len(rolls), k2)
-                if trace:
-                    ev_rstart[ui].record(s_roll)
-                self._rollout(u)
-                if out.is_cuda:
-                    for h in range(nb):
-                        out[u0 + h].copy_(u.buf[h * B:(h + 1) * B])
-                    ev_roll[ui].record(s_roll)
-                    if decoded is not None:
-                        # decode stage: reads the unit's slots from `out` (the unit buffer is free for the next encode at once), on an
-                        # unmasked stream of its own, one batch after the other
-                        with torch.cuda.stream(self._s_dec):
-                            self._s_dec.wait_event(ev_roll[ui])
-                            for h in range(nb):
-                                self._decode_batch(u0 + h, out[u0 + h], rc_all, sg_all, u8_all)
-                            ev_dec.record(self._s_dec)
-                else:
-                    # pinned host output: the downloads run on a torch-owned stream -- PyTorch's host allocator records an event
-                    # on every stream a pinned block was used on when the block is freed, and the CU-masked streams of this
-                    # object may be gone by then (close())
-                    # The download stream must not sit PARKED in a wait for the unit's rollout (a queue stalled in a cross-queue
-                    # wait slows the queues that are running on this platform: the masked encode lane ran at 5.7 instead of 4.05 ms
-                    # per batch, 312 vs 390 k frames/s) -- the host enqueues the copies once the rollout is done (download_ready)
-                    done = torch.cuda.Event()
-                    done.record(s_roll)
-                    downloads.append((ui, u0, nb, u, done))
-                u.busy = ev_roll[ui]
-                if steal and ui + lead < nu:
-                    # their feature buffers were last read by the encodes of batches <= u0 + nb - 1 ... (NF = lead*G + G apart),
-                    # which this stream has waited for
-                    tu0, tnb = units[ui + lead][:2]
-                    for jj in range(tu0, tu0 + tnb):
-                        steal_for(jj, s_roll, ui % len(rolls))
-        # The host waits for the last units HERE, before the calling stream is made to wait for the pipeline's streams: a
-        # wait that sits pending on the calling stream (PyTorch's default stream is the legacy null stream) for the whole
-        # run was measured to slow the kernels of the masked encode lane that shares shader engines with the rollout by
-        # 30 % (7.7 instead of 6.4 ms per batch, tools/lane_probe.py COPY=1) -- so run() returns when the results are done.
-        download_ready(everything=True)
-        for e in ev_roll[-(len(rolls) + 4):]:   # (the drain units on the unmasked streams may overtake the units before them)
-            e.synchronize()
-        if decoded is not None:
-            ev_dec.synchronize()   # (the last decode: the stage runs in order on one stream)
-            cur.wait_stream(self._s_dec)
-        for st, _, _ in lanes:
-            cur.wait_stream(st)
-        for st in rolls + list(self.s_free) + ([self._s_copy] if staged else []) + ([self._s_out] if not out.is_cuda else []):
-            cur.wait_stream(st)
-        self.completion_events = ev_roll
-        self.completion_batches = [nb for _, nb, _, _ in units]
-        if trace:
-            torch.cuda.synchronize(self.dev)
-            self.timeline = {'encode_end_ms': [max(ev_t0.elapsed_time(e) for e in ev_enc[j][:1 if j < n_fill else nl]) for j in range(n)],
-                             'rollout_start_ms': [ev_t0.elapsed_time(e) for e in ev_rstart],
-                             'rollout_end_ms': [ev_t0.elapsed_time(e) for e in ev_roll],
-                             'units': [(u0, nb) for u0, nb, _, _ in units]}
+                self._chain(u)
+            self._rollout(u)
+            for h in range(nb):
+                out[u0 + h].copy_(u.buf[h * B:(h + 1) * B], non_blocking=True)
+                if r.decoded:
+                    self._decode_batch(u0 + h, out[u0 + h], r.rc_all, r.sg_all, r.u8_all)
+        if r.u8_all is not None and not (r.u8_all.is_cuda and r.sg_all.is_cuda):
+            r.cur.synchronize()   # (the copies into the caller's pinned tensors)
         self._check_seam()
         return out
+
+    def _steal_for(self, r, jj, stream, tag):
+        """features of the first steps of batch jj on `stream` (the current stream)"""
+        kj = self._steal_of(jj)
+        if kj:
+            im = self._ring.frames(jj, stream)
+            for li, (_, lo, hi) in enumerate(self.lanes):
+                engine.savi_cnn(self.savi, im[lo:hi], 0, kj, out=self.feat_bufs[li][jj % r.NF][:kj],
+                                ws_slot=self._key + ('steal', li, tag))
+        r.stolen[jj] = kj
+        r.ev_pre[jj].record(stream)
+
+    def _encode_hybrid(self, r, j, u, h):
+        """Batch j (batch h of unit u) on the hybrid lane.  Returns the stream it was issued on and the events of its end."""
+        # hybrid lane: every `hybrid`-th batch behind the fill is encoded on an UNMASKED stream (fill graph 1) beside the masked
+        # lane -- the rollout partition has slack, the encode lane is the bound
+        fs = self.s_free[0]
+        if r.fill_last.get(1) is not None:
+            fs.wait_event(r.ev_enc[r.fill_last[1]][0])
+        if u.busy is not None:
+            fs.wait_event(u.busy)
+        with torch.cuda.stream(fs):
+            self._encode(self._ring.frames(j, fs), r.noise(j), u.buf[h * self.B:(h + 1) * self.B], None, lane=('fill', 1), unit=(u, h))
+            r.ev_enc[j][0].record(fs)
+        r.fill_last[1] = j
+        return fs, r.ev_enc[j][:1]
+
+    def _encode_fill(self, r, j, u, h):
+        """Batch j (batch h of unit u) in the whole-chip fill of a run.  Returns the stream it was issued on and the events of its end."""
+        # pipeline fill: the first encodes take the whole chip (unmasked streams); the masked lanes start after them.  One
+        # encode alone cannot fill 256 CUs (2.7 ms for 470 CU-ms of work), so `fill_par` of them run side by side,
+        # each from its own graph / buffers (380-382 vs 375-378 k frames/s at 20 batches).  The host waits: with the
+        # other queues parked in a wait on this event the encode was measured at 4.8 instead of 3.05 ms (a queue stalled
+        # in a cross-queue wait slows the queue that is running)
+        units, rolls, ev_enc, n_fill = r.units, self.roll_streams, r.ev_enc, r.n_fill
+        fill_par = self.fill_par if self.s_free else 1
+        fi = j % fill_par
+        fs = r.cur if fi == 0 else self.s_free[(fi - 1) % len(self.s_free)]
+        if (j >= units[0][1] or self.split) and self.s_free and fi == 0:
+            # fill batches behind the first unit: a rollout is already enqueued, and the calling stream -- the legacy null
+            # stream -- would wait for it.  Fill graph 0 (its fixed buffers) moves to an unmasked stream, behind its last use
+            fs = self.s_free[-1]
+        if j >= fill_par:
+            fs.wait_event(ev_enc[j - fill_par][0])   # the previous batch through this fill graph / its buffers
+        with torch.cuda.stream(fs):
+            self._encode(self._ring.frames(j, fs), r.noise(j), u.buf[h * self.B:(h + 1) * self.B], None, lane=('fill', fi) if fill_par > 1 else 0, unit=(u, h))
+            ev_enc[j][0].record(fs)
+        r.fill_last[fi] = j
+        if j == 0 and self.steal and len(rolls) > 1:
+            # the rollout streams idle until the first unit is encoded: they compute the stolen features of the
+            # batches behind the fill now (round-robin), so that only the fill batches pay for their own convolutions
+            # (all on the LAST rollout stream, whose first unit starts latest: on the first one they delayed the first
+            #  rollout of a run by 3.3 ms, tools/pipe_timeline.py)
+            first = max(n_fill, 1)
+            fill_end = units[self.lead][0] if len(units) > self.lead else r.n      # (unit `lead` onwards: stolen behind the rollouts)
+            for jj in range(first, fill_end):
+                with torch.cuda.stream(rolls[-1]):
+                    self._steal_for(r, jj, rolls[-1], len(rolls) - 1)
+        if j == n_fill - 1:
+            for jj in range(max(0, n_fill - fill_par), n_fill):
+                ev_enc[jj][0].synchronize()
+            for st, _, _ in self.lanes:
+                for jj in range(max(0, n_fill - fill_par), n_fill):
+                    st.wait_event(ev_enc[jj][0])
+        return fs, ev_enc[j][:1]
+
+    def _encode_lanes(self, r, j, u, h):
+        """Batch j (batch h of unit u) on the CU-masked lanes.  Returns the first lane's stream and the events of its end."""
+        for li, (st, lo, hi) in enumerate(self.lanes):
+            with torch.cuda.stream(st):
+                if u.busy is not None:
+                    st.wait_event(u.busy)   # the unit buffer is free once its previous rollout + copy-out are done
+                pre = None
+                if r.stolen[j]:
+                    st.wait_event(r.ev_pre[j])
+                    pre = self.feat_bufs[li][j % r.NF][:r.stolen[j]]
+                self._encode(self._ring.frames(j, st), r.noise(j), u.buf[h * self.B:(h + 1) * self.B], pre, lo, hi, li, unit=(u, h))
+                r.ev_enc[j][li].record(st)
+        return self.lanes[0][0], r.ev_enc[j]
+
+    def _chain_unit(self, u, cst, ev_wait):
+        """split encode: the slot branch of the unit on the stream that encoded its last batch, behind the features of all its batches.
+        Returns what the unit's rollout then waits for."""
+        with torch.cuda.stream(cst):
+            for e in ev_wait:
+                cst.wait_event(e)
+            self._chain(u)
+            ev_c = torch.cuda.Event()
+            ev_c.record(cst)
+        return [ev_c]
+
+    def _rollout_unit(self, r, ui, ev_wait):
+        """Unit ui of the run behind its encodes (ev_wait): the rollout on its stream, the slots to `out` (or handed to the downloads), the
+        decode stage behind them, and the stolen features of unit ui + lead behind the rollout."""
+        u0, nb, u, drain = r.units[ui]
+        B, out, rolls, nu = self.B, r.out, self.roll_streams, len(r.units)
+        s_roll = rolls[ui % len(rolls)]
+        if len(rolls) > 1 and drain and self.s_free:
+            # drain: the encode lane is (about to be) idle -- the last units take unmasked streams (all CUs) instead of queueing
+            # behind the full units on the rollout partition (their slot / feature buffers are ordered by events)
+            s_roll = self.s_free[r.n_free % len(self.s_free)]
+            r.n_free += 1
+        with torch.cuda.stream(s_roll):
+            for e in ev_wait:
+                s_roll.wait_event(e)
+            if r.ev_rstart is not None:
+                r.ev_rstart[ui].record(s_roll)
+            self._rollout(u)
+            if out.is_cuda:
+                for h in range(nb):
+                    out[u0 + h].copy_(u.buf[h * B:(h + 1) * B])
+                r.ev_roll[ui].record(s_roll)
+                if r.decoded:
+                    # decode stage: reads the unit's slots from `out` (the unit buffer is free for the next encode at once), on an
+                    # unmasked stream of its own, one batch after the other
+                    with torch.cuda.stream(self._s_dec):
+                        self._s_dec.wait_event(r.ev_roll[ui])
+                        for h in range(nb):
+                            self._decode_batch(u0 + h, out[u0 + h], r.rc_all, r.sg_all, r.u8_all)
+                        r.ev_dec.record(self._s_dec)
+            else:
+                # pinned host output: the downloads run on a torch-owned stream -- PyTorch's host allocator records an event
+                # on every stream a pinned block was used on when the block is freed, and the CU-masked streams of this
+                # object may be gone by then (close())
+                # The download stream must not sit PARKED in a wait for the unit's rollout (a queue stalled in a cross-queue
+                # wait slows the queues that are running on this platform: the masked encode lane ran at 5.7 instead of 4.05 ms
+                # per batch, 312 vs 390 k frames/s) -- the host enqueues the copies once the rollout is done (_Downloads.ready)
+                done = torch.cuda.Event()
+                done.record(s_roll)
+                r.downloads.add(ui, u0, nb, u, done)
+            u.busy = r.ev_roll[ui]
+            if self.steal and ui + self.lead < nu:
+                # their feature buffers were last read by the encodes of batches <= u0 + nb - 1 ... (NF = lead*G + G apart),
+                # which this stream has waited for
+                tu0, tnb = r.units[ui + self.lead][:2]
+                for jj in range(tu0, tu0 + tnb):
+                    self._steal_for(r, jj, s_roll, ui % len(rolls))
 
     def _check_seam(self):
         """Seam launches (only when the rollout options turn them on) hand rows over inside a launch with a bounded wait; a

@@ -2,7 +2,7 @@
 The pipeline itself (streams, graphs, bit-identity of every plan with the serial calls) is tests/test_pipeline_gpu.py."""
 import pytest
 
-from slotformer_amd.pipeline import unit_sizes_for
+from slotformer_amd.pipeline import encode_lane_for, unit_sizes_for
 
 C2_ROWS = 32 * 7 * 6      # token rows of a C2 batch (32 videos x 7 slots x 6 frames): 6 batches fill one round of row tiles
 C5_ROWS = 64 * 6 * 8      # a C5 batch is more than a third of a round: units never grow
@@ -33,3 +33,36 @@ def test_c2_plans():
     assert unit_sizes_for(21, 4, C5_ROWS)[0] == [4, 4, 4, 4, 4, 1]
     # the ramp (off by default): the last batches in ever smaller units, which replace at most one full unit
     assert unit_sizes_for(20, 4, C2_ROWS, ramp=True) == ([4, 4, 4, 4, 2, 1, 1], 3)
+
+
+# encode_lane_for: where every batch of a run is encoded.  (n_fill of a run of n, hybrid, hybrid_tail, n) -> the batches of the hybrid lane, worked by
+# hand from the rule with two unmasked streams and two fill graphs: behind the fill every hybrid-th batch, none among the last hybrid_tail of the run
+TOK_C2 = lambda n: dict(n=n, n_fill=min(18, n), hybrid=8, hybrid_tail=3)      # noqa: E731  (token-stationary C2: the fill is three units of 6 batches)
+LANE_CASES = {
+    'tok-C2-40': (TOK_C2(40), [25, 33]),
+    'tok-C2-36': (TOK_C2(36), [25]),            # 33 + 3 is not < 36
+    'tok-C2-20': (TOK_C2(20), []),
+    'tok-C2-10': (TOK_C2(10), []),              # the fill covers the run
+    'rows-C2-40': (dict(n=40, n_fill=12, hybrid=5, hybrid_tail=3), [16, 21, 26, 31, 36]),
+}
+
+
+def _lanes(n, n_fill, hybrid, hybrid_tail, free_streams=2, fill_par=2):
+    return [encode_lane_for(j, n, n_fill, hybrid, hybrid_tail, free_streams, fill_par) for j in range(n)]
+
+
+@pytest.mark.parametrize('case', sorted(LANE_CASES))
+def test_encode_lanes(case):
+    kw, hybrid_batches = LANE_CASES[case]
+    n, n_fill = kw['n'], kw['n_fill']
+    lanes = _lanes(**kw)
+    assert [j for j, w in enumerate(lanes) if w == 'hybrid'] == hybrid_batches
+    # batches below n_fill are 'fill', every other batch 'lane'
+    assert all(w == ('fill' if j < n_fill else 'lane') for j, w in enumerate(lanes) if w != 'hybrid')
+    assert all(j >= n_fill for j in hybrid_batches)
+    if case == 'tok-C2-10':
+        assert lanes == ['fill'] * 10
+    plain = ['fill'] * n_fill + ['lane'] * (n - n_fill)
+    assert _lanes(**dict(kw, hybrid=0)) == plain                       # hybrid = 0: no hybrid batch
+    assert _lanes(**kw, free_streams=0) == plain                       # no free stream: no hybrid batch
+    assert _lanes(**dict(kw, n_fill=0)) == ['lane'] * n                # no fill: no hybrid batch and no fill batch

@@ -31,7 +31,7 @@ with torch.no_grad():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     tl = pipe.timeline
-    print(f'n={n} wall {1e3 * wall:.2f} ms ({n * B * (T + H) / wall / 1e3:.1f} k frames/s)  group {pipe.G} steal {pipe.steal} ramp {pipe.ramp}')
+    print(f'n={n} wall {1e3 * wall:.2f} ms ({n * B * (T + H) / wall / 1e3:.1f} k frames/s)  group {pipe.G} steal {pipe.steal}')
     print('encode end  :', ' '.join(f'{t:6.2f}' for t in tl['encode_end_ms']))
     for (u0, nb), rs, re_ in zip(tl['units'], tl['rollout_start_ms'], tl['rollout_end_ms']):
         print(f'unit batches {u0:2d}..{u0 + nb - 1:2d}: rollout {rs:6.2f} -> {re_:6.2f}  ({re_ - rs:5.2f} ms; waited {rs - tl["encode_end_ms"][u0 + nb - 1]:5.2f} after its last encode)')
