@@ -744,7 +744,7 @@ int sf_phyre_readout_fwd_f32(const float* slots, long long stride_v, long long s
 int sf_phyre_auccess_f32(const float* conf, const int* status, int* first_rank, int tasks, int actions, void* stream);
 
 /* ---- CLEVRER VQA: the Aloe reasoner (clevrer_vqa/models/transformer.py, aloe.py; csrc/aloe.hip) ---------------------------------------------------
- * Inference only.  tokens[b] = [CLS ; vision_in_proj([slot | 0 1]) for (t, n) t-major ; q_in_proj([q_embedding[token] | type pair | 1 0])] + pos,
+ * The forward (training: sf_aloe_train_fwd_f32 below).  tokens[b] = [CLS ; vision_in_proj([slot | 0 1]) for (t, n) t-major ; q_in_proj([q_embedding[token] | type pair | 1 0])] + pos,
  * L = 1 + T N + text_len rows of d_model; num_layers pre-LN nn.TransformerEncoderLayer (relu, eps 1e-5) with the padded text positions masked out as
  * keys; logits[b] = W2 relu(W1 x[b, 0] + b1) + b2.  Launches: the token rows (split-bf16 on MFMA), per layer LN1 + q|k|v, the masked attention
  * (split-bf16 on MFMA, f32 softmax), out_proj + residual, LN2 + linear1 + ReLU, linear2 + residual (the library's GEMM), and a plain-f32 head.  The
@@ -1068,6 +1068,63 @@ int sf_phyre_readout_train_fwd_f32(const sf_phyre_readout_model* m, const float*
 int sf_phyre_readout_train_bwd_f32(const sf_phyre_readout_model* m, const float* slots, long long stride_v, long long stride_t, int V, int T_all,
                                    const int* video_index, const int* sel, int B, int T, const float* g, const sf_phyre_readout_grads* grads,
                                    float dropout_p, unsigned long long seed, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Training of the Aloe reasoner (csrc/aloe_train.hip; clevrer_vqa.fit, train.aloe_with_grad) ---------------------------------------------------
+ * CLEVRERTransformerModel.forward in train mode + the gradient of its logits, as the reference's clevrer_vqa/method.py step differentiates it.  A
+ * batch is ONE pass over B = B1 + Bn sequences: the B1 descriptive questions first, then the Bn choices of the multiple-choice questions (the order
+ * the dataset collates); slots, video_index, start, frame_offset, tokens [B][text_len], pad_mask [B][text_len] as sf_aloe_fwd_f32 takes them.  The
+ * launch chain is that of sf_aloe_fwd_f32 (no row-pruned last layer) with the text table recomputed every call and the four dropout sites of
+ * nn.TransformerEncoderLayer (dropout_p == 0: no mask is evaluated): masks are a pure function of (seed, layer, site, element) -- csrc/dropout_mask.h,
+ * train.dropout_keep_mask; element index site 0: ((b heads + h) L + i) L + j, sites 1 and 3: (b L + token) d_model + c, site 2: (b L + token) ffn + j.
+ * Pass the same batch / dropout_p / seed to both calls and leave the workspace (16-byte aligned, sf_aloe_train_workspace_bytes; 0 for unsupported
+ * arguments or B outside [1, 65535]) untouched in between.  All parameter pointers are DEVICE memory in torch layouts (`layers`: a HOST array, the
+ * torch-layout leaves only), read every call, so they may move between steps; gradients are WRITTEN, not accumulated.  Aligned to 16 bytes: slots,
+ * vision_w, every layer's matrices and LayerNorm parameters, and the gradients of every layer's matrices and biases; every other leaf may stand at
+ * an odd offset of a flat bucket.  Limits: sf_aloe_train_ok == sf_aloe_ok; B heads L^2 < 2^32.  Split-bf16 products whatever sf_set_precision says:
+ * any other process precision is refused.  Every argument error (shape, NULL, alignment, workspace too small, precision, B) is a negative return
+ * code with a message before any launch.  video_index / start / tokens are TRUSTED as in sf_aloe_fwd_f32: an entry outside its table is never an
+ * address -- it is a zero operand and gives NaN logits for its sequence; a loss over them is NaN and so is every gradient of that step (validate
+ * the indices on the host once: clevrer_vqa.fit does).  No allocation, no synchronisation; fixed summation orders, no float atomics. */
+typedef struct {
+  int num_slots, slot_size, T, text_len, question_len;
+  int d_model, num_heads, ffn_dim, num_layers;
+  int vocab, emb_dim;                      /* q_embedding [vocab][emb_dim] */
+  int mlp_hidden, num_answers;             /* both answer MLPs: d_model -> mlp_hidden -> num_answers (cls) / 1 (mc) */
+  const float* cls;                        /* [d_model] */
+  const float* pos;                        /* [L][d_model] */
+  const float *vision_w, *vision_b;        /* [d_model][C + 2], [d_model] */
+  const float* q_embedding;
+  const float *q_in_proj_w, *q_in_proj_b;  /* [d_model][emb_dim + 4], [d_model] */
+  const sf_tfm_layer* layers;              /* HOST array [num_layers] */
+  const float *cls_w1, *cls_b1, *cls_w2, *cls_b2;
+  const float *mc_w1, *mc_b1, *mc_w2, *mc_b2;
+} sf_aloe_model;
+
+/* The same leaves (d vision_w column C is 0, d q_in_proj_w column emb_dim + 3 is 0: their inputs are 0). */
+typedef struct {
+  float *cls, *pos, *vision_w, *vision_b, *q_embedding, *q_in_proj_w, *q_in_proj_b;
+  const sf_tfm_layer_grads* layers;        /* HOST array [num_layers] */
+  float *cls_w1, *cls_b1, *cls_w2, *cls_b2;
+  float *mc_w1, *mc_b1, *mc_w2, *mc_b2;
+} sf_aloe_grads;
+
+int sf_aloe_train_ok(int num_slots, int slot_size, int T, int text_len, int d_model, int num_heads, int ffn, int num_layers);
+size_t sf_aloe_train_workspace_bytes(const sf_aloe_model* m, int B);
+/* -> cls_logits [B1][num_answers], mc_logits [Bn] (NULL for an empty kind).  gates (or NULL): [num_layers][B * L][ffn] bytes, the ReLU decisions of
+ * the layers (1: passed); head_gates (or NULL): [B][mlp_hidden] bytes, those of each sequence's head. */
+int sf_aloe_train_fwd_f32(const sf_aloe_model* m, const float* slots, long long stride_v, long long stride_t, int V, int T_all, const int* video_index,
+                          const int* start, int frame_offset, const int* tokens, const unsigned char* pad_mask, int B1, int Bn, float dropout_p,
+                          unsigned long long seed, float* cls_logits, float* mc_logits, unsigned char* gates, unsigned char* head_gates, void* ws,
+                          size_t ws_bytes, void* stream);
+/* g_cls [B1][num_answers], g_mc [Bn] = d loss / d logits -> every parameter gradient in *grads; a kind without rows leaves zeros in its head. */
+int sf_aloe_train_bwd_f32(const sf_aloe_model* m, const float* slots, long long stride_v, long long stride_t, int V, int T_all, const int* video_index,
+                          const int* start, int frame_offset, const int* tokens, const unsigned char* pad_mask, int B1, int Bn, const float* g_cls,
+                          const float* g_mc, const sf_aloe_grads* grads, float dropout_p, unsigned long long seed, void* ws, size_t ws_bytes, void* stream);
+/* One launch of one workgroup: losses [2] as sf_aloe_score_f32 computes them (mean cross-entropy, mean BCE-with-logits, in double; 0 for an empty
+ * kind) and the gradient of w_cls * losses[0] + w_mc * losses[1]: g_cls [B1][num_answers] = w_cls (softmax - onehot) / B1, g_mc [Bn] =
+ * w_mc (sigmoid - label) / Bn.  losses, g_cls, g_mc may be NULL. */
+int sf_aloe_score_grad_f32(const float* cls_logits, const int* cls_labels, int B1, int num_answers, const float* mc_logits, const float* mc_labels, int Bn,
+                           float w_cls, float w_mc, float* losses, float* g_cls, float* g_mc, void* stream);
 
 /* ---- SlotFormer training on clips of a device-resident table (csrc/clip_train.hip; video_prediction.fit) ----------------------------------
  * A batch is B (video, start) pairs in two int32 DEVICE arrays, never a gathered copy.  The index arrays are TRUSTED: they are not read back,

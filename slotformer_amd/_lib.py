@@ -53,6 +53,20 @@ class sf_phyre_readout_grads(C.Structure):
         (n, FP) for n in ('mlp_w1', 'mlp_b1', 'mlp_w2', 'mlp_b2')]
 
 
+_ALOE_HEADS = ('cls_w1', 'cls_b1', 'cls_w2', 'cls_b2', 'mc_w1', 'mc_b1', 'mc_w2', 'mc_b2')
+_ALOE_LEAVES = ('cls', 'pos', 'vision_w', 'vision_b', 'q_embedding', 'q_in_proj_w', 'q_in_proj_b')
+
+
+class sf_aloe_model(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('num_slots', 'slot_size', 'T', 'text_len', 'question_len', 'd_model', 'num_heads', 'ffn_dim', 'num_layers',
+                                       'vocab', 'emb_dim', 'mlp_hidden', 'num_answers')] + [(n, FP) for n in _ALOE_LEAVES] + [
+                                           ('layers', C.POINTER(sf_tfm_layer))] + [(n, FP) for n in _ALOE_HEADS]
+
+
+class sf_aloe_grads(C.Structure):
+    _fields_ = [(n, FP) for n in _ALOE_LEAVES] + [('layers', C.POINTER(sf_tfm_layer_grads))] + [(n, FP) for n in _ALOE_HEADS]
+
+
 class sf_rollouter_grads(C.Structure):
     _fields_ = [(n, FP) for n in ('in_proj_w', 'in_proj_b', 'out_proj_w', 'out_proj_b')] + [
         ('layers', C.POINTER(sf_tfm_layer_grads)), ('pe_tok', FP)]
@@ -349,6 +363,12 @@ SIGNATURES = {
     'sf_aloe_text_table_f32': (I, [FP, FP, FP, FP, I, I, I, VP]),
     'sf_aloe_fwd_f32': (I, [C.POINTER(sf_aloe), FP, LL, LL, I, I, VP, VP, I, VP, VP, I, FP, FP, FP, FP, I, I, FP, VP, I, VP, SZ, VP]),
     'sf_aloe_score_f32': (I, [FP, VP, I, I, FP, FP, VP, I, VP, I, FP, VP, VP, VP]),
+    'sf_aloe_train_ok': (I, [I, I, I, I, I, I, I, I]),
+    'sf_aloe_train_workspace_bytes': (SZ, [C.POINTER(sf_aloe_model), I]),
+    'sf_aloe_train_fwd_f32': (I, [C.POINTER(sf_aloe_model), FP, LL, LL, I, I, VP, VP, I, VP, VP, I, I, F32, C.c_ulonglong, FP, FP, VP, VP, VP, SZ, VP]),
+    'sf_aloe_train_bwd_f32': (I, [C.POINTER(sf_aloe_model), FP, LL, LL, I, I, VP, VP, I, VP, VP, I, I, FP, FP, C.POINTER(sf_aloe_grads), F32,
+                                  C.c_ulonglong, VP, SZ, VP]),
+    'sf_aloe_score_grad_f32': (I, [FP, VP, I, I, FP, FP, I, F32, F32, FP, FP, FP, VP]),
     'sf_packed_linear_bytes': (SZ, [I, I]),
     'sf_pack_linear_weights': (I, [FP, VP, I, I, VP]),
     'sf_attn_packed_bytes': (SZ, [I, I]),

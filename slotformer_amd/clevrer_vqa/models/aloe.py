@@ -22,7 +22,7 @@ class CLEVRERAloe(BaseModel):
         return self.transformer_model(data_dict)
 
     def calc_train_loss(self, data_dict, out_dict):
-        """Values only: the backward of the reasoner is not built."""
+        """Values only, no graph attached: the differentiable loss is `train.aloe_loss` on the logits of `train.aloe_with_grad`."""
         loss_dict = self.transformer_model.loss_function(data_dict, out_dict)
         loss_dict['cls_bs'] = 0 if out_dict['cls_answer_logits'] is None else out_dict['cls_answer_logits'].shape[0]
         loss_dict['mc_bs'] = 0 if out_dict['mc_answer_logits'] is None else out_dict['mc_answer_logits'].shape[0]

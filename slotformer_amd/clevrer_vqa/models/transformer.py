@@ -5,7 +5,8 @@ A CLS token, the slots of T frames (t-major, slot-minor) and the question (and c
 vision_in_proj([slot | 0 1]), every text row q_in_proj([q_embedding[token] | type pair | 1 0]); a learnable position row is added to every row;
 a pre-LN Transformer encoder runs with the padded text positions masked out as keys; an MLP on the CLS row gives the answer logits
 (`cls_answer_mlp`: one per answer word; `mc_answer_mlp`: one logit per choice).  The module holds the parameters under the reference's names
-and construction order; the forward is csrc/aloe.hip (`sf_aloe_fwd_f32`).  Inference only: the backward is not built.
+and construction order; the forward is csrc/aloe.hip (`sf_aloe_fwd_f32`).  `forward` / `answer` are inference: training runs through `clevrer_vqa.fit` and
+`train.aloe_with_grad` (csrc/aloe_train.hip).
 
 The reference builds its encoder with nerv.models.transformer.build_transformer_encoder, a third-party function that is not part of the
 reference tree.  From the call sites: it takes (x, src_key_padding_mask=), has a 'learnable' position encoding of input_len rows and is built

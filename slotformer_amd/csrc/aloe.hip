@@ -18,7 +18,8 @@
 //                           product -- the contraction slots of P V are assigned to (key tile pair, lane group) accordingly and P never touches LDS.
 //                           Softmax in f32 (v_exp_f32), padded text positions and keys past L carry a -inf bias: they are never keys.  Padded rows are
 //                           computed as queries like any other; nothing reads them.  In the LAST layer only the CLS row is a query (keys and values
-//                           from all rows), and the GEMMs around it run on the B CLS rows.
+//                           from all rows), and the GEMMs around it run on the B CLS rows.  aloe_attn_kernel<true> is the training form (aloe_train.hip): every
+//                           row a query, the row log-sum-exp kept, dropout on P.
 //                           LDS per workgroup: K 2 x 256 x 80 B = 40 KB, V^T 2 x 32 x 528 B = 33 KB, key bias 1 KB: 74 KB of the 160 KB of a CU -- two
 //                           workgroups (eight waves) share a CU.
 //   aloe_head_kernel        one workgroup per sequence, plain f32: row 0 in LDS, a wave per hidden unit (lanes stride over k, sf_wave_sum), a wave per
@@ -34,6 +35,8 @@
 
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "train_blocks.h"
+#include "dropout_mask.h"
 
 namespace {
 
@@ -80,7 +83,7 @@ struct AlEmbed {
   const float *cls, *pos;      // [d], [L][d]
   const float *Wq, *table;     // q_in_proj.weight [d][E + 4] (its type columns E, E + 1), P [vocab][d]
   const int* tokens;           // [B][text_len]
-  int vocab, E, question_len, mc;
+  int vocab, E, question_len, mc_from;   // sequences b >= mc_from are multiple choice
   float* x;                    // [B][L][d]
   int B, T, N, C, text_len, d;
   long long rows;              // B T N
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(AL_THREADS) void aloe_embed_kernel(const AlEmbed a)
     for (int idx = tid; idx < a.text_len * d; idx += AL_THREADS) {
       const int j = idx / d, c = idx - j * d, row = 1 + TN + j;
       const int tok = a.tokens[(long long)b * a.text_len + j];
-      const int type = (a.mc && j < a.question_len) ? 0 : 1;   // cls_token / mc_choice_token = [0 1], mc_question_token = [1 0]
+      const int type = (b >= a.mc_from && j < a.question_len) ? 0 : 1;   // cls_token / mc_choice_token = [0 1], mc_question_token = [1 0]
       const float p = (tok >= 0 && tok < a.vocab) ? a.table[(long long)tok * d + c] : 0.f;
       xb[(long long)row * d + c] = (p + a.Wq[(long long)c * (a.E + 4) + a.E + type]) + a.pos[(long long)row * d + c];
     }
@@ -175,8 +178,12 @@ __global__ __launch_bounds__(AL_THREADS) void aloe_embed_kernel(const AlEmbed a)
 }
 
 // qkv [B L][3 d] (q | k | v, head h at columns h hd ..) -> rows [0, nq) of every sequence of out [B L][d]; pad [B][text_len], 1 = a padded text position (token 1 + TN + j)
+// TRAIN (aloe_train.hip): also lse [B][heads][L] = the row's log-sum-exp of the scaled, biased scores, and with thresh != 0 the dropout of
+// nn.MultiheadAttention on P before P V: element ((b heads + h) L + query) L + key of the site-0 mask (dropout_mask.h), kept values * inv_keep.
+template <bool TRAIN>
 __global__ __launch_bounds__(AL_THREADS) void aloe_attn_kernel(const float* __restrict__ qkv, const unsigned char* __restrict__ pad, float* __restrict__ out,
-                                                               int L, int nq, int text0, int text_len, int d, int hd, float scale) {
+                                                               int L, int nq, int text0, int text_len, int d, int hd, float scale, float* __restrict__ lse,
+                                                               uint32_t sseed, uint32_t thresh, float inv_keep) {
   extern __shared__ __attribute__((aligned(16))) char al_smem[];
   __bf16* Kh = reinterpret_cast<__bf16*>(al_smem);
   __bf16* Kl = Kh + AL_MAXL * AL_KP;
@@ -259,13 +266,28 @@ __global__ __launch_bounds__(AL_THREADS) void aloe_attn_kernel(const float* __re
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.0f / sum;
+    if constexpr (TRAIN) {
+      const int row = qt * 16 + l15;
+      if (q == 0 && row < L) lse[((long long)b * gridDim.x + h) * L + row] = m + logf(sum);
+    }
     // P V: contraction slot j of lane group q in step s is key 32 s + 4 q + j (j < 4) or 32 s + 16 + 4 q + j - 4: what the lane already holds
     f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int s = 0; s < AL_KT / 2; ++s)
       if (2 * s < nkt) {
         bf16x8 ph, pl;
-        sf_split8(acc[2 * s] * inv, acc[2 * s + 1] * inv, ph, pl);
+        f32x4 p0 = acc[2 * s] * inv, p1 = acc[2 * s + 1] * inv;
+        if constexpr (TRAIN) {
+          if (thresh) {
+            const uint32_t e0 = (uint32_t)((((long long)b * gridDim.x + h) * L + qt * 16 + l15) * L + s * 32 + 4 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              p0[e] = sf_keep(sseed, e0 + e, thresh) ? p0[e] * inv_keep : 0.f;
+              p1[e] = sf_keep(sseed, e0 + 16 + e, thresh) ? p1[e] * inv_keep : 0.f;
+            }
+          }
+        }
+        sf_split8(p0, p1, ph, pl);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
           if (dt * 16 < hd) {
@@ -445,6 +467,33 @@ inline bool al_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
   "1 <= num_slots <= 16, slot_size a multiple of 32 in [32, 256], T >= 1, text_len >= 1, 1 + T * num_slots + text_len <= 256, d_model = heads * "    \
   "head_dim <= 256 and a multiple of 4, head_dim even in [4, 32], ffn a multiple of 64 in [64, 1024], 1 <= num_layers <= 32"
 
+// the token rows [B][L][d] of a batch whose sequences b >= mc_from are multiple choice (arguments validated by the caller)
+int sf_aloe_embed_ex(const sf_aloe* m, const float* slots, long long stride_v, long long stride_t, int V, int T_all, const int* video_index, const int* start,
+                     int frame_offset, const int* tokens, int mc_from, float* x, int B, hipStream_t st) {
+  AlEmbed a;
+  a.slots = slots; a.stride_v = stride_v; a.stride_t = stride_t; a.V = V; a.T_all = T_all; a.video_index = video_index; a.start = start;
+  a.frame_offset = frame_offset; a.Wv = m->vision_w; a.bv = m->vision_b; a.cls = m->cls; a.pos = m->pos; a.Wq = m->q_in_proj_w; a.table = m->text_table;
+  a.tokens = tokens; a.vocab = m->vocab; a.E = m->emb_dim; a.question_len = m->question_len; a.mc_from = mc_from; a.x = x;
+  a.B = B; a.T = m->T; a.N = m->num_slots; a.C = m->slot_size; a.text_len = m->text_len; a.d = m->d_model;
+  a.rows = (long long)B * a.T * a.N;
+  a.ntiles = (int)((a.rows + AL_ROWS - 1) / AL_ROWS);
+  const size_t lds = al_embed_lds(a.C);
+  SF_TRY(sf_ensure_dyn_lds((const void*)aloe_embed_kernel, lds));
+  hipLaunchKernelGGL(aloe_embed_kernel, dim3((unsigned)(a.ntiles + B)), dim3(AL_THREADS), lds, st, a);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
+// the attention launch of a training layer: every row a query; lse [B][heads][L]; thresh 0: no mask is evaluated
+int sf_aloe_attn_train_ex(const float* qkv, const unsigned char* pad, float* out, float* lse, int B, int L, int text0, int text_len, int d, int heads,
+                          uint32_t sseed, uint32_t thresh, float inv_keep, hipStream_t st) {
+  SF_TRY(sf_ensure_dyn_lds((const void*)aloe_attn_kernel<true>, AL_ATTN_LDS));
+  const int hd = d / heads;
+  hipLaunchKernelGGL(aloe_attn_kernel<true>, dim3((unsigned)heads, (unsigned)B), dim3(AL_THREADS), AL_ATTN_LDS, st, qkv, pad, out, L, L, text0, text_len, d, hd,
+                     1.0f / sqrtf((float)hd), lse, sseed, thresh, inv_keep);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" {
 
 int sf_aloe_ok(int num_slots, int slot_size, int T, int text_len, int d_model, int num_heads, int ffn, int num_layers) {
@@ -503,24 +552,15 @@ int sf_aloe_fwd_f32(const sf_aloe* m, const float* slots, long long stride_v, lo
   float* qkv = att + (size_t)M * d;
   float* hid = qkv + (size_t)M * 3 * d;
   hipStream_t st = (hipStream_t)stream;
-  AlEmbed a;
-  a.slots = slots; a.stride_v = stride_v; a.stride_t = stride_t; a.V = V; a.T_all = T_all; a.video_index = video_index; a.start = start;
-  a.frame_offset = frame_offset; a.Wv = m->vision_w; a.bv = m->vision_b; a.cls = m->cls; a.pos = m->pos; a.Wq = m->q_in_proj_w; a.table = m->text_table;
-  a.tokens = tokens; a.vocab = m->vocab; a.E = m->emb_dim; a.question_len = m->question_len; a.mc = multiple_choice ? 1 : 0; a.x = x;
-  a.B = B; a.T = T; a.N = N; a.C = C; a.text_len = TL; a.d = d;
-  a.rows = (long long)B * T * N;
-  a.ntiles = (int)((a.rows + AL_ROWS - 1) / AL_ROWS);
-  const size_t lds = al_embed_lds(C);
-  SF_TRY(sf_ensure_dyn_lds((const void*)aloe_embed_kernel, lds));
-  SF_TRY(sf_ensure_dyn_lds((const void*)aloe_attn_kernel, AL_ATTN_LDS));
-  hipLaunchKernelGGL(aloe_embed_kernel, dim3((unsigned)(a.ntiles + B)), dim3(AL_THREADS), lds, st, a);
-  SF_CHECK_LAUNCH();
+  SF_TRY(sf_aloe_embed_ex(m, slots, stride_v, stride_t, V, T_all, video_index, start, frame_offset, tokens, multiple_choice ? 0 : B, x, B, st));
+  SF_TRY(sf_ensure_dyn_lds((const void*)aloe_attn_kernel<false>, AL_ATTN_LDS));
   const float scale = 1.0f / sqrtf((float)hd);
   for (int l = 0; l < nl; ++l) {
     const sf_tfm_layer& w = m->layers[l];
     if (l < nl - 1) {
       SF_TRY(sf_linear_ex(x, sf_rows(d), w.in_proj_w, w.in_proj_b, w.norm1_g, w.norm1_b, 1e-5f, nullptr, sf_rows(3 * d), 0, qkv, sf_rows(3 * d), M, 3 * d, d, 0, st));
-      hipLaunchKernelGGL(aloe_attn_kernel, dim3((unsigned)nh, (unsigned)B), dim3(AL_THREADS), AL_ATTN_LDS, st, qkv, pad_mask, att, L, L, 1 + T * N, TL, d, hd, scale);
+      hipLaunchKernelGGL(aloe_attn_kernel<false>, dim3((unsigned)nh, (unsigned)B), dim3(AL_THREADS), AL_ATTN_LDS, st, qkv, pad_mask, att, L, L, 1 + T * N, TL, d, hd, scale,
+                         (float*)nullptr, 0u, 0u, 1.f);
       SF_CHECK_LAUNCH();
       SF_TRY(sf_linear_ex(att, sf_rows(d), w.out_proj_w, w.out_proj_b, nullptr, nullptr, 0.f, x, sf_rows(d), 0, y, sf_rows(d), M, d, d, 0, st));
       SF_TRY(sf_linear_ex(y, sf_rows(d), w.lin1_w, w.lin1_b, w.norm2_g, w.norm2_b, 1e-5f, nullptr, sf_rows(ffn), 0, hid, sf_rows(ffn), M, ffn, d, 1, st));
@@ -532,7 +572,8 @@ int sf_aloe_fwd_f32(const sf_aloe* m, const float* slots, long long stride_v, lo
     const SfRowMap kv_out = SfRowMap{0, 0, 3 * d, d};
     SF_TRY(sf_linear_ex(x, sf_rows(d), w.in_proj_w + (size_t)d * d, w.in_proj_b + d, w.norm1_g, w.norm1_b, 1e-5f, nullptr, kv_out, 0, qkv, kv_out, M, 2 * d, d, 0, st));
     SF_TRY(sf_linear_ex(x, sf_rows(L * d), w.in_proj_w, w.in_proj_b, w.norm1_g, w.norm1_b, 1e-5f, nullptr, sf_rows(3 * d * L), 0, qkv, sf_rows(3 * d * L), B, d, d, 0, st));
-    hipLaunchKernelGGL(aloe_attn_kernel, dim3((unsigned)nh, (unsigned)B), dim3(AL_THREADS), AL_ATTN_LDS, st, qkv, pad_mask, att, L, 1, 1 + T * N, TL, d, hd, scale);
+    hipLaunchKernelGGL(aloe_attn_kernel<false>, dim3((unsigned)nh, (unsigned)B), dim3(AL_THREADS), AL_ATTN_LDS, st, qkv, pad_mask, att, L, 1, 1 + T * N, TL, d, hd, scale,
+                       (float*)nullptr, 0u, 0u, 1.f);
     SF_CHECK_LAUNCH();
     SF_TRY(sf_linear_ex(att, sf_rows(L * d), w.out_proj_w, w.out_proj_b, nullptr, nullptr, 0.f, x, sf_rows(L * d), 0, y, sf_rows(L * d), B, d, d, 0, st));
     SF_TRY(sf_linear_ex(y, sf_rows(L * d), w.lin1_w, w.lin1_b, w.norm2_g, w.norm2_b, 1e-5f, nullptr, sf_rows(ffn), 0, hid, sf_rows(ffn), B, ffn, d, 1, st));

@@ -296,14 +296,16 @@ inline void launch_reduce_partials(const float* partial, float* out, int G, long
 // reads per plane and k16 step instead of eight scalar reads + a conversion chain.  Row pitch 192 bytes: the four rows x two 16-column groups a
 // half-wave touches per read land on disjoint banks.
 #define TN_PB 192
-template <int MODE>   // 0: hi*hi + hi*lo + lo*hi + lo*lo, 1: without lo*lo (split-bf16), 2: hi*hi only (single-pass bf16)
+// EDGE: N and K multiples of 4 only -- the tiles of the last tile row / column load zeros past the matrix (a float4 lies inside or outside as a whole) and
+// store inside it; the arithmetic of an interior element is that of the plain form.
+template <int MODE, bool EDGE = false>   // 0: hi*hi + hi*lo + lo*hi + lo*lo, 1: without lo*lo (split-bf16), 2: hi*hi only (single-pass bf16)
 __global__ __launch_bounds__(256) void grad_gemm_tn_kernel(const float* __restrict__ Y, const float* __restrict__ X,
                                                            float* __restrict__ partial, long long rows, int rps, int N,
                                                            int K) {
   constexpr int PT = 32 * TN_PB, YH = 0, YL = PT, XH = 2 * PT, XL = 3 * PT;
   __shared__ __attribute__((aligned(16))) char tsm[4 * PT + 64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tk = K / 64;
+  const int tk = EDGE ? (K + 63) / 64 : K / 64;
   const int n0 = (blockIdx.x / tk) * 64, k0 = (blockIdx.x % tk) * 64;
   const long long r0 = (long long)blockIdx.y * rps;
   const long long r1 = r0 + rps < rows ? r0 + rps : rows;
@@ -317,14 +319,15 @@ __global__ __launch_bounds__(256) void grad_gemm_tn_kernel(const float* __restri
   const float* Yb = Y + r0 * N + n0 + lc;
   const float* Xb = X + r0 * K + k0 + lc;
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const bool yin = !EDGE || n0 + lc < N, xin = !EDGE || k0 + lc < K;   // (EDGE: this thread's float4 column lies inside the matrix)
   float4 py0 = zero4, py1 = zero4, px0 = zero4, px1 = zero4;
   if (lr < nrows) {
-    py0 = *reinterpret_cast<const float4*>(Yb + (long long)lr * N);
-    px0 = *reinterpret_cast<const float4*>(Xb + (long long)lr * K);
+    if (yin) py0 = *reinterpret_cast<const float4*>(Yb + (long long)lr * N);
+    if (xin) px0 = *reinterpret_cast<const float4*>(Xb + (long long)lr * K);
   }
   if (lr + 16 < nrows) {
-    py1 = *reinterpret_cast<const float4*>(Yb + (long long)(lr + 16) * N);
-    px1 = *reinterpret_cast<const float4*>(Xb + (long long)(lr + 16) * K);
+    if (yin) py1 = *reinterpret_cast<const float4*>(Yb + (long long)(lr + 16) * N);
+    if (xin) px1 = *reinterpret_cast<const float4*>(Xb + (long long)(lr + 16) * K);
   }
   auto stage = [&](const float4 v, int hoff, int loff, int row) {
     unsigned h0, l0, h1, l1;
@@ -343,12 +346,12 @@ __global__ __launch_bounds__(256) void grad_gemm_tn_kernel(const float* __restri
     py0 = py1 = px0 = px1 = zero4;
     const int ra = rb + 32 + lr;
     if (ra < nrows) {
-      py0 = *reinterpret_cast<const float4*>(Yb + (long long)ra * N);
-      px0 = *reinterpret_cast<const float4*>(Xb + (long long)ra * K);
+      if (yin) py0 = *reinterpret_cast<const float4*>(Yb + (long long)ra * N);
+      if (xin) px0 = *reinterpret_cast<const float4*>(Xb + (long long)ra * K);
     }
     if (ra + 16 < nrows) {
-      py1 = *reinterpret_cast<const float4*>(Yb + (long long)(ra + 16) * N);
-      px1 = *reinterpret_cast<const float4*>(Xb + (long long)(ra + 16) * K);
+      if (yin) py1 = *reinterpret_cast<const float4*>(Yb + (long long)(ra + 16) * N);
+      if (xin) px1 = *reinterpret_cast<const float4*>(Xb + (long long)(ra + 16) * K);
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -366,7 +369,7 @@ __global__ __launch_bounds__(256) void grad_gemm_tn_kernel(const float* __restri
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int n = n0 + wn + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    out[(long long)n * K + k0 + wk + (lane & 31)] = acc[r];
+    if (!EDGE || (n < N && k0 + wk + (lane & 31) < K)) out[(long long)n * K + k0 + wk + (lane & 31)] = acc[r];
   }
 }
 // ---- host side ----
@@ -404,6 +407,29 @@ int sf_grad_weight_ex(const float* Y, const float* X, float* dW, long long rows,
   if (splits > 1) {
     const long long n4 = (long long)N * K / 4;
     launch_reduce_partials(partial, dW, splits, n4, st);
+    SF_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// The same contraction at N, K multiples of 4 (the Aloe reasoner: 144, 432, 130 ...): the edge-tile form, split-bf16 whatever the process precision;
+// the row split and the fixed-order reduction are those of sf_grad_weight_ex.  dW 16-byte aligned when the rows are split.
+size_t sf_grad_partial_edge_floats(long long rows, int N, int K) {
+  const size_t a = (size_t)tn_splits_edge(rows, N, K) * N * K;
+  const size_t b = sf_colsum_partial_floats(N > K ? N : K);
+  return a > b ? a : b;
+}
+int sf_grad_weight_edge_ex(const float* Y, const float* X, float* dW, long long rows, int N, int K, float* partial, hipStream_t st) {
+  SF_REQUIRE(N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, "edge weight-gradient contraction needs multiples of 4");
+  const int splits = tn_splits_edge(rows, N, K);
+  int rps = (int)((rows + splits - 1) / splits);
+  rps = (rps + 31) & ~31;
+  float* dst = splits == 1 ? dW : partial;
+  const dim3 grid(((N + 63) / 64) * ((K + 63) / 64), splits);
+  hipLaunchKernelGGL((grad_gemm_tn_kernel<1, true>), grid, dim3(256), 0, st, Y, X, dst, rows, rps, N, K);
+  SF_CHECK_LAUNCH();
+  if (splits > 1) {
+    launch_reduce_partials(partial, dW, splits, (long long)N * K / 4, st);
     SF_CHECK_LAUNCH();
   }
   return 0;
@@ -456,6 +482,11 @@ int sf_ln_bwd_ex(const float* x, const float* dy, const float* gamma, const floa
 }
 int sf_transpose_ex(const float* in, float* out, int R, int Cn, hipStream_t st) {
   hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(Cn, 32), cdiv(R, 32)), dim3(256), 0, st, in, out, R, Cn);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
+int sf_relu_dropout_bwd_ex(float* dh, const float* hdn, long long n, float inv_keep, hipStream_t st) {
+  hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, dh, hdn, n / 4, inv_keep);
   SF_CHECK_LAUNCH();
   return 0;
 }

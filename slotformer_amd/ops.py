@@ -5,7 +5,7 @@ current stream.  There is no CPU path.
 """
 import torch
 
-from ._call import ptr, scratch, stream
+from ._call import ptr, require_device, scratch, stream
 from ._lib import lib, check
 
 
@@ -1007,3 +1007,129 @@ def aloe_score(cls_logits=None, cls_labels=None, mc_logits=None, mc_labels=None,
     check(lib().sf_aloe_score_f32(ptr(cls_logits), ptr(cls_labels), B1, A, ptr(mc_logits), ptr(mc_labels), ptr(mc_flag), Bn, ptr(mc_subtype), Q, ptr(losses),
                                   ques.data_ptr() if Q else None, ptr(counts), stream()))
     return losses, ques, counts
+
+
+# ---- training of the Aloe reasoner (csrc/aloe_train.hip) -----------------------------------------------------------------------------------------
+ALOE_LAYER_FIELDS = PHYRE_LAYER_FIELDS
+
+
+def aloe_train_ok(num_slots, slot_size, T, text_len, d_model, num_heads, ffn, num_layers):
+    """Whether the Aloe training kernels take these shapes (`sf_aloe_train_ok`: what `aloe_ok` accepts; no device needed)."""
+    return bool(lib().sf_aloe_train_ok(int(num_slots), int(slot_size), int(T), int(text_len), int(d_model), int(num_heads), int(ffn), int(num_layers)))
+
+
+def aloe_grad_layout(slot_size, L, d_model, ffn, num_layers, vocab, emb_dim, mlp_hidden, num_answers):
+    """[(name, numel)] of the flat gradient buffer `aloe_train_bwd` writes -- the order of `train.aloe_parameters`: CLS, pos_enc,
+    vision_in_proj.weight / .bias, q_in_proj.weight / .bias, each layer's twelve leaves (ALOE_LAYER_FIELDS), the first linear of both answer MLPs,
+    then the leaves whose size need not be a multiple of four: q_embedding, cls_answer_mlp.2, mc_answer_mlp.2.  Every leaf up to and including the
+    layers' starts on a multiple of four floats (d_model is one)."""
+    d, f, H, A, E = int(d_model), int(ffn), int(mlp_hidden), int(num_answers), int(emb_dim)
+    out = [('cls', d), ('pos', int(L) * d), ('vision_w', d * (int(slot_size) + 2)), ('vision_b', d), ('q_in_proj_w', d * (E + 4)), ('q_in_proj_b', d)]
+    sizes = (d, d, 3 * d * d, 3 * d, d * d, d, d, d, f * d, f, d * f, d)
+    for i in range(int(num_layers)):
+        out += [(f'layers.{i}.{n}', k) for n, k in zip(ALOE_LAYER_FIELDS, sizes)]
+    return out + [('cls_w1', H * d), ('cls_b1', H), ('mc_w1', H * d), ('mc_b1', H), ('q_embedding', int(vocab) * E), ('cls_w2', A * H), ('cls_b2', A),
+                  ('mc_w2', H), ('mc_b2', 1)]
+
+
+def _aloe_layout_of(model):
+    L = 1 + model.T * model.num_slots + model.text_len
+    return aloe_grad_layout(model.slot_size, L, model.d_model, model.ffn_dim, model.num_layers, model.vocab, model.emb_dim, model.mlp_hidden,
+                            model.num_answers)
+
+
+def _aloe_train_args(model, slots, batch):
+    """batch: dict(tokens [B, text_len], pad_mask [B, text_len], B1 -- the first B1 sequences are descriptive, the others choices --, video_index
+    [B] or None, start [B] or None, frame_offset) -> the checked device tensors."""
+    slots, T_all = _readout_slots(slots, None)
+    dev = slots.device
+    if tuple(slots.shape[2:]) != (model.num_slots, model.slot_size):
+        raise ValueError(f'slotformer_amd: slots are [V, T, {model.num_slots}, {model.slot_size}], got {tuple(slots.shape)}')
+    tokens = torch.as_tensor(batch['tokens'], device=dev).to(torch.int32).contiguous()
+    pad = torch.as_tensor(batch['pad_mask'], device=dev).to(torch.uint8).contiguous()
+    if tokens.dim() != 2 or tokens.shape[1] != model.text_len or tuple(pad.shape) != tuple(tokens.shape):
+        raise ValueError(f'slotformer_amd: tokens and pad mask are [B, {model.text_len}], got {tuple(tokens.shape)} and {tuple(pad.shape)}')
+    B = tokens.shape[0]
+    B1 = int(batch['B1'])
+    if not 0 <= B1 <= B:
+        raise ValueError(f'slotformer_amd: B1 = {B1} descriptive sequences in a batch of {B}')
+    vidx, start = _index32(batch.get('video_index'), dev), _index32(batch.get('start'), dev)
+    for name, t in (('video_index', vidx), ('start', start)):
+        if t is not None and t.numel() != B:
+            raise ValueError(f'slotformer_amd: {name} holds one entry per batch entry ({B}), got {t.numel()}')
+    return slots, T_all, tokens, pad, B, B1, vidx, start, int(batch.get('frame_offset', 1))
+
+
+def aloe_train_fwd(model, slots, batch, p=0., seed=0, want_gates=False, ws=None):
+    """The training forward of the Aloe reasoner (`sf_aloe_train_fwd_f32`).  model: an `sf_aloe_model` (train.aloe_model); slots [V, T_all, N, C] read
+    in place; batch: see `_aloe_train_args`.  p, seed: the dropout rate and the seed of its masks.  ws: a uint8 workspace to reuse.
+    -> (cls_logits [B1, A], mc_logits [Bn], ws, gates, head_gates): the workspace holds what the backward reads; with want_gates the ReLU
+    decisions, uint8 [num_layers, B * L, ffn] and [B, mlp_hidden], else None."""
+    import ctypes as C
+    slots, T_all, tokens, pad, B, B1, vidx, start, offset = _aloe_train_args(model, slots, batch)
+    dev = slots.device
+    if int(lib().sf_aloe_train_workspace_bytes(C.byref(model), B)) == 0:
+        raise NotImplementedError(f'slotformer_amd: the Aloe reasoner has no training kernel for this model or batch of {B}: {ALOE_LIMITS}, '
+                                  '1 <= B <= 65535')
+    ws = scratch(lib().sf_aloe_train_workspace_bytes, C.byref(model), B, device=dev, reuse=ws)
+    L = 1 + model.T * model.num_slots + model.text_len
+    cls_logits = torch.empty(B1, model.num_answers, dtype=torch.float32, device=dev)
+    mc_logits = torch.empty(B - B1, dtype=torch.float32, device=dev)
+    gates = torch.empty(model.num_layers, B * L, model.ffn_dim, dtype=torch.uint8, device=dev) if want_gates else None
+    head_gates = torch.empty(B, model.mlp_hidden, dtype=torch.uint8, device=dev) if want_gates else None
+    check(lib().sf_aloe_train_fwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), slots.shape[0], T_all, ptr(vidx), ptr(start),
+                                      offset, ptr(tokens), ptr(pad), B1, B - B1, float(p), int(seed), ptr(cls_logits) if B1 else None,
+                                      ptr(mc_logits) if B > B1 else None, ptr(gates), ptr(head_gates), ws.data_ptr(), ws.numel(), stream()))
+    return cls_logits, mc_logits, ws, gates, head_gates
+
+
+def aloe_train_bwd(model, slots, batch, g_cls, g_mc, ws, p=0., seed=0, out=None):
+    """Every parameter gradient of the Aloe reasoner from g_cls [B1, A] and g_mc [Bn] = dL/dlogits and the workspace of `aloe_train_fwd` (same
+    slots, batch, p, seed): `sf_aloe_train_bwd_f32`.  The gradients are WRITTEN into one flat float32 buffer in `aloe_grad_layout` order (out: a
+    caller's buffer of that size, e.g. `FlatAdam.grad`).  -> the flat buffer."""
+    import ctypes as C
+    from ._lib import sf_aloe_grads, sf_tfm_layer_grads
+    slots, T_all, tokens, pad, B, B1, vidx, start, offset = _aloe_train_args(model, slots, batch)
+    layout = _aloe_layout_of(model)
+    n = sum(k for _, k in layout)
+    flat = torch.empty(n, dtype=torch.float32, device=slots.device) if out is None else out
+    if not (torch.is_tensor(flat) and flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous() and flat.numel() == n):
+        raise ValueError(f'slotformer_amd: the Aloe gradient buffer holds {n} contiguous float32 elements on the device')
+    g_cls = None if B1 == 0 else g_cls.detach().float().reshape(B1, model.num_answers).contiguous()
+    g_mc = None if B == B1 else g_mc.detach().float().reshape(B - B1).contiguous()
+    gs = sf_aloe_grads()
+    arr = (sf_tfm_layer_grads * model.num_layers)()
+    off = 0
+    for name, k in layout:
+        addr = flat.data_ptr() + 4 * off
+        if name.startswith('layers.'):
+            _, i, field = name.split('.')
+            setattr(arr[int(i)], field, addr)
+        else:
+            setattr(gs, name, addr)
+        off += k
+    gs.layers = C.cast(arr, C.POINTER(sf_tfm_layer_grads))
+    check(lib().sf_aloe_train_bwd_f32(C.byref(model), slots.data_ptr(), slots.stride(0), slots.stride(1), slots.shape[0], T_all, ptr(vidx), ptr(start),
+                                      offset, ptr(tokens), ptr(pad), B1, B - B1, ptr(g_cls), ptr(g_mc), C.byref(gs), float(p), int(seed), ws.data_ptr(),
+                                      ws.numel(), stream()))
+    return flat
+
+
+def aloe_score_grad(cls_logits, cls_labels, mc_logits, mc_labels, w_cls=1., w_mc=1., want_grad=True):
+    """One launch (`sf_aloe_score_grad_f32`): losses [2] = (mean cross-entropy of cls_logits [B1, A] against cls_labels, mean BCE-with-logits of
+    mc_logits [Bn] against mc_labels; 0 for an empty kind) and the gradient of w_cls * losses[0] + w_mc * losses[1] in the logits.
+    -> (losses, g_cls [B1, A], g_mc [Bn]); the gradients are None with want_grad=False."""
+    require_device(cls_logits, mc_logits, what='the logits')
+    dev = cls_logits.device
+    cls_logits = cls_logits.detach().float().contiguous()
+    mc_logits = mc_logits.detach().float().reshape(-1).contiguous()
+    B1, A = cls_logits.shape
+    Bn = mc_logits.numel()
+    cls_labels = torch.as_tensor(cls_labels, device=dev).reshape(B1).to(torch.int32).contiguous() if B1 else None
+    mc_labels = torch.as_tensor(mc_labels, device=dev).reshape(Bn).float().contiguous() if Bn else None
+    losses = torch.empty(2, dtype=torch.float32, device=dev)
+    g_cls = torch.empty_like(cls_logits) if want_grad else None
+    g_mc = torch.empty_like(mc_logits) if want_grad else None
+    check(lib().sf_aloe_score_grad_f32(ptr(cls_logits) if B1 else None, ptr(cls_labels), B1, A, ptr(mc_logits) if Bn else None, ptr(mc_labels), Bn,
+                                       float(w_cls), float(w_mc), ptr(losses), ptr(g_cls) if B1 else None, ptr(g_mc) if Bn else None, stream()))
+    return losses, g_cls, g_mc

@@ -6,7 +6,7 @@ import torch
 
 from .models import build_model, PHYREReadout
 from .models.readout import ACC_THRESHS
-from ..physion_vqa import batch_schedule   # (one rule for the batches of both readouts)
+from ..physion_vqa import batch_schedule, step_seed   # noqa: F401  (one rule for the batches and the dropout seeds of every fit)
 from .. import ops
 
 # phyre.SimulationStatus, as the simulation caches store it
@@ -24,11 +24,6 @@ def build_dataset(params, *a, **k):
 def build_method(*a, **k):
     raise NotImplementedError('the nerv trainer is outside the hot path (SURVEY.md 2.1 row 12); the training kernels of PHYREReadout are reached through '
                               'phyre_planning.fit / train.phyre_readout_with_grad; a trainer object is not built')
-
-
-def step_seed(seed, step):
-    """The dropout seed of optimiser step `step` of a `fit` run seeded with `seed`: the run's seed in the high word, the step in the low one."""
-    return ((int(seed) & 0xffffffff) << 32) | (int(step) & 0xffffffff)
 
 
 def fit(readout, slots, labels, epochs, batch_size=256, lr=1e-3, seed=0, warmup_steps_pct=0.1, sel=None):

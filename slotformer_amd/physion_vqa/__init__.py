@@ -28,6 +28,12 @@ def batch_schedule(num_videos, epochs, batch_size, seed):
     return [list(torch.randperm(int(num_videos), generator=gen).to(torch.int32).split(int(batch_size))) for _ in range(int(epochs))]
 
 
+def step_seed(seed, step):
+    """The dropout seed of optimiser step `step` of a `fit` run seeded with `seed`: the run's seed in the high word, the step in the low one
+    (one rule for every `fit` whose layers drop: phyre_planning, clevrer_vqa)."""
+    return ((int(seed) & 0xffffffff) << 32) | (int(step) & 0xffffffff)
+
+
 def _head(readout):
     return readout.linear1.weight, readout.linear1.bias, readout.linear2.weight, readout.linear2.bias
 

@@ -1464,3 +1464,132 @@ def phyre_readout_with_grad(readout, slots, sel=None, video_index=None, p=None, 
     if len(sel) != readout.T:
         raise ValueError(f'PHYREReadout: the frame table holds {readout.T} entries (len(sel_slots)), got {len(sel)}')
     return _PhyreReadout.apply(readout, slots, sel, video_index, float(p), int(seed), grad_out, *phyre_readout_parameters(readout))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The Aloe reasoner (clevrer_vqa/models/transformer.py) under autograd: ONE node over the two calls of csrc/aloe_train.hip
+# ---------------------------------------------------------------------------------------------------------------------
+def aloe_parameters(tm):
+    """The trainable leaves of a CLEVRERTransformerModel in bucket order -- the order `ops.aloe_grad_layout` lays the gradients out in: CLS, pos_enc,
+    vision_in_proj, q_in_proj, every layer's leaves, the first linear of both answer MLPs, then the leaves of odd size: q_embedding and the second
+    linear of both MLPs.  (The five id pairs are fixed: requires_grad False.)"""
+    ps = [tm.CLS, tm.transformer_encoder.pos_enc, tm.vision_in_proj.weight, tm.vision_in_proj.bias, tm.q_in_proj.weight, tm.q_in_proj.bias]
+    for layer in tm.transformer_encoder.layers:
+        ps += [_leaf(layer, n) for n in _LAYER_LEAVES]
+    return ps + [tm.cls_answer_mlp[0].weight, tm.cls_answer_mlp[0].bias, tm.mc_answer_mlp[0].weight, tm.mc_answer_mlp[0].bias, tm.q_embedding.weight,
+                 tm.cls_answer_mlp[2].weight, tm.cls_answer_mlp[2].bias, tm.mc_answer_mlp[2].weight, tm.mc_answer_mlp[2].bias]
+
+
+def aloe_model(tm, num_slots, T, text_len):
+    """The `sf_aloe_model` descriptor of a CLEVRERTransformerModel on the device for sequences of 1 + T * num_slots + text_len tokens: raw pointers
+    to its float32 parameters in their torch layouts.  -> (struct, keep): hold `keep` while the struct is in use.  The pointers follow the
+    parameters' storage, so build it after a FlatAdam has re-pointed them at its bucket."""
+    from ._lib import sf_aloe_model, sf_tfm_layer
+    from . import ops
+    td = tm.transformer_dict
+    if 1 + T * num_slots + text_len != tm.input_len:
+        raise ValueError(f'CLEVRERTransformerModel: 1 + {T} frames x {num_slots} slots + {text_len} text positions, the position table holds '
+                         f'{tm.input_len}')
+    if not (td['norm_first'] and ops.aloe_train_ok(num_slots, tm.vision_in_proj.in_features - 2, T, text_len, tm.d_model, td['num_heads'], td['ffn_dim'],
+                                                   td['num_layers'])):
+        raise NotImplementedError(f'CLEVRERTransformerModel({td!r}) on {num_slots} slots, {T} frames, {text_len} text positions has no training '
+                                  f'kernel: {ops.ALOE_LIMITS}')
+    keep = []
+
+    def dp(t):
+        t = t.detach()
+        if not t.is_cuda:
+            raise RuntimeError('slotformer_amd: CLEVRERAloe trains on a HIP device only; there is no CPU fallback')
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('slotformer_amd: CLEVRERAloe trains on contiguous float32 parameters')
+        keep.append(t)
+        return t.data_ptr()
+
+    m = sf_aloe_model()
+    m.num_slots, m.slot_size, m.T, m.text_len, m.question_len = num_slots, tm.vision_in_proj.in_features - 2, T, text_len, tm.question_len
+    m.d_model, m.num_heads, m.ffn_dim, m.num_layers = tm.d_model, td['num_heads'], td['ffn_dim'], td['num_layers']
+    m.vocab, m.emb_dim = tm.q_embedding.weight.shape
+    m.mlp_hidden, m.num_answers = tm.cls_answer_mlp[0].out_features, tm.num_answer_classes
+    m.cls, m.pos = dp(tm.CLS), dp(tm.transformer_encoder.pos_enc)
+    m.vision_w, m.vision_b = dp(tm.vision_in_proj.weight), dp(tm.vision_in_proj.bias)
+    m.q_embedding, m.q_in_proj_w, m.q_in_proj_b = dp(tm.q_embedding.weight), dp(tm.q_in_proj.weight), dp(tm.q_in_proj.bias)
+    arr = (sf_tfm_layer * td['num_layers'])()
+    for i, layer in enumerate(tm.transformer_encoder.layers):
+        for leaf, field in zip(_LAYER_LEAVES, _LAYER_FIELDS):
+            setattr(arr[i], field, dp(_leaf(layer, leaf)))
+    m.layers = C.cast(arr, C.POINTER(sf_tfm_layer))
+    for kind, mlp in (('cls', tm.cls_answer_mlp), ('mc', tm.mc_answer_mlp)):
+        for name, t in (('w1', mlp[0].weight), ('b1', mlp[0].bias), ('w2', mlp[2].weight), ('b2', mlp[2].bias)):
+            setattr(m, f'{kind}_{name}', dp(t))
+    keep.append(arr)
+    return m, keep
+
+
+def _aloe_model_cached(tm, num_slots, T, text_len):
+    """`aloe_model` kept in the module's plan cache (plans.py: it copies and pickles as empty, and `plans.invalidate` drops it) for as long as
+    the geometry and the storage of every parameter stay what they were: an optimiser that re-points the parameters, a .to(), a load into new
+    tensors give a new descriptor.  The descriptor holds pointers only, so a parameter's version does not enter the key."""
+    from . import plans
+    key = (num_slots, T, text_len) + tuple(p.data_ptr() for p in aloe_parameters(tm))
+    return plans.cached(tm, 'aloe_train_model', key, aloe_model, tm, num_slots, T, text_len)
+
+
+class _Aloe(torch.autograd.Function):
+    """(cls_logits [B1, A], mc_logits [Bn]) = CLEVRERTransformerModel(batch) as a single autograd node; the slots are frozen inputs."""
+
+    @staticmethod
+    def forward(ctx, tm, slots, batch, p, seed, grad_out, *params):
+        from . import ops
+        model, keep = _aloe_model_cached(tm, slots.shape[2], int(batch.get('num_frames') or slots.shape[1]), batch['tokens'].shape[-1])
+        cls_logits, mc_logits, ws, _, _ = ops.aloe_train_fwd(model, slots, batch, p=p, seed=seed)
+        ctx.keep = (tm, model, keep, slots, batch, p, seed, grad_out, ws, params)
+        return cls_logits, mc_logits
+
+    @staticmethod
+    def backward(ctx, g_cls, g_mc):
+        from . import ops
+        tm, model, keep, slots, batch, p, seed, grad_out, ws, params = ctx.keep
+        flat = ops.aloe_train_bwd(model, slots, batch, g_cls, g_mc, ws, p=p, seed=seed, out=grad_out)
+        ctx.keep = None
+        if grad_out is not None:   # the caller's bucket holds them: nothing for autograd to accumulate
+            return (None, ) * (6 + len(params))
+        tm.last_grad_bucket = flat
+        return (None, ) * 6 + tuple(g_ if ctx.needs_input_grad[6 + i] else None for i, g_ in enumerate(_split(flat, params)))
+
+
+def aloe_with_grad(tm, slots, batch, p=None, seed=None, grad_out=None):
+    """CLEVRERTransformerModel.forward under autograd: slots [V, T_all, N, C] on the device, batch = dict(tokens [B, text_len], pad_mask, B1 -- the
+    first B1 sequences are descriptive questions, the others the choices of multiple-choice ones --, video_index [B], start [B], frame_offset,
+    num_frames) -> (cls_logits [B1, A], mc_logits [Bn]), differentiable in every parameter.  One node over `sf_aloe_train_fwd_f32` /
+    `sf_aloe_train_bwd_f32`.  p: the dropout rate -- default the layers' own when tm.training, else 0; seed: the seed of the masks (default a
+    fresh one).  grad_out: a flat fp32 buffer laid out as FlatAdam's bucket over aloe_parameters(tm) (`FlatAdam.grad`): the backward writes the
+    gradients there -- then step with `FlatAdam.step(gathered=True)` -- and leaves `.grad` alone."""
+    require_device(slots, what='the slots')
+    if p is None:
+        p = float(tm.transformer_encoder.layers[0].dropout.p) if tm.training else 0.0
+    if seed is None:
+        seed = _new_seed() if p > 0 else 0
+    return _Aloe.apply(tm, slots, batch, float(p), int(seed), grad_out, *aloe_parameters(tm))
+
+
+class _AloeLoss(torch.autograd.Function):
+    """w_cls * cross-entropy + w_mc * BCE-with-logits on the score-gradient launch; its backward is the two gradients that launch wrote."""
+
+    @staticmethod
+    def forward(ctx, cls_logits, mc_logits, cls_labels, mc_labels, w_cls, w_mc):
+        from . import ops
+        losses, g_cls, g_mc = ops.aloe_score_grad(cls_logits, cls_labels, mc_logits, mc_labels, w_cls, w_mc)
+        ctx.save_for_backward(g_cls, g_mc)
+        ctx.mark_non_differentiable(losses)
+        return w_cls * losses[0] + w_mc * losses[1], losses
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_losses):
+        g_cls, g_mc = ctx.saved_tensors
+        return g_cls * d_loss, g_mc * d_loss, None, None, None, None
+
+
+def aloe_loss(cls_logits, mc_logits, cls_labels, mc_labels, w_cls=1., w_mc=1.):
+    """(w_cls * F.cross_entropy(cls_logits, cls_labels) + w_mc * F.binary_cross_entropy_with_logits(mc_logits, mc_labels), losses [2]) -- the
+    reference's training loss (transformer.py: loss_function; an empty kind counts 0) -- differentiable in both logits; one launch."""
+    return _AloeLoss.apply(cls_logits, mc_logits, cls_labels, mc_labels, float(w_cls), float(w_mc))
