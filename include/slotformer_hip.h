@@ -575,7 +575,8 @@ int sf_dvae_head_argmax_f32(const float* x, long long ld, const void* w_packed, 
  * logits [R,V] in MFMA accumulators only:
  *   lse[r] = log sum_v exp(W[v] . x[r]),  loss[r] = lse[r] - W[t_r] . x[r],  dx[r,:] = c_r (sum_v exp(W[v] . x[r] - lse[r]) W[v,:] - W[t_r,:]).
  * The target's logit (forward) and the one-hot (backward) are picked by comparing the swept word index with t_r, never by an address formed from
- * it: a target outside [0, V) matches no word -- loss[r] = lse[r], dx[r,:] = c_r sum_v p W[v,:] -- and reads nothing.  There is no gradient for W.
+ * it: a target outside [0, V) matches no word -- loss[r] = lse[r], dx[r,:] = c_r sum_v p W[v,:] -- and reads nothing.  The gradient of W is a launch
+ * of its own, sf_head_ce_wgrad_f32.
  * Arithmetic: split-bf16 (every f32 operand = bf16 hi + bf16 lo, three products, f32 accumulation) WHATEVER sf_set_precision says, as for the dVAE
  * tokens; the exponentials are summed against the running maximum; every sum in a fixed order, no atomics, no communication between workgroups: two
  * calls give the same bits, and a row's results do not depend on its place in the batch.
@@ -608,6 +609,17 @@ int sf_head_ce_fwd_f32(const float* x, long long ld, const void* w_packed, const
 int sf_head_ce_bwd_f32(const float* x, long long ld, const void* w_packed, const long long* target_i64, const short* target_i16,
                        const float* group_w, int group, const float* lse, const float* g, float* dx, long long ldx, long long R, int V, int K,
                        void* stream);
+/* The head's own gradient, for a head that is trained (STEVE):  dW[v,:] = sum_r c_r (exp(W[v] . x[r] - lse[r]) - [v == t_r]) x[r,:], again without
+ * the logits.  x, ld, w_packed, targets, group_w, group, lse, g as in the backward; dW [V,K] with row stride ldw >= K is OVERWRITTEN (R == 0: with
+ * zeros).  A launch of (slabs of 128 words) x (S row splits) workgroups keeps a wave's 32 words x K block of dW in accumulators over its split's
+ * rows and writes it to ws; a second launch adds the S blocks in index order.  S depends on (R, V) alone -- min(8, ceil(256 / slabs), tiles of 32
+ * rows), then the fewest splits of that run length -- never on the device, so equal inputs give equal bits everywhere.  ws: 16-byte aligned,
+ * sf_head_ce_wgrad_workspace_bytes(R, V, K) = S * V * K * 4 bytes (at most 8 blocks of dW whatever R is; needs no initial value); 0 for a shape
+ * sf_head_ce_ok refuses or an R outside [0, 2^29). */
+size_t sf_head_ce_wgrad_workspace_bytes(long long R, int V, int K);
+int sf_head_ce_wgrad_f32(const float* x, long long ld, const void* w_packed, const long long* target_i64, const short* target_i16,
+                         const float* group_w, const float* lse, const float* g, float* dW, long long ldw, long long R, int V, int K, int group,
+                         void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Physion VQA readout on rolled-out slots (physion_vqa/models/readout.py; csrc/physion_readout.hip) -------------------------------------------
  * logit[k][b] = max_t ( w2_k . agg_{i<j} ( W1_k cat(s_ti, s_tj) + b1_k ) + b2_k ) for a stack of K heads, agg = 0 max / 1 sum / 2 mean over the

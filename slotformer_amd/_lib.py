@@ -343,6 +343,8 @@ SIGNATURES = {
     'sf_head_ce_pack_weights_host': (I, [VP, VP, I, I]),
     'sf_head_ce_fwd_f32': (I, [FP, LL, VP, VP, VP, FP, I, FP, FP, VP, LL, I, I, VP, SZ, VP]),
     'sf_head_ce_bwd_f32': (I, [FP, LL, VP, VP, VP, FP, I, FP, FP, FP, LL, LL, I, I, VP]),
+    'sf_head_ce_wgrad_workspace_bytes': (SZ, [LL, I, I]),
+    'sf_head_ce_wgrad_f32': (I, [FP, LL, VP, VP, VP, FP, FP, FP, FP, LL, LL, I, I, I, VP, SZ, VP]),
     'sf_physion_readout_ok': (I, [I, I, I]),
     'sf_physion_readout_fwd_f32': (I, [FP, LL, LL, I, VP, FP, FP, FP, FP, FP, VP, FP, VP, I, I, I, I, I, I, I, VP]),
     'sf_physion_readout_bwd_workspace_bytes': (SZ, [I, I, I]),

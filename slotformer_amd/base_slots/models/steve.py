@@ -25,7 +25,15 @@ class SlotAttentionWMask(SlotAttention):
 
 class STEVE(StoSAVi):
     """STEVE (steve.py:76-351): SAVi's encoder side with mask-returning Slot Attention, plus the frozen dVAE tokenizer and
-    the slot-conditioned Transformer decoder that predicts its tokens."""
+    the slot-conditioned Transformer decoder that predicts its tokens.
+
+    `fused_token_loss` (False by default): set it to True and a training step computes the token loss from the decoder's hidden rows with
+    `train.head_cross_entropy(..., weight_grad=True)` -- head, cross-entropy and the head's own gradient without the logits [B*T*h*w, V] or their
+    gradient in memory.  The output dict of such a step holds `token_hidden` and no `pred_token_id`.  It applies only where the decoder runs under
+    autograd and `use_img_recon_loss` is False: the image loss draws its Gumbel-softmax sample from the logits, so with it the attribute is ignored
+    and the logits are formed as before.  Inference and evaluation are untouched."""
+
+    fused_token_loss = False
 
     DEFAULTS = dict(
         slot_dict=dict(num_slots=7, slot_size=128, slot_mlp_size=256, num_iterations=2),
@@ -135,7 +143,17 @@ class STEVE(StoSAVi):
         target_token_id = img_token_id.flatten(0, 1).long().contiguous()   # [B*T, h*w]
         in_slots = slots.flatten(0, 1)
         in_token_id = target_token_id[:, :-1].contiguous()
-        pred_token_id = self.trans_decoder(in_slots, in_token_id)
+        dec = self.trans_decoder
+        with_graph = torch.is_grad_enabled() and (in_slots.requires_grad or any(p.requires_grad for p in dec.parameters()))
+        if self.fused_token_loss and with_graph and not self.use_img_recon_loss:
+            # the decoder up to its final LayerNorm; calc_train_loss takes these rows through head + cross-entropy in one node, without the logits
+            from ... import train
+            hidden = train.slate_decoder_hidden(dec, in_slots, in_token_id)
+            if hidden.shape[1] != h * w:
+                hidden = hidden[:, -(h * w):]
+            out_dict.update({'token_hidden': hidden, 'target_token_id': target_token_id})
+            return out_dict
+        pred_token_id = dec(in_slots, in_token_id)
         if pred_token_id.shape[1] != h * w:   # (a no-op slice would still cost autograd a zero-filled copy of the logits)
             pred_token_id = pred_token_id[:, -(h * w):]
         out_dict.update({'pred_token_id': pred_token_id, 'target_token_id': target_token_id})
@@ -153,9 +171,14 @@ class STEVE(StoSAVi):
         return out_dict
 
     def calc_train_loss(self, data_dict, out_dict):
-        """Token cross-entropy of steve.py:339-351; differentiable when the logits carry a graph (row N1)."""
-        pred = out_dict['pred_token_id'].flatten(0, 1).contiguous()
+        """Token cross-entropy of steve.py:339-351; differentiable when the logits carry a graph (row N1).  An out_dict of the
+        `fused_token_loss` route holds the decoder's hidden rows in place of the logits: the loss and the gradients of the rows and of the head
+        come from `train.head_cross_entropy(..., weight_grad=True)`."""
         target = out_dict['target_token_id'].flatten(0, 1).contiguous()
+        if 'token_hidden' in out_dict:
+            from ... import train
+            return {'token_recon_loss': train.head_cross_entropy(out_dict['token_hidden'], self.trans_decoder.head, target, weight_grad=True)[0]}
+        pred = out_dict['pred_token_id'].flatten(0, 1).contiguous()
         if pred.requires_grad:
             from ... import train
             loss_dict = {'token_recon_loss': train.token_cross_entropy(pred, target)}

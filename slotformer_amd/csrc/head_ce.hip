@@ -15,6 +15,16 @@
 //                   registers 8 c .. 8 c + 7, word(c, kk, j) = 16 c + 8 (j >> 2) + 4 kk + (j & 3), and the SECOND packed copy of W holds its fragments
 //                   in exactly that order.  A wave's part of dx (K / 32 accumulator blocks) stays in its registers through the sweep; the four parts
 //                   meet once, in a fixed order, through the LDS the rows were staged in, and wave 0 writes 128 contiguous bytes of two rows per store.
+//   hc_wgrad_kernel dW[v,:] = sum_r c_r (p[r,v] - [v == t_r]) x[r,:], the gradient of a head that is trained (STEVE): hc_bwd_kernel with the two operands
+//                   in each other's place.  A wave owns 32 WORDS: their fragments of packed copy A stay in its registers as the B operand of the
+//                   first product and its 32 x K block of dW in K / 32 accumulator blocks, while it sweeps the rows in tiles of 32, staged once per
+//                   workgroup (four waves: a slab of 128 words) as bf16 planes in two LDS buffers -- the loads of the next tile are issued before the
+//                   products of the current one.  D1[row][word] leaves the lane with ONE word and sixteen rows, whose lse, target and c_r come from
+//                   384 bytes of LDS staged with the tile; registers 8 c .. 8 c + 7 of c_r (exp(D1 - lse_r) - [word == t_r]) are the A operand of
+//                   k-step c of D3[word][feature] += P x, and x read DOWN the staged rows in the accumulator's row order (pl_rd_tr, kstep 4, second 8)
+//                   is its B operand: no second staging, no second packed copy.  The grid is slabs x S row splits; S is a function of (R, V) alone
+//                   (hc_wg_splits), capped at 8, so that equal shapes split equally on every device.  Each split writes its [V][K] block to the workspace.
+//   hc_wgrad_sum_kernel adds the S blocks in index order into dW.
 //
 // Arithmetic: split-bf16 -- every f32 operand is bf16 hi + bf16 lo, three products a_hi.b_lo + a_lo.b_hi + a_hi.b_hi with f32 accumulation -- WHATEVER
 // sf_set_precision says, as in dvae_tokens.hip: the token loss has one definition.  Every sum has a fixed order, there is no atomic and no
@@ -309,6 +319,167 @@ int hc_launch_bwd(const float* x, long long ld, const uint4* wp, long long n8, c
   return 0;
 }
 
+// ---- the head's own gradient ---------------------------------------------------------------------------------------------------------------------
+constexpr int HC_WG_ROWS = 32;       // rows of a tile of the weight gradient's sweep: one MFMA block
+constexpr int HC_WG_MAX_SPLIT = 8;   // most row splits of a launch: the workspace is at most this many [V][K] blocks
+constexpr int HC_WG_FILL = 256;      // workgroups a launch aims at.  A constant, not the device's CU count: equal shapes split equally everywhere
+
+// Row splits of a launch over R rows and V words: S0 = min(HC_WG_MAX_SPLIT, ceil(HC_WG_FILL / slabs), tiles) runs of ceil(tiles / S0) tiles each, and S
+// the number of such runs that hold a tile.  The kernel finds the run length again as ceil(tiles / S).
+inline int hc_wg_splits(long long R, int V) {
+  const long long tiles = hc_tiles(R, HC_WG_ROWS), slabs = (V + HC_VB * HC_WAVES - 1) / (HC_VB * HC_WAVES);
+  long long s0 = (HC_WG_FILL + slabs - 1) / slabs;
+  if (s0 > HC_WG_MAX_SPLIT) s0 = HC_WG_MAX_SPLIT;
+  if (s0 > tiles) s0 = tiles;
+  if (s0 < 1) return 1;
+  const long long per = (tiles + s0 - 1) / s0;
+  return (int)((tiles + per - 1) / per);
+}
+
+template <int KB>   // K / 32
+__global__ __launch_bounds__(64 * HC_WAVES) void hc_wgrad_kernel(const float* __restrict__ x, long long ld, const uint4* __restrict__ wa_hi,
+                                                                 const uint4* __restrict__ wa_lo, const long long* __restrict__ t64,
+                                                                 const short* __restrict__ t16, const float* __restrict__ group_w, int group,
+                                                                 const float* __restrict__ lse, const float* __restrict__ g, float* __restrict__ part,
+                                                                 long long R, int V) {
+  extern __shared__ __attribute__((aligned(16))) char hc_lds[];
+  __shared__ __attribute__((aligned(16))) float sl[2][HC_WG_ROWS], sc[2][HC_WG_ROWS];
+  __shared__ __attribute__((aligned(16))) int stg[2][HC_WG_ROWS];
+  constexpr int K = 32 * KB, KS = 2 * KB, k8 = K / 8, pitch = 2 * K + 16, loff = HC_WG_ROWS * pitch, buf = 2 * loff;
+  constexpr int units = HC_WG_ROWS * k8, U = (units + 64 * HC_WAVES - 1) / (64 * HC_WAVES);   // 16-byte column groups of a tile, and a thread's share
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int nvb = V / HC_VB, vb = (int)blockIdx.x * HC_WAVES + q;   // wave-uniform
+  // a wave past the last block works on that block again and stores nothing: it stages its share of every tile and meets every barrier
+  const int vbl = vb < nvb ? vb : nvb - 1;
+  const long long tiles = (R + HC_WG_ROWS - 1) / HC_WG_ROWS, per = (tiles + gridDim.y - 1) / gridDim.y;
+  const long long t0 = (long long)blockIdx.y * per, t1 = t0 + per < tiles ? t0 + per : tiles;
+  const float gs = g[0];
+  PlFrag wf[KS];   // the wave's 32 words as the B operand of the first product, for the whole sweep
+  {
+    const long long f0 = (long long)vbl * KS * 64 + lane;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      wf[ks].h = __builtin_bit_cast(bf16x8, wa_hi[f0 + ks * 64]);
+      wf[ks].l = __builtin_bit_cast(bf16x8, wa_lo[f0 + ks * 64]);
+    }
+  }
+  f32x16 acc[KB];
+#pragma unroll
+  for (int kfb = 0; kfb < KB; ++kfb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[kfb][i] = 0.f;
+  // a thread's share of the next tile on its way from memory to LDS: the loads are issued before the products of the current tile and land behind them
+  f32x4 pa[U], pb[U];
+  int mt = -1;
+  float ml = INFINITY, mc = 0.f;
+  auto fetch = [&](long long row0) {
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int u = tid + 64 * HC_WAVES * j, row = u / k8, c = u - row * k8;
+      pa[j] = f32x4{0.f, 0.f, 0.f, 0.f}, pb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (u < units && row0 + row < R) {   // a row past the end is a zero operand, never an address
+        const float* xp = x + (row0 + row) * ld + 8 * c;
+        pa[j] = *reinterpret_cast<const f32x4*>(xp);
+        pb[j] = *reinterpret_cast<const f32x4*>(xp + 4);
+      }
+    }
+    mt = -1, ml = INFINITY, mc = 0.f;   // a row past the end: c = 0, nothing added
+    const long long p = row0 + tid;
+    if (tid < HC_WG_ROWS && p < R) {
+      mt = hc_target(t64, t16, p, V);
+      ml = lse[p];
+      mc = gs * (group_w ? group_w[p / group] : 1.f);
+    }
+  };
+  auto put = [&](int b) {
+    char* dst = hc_lds + b * buf;
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const int u = tid + 64 * HC_WAVES * j, row = u / k8, c = u - row * k8;
+      if (u < units) {
+        bf16x8 hi, lo;
+        sf_split8(pa[j], pb[j], hi, lo);
+        *reinterpret_cast<bf16x8*>(dst + row * pitch + c * 16) = hi;
+        *reinterpret_cast<bf16x8*>(dst + loff + row * pitch + c * 16) = lo;
+      }
+    }
+    if (tid < HC_WG_ROWS) stg[b][tid] = mt, sl[b][tid] = ml, sc[b][tid] = mc;
+  };
+  if (t0 < t1) {   // uniform over the workgroup
+    fetch(t0 * HC_WG_ROWS);
+    put(0);
+  }
+  __syncthreads();
+  const int word = vbl * HC_VB + r;
+  for (long long t = t0; t < t1; ++t) {
+    const int cur = (int)(t - t0) & 1;
+    const char* tile = hc_lds + cur * buf;
+    if (t + 1 < t1) fetch((t + 1) * HC_WG_ROWS);
+    // D1[row][word]: the lane holds its word's logit of row MM_ROW(i, lane) in register i
+    f32x16 a1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) a1[i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) pl_mma(a1, pl_rd(tile, 0, loff, pitch, 0, 16 * ks, lane), wf[ks]);
+    // c_r (softmax - onehot), in place; a dropped row (c_r = 0) is an exact zero whatever its lse
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const f32x4 l4 = *reinterpret_cast<const f32x4*>(&sl[cur][8 * qd + 4 * h]);
+      const f32x4 c4 = *reinterpret_cast<const f32x4*>(&sc[cur][8 * qd + 4 * h]);
+      const int4 t4 = *reinterpret_cast<const int4*>(&stg[cur][8 * qd + 4 * h]);
+      const int tt[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int i = 4 * qd + j;
+        a1[i] = c4[j] != 0.f ? c4[j] * (__expf(a1[i] - l4[j]) - (word == tt[j] ? 1.f : 0.f)) : 0.f;
+      }
+    }
+    // D3[word][feature] += P x: registers 8 c .. 8 c + 7 are the A operand of k-step c (rows 16 c + 8 (j >> 2) + 4 h + (j & 3)), and x read down the
+    // tile's rows in that order is its B operand
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      PlFrag pf;
+      sf_split8(f32x8{a1[8 * c], a1[8 * c + 1], a1[8 * c + 2], a1[8 * c + 3], a1[8 * c + 4], a1[8 * c + 5], a1[8 * c + 6], a1[8 * c + 7]}, pf.h, pf.l);
+#pragma unroll
+      for (int kfb = 0; kfb < KB; ++kfb) pl_mma(acc[kfb], pf, pl_rd_tr(tile, 0, loff, pitch, 16 * c, 32 * kfb, lane, 4, 8));
+    }
+    if (t + 1 < t1) put(cur ^ 1);   // the other buffer: every wave left it before the barrier that ended the previous tile
+    __syncthreads();
+  }
+  if (vb >= nvb) return;
+  // block kfb: the lane holds feature 32 kfb + r and, in register i, word MM_ROW(i, lane) of the wave's 32
+  float* out = part + ((long long)blockIdx.y * V + (long long)vb * HC_VB) * K;
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+#pragma unroll
+    for (int kfb = 0; kfb < KB; ++kfb) out[MM_ROW(i, lane) * K + 32 * kfb + r] = acc[kfb][i];
+}
+
+// dW = the splits' partial blocks, added in index order
+__global__ __launch_bounds__(256) void hc_wgrad_sum_kernel(const float* __restrict__ part, int S, float* __restrict__ dW, long long ldw, long long n,
+                                                           int K) {
+  const long long idx = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;   // n and K are multiples of 4: the four elements share a row
+  if (idx >= n) return;
+  f32x4 a = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < S; ++s) a += *reinterpret_cast<const f32x4*>(part + s * n + idx);
+  const long long v = idx / K;
+  float* o = dW + v * ldw + (idx - v * K);
+  o[0] = a[0], o[1] = a[1], o[2] = a[2], o[3] = a[3];
+}
+
+template <int KB>
+int hc_launch_wgrad(const float* x, long long ld, const uint4* wp, long long n8, const long long* t64, const short* t16, const float* group_w, int group,
+                    const float* lse, const float* g, float* part, long long R, int V, int S, hipStream_t st) {
+  const size_t lds = 2 * hc_lds_bytes(32 * KB, HC_WG_ROWS);   // two buffers: at most 66 KiB
+  if (lds > 64 * 1024) SF_TRY(sf_ensure_dyn_lds((const void*)hc_wgrad_kernel<KB>, lds));
+  hipLaunchKernelGGL(hc_wgrad_kernel<KB>, dim3((unsigned)((V + HC_VB * HC_WAVES - 1) / (HC_VB * HC_WAVES)), (unsigned)S), dim3(64 * HC_WAVES), lds, st, x,
+                     ld, wp, wp + n8, t64, t16, group_w, group, lse, g, part, R, V);
+  SF_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 #define HC_SHAPE_MSG "K must be a multiple of 32 in [32, 256] and V a multiple of 32 in [32, 2^20]"
@@ -391,6 +562,42 @@ int sf_head_ce_bwd_f32(const float* x, long long ld, const void* w_packed, const
   }
 #undef HC_CASE
   return sf_set_err(-1, "invalid argument: sf_head_ce_bwd_f32: " HC_SHAPE_MSG, __FILE__, __LINE__);
+}
+
+size_t sf_head_ce_wgrad_workspace_bytes(long long R, int V, int K) {
+  return hc_ok(V, K) && R >= 0 && R < HC_MAX_R ? (size_t)hc_wg_splits(R, V) * V * K * sizeof(float) : 0;
+}
+
+int sf_head_ce_wgrad_f32(const float* x, long long ld, const void* w_packed, const long long* target_i64, const short* target_i16, const float* group_w,
+                         const float* lse, const float* g, float* dW, long long ldw, long long R, int V, int K, int group, void* ws, size_t ws_bytes,
+                         void* stream) {
+  SF_REQUIRE(x && w_packed && lse && g && dW && ws, "sf_head_ce_wgrad_f32: null pointer");
+  SF_REQUIRE((target_i64 != nullptr) != (target_i16 != nullptr), "sf_head_ce_wgrad_f32: exactly one of target_i64 and target_i16");
+  SF_REQUIRE(hc_ok(V, K), "sf_head_ce_wgrad_f32: " HC_SHAPE_MSG);
+  SF_REQUIRE(!target_i16 || V <= 32768, "sf_head_ce_wgrad_f32: int16 targets need V <= 32768");
+  SF_REQUIRE(ld >= K && ld % 4 == 0, "sf_head_ce_wgrad_f32: the row stride of x must be at least K and a multiple of 4");
+  SF_REQUIRE(ldw >= K, "sf_head_ce_wgrad_f32: the row stride of dW must be at least K");
+  SF_REQUIRE(R >= 0 && R < HC_MAX_R, "sf_head_ce_wgrad_f32: bad row count");
+  SF_REQUIRE(group >= 1 && R % group == 0, "sf_head_ce_wgrad_f32: group must be at least 1 and divide R");
+  SF_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w_packed & 15) == 0, "sf_head_ce_wgrad_f32: x and w_packed must be 16-byte aligned");
+  SF_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_bytes >= sf_head_ce_wgrad_workspace_bytes(R, V, K),
+             "sf_head_ce_wgrad_f32: needs a 16-byte aligned workspace of sf_head_ce_wgrad_workspace_bytes(R, V, K)");
+  hipStream_t st = (hipStream_t)stream;
+  const uint4* wp = static_cast<const uint4*>(w_packed);
+  const long long n = (long long)V * K, n8 = n / 8;
+  const int S = R > 0 ? hc_wg_splits(R, V) : 0;   // no rows: the sum of no blocks, zeros
+  float* part = static_cast<float*>(ws);
+  int rc = 0;
+#define HC_CASE(KB) \
+  case KB:          \
+    rc = hc_launch_wgrad<KB>(x, ld, wp, n8, target_i64, target_i16, group_w, group, lse, g, part, R, V, S, st); \
+    break;
+  if (S > 0) switch (K / 32) { HC_CASE(1) HC_CASE(2) HC_CASE(3) HC_CASE(4) HC_CASE(5) HC_CASE(6) HC_CASE(7) HC_CASE(8) }
+#undef HC_CASE
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(hc_wgrad_sum_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, part, S, dW, ldw, n, K);
+  SF_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // extern "C"

@@ -602,6 +602,25 @@ def head_ce_backward(x, w_packed, target, V, lse, g, group_w=None, group=1, out=
     return out
 
 
+def head_ce_wgrad(x, w_packed, target, V, lse, g, group_w=None, group=1, out=None):
+    """dW[v] = sum_r g * w(r) * (softmax(W x[r])[v] - [v == target[r]]) x[r], the head's own gradient with the logits recomputed from x and `lse`
+    (`sf_head_ce_wgrad_f32`); arguments as for `head_ce_backward`.  out: float32 [V, K] with unit column stride, OVERWRITTEN.  The workspace holds
+    at most eight [V, K] blocks, whatever R is."""
+    ld, R, K, t64, t16 = _head_ce_args(x, w_packed, target, group_w, group, V)
+    _chk(lse, g)
+    if lse.numel() != R or g.numel() != 1:
+        raise ValueError(f'slotformer_amd head_ce: lse has {R} elements and g one')
+    V = int(V)
+    if out is None:
+        out = torch.empty(V, K, device=x.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (V, K) and out.stride(1) == 1 and out.stride(0) >= K):
+        raise TypeError(f'slotformer_amd head_ce: out is a float32 [{V}, {K}] device tensor with unit column stride')
+    ws = scratch(lib().sf_head_ce_wgrad_workspace_bytes, R, V, K, device=x.device)
+    check(lib().sf_head_ce_wgrad_f32(x.data_ptr(), ld, w_packed.data_ptr(), t64, t16, ptr(group_w), ptr(lse), ptr(g), out.data_ptr(), out.stride(0),
+                                     R, V, K, int(group), ws.data_ptr(), ws.numel(), stream()))
+    return out
+
+
 def cross_entropy(logits, target):
     """F.cross_entropy(logits [R,V], target int64 [R]) with mean reduction -> 0-dim tensor."""
     _chk(logits)

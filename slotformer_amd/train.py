@@ -847,10 +847,11 @@ def token_cross_entropy(logits, target):
 
 class _HeadCrossEntropy(torch.autograd.Function):
     """(weighted mean loss, stats) of sf_head_ce_fwd_f32 / sf_head_ce_bwd_f32: the head's product and the cross-entropy in one pass each way.
-    Saved for the backward: x, lse [R] and the targets -- nothing of R * V elements exists at any time."""
+    Saved for the backward: x, lse [R] and the targets -- nothing of R * V elements exists at any time.  `weight` is the head's [V, K] parameter
+    when it is trained (its gradient: one sf_head_ce_wgrad_f32 call) and None for a frozen head; the products read `w_packed` either way."""
 
     @staticmethod
-    def forward(ctx, x, w_packed, target, group_w, group, V):
+    def forward(ctx, x, weight, w_packed, target, group_w, group, V):
         from . import ops
         K = x.shape[-1]
         xd = x.detach().float().reshape(-1, K)
@@ -870,26 +871,29 @@ class _HeadCrossEntropy(torch.autograd.Function):
         xd, w_packed, target, group_w, lse, stats = ctx.saved_tensors
         n = stats[1]
         gd = torch.where(n > 0, g.double() / n, torch.zeros_like(n)).float().reshape(1)   # stays on the device
-        dx = ops.head_ce_backward(xd, w_packed, target, ctx.V, lse, gd, group_w, ctx.group)
-        return dx.view(ctx.xshape), None, None, None, None, None
+        dx = ops.head_ce_backward(xd, w_packed, target, ctx.V, lse, gd, group_w, ctx.group).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        dw = ops.head_ce_wgrad(xd, w_packed, target, ctx.V, lse, gd, group_w, ctx.group) if ctx.needs_input_grad[1] else None
+        return dx, dw, None, None, None, None, None
 
 
-def head_cross_entropy(x, weight, target, group_w=None, group=1):
-    """The token loss of a FROZEN vocabulary head without its logits: x [..., K] (the rows behind the decoder's final LayerNorm,
+def head_cross_entropy(x, weight, target, group_w=None, group=1, weight_grad=False):
+    """The token loss of a vocabulary head without its logits: x [..., K] (the rows behind the decoder's final LayerNorm,
     `slate_decoder_hidden`), weight = the head, an nn.Linear without bias or its [V, K] weight, target int64 / int16 ids of x's leading shape ->
     (loss, stats).  loss: the mean over the rows of logsumexp(W x[r]) - W[target[r]] . x[r], weighted by group_w [R / group] float32 (the weight of
     each run of `group` consecutive rows -- a frame's tokens; 0 drops the frame), a float32 device scalar; stats float64 [2] = (sum w loss, sum w),
-    not differentiable.  The gradient reaches x only: a head that requires grad is refused (STEVE's own training keeps the `linear` +
-    `token_cross_entropy` path).  The packed copy of the weight is cached on its owner and rebuilt when the weight's version changes."""
+    not differentiable.  By default the gradient reaches x only and a head that requires grad is refused.  weight_grad=True takes such a head: the
+    backward then also returns its gradient [V, K] float32 (`ops.head_ce_wgrad`, again without the logits; its workspace is at most eight [V, K]
+    blocks), and skips dx when x needs none; with a frozen head the keyword changes nothing.  The packed copy of the weight is cached on its owner
+    and rebuilt when the weight's version changes -- after every optimiser step of a trained head."""
     from . import ops, plans
     w = weight.weight if isinstance(weight, torch.nn.Module) else weight
     if isinstance(weight, torch.nn.Module) and getattr(weight, 'bias', None) is not None:
         raise NotImplementedError('slotformer_amd: head_cross_entropy takes a head without bias')
     if not (torch.is_tensor(w) and w.is_cuda and w.dim() == 2):
         raise RuntimeError('slotformer_amd: head_cross_entropy needs a [V, K] weight on a HIP device; there is no CPU fallback')
-    if w.requires_grad:
-        raise NotImplementedError('slotformer_amd: head_cross_entropy has no gradient for the head weight (the weight gradient of the fused head is '
-                                  'not implemented); freeze it, or use train.linear + train.token_cross_entropy')
+    if w.requires_grad and not weight_grad:
+        raise NotImplementedError('slotformer_amd: head_cross_entropy gives no gradient to the head weight unless asked (the weight gradient of the '
+                                  'fused head is opt-in): pass weight_grad=True, freeze the head, or use train.linear + train.token_cross_entropy')
     V, K = w.shape
     if x.shape[-1] != K or not lib().sf_head_ce_ok(V, K):
         raise NotImplementedError(f'slotformer_amd: head_cross_entropy takes K a multiple of 32 in [32, 256] and V a multiple of 32 in [32, 2^20], '
@@ -899,7 +903,7 @@ def head_cross_entropy(x, weight, target, group_w=None, group=1):
     if group_w is not None:
         group_w = group_w.detach().float().contiguous()
     packed = plans.cached(weight, 'head_ce', plans.signature(w), lambda: ops.pack_head_ce_weight(w.detach().float().contiguous()))
-    return _HeadCrossEntropy.apply(x, packed, target.contiguous().reshape(-1), group_w, int(group), V)
+    return _HeadCrossEntropy.apply(x, w if w.requires_grad else None, packed, target.contiguous().reshape(-1), group_w, int(group), V)
 
 
 class _LinearCat(torch.autograd.Function):

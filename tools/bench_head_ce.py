@@ -1,5 +1,6 @@
 """The fused vocabulary head + cross-entropy against the chain it replaces (profiles/head_ce.md).
     python tools/bench_head_ce.py [--json PATH] [--seconds 1.0] [--windows 3] [--frames 16,64,192] [--fit-batches 2,4] [--no-fit]
+    python tools/bench_head_ce.py --wgrad [--json PATH] [--seconds 1.0] [--windows 3] [--frames 16,64,72,192]     (profiles/head_ce_wgrad.md)
 
   fused   train.head_cross_entropy forward + backward: sf_head_ce_fwd_f32 / sf_head_ce_bwd_f32, no [R, V] tensor.
   chain   train.linear(x, head) + train.token_cross_entropy forward + backward: the logits, a saved copy's worth and their gradient.
@@ -108,6 +109,40 @@ def bench_head(frames, seconds, windows, dev):
     return out
 
 
+def bench_wgrad(frames, seconds, windows, dev):
+    """forward + backward with a TRAINED head: head_cross_entropy(..., weight_grad=True) (loss, dx and dW without the logits: five products of
+    2 R V K FLOP -- one forward, two in each of the two backward launches) against the chain, which forms the logits once (three products)"""
+    from slotformer_amd import train
+    gen = torch.Generator().manual_seed(0)
+    head = torch.nn.Linear(K, V, bias=False).to(dev)
+    with torch.no_grad():
+        head.weight.copy_(torch.randn(V, K, generator=gen) / K**0.5)
+    out = {}
+    for nf in frames:
+        R = nf * TOKENS
+        x0 = (torch.randn(R, K, generator=gen) * 2).to(dev)
+        t = torch.randint(0, V, (R, ), generator=gen).to(dev)
+
+        def fused():
+            x = x0.detach().requires_grad_(True)
+            train.head_cross_entropy(x, head, t, weight_grad=True)[0].backward()
+            head.weight.grad = None
+
+        def chain():
+            x = x0.detach().requires_grad_(True)
+            train.token_cross_entropy(train.linear(x, head), t).backward()
+            head.weight.grad = None
+
+        tf, tc, n = alternate(fused, chain, seconds, windows)
+        mf, mc = statistics.median(tf), statistics.median(tc)
+        out[f'{nf}_frames'] = {'rows': R, 'fused': stats(tf), 'chain': stats(tc), 'calls_per_window': n, 'chain_over_fused': round(mc / mf, 3),
+                               'fused_fraction_of_split_bf16_roof': round(5 * 2 * R * V * K / (mf * 1e-3) / ROOF, 4),
+                               'chain_fraction_of_split_bf16_roof': round(3 * 2 * R * V * K / (mc * 1e-3) / ROOF, 4),
+                               'fused_peak_MiB': round(peak(fused), 1), 'chain_peak_MiB': round(peak(chain), 1), 'one_RxV_tensor_MiB': R * V * 4 / 2**20}
+        del x0, t
+    return out
+
+
 def physion_model(dev):
     """STEVESlotFormer at slotformer_physion_params.py on a STEVE of seeded weights (both frozen parts: their values do not matter to the time)."""
     import golden_util as gu
@@ -183,13 +218,18 @@ def main():
     ap.add_argument('--frames', default='16,64,192')
     ap.add_argument('--fit-batches', default='2,4')
     ap.add_argument('--no-fit', action='store_true')
+    ap.add_argument('--wgrad', action='store_true', help='a TRAINED head instead: weight_grad=True against the chain, at --frames (16,64,72,192)')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_head_ce: no GPU; nothing is measured without one')
     dev = torch.device('cuda:0')
-    res = {'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'head': dict(V=V, K=K, tokens_per_frame=TOKENS),
-           'head_ce': bench_head([int(f) for f in a.frames.split(',')], a.seconds, a.windows, dev)}
-    if not a.no_fit:
+    res = {'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'head': dict(V=V, K=K, tokens_per_frame=TOKENS)}
+    if a.wgrad:
+        frames = '16,64,72,192' if a.frames == ap.get_default('frames') else a.frames
+        res['head_ce_wgrad'] = bench_wgrad([int(f) for f in frames.split(',')], a.seconds, a.windows, dev)
+    else:
+        res['head_ce'] = bench_head([int(f) for f in a.frames.split(',')], a.seconds, a.windows, dev)
+    if not a.no_fit and not a.wgrad:
         res['fit_step'] = bench_fit([int(b) for b in a.fit_batches.split(',')], a.seconds, a.windows, dev)
     text = json.dumps(res, indent=1)
     print(text)

@@ -2,15 +2,20 @@
 12 clips per GPU x 6 frames at 128x128, 6 slots of 192, Transformer + LSTM predictor, frozen dVAE with 4096 tokens on a
 32x32 grid, 4-block Transformer decoder of width 192, token cross-entropy, Adam).
 
-  python tools/bench_train_steve.py [--batch 12] [--steps 5] [--warmup 1] [--eager] [--clip 0.05] [--dec-lr 3e-4]
+  python tools/bench_train_steve.py [--batch 12] [--steps 5] [--warmup 1] [--eager] [--clip 0.05] [--dec-lr 3e-4] [--fused-head]
 
 One JSON line: ms per iteration of the HIP path (forward + loss + backward + optimiser); --eager adds the same step with torch
-ops (autograd) on the same GPU, sharing the parameters and the (inference-path) dVAE tokens.
+ops (autograd) on the same GPU, sharing the parameters and the (inference-path) dVAE tokens.  --fused-head runs the HIP step with
+`STEVE.fused_token_loss` on (head + cross-entropy + the head's gradient without the logits) and adds `fused_head`: that step against
+the step through the logits in the SAME process, in alternating windows of at least --seconds each (ms per step: the median over
+--windows windows with minimum and maximum), and the peak of torch's allocator over one step of each above what is allocated before it.
 """
 import argparse
 import json
 import os
+import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -96,6 +101,48 @@ def eager_forward(m, img, tgt):
     return F.cross_entropy(logits.flatten(0, 1), tgt.flatten(0, 1))
 
 
+def compare_routes(m, step, seconds, windows):
+    """The step with `fused_token_loss` on and off, in alternating windows of at least `seconds`, and the allocator's peak over one step of each."""
+    def run(fused, n):
+        m.fused_token_loss = fused
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            step()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def peak(fused):
+        m.fused_token_loss = fused
+        step()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        step()
+        torch.cuda.synchronize()
+        return round((torch.cuda.max_memory_allocated() - base) / 2**20, 1)
+
+    n = [max(3, int(seconds / (run(f, 3) / 3)) + 1) for f in (True, False)]
+    t = ([], [])
+    while len(t[1]) < windows:
+        w = [run(True, n[0]), run(False, n[1])]
+        if min(w) < seconds:   # a probe was optimistic: a window shorter than asked for is not kept
+            n = [int(1.3 * k * seconds / x) + 1 if x < seconds else k for k, x in zip(n, w)]
+            continue
+        t[0].append(w[0] / n[0] * 1e3)
+        t[1].append(w[1] / n[1] * 1e3)
+    out = {}
+    for key, v, fused in (('fused', t[0], True), ('logits', t[1], False)):
+        out[key] = {'median_ms': round(statistics.median(v), 2), 'min_ms': round(min(v), 2), 'max_ms': round(max(v), 2), 'windows': len(v),
+                    'peak_MiB': peak(fused)}
+    out['steps_per_window'] = n
+    out['logits_over_fused'] = round(out['logits']['median_ms'] / out['fused']['median_ms'], 3)
+    out['peak_saved_MiB'] = round(out['logits']['peak_MiB'] - out['fused']['peak_MiB'], 1)
+    m.fused_token_loss = True
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=12)
@@ -105,6 +152,9 @@ def main():
     ap.add_argument('--eager', action='store_true')
     ap.add_argument('--clip', type=float, default=0., help='clip the gradient norm inside FlatAdam (steve_physion_params: 0.05); 0 = off')
     ap.add_argument('--dec-lr', type=float, default=0., help="the Transformer decoder's own rate (steve_physion_params: 3e-4); 0 = one group")
+    ap.add_argument('--fused-head', action='store_true', help='STEVE.fused_token_loss = True, and the comparison with the step through the logits')
+    ap.add_argument('--seconds', type=float, default=1.0)
+    ap.add_argument('--windows', type=int, default=3)
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     from slotformer_amd.base_slots import build_model
@@ -112,6 +162,7 @@ def main():
     torch.manual_seed(0)
     m = build_model(gu.ParamsView(physion_cfg())).to(dev).train()
     m.testing = False
+    m.fused_token_loss = a.fused_head
     B, T = a.batch, a.frames
     img = torch.rand(B, T, 3, 128, 128, device=dev) * 2 - 1
     with torch.no_grad():
@@ -143,6 +194,9 @@ def main():
 
         ems = time_loop(estep, a.steps, a.warmup)
         res['torch_eager_same_gpu'] = {'ms_per_iter': round(ems, 1), 'speedup': round(ems / ms, 2)}
+    if a.fused_head:
+        res['config']['workload'] += ', fused_token_loss'
+        res['fused_head'] = compare_routes(m, step, a.seconds, a.windows)
     print(json.dumps(res))
 
 
