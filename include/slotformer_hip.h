@@ -1170,6 +1170,30 @@ int sf_clip_mse_f32(const float* pred, const float* target, const int* clip_vide
 int sf_clip_frames_f32(const unsigned char* table, int T_total, const int* clip_video, const int* clip_start, int first_frame, int frame_step,
                        const float* mean3, const float* std3, float* out, int B, int S, int H, int W, void* stream);
 
+/* ---- The stochastic kernels of StoSAVi in training (csrc/kernel_sample.hip, csrc/normal_noise.h; base_slots.fit) ------------------------------
+ * Standard-normal noise as a pure function of (seed, tag, element index): out[i] = eps(seed, tag, i), n <= 2^31 elements.
+ *   s   = mix32((u32)seed ^ mix32((u32)(seed >> 32) + 0x9e3779b9 * (tag + 1)))           (mix32: the dropout masks' finaliser)
+ *   u1  = ((mix32((2 i) ^ s) >> 9) + 0.5) * 2^-23,  u2 the same from 2 i + 1               (exact in float32)
+ *   eps = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2)                                      (full-precision functions; |eps| <= 5.77)
+ * The two entry points below call the same device function, so a seed gives them these bits; train.normal_noise restates it on the host. */
+int sf_normal_noise_f32(float* out, long long n, unsigned long long seed, unsigned tag, void* stream);
+/* dist [R, 2 D] = (mu | log_var) -> kernels [R, D] = mu + eps * exp(0.5 * log_var) (savi.py:355-365).  eps = noise [R, D] when given, else
+ * eps(seed, tag, r * D + c), generated in registers.  *kld_sum, a DEVICE double, is ADDED to: the sum over rows and channels of
+ * 0.5 * (prior_log_var - log_var) + exp(log_var) / (2 exp(prior_log_var)) - 0.5 -- savi.py:337-353 with the prior at the posterior's mean, before
+ * its mean over rows -- evaluated per element in float32 as 0.5 * (expm1f(x) - x), x = log_var - prior_log_var (the same value without the
+ * cancellation near x = 0), accumulated in float64, per-workgroup partials combined in index order by the last workgroup to arrive: bit-identical
+ * from call to call.  ws: the workspace query's bytes, 16-byte aligned, ZERO-FILLED before its first use; every call leaves its arrival counter at
+ * zero.  D % 4 == 0, D <= 1024, R >= 1, R * D <= 2^31; dist, noise, kernels 16-byte aligned.  The query returns 0 for a refused shape. */
+size_t sf_kernel_sample_workspace_bytes(long long R, int D);
+int sf_kernel_sample_fwd_f32(const float* dist, const float* noise, unsigned long long seed, unsigned tag, float prior_log_var, float* kernels,
+                             double* kld_sum, long long R, int D, void* ws, size_t ws_bytes, void* stream);
+/* Its gradient; eps is the same tensor or is regenerated from (seed, tag), never stored.  d_kernels [R, D] (NULL: zero); d_kld a DEVICE float, the
+ * gradient arriving at the mean KL term; kld_scale a host float, 1 / rows of that mean.  d_dist [R, 2 D] = (d_mu | d_log_var):
+ *   d_mu      = d_kernels
+ *   d_log_var = d_kernels * eps * 0.5 * exp(0.5 * log_var) + d_kld * kld_scale * 0.5 * (exp(log_var - prior_log_var) - 1) */
+int sf_kernel_sample_bwd_f32(const float* dist, const float* noise, unsigned long long seed, unsigned tag, float prior_log_var,
+                             const float* d_kernels, const float* d_kld, float kld_scale, float* d_dist, long long R, int D, void* stream);
+
 /* StoSAVi / STEVE encoder side (savi.py:177-250,295-322,367-416; steve.py:198-240). */
 typedef struct {
   int resolution;      /* input H == W (64 or 128) */

@@ -302,6 +302,10 @@ SIGNATURES = {
     'sf_clip_mse_workspace_bytes': (SZ, [I, I, LL]),
     'sf_clip_mse_f32': (I, [FP, FP, VP, VP, I, I, I, FP, VP, I, F32, FP, VP, I, I, LL, VP, SZ, VP]),
     'sf_clip_frames_f32': (I, [VP, I, VP, VP, I, I, FP, FP, FP, I, I, I, I, VP]),
+    'sf_normal_noise_f32': (I, [FP, LL, C.c_ulonglong, C.c_uint, VP]),
+    'sf_kernel_sample_workspace_bytes': (SZ, [LL, I]),
+    'sf_kernel_sample_fwd_f32': (I, [FP, FP, C.c_ulonglong, C.c_uint, F32, FP, VP, LL, I, VP, SZ, VP]),
+    'sf_kernel_sample_bwd_f32': (I, [FP, FP, C.c_ulonglong, C.c_uint, F32, FP, FP, F32, FP, LL, I, VP]),
     'sf_savi_encode_workspace_bytes': (SZ, [C.POINTER(sf_savi_encoder), I]),
     'sf_savi_encode_f32': (I, [C.POINTER(sf_savi_encoder), FP, FP, FP, FP, FP, I, FP, FP, FP, I, I, VP, SZ,
                                VP]),

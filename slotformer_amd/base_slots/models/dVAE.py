@@ -214,7 +214,9 @@ class dVAE(BaseModel):
 
     def forward(self, data_dict):
         """`img` [B,(T,)3,H,W]; optional `gumbel_tau`, `hard` as in the reference, and `gumbel` [B,(T,)V,h,w]: the Gumbel noise
-        to use instead of a fresh draw (the reference draws it inside steve_utils.gumbel_softmax)."""
+        to use instead of a fresh draw (the reference draws it inside steve_utils.gumbel_softmax), or `gumbel_seed` (an int): the
+        seed of the noise generated inside the softmax kernel (`train.gumbel_noise` rebuilds it), in place of one drawn from torch's
+        CPU generator."""
         if self.testing:
             return self.tokenize(data_dict['img'], one_hot=False)
         from ... import train
@@ -240,7 +242,8 @@ class dVAE(BaseModel):
         g = data_dict.get('gumbel')
         if g is not None:
             g = (g.flatten(0, 1) if unflatten else g).permute(0, 2, 3, 1).to(logits.device).float().contiguous()
-        z = train.gumbel_softmax(logits, g, tau, hard)   # without `gumbel`: noise generated inside the softmax kernel
+        # without `gumbel`: noise generated inside the softmax kernel, from `gumbel_seed` when given, else from a fresh seed
+        z = train.gumbel_softmax(logits, g, tau, hard, seed=data_dict.get('gumbel_seed'))
         recon = self.decode_nhwc(z).permute(0, 3, 1, 2)
         # log-probabilities of the token map: reported, not part of the loss
         z_logits = ops.log_softmax_rows(logits.detach()).permute(0, 3, 1, 2)

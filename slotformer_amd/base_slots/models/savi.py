@@ -178,16 +178,22 @@ class StoSAVi(BaseModel):
             return None
         return torch.stack([torch.randn(B, self.num_slots, self.slot_size, device=device) for _ in range(T)], 1)
 
-    def _encode_with_grad(self, img, prev_slots, noise):
+    def seeded_noise(self, seed, B, T, device):
+        """The noise a `noise_seed` stands for, as a tensor [B,T,N,D]: frame t is `ops.normal_noise(seed, t, [B,N,D])`."""
+        return torch.stack([ops.normal_noise(seed, t, (B, self.num_slots, self.slot_size), device) for t in range(T)], 1)
+
+    def _encode_with_grad(self, img, prev_slots, noise, noise_seed=None):
         """The same recurrence (savi.py:379-416) as a chain of autograd nodes on the HIP library (row N1): one node for
         the image encoder of all frames, then per frame predictor -> kernel distribution -> sample -> Slot Attention.
-        Only the tiny elementwise glue on [B,N,D] tensors (sampling, residual add) runs as torch ops."""
+        Only the tiny elementwise glue on [B,N,D] tensors (sampling, residual add) runs as torch ops.  With `noise_seed`
+        frame t samples through `train.kernel_sample(seed=noise_seed, tag=t)` -- noise, sample and KL term in one launch --
+        and the third item returned is the frames' mean KL term; otherwise it is None."""
         from ... import train
         B, T = img.shape[:2]
         feats = train.features_with_grad(self, img.transpose(0, 1).flatten(0, 1))   # time-major: feats[t*B:(t+1)*B] is contiguous
         feats = feats.unflatten(0, (T, B))
         kd_layers, D = getattr(self, 'kernel_dist_layer', None), self.slot_size   # STEVE has no kernel distribution
-        dists, posts = [], []
+        dists, posts, klds = [], [], []
         for t in range(T):
             if prev_slots is None:
                 latents = self.init_latents.repeat(B, 1, 1)
@@ -200,13 +206,17 @@ class StoSAVi(BaseModel):
                     dist = train.linear(latents, kd_layers[0])
                 else:   # kernel_mlp: Linear -> LayerNorm -> ReLU -> Linear (savi.py:190-200)
                     dist = train.linear(torch.relu(train.layer_norm(train.linear(latents, kd_layers[0]), kd_layers[1])), kd_layers[3])
-                kernels = dist[..., :D]
-                if noise is not None:
-                    kernels = kernels + noise[:, t] * torch.exp(0.5 * dist[..., D:])
+                if noise_seed is not None:
+                    kernels, kld = train.kernel_sample(dist, D, self.kld_log_var, seed=noise_seed, tag=t)
+                    klds.append(kld)
+                else:
+                    kernels = dist[..., :D]
+                    if noise is not None:
+                        kernels = kernels + noise[:, t] * torch.exp(0.5 * dist[..., D:])
             prev_slots = train.slot_attention_with_grad(self.slot_attention, feats[t], kernels.contiguous())
             dists.append(dist)
             posts.append(prev_slots)
-        return torch.stack(dists, 1), torch.stack(posts, 1), None
+        return torch.stack(dists, 1), torch.stack(posts, 1), torch.stack(klds).mean() if klds else None
 
     def _predict_with_grad(self, slots, train):
         """predictor(prev_slots) under autograd (predictor.py:20-135): residual MLP, or Transformer over the slots, each
@@ -252,20 +262,31 @@ class StoSAVi(BaseModel):
         self.predictor.reset()
 
     def forward(self, data_dict):
-        """{'img' [B,T,3,H,W] (+ 'noise')} -> {'post_slots', 'kernel_dist', 'img'} (+ reconstructions unless `testing`).
+        """{'img' [B,T,3,H,W] (+ 'noise' or 'noise_seed')} -> {'post_slots', 'kernel_dist', 'img'} (+ reconstructions unless `testing`).
+        'noise_seed' (an int) stands for the noise `seeded_noise(noise_seed, ...)` and takes precedence over 'noise': a training step
+        then samples and takes its KL term through `train.kernel_sample`, and the output has 'kld', which `calc_train_loss` uses.
         The engine walks the clip one time step at a time with O(1) activation memory in T, so the reference's
         OOM-probing temporal chunking (savi.py:421-463) is unnecessary: any T is one call, and the result equals every
         chunking because the predictor state is carried frame to frame."""
         img = data_dict['img']
         if not self.training:
             self.clip_len = max(self.clip_len, img.shape[1])
-        return self._forward(img, None, noise=data_dict.get('noise', None))
+        return self._forward(img, None, noise=data_dict.get('noise', None), noise_seed=data_dict.get('noise_seed', None))
 
-    def _forward(self, img, prev_slots=None, noise=None):
+    def _forward(self, img, prev_slots=None, noise=None, noise_seed=None):
         if prev_slots is None:
             self._reset_rnn()   # a new video: forget the predictor's recurrent state
-        kernel_dist, post_slots, _ = self.encode(img, prev_slots=prev_slots, noise=noise)
+        kld = None
+        if noise_seed is None or self.kld_method == 'none':
+            kernel_dist, post_slots, _ = self.encode(img, prev_slots=prev_slots, noise=noise)
+        elif torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            kernel_dist, post_slots, kld = self._encode_with_grad(img.float().contiguous(), prev_slots, None, int(noise_seed))
+        else:
+            seeded = self.seeded_noise(int(noise_seed), img.shape[0], img.shape[1], img.device)
+            kernel_dist, post_slots, _ = self.encode(img, prev_slots=prev_slots, noise=seeded)
         out = {'post_slots': post_slots, 'kernel_dist': kernel_dist, 'img': img}
+        if kld is not None:
+            out['kld'] = kld
         if self.testing or not self.use_post_recon_loss:
             return out
         B, T = img.shape[:2]
@@ -286,7 +307,8 @@ class StoSAVi(BaseModel):
         return losses.kernel_kld(prior_dist, self.slot_size, self.kld_log_var)
 
     def calc_train_loss(self, data_dict, out_dict):
-        terms = {'kld_loss': self._kld_loss(out_dict['kernel_dist'], out_dict['post_slots'])}
+        kld = out_dict.get('kld')   # a step sampled from 'noise_seed': the term came with the sample
+        terms = {'kld_loss': kld if kld is not None else self._kld_loss(out_dict['kernel_dist'], out_dict['post_slots'])}
         if self.use_post_recon_loss:
             terms['post_recon_loss'] = losses.image_recon_loss(out_dict['post_recon_combined'], out_dict['img'])
         return terms

@@ -126,15 +126,22 @@ class STEVE(StoSAVi):
         return slots, masks, None
 
     def forward(self, data_dict):
-        return self._forward(data_dict['img'], img_token_id=data_dict.get('token_id', None), gumbel=data_dict.get('gumbel', None))
+        return self._forward(data_dict['img'], img_token_id=data_dict.get('token_id', None), gumbel=data_dict.get('gumbel', None),
+                             gumbel_seed=data_dict.get('gumbel_seed', None))
 
-    def _forward(self, img, img_token_id=None, prev_slots=None, gumbel=None):
+    def _forward(self, img, img_token_id=None, prev_slots=None, gumbel=None, gumbel_seed=None):
         if prev_slots is None:
             self._reset_rnn()
         slots, masks, _ = self.encode(img, prev_slots)
         out_dict = {'slots': slots, 'masks': masks}
         if self.testing:
             return out_dict
+        out_dict.update(self._decode_tokens(img, slots, img_token_id, gumbel, gumbel_seed))
+        return out_dict
+
+    def _decode_tokens(self, img, slots, img_token_id=None, gumbel=None, gumbel_seed=None):
+        """The image side of `_forward` (steve.py:306-335) on given slots [B,T,N,D] -> the entries it adds to the output dict."""
+        out_dict = {}
         # token targets from the frozen dVAE, teacher-forced decoder logits (steve.py:306-322)
         if img_token_id is None:
             with torch.no_grad():   # the dVAE is frozen: the tokens are targets, not part of the graph (steve.py:306-311)
@@ -159,13 +166,13 @@ class STEVE(StoSAVi):
         out_dict.update({'pred_token_id': pred_token_id, 'target_token_id': target_token_id})
         if self.use_img_recon_loss:
             # steve.py:327-335: relaxed sample (tau 0.1) of the predicted token map, decoded by the frozen dVAE.  `gumbel`
-            # [B*T,V,h,w] fixes the noise the reference draws inside gumbel_softmax.
+            # [B*T,V,h,w] fixes the noise the reference draws inside gumbel_softmax; `gumbel_seed` the seed of the noise generated in the kernel.
             from ... import train
             logits = pred_token_id.reshape(-1, h, w, self.vocab_size)
             g = None   # no noise given: generated inside the softmax kernel
             if gumbel is not None:
                 g = gumbel.reshape(-1, self.vocab_size, h, w).permute(0, 2, 3, 1).to(logits.device).float().contiguous()
-            z = train.gumbel_softmax(logits, g, tau=0.1, hard=False)
+            z = train.gumbel_softmax(logits, g, tau=0.1, hard=False, seed=gumbel_seed)
             out_dict['gt_img'] = img.flatten(0, 1)
             out_dict['recon_img'] = self.dvae.decode_nhwc(z).permute(0, 3, 1, 2)
         return out_dict
@@ -174,20 +181,22 @@ class STEVE(StoSAVi):
         """Token cross-entropy of steve.py:339-351; differentiable when the logits carry a graph (row N1).  An out_dict of the
         `fused_token_loss` route holds the decoder's hidden rows in place of the logits: the loss and the gradients of the rows and of the head
         come from `train.head_cross_entropy(..., weight_grad=True)`."""
-        target = out_dict['target_token_id'].flatten(0, 1).contiguous()
-        if 'token_hidden' in out_dict:
-            from ... import train
-            return {'token_recon_loss': train.head_cross_entropy(out_dict['token_hidden'], self.trans_decoder.head, target, weight_grad=True)[0]}
-        pred = out_dict['pred_token_id'].flatten(0, 1).contiguous()
-        if pred.requires_grad:
-            from ... import train
-            loss_dict = {'token_recon_loss': train.token_cross_entropy(pred, target)}
-        else:
-            loss_dict = {'token_recon_loss': ops.cross_entropy(pred, target)}
-        if self.use_img_recon_loss:
+        loss_dict = {'token_recon_loss': self._token_recon_loss(out_dict)}
+        if self.use_img_recon_loss:   # (never with 'token_hidden': the fused route is taken only without the image loss)
             from ...host import losses
             loss_dict['img_recon_loss'] = losses.image_recon_loss(out_dict['recon_img'], out_dict['gt_img'])
         return loss_dict
+
+    def _token_recon_loss(self, out_dict):
+        target = out_dict['target_token_id'].flatten(0, 1).contiguous()
+        if 'token_hidden' in out_dict:
+            from ... import train
+            return train.head_cross_entropy(out_dict['token_hidden'], self.trans_decoder.head, target, weight_grad=True)[0]
+        pred = out_dict['pred_token_id'].flatten(0, 1).contiguous()
+        if pred.requires_grad:
+            from ... import train
+            return train.token_cross_entropy(pred, target)
+        return ops.cross_entropy(pred, target)
 
     def render(self, slots, soft=False, gumbel=None, seed=None, frames_per_wg=0):
         """Slots [F,N,D] -> frames on the device, the reconstruction of base_slots/method.py:353-378 (`trans_decoder` generates the

@@ -661,6 +661,72 @@ def gumbel_softmax_rows(x, seed, scale=1.0):
     return out
 
 
+_U64 = 0xffffffffffffffff
+_KERNEL_SAMPLE_WS = {}
+
+
+def normal_noise(seed, tag, shape, device=None):
+    """sf_normal_noise_f32: standard-normal noise as a pure function of (seed, tag, flat element index) -> float32 `shape` (an int or a
+    tuple) on `device` (default: the current HIP device).  train.normal_noise rebuilds it on the host."""
+    shape = (int(shape), ) if not hasattr(shape, '__len__') else tuple(int(s) for s in shape)
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('slotformer_amd: normal_noise is generated on a HIP device; there is no CPU fallback (train.normal_noise is the host twin)')
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    check(lib().sf_normal_noise_f32(ptr(out), out.numel(), int(seed) & _U64, int(tag) & 0xffffffff, stream(out)))
+    return out
+
+
+def _kernel_sample_ws(device, R, D):
+    """The forward's workspace, one per device: zero-filled once; every launch leaves its arrival counter at zero (as train._clip_mse_ws)."""
+    old = _KERNEL_SAMPLE_WS.get(device)
+    ws = scratch(lib().sf_kernel_sample_workspace_bytes, R, D, device=device, reuse=old, at_least=4096)
+    if ws is not old:
+        _KERNEL_SAMPLE_WS[device] = ws.zero_()
+    return ws
+
+
+def _kernel_sample_args(dist, noise, seed, D):
+    _chk(dist, noise)
+    D = int(D)
+    if dist.dim() < 1 or dist.shape[-1] != 2 * D:
+        raise ValueError(f'slotformer_amd: kernel_sample takes dist [..., {2 * D}] = (mu | log_var), got {tuple(dist.shape)}')
+    R = dist.numel() // (2 * D)
+    if noise is not None and noise.numel() != R * D:
+        raise ValueError(f'slotformer_amd: kernel_sample noise has {R * D} elements, got {tuple(noise.shape)}')
+    if noise is None and seed is None:
+        raise ValueError('slotformer_amd: kernel_sample needs noise= or seed=')
+    return R, D
+
+
+def kernel_sample_fwd(dist, D, prior_log_var, kld_sum, noise=None, seed=None, tag=0):
+    """sf_kernel_sample_fwd_f32: dist [..., 2 D] -> kernels [..., D] = mu + eps * exp(log_var / 2); the KL sum against the prior of log-variance
+    `prior_log_var` is ADDED to kld_sum (float64 [1] on the device).  eps: `noise` (kernels' shape), else generated from (seed, tag)."""
+    R, D = _kernel_sample_args(dist, noise, seed, D)
+    if not (torch.is_tensor(kld_sum) and kld_sum.is_cuda and kld_sum.dtype == torch.float64 and kld_sum.numel() == 1):
+        raise ValueError('slotformer_amd: kernel_sample adds the KL sum to a float64 [1] device tensor')
+    out = torch.empty(*dist.shape[:-1], D, dtype=torch.float32, device=dist.device)
+    ws = _kernel_sample_ws(dist.device, R, D)
+    check(lib().sf_kernel_sample_fwd_f32(ptr(dist), ptr(noise), int(seed or 0) & _U64, int(tag) & 0xffffffff, float(prior_log_var), ptr(out),
+                                         kld_sum.data_ptr(), R, D, ws.data_ptr(), ws.numel(), stream(dist)))
+    return out
+
+
+def kernel_sample_bwd(dist, D, prior_log_var, d_kernels, d_kld, kld_scale, noise=None, seed=None, tag=0):
+    """sf_kernel_sample_bwd_f32 -> d_dist, dist's shape.  d_kernels: kernels' shape or None (zero); d_kld: float32 [1] on the device, the gradient
+    at the mean KL term; kld_scale: 1 / rows of that mean."""
+    R, D = _kernel_sample_args(dist, noise, seed, D)
+    _chk(d_kernels, d_kld)
+    if d_kernels is not None and d_kernels.numel() != R * D:
+        raise ValueError(f'slotformer_amd: kernel_sample d_kernels has {R * D} elements, got {tuple(d_kernels.shape)}')
+    if d_kld.numel() != 1:
+        raise ValueError('slotformer_amd: kernel_sample d_kld is a float32 scalar on the device')
+    out = torch.empty_like(dist)
+    check(lib().sf_kernel_sample_bwd_f32(ptr(dist), ptr(noise), int(seed or 0) & _U64, int(tag) & 0xffffffff, float(prior_log_var), ptr(d_kernels),
+                                         ptr(d_kld), float(kld_scale), ptr(out), R, D, stream(dist)))
+    return out
+
+
 def slate_attention_cached(q, kv_cache, Lk, num_heads, d_model, k_off, v_off):
     """One-query-per-sequence attention over the first Lk rows of a K/V cache.  q [B,1,ldq] (head block at column 0),
     kv_cache [B,Lmax,ld] holding k at column k_off and v at column v_off of each row."""

@@ -1043,6 +1043,69 @@ def gumbel_noise(seed, numel):
     return torch.from_numpy(-np.log(-np.log(u)))
 
 
+def _mix32_np(h):
+    """sf_mix32 (csrc/sf_common.h) on a NumPy uint32 array."""
+    import numpy as np
+    with np.errstate(over='ignore'):
+        h = h.astype(np.uint32)
+        h ^= h >> np.uint32(16)
+        h = (h * np.uint32(0x7feb352d)).astype(np.uint32)
+        h ^= h >> np.uint32(15)
+        h = (h * np.uint32(0x846ca68b)).astype(np.uint32)
+        h ^= h >> np.uint32(16)
+    return h
+
+
+def normal_noise(seed, tag, numel):
+    """Host restatement of the in-kernel normal noise (csrc/normal_noise.h: sf_normal_seed / sf_normal; ops.normal_noise) for tests: the same
+    hashed uniforms, Box-Muller evaluated in float64, returned as float32 [numel]."""
+    import numpy as np
+    seed, tag = int(seed) & 0xffffffffffffffff, int(tag) & 0xffffffff
+    inner = _mix32_np(np.array([((seed >> 32) + 0x9e3779b9 * (tag + 1)) & 0xffffffff], dtype=np.uint32))
+    sseed = _mix32_np(np.array([seed & 0xffffffff], dtype=np.uint32) ^ inner)[0]
+    i2 = np.arange(int(numel), dtype=np.uint32) * np.uint32(2)
+    u1 = ((_mix32_np(i2 ^ sseed) >> np.uint32(9)).astype(np.float64) + 0.5) * 2.**-23
+    u2 = ((_mix32_np((i2 + np.uint32(1)) ^ sseed) >> np.uint32(9)).astype(np.float64) + 0.5) * 2.**-23
+    eps = np.sqrt(-2. * np.log(u1)) * np.cos(np.float64(np.float32(6.2831855)) * u2)
+    return torch.from_numpy(eps.astype(np.float32))
+
+
+class _KernelSample(torch.autograd.Function):
+    """(kernels, kld) of sf_kernel_sample_fwd_f32 / _bwd_f32: the sampling of StoSAVi's stochastic kernels and their KL term in one launch each
+    way.  Saves `dist` (and the noise tensor when one was given): a seeded draw is regenerated in the backward."""
+
+    @staticmethod
+    def forward(ctx, dist, slot_size, prior_log_var, noise, seed, tag):
+        from . import ops
+        dist = dist.detach().float().contiguous()
+        noise = None if noise is None else noise.detach().float().contiguous()
+        kld_sum = torch.zeros(1, dtype=torch.float64, device=dist.device)
+        kernels = ops.kernel_sample_fwd(dist, slot_size, prior_log_var, kld_sum, noise, seed, tag)
+        rows = dist.numel() // (2 * slot_size)
+        ctx.save_for_backward(dist, noise)
+        ctx.args = (slot_size, prior_log_var, seed, tag, rows)
+        return kernels, (kld_sum[0] / rows).float()
+
+    @staticmethod
+    def backward(ctx, d_kernels, d_kld):
+        from . import ops
+        dist, noise = ctx.saved_tensors
+        slot_size, prior_log_var, seed, tag, rows = ctx.args
+        d_dist = ops.kernel_sample_bwd(dist, slot_size, prior_log_var, d_kernels.float().contiguous(), d_kld.float().reshape(1).contiguous(),
+                                       1. / rows, noise, seed, tag)
+        return d_dist, None, None, None, None, None
+
+
+def kernel_sample(dist, slot_size, prior_log_var, noise=None, seed=None, tag=0):
+    """StoSAVi's stochastic kernels under autograd (savi.py:337-365): dist [..., 2 * slot_size] = (mu | log_var) -> (kernels [..., slot_size] =
+    mu + eps * exp(log_var / 2), kld), kld = the KL divergence from the prior N(mu, exp(prior_log_var)) summed over channels and averaged over rows
+    (`host.losses.kernel_kld`), a differentiable float32 scalar on the device.  eps is `noise` (kernels' shape) when given, else
+    `ops.normal_noise(seed, tag, kernels.shape)` generated inside the kernel and regenerated in the backward.  No synchronisation."""
+    if noise is None and seed is None:
+        raise ValueError('slotformer_amd: kernel_sample needs noise= or seed=')
+    return _KernelSample.apply(dist, int(slot_size), float(prior_log_var), noise, None if noise is not None or seed is None else int(seed), int(tag))
+
+
 def linear_weight(x, weight, bias=None, relu=False):
     """act(x W^T + b) for a bare [N, K] weight under autograd.  The backward contractions work on multiples of 64, so other
     widths (the dVAE's 48-wide patch vectors, its 3-channel output) are zero-padded up and the result sliced back."""
