@@ -538,6 +538,41 @@ size_t sf_slate_generate_tok_workspace_bytes(const sf_slate_decoder* m, int B, i
 int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int B, int steps, long long* tokens_out,
                               float* logits_out, int frames_per_wg, void* ws, size_t ws_bytes, void* stream,
                               int* frames_per_wg_ran);
+/* Two things the fused step can do inside its vocabulary sweep, each logit still in a register (csrc/slate_step.hip); both add the library's
+ * counter-based Gumbel noise G(seed, i) = -log(-log(u)), u = ((mix32(i ^ s) >> 9) + 0.5) * 2^-23 with s derived from the 64-bit seed as
+ * sf_gumbel_softmax_rows_f32 derives it.  Row r = row_base + b * steps + t, element i = r * V + v (uint32): with row_base = 0 the noise is what
+ * sf_gumbel_softmax_rows_f32 adds to logits viewed as [B * steps, V]; a caller that renders a sequence in several calls passes the rows before a
+ * call as row_base and gets the bits of one call.
+ *   soft_rows (device [B][steps][64], or NULL = off): soft_rows[b, t, c] = sum_v z_v * conv0_t[v, c], z = softmax_v((l_v + G(soft_seed, i)) *
+ *     soft_scale) -- the first dVAE decoder block (a bias-free 1x1 convolution V -> 64) applied to the Gumbel-softmax relaxation of
+ *     steve_slotformer.py:97-98, computed online (running max, sum, 64 weighted accumulators; partial records merged in a fixed order), so neither
+ *     the logits nor the relaxation [B, steps, V] need exist.  conv0_t: device [V][64], the transposed weight; conv0_width must be 64.  A frame's row
+ *     does not depend on the other frames of the call.  Tokens and logits are bit-identical to a call without soft_rows.
+ *   sample != 0: token[b, t] = argmax_v(l_v * inv_temperature + G(sample_seed, i)) (fp32; ties to the lowest index) -- Gumbel-max, an exact draw
+ *     from softmax(l / T) -- and the drawn token feeds the next step.  Soft rows are computed from the raw logits either way.
+ * With an option on the fused step always runs: frames_per_wg = 0 then means ONE frame per workgroup at any batch size (beyond 192 frames that
+ * form is unmeasured, profiles/steve_render.md), and a decoder sf_slate_step_ok refuses is an error (negative code, nothing launched).
+ * Argument errors -- soft_rows without conv0_t, conv0_width != 64, a non-finite or non-positive soft_scale (with soft_rows) or inv_temperature (with
+ * sample), row_base < 0, (row_base + B * steps) * V >= 2^32 -- are reported before any device work. */
+typedef struct {
+  float* soft_rows;
+  const float* conv0_t;
+  int conv0_width;
+  float soft_scale;
+  unsigned long long soft_seed;
+  int sample;
+  float inv_temperature;
+  unsigned long long sample_seed;
+  long long row_base;
+} sf_slate_step_opts;
+/* With an option on (and a decoder the fused step takes): the fused step's own scratch -- the K/V cache [B, steps, 2 d] per block and the
+ * projected slots, nothing that grows with the vocabulary; it is at most sf_slate_generate_tok_workspace_bytes, which must also fit the launch chain.
+ * Otherwise that query's value. */
+size_t sf_slate_generate_tok_opts_workspace_bytes(const sf_slate_decoder* m, int B, int steps, const sf_slate_step_opts* opts);
+/* sf_slate_generate_tok_f32 with options; opts NULL, or soft_rows NULL and sample 0, behaves exactly as sf_slate_generate_tok_f32 does. */
+int sf_slate_generate_tok_opts_f32(const sf_slate_decoder* m, const float* slots, int B, int steps, long long* tokens_out,
+                                   float* logits_out, int frames_per_wg, void* ws, size_t ws_bytes, void* stream,
+                                   int* frames_per_wg_ran, const sf_slate_step_opts* opts);
 /* out[r, :] = table[ids[r], :], ids int64 [R], table [table_rows, d], d % 4 == 0 (the first 1x1 convolution of the dVAE decoder
  * on a one-hot token map).  An id outside the table is clamped to its ends, so a wrong id never reads out of bounds. */
 int sf_gather_rows_f32(const float* table, const long long* ids, float* out, long long R, int d, long long table_rows,

@@ -141,6 +141,11 @@ class sf_slate_decoder(C.Structure):
             ('blocks', C.POINTER(sf_slate_block))]
 
 
+class sf_slate_step_opts(C.Structure):
+    _fields_ = [('soft_rows', FP), ('conv0_t', FP), ('conv0_width', C.c_int), ('soft_scale', C.c_float), ('soft_seed', C.c_ulonglong),
+                ('sample', C.c_int), ('inv_temperature', C.c_float), ('sample_seed', C.c_ulonglong), ('row_base', C.c_longlong)]
+
+
 class sf_savi_decoder(C.Structure):
     _fields_ = ([('resolution', C.c_int), ('dec_layers', C.c_int), ('dec_channels', C.c_int * 9),
                  ('dec_strides', C.c_int * 8), ('dec_ks', C.c_int), ('dec_res', C.c_int), ('num_slots', C.c_int),
@@ -333,6 +338,9 @@ SIGNATURES = {
     'sf_slate_step_ok': (I, [C.POINTER(sf_slate_decoder)]),
     'sf_slate_generate_tok_workspace_bytes': (SZ, [C.POINTER(sf_slate_decoder), I, I]),
     'sf_slate_generate_tok_f32': (I, [C.POINTER(sf_slate_decoder), FP, I, I, VP, FP, I, VP, SZ, VP, C.POINTER(I)]),
+    'sf_slate_generate_tok_opts_workspace_bytes': (SZ, [C.POINTER(sf_slate_decoder), I, I, C.POINTER(sf_slate_step_opts)]),
+    'sf_slate_generate_tok_opts_f32': (I, [C.POINTER(sf_slate_decoder), FP, I, I, VP, FP, I, VP, SZ, VP, C.POINTER(I),
+                                           C.POINTER(sf_slate_step_opts)]),
     'sf_gather_rows_f32': (I, [FP, VP, FP, LL, I, LL, VP]),
     'sf_dvae_tokens_ok': (I, [I, I, I, I, I]),
     'sf_dvae_head_packed_bytes': (SZ, [I, I]),

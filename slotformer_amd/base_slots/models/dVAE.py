@@ -183,11 +183,25 @@ class dVAE(BaseModel):
             raise RuntimeError('slotformer_amd dVAE.detokenize_ids is inference-only: call it under torch.no_grad()')
         if not (torch.is_tensor(ids) and ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 3):
             raise RuntimeError('detokenize_ids needs int64 token ids [F,h,w] on a HIP device; there is no CPU fallback')
+        return self.detokenize_rows(ops.gather_rows(self.conv0_table(), ids.contiguous()))          # [F,h,w,64]
+
+    def conv0_table(self):
+        """The first decoder block's bias-free 1x1 convolution as a table [V, 64] (its transposed weight; cached until the weight changes):
+        what `detokenize_ids` gathers from and the fused token step of the STEVE decoder weighs its soft rows with."""
         blk = self.decoder[0]
         w = blk.m.weight
-        table = plans.cached(blk, 'ids', plans.signature(w), lambda: w.detach().reshape(w.shape[0], w.shape[1]).t().float().contiguous())   # [V, 64]
-        y = ops.gather_rows(table, ids.contiguous())                                               # [F,h,w,64]
-        return self._decoder_tail(ops.groupnorm1_nhwc(y, blk.weight.detach(), blk.bias.detach(), relu=True))
+        return plans.cached(blk, 'ids', plans.signature(w), lambda: w.detach().reshape(w.shape[0], w.shape[1]).t().float().contiguous())
+
+    def detokenize_rows(self, y):
+        """y [F,h,w,64] float32 on the device -- the output of the first decoder block's convolution, however it was computed (a row gather for
+        token ids, the fused token step's soft rows for a relaxed sample) -> image [F,3,4h,4w]: block 0's GroupNorm + ReLU, then the rest of
+        the decoder stack."""
+        if torch.is_grad_enabled():
+            raise RuntimeError('slotformer_amd dVAE.detokenize_rows is inference-only: call it under torch.no_grad()')
+        blk = self.decoder[0]
+        if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.shape[-1] == blk.m.weight.shape[0]):
+            raise RuntimeError('detokenize_rows needs float32 rows [F,h,w,%d] on a HIP device; there is no CPU fallback' % blk.m.weight.shape[0])
+        return self._decoder_tail(ops.groupnorm1_nhwc(y.contiguous(), blk.weight.detach(), blk.bias.detach(), relu=True))
 
     # ---- training forward (dVAE.py:113-139) ---------------------------------------------------------------
     def _block_t(self, x, blk, pixel_shuffle=1):

@@ -198,12 +198,14 @@ class STEVE(StoSAVi):
             return train.token_cross_entropy(pred, target)
         return ops.cross_entropy(pred, target)
 
-    def render(self, slots, soft=False, gumbel=None, seed=None, frames_per_wg=0):
+    def render(self, slots, soft=False, gumbel=None, seed=None, frames_per_wg=0, fused=False, first_frame=0, sample=False, temperature=1.0,
+               sample_seed=None):
         """Slots [F,N,D] -> frames on the device, the reconstruction of base_slots/method.py:353-378 (`trans_decoder` generates the
         token grid, `dvae` detokenises it): {'tokens' [F,h,w], 'hard' [F,3,H,W]} (+ 'soft' with soft=True); see
         `steve_render.render_slots`."""
         from ...steve_render import render_slots
-        return render_slots(self.trans_decoder, self.dvae, slots, soft=soft, gumbel=gumbel, seed=seed, frames_per_wg=frames_per_wg)
+        return render_slots(self.trans_decoder, self.dvae, slots, soft=soft, gumbel=gumbel, seed=seed, frames_per_wg=frames_per_wg, fused=fused,
+                            first_frame=first_frame, sample=sample, temperature=temperature, sample_seed=sample_seed)
 
     def train(self, mode=True):
         """steve.py: the dVAE stays in eval mode."""

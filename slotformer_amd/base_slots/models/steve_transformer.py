@@ -199,14 +199,22 @@ class STEVETransformerDecoder(nn.Module):
                                           ws.data_ptr(), ws.numel(), stream()))
         return tokens, logits.cpu()
 
-    def generate_tokens(self, slots, steps, return_logits=False, frames_per_wg=0):
-        """Greedy generation that stays on the device (`sf_slate_generate_tok_f32`): one launch per token where the fused step
+    def generate_tokens(self, slots, steps, return_logits=False, frames_per_wg=0, *, soft_table=None, soft_scale=10.0, soft_seed=0,
+                        sample=False, temperature=1.0, sample_seed=0, row_base=0):
+        """Generation that stays on the device (`sf_slate_generate_tok_opts_f32`): one launch per token where the fused step
         applies (`sf_slate_step_ok`), a workgroup owning `frames_per_wg` frames (1, 2 or 4; 0 = the library's choice, which may
         be the launch chain of `generate_cached`).  Returns (tokens [B,steps] int64, logits [B,steps,V] or None), both on the
         device; the logits are only written with return_logits=True.  `self.last_generate_form` is the form that ran: 0 for the
-        launch chain, else the frames per workgroup of the fused step."""
+        launch chain, else the frames per workgroup of the fused step.
+
+        Keyword-only, inside the fused step's vocabulary sweep (an error where the fused step refuses the decoder; frames_per_wg = 0
+        then means one frame per workgroup).  `soft_table` [V,64] (`dVAE.conv0_table()`): a third value is returned, the soft rows
+        [B,steps,64] = softmax((logits + Gumbel(soft_seed)) * soft_scale) @ soft_table, without the [B,steps,V] buffers.
+        `sample=True`: the tokens are drawn from softmax(logits / temperature) by Gumbel-max with the noise of `sample_seed` instead
+        of taken greedily.  Noise row r = row_base + b * steps + t, element r * V + v of `train.gumbel_noise`: a caller that splits a
+        sequence of frames over several calls passes the rows before the call as `row_base`."""
         import ctypes as C
-        from ..._lib import check, lib
+        from ..._lib import check, lib, sf_slate_step_opts
         if self.training or torch.is_grad_enabled():
             raise RuntimeError('slotformer_amd STEVETransformerDecoder is inference-only: .eval() + torch.no_grad()')
         if not (torch.is_tensor(slots) and slots.is_cuda and slots.dtype == torch.float32):
@@ -219,21 +227,56 @@ class STEVETransformerDecoder(nn.Module):
         m = self._slate_plan().struct
         tokens = torch.empty(B, steps, dtype=torch.int64, device=slots.device)
         logits = torch.empty(B, steps, self.vocab_size, dtype=torch.float32, device=slots.device) if return_logits else None
-        ws = scratch(lib().sf_slate_generate_tok_workspace_bytes, C.byref(m), B, steps, device=slots.device)
         ran = C.c_int(-1)
-        check(lib().sf_slate_generate_tok_f32(C.byref(m), slots.data_ptr(), B, steps, tokens.data_ptr(), ptr(logits), int(frames_per_wg),
-                                              ws.data_ptr(), ws.numel(), stream(), C.byref(ran)))
+        if soft_table is None and not sample:
+            ws = scratch(lib().sf_slate_generate_tok_workspace_bytes, C.byref(m), B, steps, device=slots.device)
+            check(lib().sf_slate_generate_tok_f32(C.byref(m), slots.data_ptr(), B, steps, tokens.data_ptr(), ptr(logits), int(frames_per_wg),
+                                                  ws.data_ptr(), ws.numel(), stream(), C.byref(ran)))
+            self.last_generate_form = ran.value
+            return tokens, logits
+        o = sf_slate_step_opts()
+        soft = None
+        if soft_table is not None:
+            if not (torch.is_tensor(soft_table) and soft_table.is_cuda and soft_table.dtype == torch.float32 and soft_table.is_contiguous()
+                    and soft_table.dim() == 2 and soft_table.shape[0] == self.vocab_size):
+                raise TypeError('generate_tokens: soft_table is a contiguous float32 device tensor [vocab_size, 64]')
+            soft = torch.empty(B, steps, soft_table.shape[1], dtype=torch.float32, device=slots.device)
+            o.soft_rows, o.conv0_t, o.conv0_width = soft.data_ptr(), soft_table.data_ptr(), int(soft_table.shape[1])
+            o.soft_scale, o.soft_seed = float(soft_scale), int(soft_seed) & 0xffffffffffffffff
+        if sample:
+            o.sample, o.inv_temperature, o.sample_seed = 1, 1.0 / float(temperature), int(sample_seed) & 0xffffffffffffffff
+        o.row_base = int(row_base)
+        ws = scratch(lib().sf_slate_generate_tok_opts_workspace_bytes, C.byref(m), B, steps, C.byref(o), device=slots.device)
+        check(lib().sf_slate_generate_tok_opts_f32(C.byref(m), slots.data_ptr(), B, steps, tokens.data_ptr(), ptr(logits), int(frames_per_wg),
+                                                   ws.data_ptr(), ws.numel(), stream(), C.byref(ran), C.byref(o)))
         self.last_generate_form = ran.value
-        return tokens, logits
+        return (tokens, logits) if soft_table is None else (tokens, logits, soft)
 
-    def generate(self, slots, steps, sample=False, temperature=1.0):
+    def step_ok(self):
+        """whether the fused token step (`sf_slate_step_ok`) takes this decoder's shapes"""
+        import ctypes as C
+        from ..._lib import lib, sf_slate_decoder
+        m = sf_slate_decoder()   # shapes only: the query reads no weight
+        m.d_model, m.num_heads, m.num_layers = self.d_model, self.n_head, len(self.tf_dec.blocks)
+        m.vocab_size, m.num_slots, m.max_len = self.vocab_size, self.num_slots, self.max_len
+        return bool(lib().sf_slate_step_ok(C.byref(m)))
+
+    def generate(self, slots, steps, sample=False, temperature=1.0, seed=None):
         """Autoregressive generation (steve_transformer.py:305-333): the whole prefix is re-run every step, as in the reference;
         greedy (sample=False: argmax) or sampled (sample=True: one draw per step from softmax(logits / temperature) -- the softmax a HIP
         launch, the draw torch.multinomial on the device generator, as the reference draws it).  Returns (tokens [B,steps] on device,
-        logits [B,steps,V] on the CPU like the reference)."""
+        logits [B,steps,V] on the CPU like the reference).  sample=True with `seed`: the same distribution drawn by Gumbel-max inside the
+        fused token step over the K/V cache (`generate_tokens(sample=True, sample_seed=seed)`), one launch per token instead of a forward
+        over the prefix; NotImplementedError where the fused step refuses the decoder."""
         assert not self.training
         B = slots.shape[0]
         assert steps - 1 <= self.max_len
+        if sample and seed is not None:
+            if not self.step_ok():
+                raise NotImplementedError('generate(sample=True, seed=...) runs the fused token step, which refuses this decoder '
+                                          '(sf_slate_step_ok); without seed the draw is torch.multinomial over a prefix re-run')
+            tokens, logits = self.generate_tokens(slots, steps, return_logits=True, sample=True, temperature=temperature, sample_seed=seed)
+            return tokens, logits.cpu()
         idx_cond = torch.zeros((B, 0), dtype=torch.int64, device=slots.device)
         all_logits = []
         for _ in range(steps):

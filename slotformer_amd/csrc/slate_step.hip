@@ -7,13 +7,22 @@
 // cooperative launch.  Activations of a frame stay in LDS; the weights (torch layouts, [N][K] row-major) are streamed
 // with 16-byte loads, eight lanes per weight row (128 contiguous bytes per row and load), and shared by the FR frames.
 // Arithmetic is plain fp32 FMA.
+//
+// The head's epilogue has two compile-time options (sf_slate_generate_tok_opts_f32), both built on the counter-based Gumbel noise of gumbel_noise.h
+// added to a logit while it is still in a register: the soft rows (the Gumbel-softmax relaxation times the first dVAE decoder block, as an online
+// softmax over the vocabulary sweep: 64 numbers per token instead of V) and Gumbel-max sampling of the token.  The greedy instantiation is the code
+// it was without them.
 #include "../../include/slotformer_hip.h"
 #include "sf_internal.h"
+#include "gumbel_noise.h"
+#include <cmath>
 
 namespace {
 constexpr int ST_NT = 1024;          // threads per workgroup
 constexpr int ST_NW = ST_NT / 64;    // waves
 constexpr int ST_MAXL = 8;           // decoder blocks the kernel argument holds
+constexpr int ST_SOFT_C = 64;        // channels of a soft row (the first dVAE decoder block's width): eight per lane of a weight-row group
+constexpr int ST_SOFT_REC = ST_SOFT_C + 2;   // a wave's soft record per frame: running max, sum, weighted channels
 
 struct StepBlock {
   const float *ln1_g, *ln1_b, *wqkv, *wo, *ln2_g, *ln2_b, *wq_c, *wo_c, *ln3_g, *ln3_b, *w1, *b1, *w2, *b2;
@@ -27,6 +36,12 @@ struct StepArgs {
   long long* tokens;   // [B][steps]
   float* logits;       // [B][steps][V] or NULL
   int d, H, NL, V, N, B, steps, t;
+  // the noise epilogues of the head (SOFT / SAMPLE instantiations only)
+  float* soft_rows;       // [B][steps][ST_SOFT_C]
+  const float* conv0_t;   // [V][ST_SOFT_C]
+  float soft_scale, inv_temperature;
+  uint32_t soft_sseed, sample_sseed;
+  long long row_base;
 };
 
 __device__ __forceinline__ float dot4(const f32x4 w, const f32x4 x, float acc) {
@@ -37,8 +52,9 @@ __device__ __forceinline__ float dot4(const f32x4 w, const f32x4 x, float acc) {
 }
 
 // y[fr][n] = sum_k W[n][k] * xin[fr][k] for n < N, fr < FR; K a multiple of 32.  Eight lanes share a row of W (lane l takes the 16-byte pieces
-// l, l + 8, ...), the inputs come from LDS (rows xs floats apart).  epi(fr, n, value) runs on the first lane of each group of eight.
-template <int FR, class Epi>
+// l, l + 8, ...), the inputs come from LDS (rows xs floats apart).  epi(fr, n, value) runs on the first lane of each group of eight; with ALL,
+// epi(n, values[FR]) runs once per row on all eight lanes instead (sf_sum8 leaves the same bits in each of them).
+template <int FR, bool ALL = false, class Epi>
 __device__ __forceinline__ void gemv_rows(const float* __restrict__ W, int N, int K, const float* xin, int xs, Epi epi) {
   const int l = threadIdx.x & 7, g = threadIdx.x >> 3;
   const int K4 = K >> 2, KI = K >> 5;
@@ -68,9 +84,13 @@ __device__ __forceinline__ void gemv_rows(const float* __restrict__ W, int N, in
     }
 #pragma unroll
     for (int f = 0; f < FR; ++f) acc[f] = sf_sum8(acc[f]);
-    if (l == 0) {
+    if constexpr (ALL) {
+      epi(n, acc);
+    } else {
+      if (l == 0) {
 #pragma unroll
-      for (int f = 0; f < FR; ++f) epi(f, n, acc[f]);
+        for (int f = 0; f < FR; ++f) epi(f, n, acc[f]);
+      }
     }
   }
 }
@@ -212,7 +232,10 @@ __device__ __forceinline__ void attention(const float* q, int qs, const float* k
   __syncthreads();
 }
 
-template <int FR, int HD16>
+// The head's epilogue is chosen at compile time.  Neither flag: the greedy step.  SOFT: next to the greedy (or sampled) choice, the soft row
+// y[c] = sum_v softmax_v((l_v + G(soft_seed, r V + v)) * soft_scale) * Wt[v][c] of every frame, online over the vocabulary sweep.  SAMPLE: the token
+// is argmax_v(l_v * inv_temperature + G(sample_seed, r V + v)) -- Gumbel-max, an exact draw from softmax(l / T).  r = row_base + b * steps + t.
+template <int FR, int HD16, bool SOFT, bool SAMPLE>
 __global__ __launch_bounds__(ST_NT) void slate_step_kernel(const StepArgs a) {
   extern __shared__ __attribute__((aligned(16))) float st_lds[];
   constexpr int hd = HD16 * 16;
@@ -229,6 +252,7 @@ __global__ __launch_bounds__(ST_NT) void slate_step_kernel(const StepArgs a) {
   const int nparts = (FR * H > ST_NW ? FR * H : ST_NW);
   float* bestv = part + nparts * (hd + 2);   // [ST_NW][FR]
   int* besti = (int*)(bestv + ST_NW * FR);   // [ST_NW][FR]
+  float* softrec = (float*)(besti + ST_NW * FR);   // SOFT only: [ST_NW][FR][ST_SOFT_REC]
   float* qb = qkv;
   float* kb = qkv + FR * d;
   float* vb = qkv + 2 * FR * d;
@@ -299,13 +323,103 @@ __global__ __launch_bounds__(ST_NT) void slate_step_kernel(const StepArgs a) {
   {
     float* lrow = a.logits ? a.logits + ((long long)b0 * a.steps + t) * V : nullptr;
     const long long lfs = (long long)a.steps * V;
-    gemv_rows<FR>(a.head_w, V, d, xn, d, [&](int f, int n, float v) {
-      if (lrow && f < nf) lrow[f * lfs + n] = v;
-      if (v > best[f]) {   // n grows within a lane: the first maximum is kept
-        best[f] = v;
-        bi[f] = n;
+    if constexpr (!SOFT && !SAMPLE) {
+      gemv_rows<FR>(a.head_w, V, d, xn, d, [&](int f, int n, float v) {
+        if (lrow && f < nf) lrow[f * lfs + n] = v;
+        if (v > best[f]) {   // n grows within a lane: the first maximum is kept
+          best[f] = v;
+          bi[f] = n;
+        }
+      });
+    } else {
+      const int l = tid & 7;
+      // element index of (frame f, word 0) in the noise streams: below 2^32 for every frame that exists (checked by the host)
+      uint32_t nbase[FR];
+#pragma unroll
+      for (int f = 0; f < FR; ++f) nbase[f] = (uint32_t)((a.row_base + (long long)(b0 + f) * a.steps + t) * V);
+      // this lane's share of the soft records: channels 8 l .. 8 l + 7; max and sum are the same in the eight lanes of a group
+      float sm[FR], ss[FR];
+      f32x4 sa0[FR], sa1[FR];
+#pragma unroll
+      for (int f = 0; f < FR; ++f) {
+        sm[f] = -INFINITY;
+        ss[f] = 0.f;
+        sa0[f] = sa1[f] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
-    });
+      gemv_rows<FR, true>(a.head_w, V, d, xn, d, [&](int n, const float* v) {
+        f32x4 w0, w1;
+        if constexpr (SOFT) {
+          const f32x4* wt = (const f32x4*)(a.conv0_t + (long long)n * ST_SOFT_C) + 2 * l;
+          w0 = wt[0];
+          w1 = wt[1];
+        }
+#pragma unroll
+        for (int f = 0; f < FR; ++f) {
+          if (l == 0) {
+            if (lrow && f < nf) lrow[f * lfs + n] = v[f];
+            float score = v[f];
+            if constexpr (SAMPLE) score = v[f] * a.inv_temperature + sf_gumbel(nbase[f] + (uint32_t)n, a.sample_sseed);
+            if (score > best[f]) {   // n grows within a lane: the first maximum is kept
+              best[f] = score;
+              bi[f] = n;
+            }
+          }
+          if constexpr (SOFT) {
+            const float z = (v[f] + sf_gumbel(nbase[f] + (uint32_t)n, a.soft_sseed)) * a.soft_scale;
+            const float mn = fmaxf(sm[f], z);
+            const float corr = expf(sm[f] - mn), p = expf(z - mn);   // first entry: exp(-inf) = 0
+            ss[f] = fmaf(ss[f], corr, p);
+            sa0[f] = sa0[f] * corr + w0 * p;
+            sa1[f] = sa1[f] * corr + w1 * p;
+            sm[f] = mn;
+          }
+        }
+      });
+      if constexpr (SOFT) {
+        // merge the eight groups of the wave (lanes l, l + 8, ..., l + 56), then one record per wave and frame to LDS.  A group that saw no word
+        // holds max = -inf and weighs 0, whatever its partner holds.
+        const int w = tid >> 6, lane = tid & 63;
+#pragma unroll
+        for (int f = 0; f < FR; ++f) {
+          float m = sm[f], s = ss[f];
+          f32x4 c0 = sa0[f], c1 = sa1[f];
+#pragma unroll
+          for (int o = 8; o < 64; o <<= 1) {
+            const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+            f32x4 o0, o1;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              o0[e] = __shfl_xor(c0[e], o, 64);
+              o1[e] = __shfl_xor(c1[e], o, 64);
+            }
+            const float M = fmaxf(m, om);
+            const float ea = (m == -INFINITY) ? 0.f : expf(m - M), eb = (om == -INFINITY) ? 0.f : expf(om - M);
+            // the lower lane's record first in every sum, so that both partners hold the same bits
+            const bool lo = (lane & o) == 0;
+            const float e1 = lo ? ea : eb, e2 = lo ? eb : ea;
+            s = (lo ? s : os) * e1 + (lo ? os : s) * e2;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              c0[e] = (lo ? c0[e] : o0[e]) * e1 + (lo ? o0[e] : c0[e]) * e2;
+              c1[e] = (lo ? c1[e] : o1[e]) * e1 + (lo ? o1[e] : c1[e]) * e2;
+            }
+            m = M;
+          }
+          float* rec = softrec + (w * FR + f) * ST_SOFT_REC;
+          if (lane < 8) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              rec[2 + 8 * lane + e] = c0[e];
+              rec[2 + 8 * lane + 4 + e] = c1[e];
+            }
+          }
+          if (lane == 0) {
+            rec[0] = m;
+            rec[1] = s;
+          }
+        }
+      }
+    }
   }
   const int w = tid >> 6, lane = tid & 63;
 #pragma unroll
@@ -340,28 +454,50 @@ __global__ __launch_bounds__(ST_NT) void slate_step_kernel(const StepArgs a) {
     }
     a.tokens[(long long)(b0 + tid) * a.steps + t] = bx;
   }
+  if constexpr (SOFT) {
+    // wave f merges the sixteen wave records of frame f in wave order, lane c taking channel c (the __syncthreads above ordered the records)
+    if (w < nf) {
+      float M = -INFINITY;
+      for (int ww = 0; ww < ST_NW; ++ww) M = fmaxf(M, softrec[(ww * FR + w) * ST_SOFT_REC]);
+      float num = 0.f, den = 0.f;
+      for (int ww = 0; ww < ST_NW; ++ww) {
+        const float* rec = softrec + (ww * FR + w) * ST_SOFT_REC;
+        if (rec[0] > -INFINITY) {
+          const float e = expf(rec[0] - M);
+          den = fmaf(e, rec[1], den);
+          num = fmaf(e, rec[2 + lane], num);
+        }
+      }
+      a.soft_rows[((long long)(b0 + w) * a.steps + t) * ST_SOFT_C + lane] = num / den;
+    }
+  }
 }
 
-size_t step_lds_bytes(int FR, int d, int H) {
+size_t step_lds_bytes(int FR, int d, int H, bool soft) {
   const int hd = d / H, nparts = FR * H > ST_NW ? FR * H : ST_NW;
-  return ((size_t)FR * 10 * d + (size_t)nparts * (hd + 2) + 2 * ST_NW * FR) * sizeof(float);
+  return ((size_t)FR * 10 * d + (size_t)nparts * (hd + 2) + 2 * ST_NW * FR + (soft ? (size_t)ST_NW * FR * ST_SOFT_REC : 0)) * sizeof(float);
 }
 
-template <int FR, int HD16>
+template <int FR, int HD16, bool SOFT, bool SAMPLE>
 int step_launch(const StepArgs& a, hipStream_t st) {
-  const size_t lds = step_lds_bytes(FR, a.d, a.H);
-  SF_TRY(sf_ensure_dyn_lds((const void*)slate_step_kernel<FR, HD16>, lds));
-  hipLaunchKernelGGL((slate_step_kernel<FR, HD16>), dim3((unsigned)((a.B + FR - 1) / FR)), dim3(ST_NT), lds, st, a);
+  const size_t lds = step_lds_bytes(FR, a.d, a.H, SOFT);
+  SF_TRY(sf_ensure_dyn_lds((const void*)slate_step_kernel<FR, HD16, SOFT, SAMPLE>, lds));
+  hipLaunchKernelGGL((slate_step_kernel<FR, HD16, SOFT, SAMPLE>), dim3((unsigned)((a.B + FR - 1) / FR)), dim3(ST_NT), lds, st, a);
   SF_CHECK_LAUNCH();
   return 0;
 }
+template <int FR, int HD16>
+int step_launch_mode(const StepArgs& a, bool soft, bool sample, hipStream_t st) {
+  if (soft) return sample ? step_launch<FR, HD16, true, true>(a, st) : step_launch<FR, HD16, true, false>(a, st);
+  return sample ? step_launch<FR, HD16, false, true>(a, st) : step_launch<FR, HD16, false, false>(a, st);
+}
 template <int FR>
-int step_launch_hd(const StepArgs& a, hipStream_t st) {
+int step_launch_hd(const StepArgs& a, bool soft, bool sample, hipStream_t st) {
   switch (a.d / a.H) {
-    case 16: return step_launch<FR, 1>(a, st);
-    case 32: return step_launch<FR, 2>(a, st);
-    case 48: return step_launch<FR, 3>(a, st);
-    case 64: return step_launch<FR, 4>(a, st);
+    case 16: return step_launch_mode<FR, 1>(a, soft, sample, st);
+    case 32: return step_launch_mode<FR, 2>(a, soft, sample, st);
+    case 48: return step_launch_mode<FR, 3>(a, soft, sample, st);
+    case 64: return step_launch_mode<FR, 4>(a, soft, sample, st);
   }
   return sf_set_err(-1, "invalid argument: slate_step head size", __FILE__, __LINE__);
 }
@@ -410,15 +546,45 @@ size_t sf_slate_generate_tok_workspace_bytes(const sf_slate_decoder* m, int B, i
   return fused > chain ? fused : chain;
 }
 
+size_t sf_slate_generate_tok_opts_workspace_bytes(const sf_slate_decoder* m, int B, int steps, const sf_slate_step_opts* opts) {
+  // with an option on only the fused step can run: its carve alone (a k|v cache, no row buffers, nothing that grows with the vocabulary)
+  if (opts && (opts->soft_rows || opts->sample) && m && B > 0 && steps > 0 && sf_slate_step_ok(m))
+    return sf_slate_gen_carve(nullptr, m, B, steps, (size_t)2 * m->d_model, false).bytes + STEP_WS_SLACK;
+  return sf_slate_generate_tok_workspace_bytes(m, B, steps);
+}
+
 int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int B, int steps, long long* tokens_out, float* logits_out,
                               int frames_per_wg, void* ws, size_t ws_bytes, void* stream, int* frames_per_wg_ran) {
+  return sf_slate_generate_tok_opts_f32(m, slots, B, steps, tokens_out, logits_out, frames_per_wg, ws, ws_bytes, stream, frames_per_wg_ran,
+                                        nullptr);
+}
+
+int sf_slate_generate_tok_opts_f32(const sf_slate_decoder* m, const float* slots, int B, int steps, long long* tokens_out, float* logits_out,
+                                   int frames_per_wg, void* ws, size_t ws_bytes, void* stream, int* frames_per_wg_ran,
+                                   const sf_slate_step_opts* opts) {
   SF_REQUIRE(m && slots && tokens_out && ws, "sf_slate_generate_tok_f32: null pointer");
   SF_REQUIRE(B >= 1 && steps >= 1 && steps - 1 <= m->max_len, "sf_slate_generate_tok_f32: bad batch / step count");
   SF_REQUIRE(frames_per_wg == 0 || frames_per_wg == 1 || frames_per_wg == 2 || frames_per_wg == 4,
              "sf_slate_generate_tok_f32: frames_per_wg must be 0, 1, 2 or 4");
-  SF_REQUIRE(ws_bytes >= sf_slate_generate_tok_workspace_bytes(m, B, steps), "sf_slate_generate_tok_f32: workspace too small");
+  const bool soft = opts && opts->soft_rows, sample = opts && opts->sample;
+  if (soft) {
+    SF_REQUIRE(opts->conv0_t, "sf_slate_generate_tok_opts_f32: soft_rows without the table conv0_t");
+    SF_REQUIRE(opts->conv0_width == ST_SOFT_C, "sf_slate_generate_tok_opts_f32: conv0_width must be 64");
+    SF_REQUIRE(std::isfinite(opts->soft_scale) && opts->soft_scale > 0.f, "sf_slate_generate_tok_opts_f32: soft_scale must be finite and > 0");
+  }
+  if (sample)
+    SF_REQUIRE(std::isfinite(opts->inv_temperature) && opts->inv_temperature > 0.f,
+               "sf_slate_generate_tok_opts_f32: inv_temperature must be finite and > 0");
+  if (soft || sample) {
+    SF_REQUIRE(opts->row_base >= 0, "sf_slate_generate_tok_opts_f32: negative row_base");
+    SF_REQUIRE(m->vocab_size >= 1 && opts->row_base < (1LL << 32) &&
+                   (opts->row_base + (long long)B * steps) * (long long)m->vocab_size < (1LL << 32),
+               "sf_slate_generate_tok_opts_f32: (row_base + B * steps) * V must stay below 2^32");
+    SF_REQUIRE(sf_slate_step_ok(m), "sf_slate_generate_tok_opts_f32: soft rows and sampling need the fused step, which refuses this decoder");
+  }
+  SF_REQUIRE(ws_bytes >= sf_slate_generate_tok_opts_workspace_bytes(m, B, steps, opts), "sf_slate_generate_tok_f32: workspace too small");
   int FR = 0;
-  if (sf_slate_step_ok(m)) FR = frames_per_wg ? frames_per_wg : step_rule(B);
+  if (sf_slate_step_ok(m)) FR = frames_per_wg ? frames_per_wg : ((soft || sample) ? 1 : step_rule(B));
   if (frames_per_wg_ran) *frames_per_wg_ran = FR;
   if (FR == 0) return sf_slate_generate_f32(m, slots, B, steps, tokens_out, logits_out, ws, ws_bytes, stream);
   SF_REQUIRE(m->in_proj_w && m->in_proj_b && m->tok_emb && m->pos_emb && m->lnf_g && m->lnf_b && m->head_w && m->blocks,
@@ -450,11 +616,17 @@ int sf_slate_generate_tok_f32(const sf_slate_decoder* m, const float* slots, int
   a.tok_emb = m->tok_emb, a.pos_emb = m->pos_emb, a.lnf_g = m->lnf_g, a.lnf_b = m->lnf_b, a.head_w = m->head_w;
   a.tokens = tokens_out, a.logits = logits_out;
   a.d = d, a.H = m->num_heads, a.NL = NL, a.V = m->vocab_size, a.N = N, a.B = B, a.steps = steps;
+  if (soft) {
+    a.soft_rows = opts->soft_rows, a.conv0_t = opts->conv0_t, a.soft_scale = opts->soft_scale;
+    a.soft_sseed = sf_gumbel_seed(opts->soft_seed);
+  }
+  if (sample) a.inv_temperature = opts->inv_temperature, a.sample_sseed = sf_gumbel_seed(opts->sample_seed);
+  if (soft || sample) a.row_base = opts->row_base;
   for (int t = 0; t < steps; ++t) {
     a.t = t;
-    if (FR == 1) SF_TRY(step_launch_hd<1>(a, st));
-    else if (FR == 2) SF_TRY(step_launch_hd<2>(a, st));
-    else SF_TRY(step_launch_hd<4>(a, st));
+    if (FR == 1) SF_TRY(step_launch_hd<1>(a, soft, sample, st));
+    else if (FR == 2) SF_TRY(step_launch_hd<2>(a, soft, sample, st));
+    else SF_TRY(step_launch_hd<4>(a, soft, sample, st));
   }
   return 0;
 }

@@ -7,9 +7,10 @@
 #include "train_blocks.h"
 #include "sf_arena.h"
 #include "bf16_planes.h"
+#include "gumbel_noise.h"
 
 namespace {
-constexpr int GN_P = 64;   // partial records per sample
+constexpr int GN_P = 64;  // partial records per sample
 
 // ---- GroupNorm(num_groups = 1) statistics: per sample, over all H*W*C elements (steve_utils.py:124-126) ----
 // grid (GN_P, F): block (p, f) reduces its slice to (sum, sum of squares) in double.
@@ -637,13 +638,8 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float* __restrict_
   if (t == 0) loss[r] = logf((sh[0] + sh[1]) + (sh[2] + sh[3])) + mx - xr[tgt[r]];
 }
 
-// y[r] = softmax((x[r] + add[r]) * scale) over V columns; add may be null.  One workgroup per row.
-// Gumbel(0, 1) sample of element idx as a pure function of (seed, idx): -log(E) with E = -log(u) ~ Exp(1), u uniform on the 2^23
-// midpoints of (0, 1) -- the noise of steve_utils.py:30-35 without a trip through memory (tests rebuild it on the host).
-__device__ __forceinline__ float sf_gumbel(uint32_t idx, uint32_t sseed) {
-  const float u = ((float)(sf_mix32(idx ^ sseed) >> 9) + 0.5f) * 1.1920929e-7f;
-  return -logf(-logf(u));
-}
+// y[r] = softmax((x[r] + add[r]) * scale) over V columns; add may be null.  One workgroup per row.  With `noise` the Gumbel(0, 1) sample of
+// gumbel_noise.h is added instead: the noise of steve_utils.py:30-35 without a trip through memory.
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ x, const float* __restrict__ add,
                                                            float scale, float* __restrict__ y, int V, int noise, uint32_t sseed,
                                                            int logout) {
@@ -1137,8 +1133,7 @@ int sf_gumbel_softmax_rows_f32(const float* x, unsigned long long seed, float sc
   SF_REQUIRE(x && y && R >= 0 && V > 0, "sf_gumbel_softmax_rows_f32: bad arguments");
   SF_REQUIRE(R * (long long)V < (1LL << 32), "sf_gumbel_softmax_rows_f32: more than 2^32 elements");
   if (R == 0) return 0;
-  const uint32_t sseed = sf_mix32((uint32_t)seed ^ sf_mix32((uint32_t)(seed >> 32) + 0x9e3779b9u));
-  return softmax_rows_launch(x, nullptr, scale, y, R, V, 1, sseed, (hipStream_t)stream);
+  return softmax_rows_launch(x, nullptr, scale, y, R, V, 1, sf_gumbel_seed(seed), (hipStream_t)stream);
 }
 
 // loss_rows[r] = -log softmax(x[r])[target[r]];  mean_out[0] = mean over rows (F.cross_entropy default reduction)

@@ -125,21 +125,35 @@ def render_chunks(num_frames, frames_per_call=64):
 
 
 @torch.no_grad()
-def render_video_slots(model, slots, frames_per_call=64, soft=False, to_host=False):
+def render_video_slots(model, slots, frames_per_call=64, soft=False, to_host=False, fused=False, seed=None, sample=False, temperature=1.0,
+                       sample_seed=None):
     """The device form of STEVE's `_slots2video` (video_prediction/method.py:207-219): slots [V,T,N,D] or [T,N,D] -> the frames
     `model.render` draws from them (the hard image; with soft=True the Gumbel-softmax one), float32 [V,T,3,H,W] / [T,3,H,W] on the
     device.  `model` is a STEVESlotFormer or STEVE in eval mode.  The frames go through `render` in chunks of `frames_per_call`
     (at 64 frames of the 4096-word vocabulary the optional logits take 1 GB).  to_host=True: uint8 [..., H, W, 3] in pinned host
-    memory instead (`egress.frames_to_uint8` per chunk), each chunk downloaded on a side stream behind the next chunk's generation."""
-    from . import egress
+    memory instead (`egress.frames_to_uint8` per chunk), each chunk downloaded on a side stream behind the next chunk's generation.
+    fused=True (with soft=True): the soft image from the soft rows of the fused token step, no [.., V] buffer (`render_slots(fused=True)`);
+    sample=True: tokens drawn from softmax(logits / temperature) inside the step.  With either, one `seed` / `sample_seed` (default: fresh
+    ones) serves the whole call and each chunk passes its first frame's index, so the chunked video has the bits of one `render` call
+    (the noise index frames * tokens * V must stay below 2^32 -- under 1024 frames of 1024 tokens at V 4096 -- and the library refuses more)."""
+    from . import egress, steve_render
     lead = tuple(slots.shape[:-2])
     assert slots.dim() in (3, 4), 'slots are [V, T, N, D] or [T, N, D]'
     flat = slots.reshape((-1, ) + tuple(slots.shape[-2:])).float().to(model.device).contiguous()
     key = 'soft' if soft else 'hard'
     F_ = flat.shape[0]
     out, copies, keep = None, None, []
+    kw = {}
+    if fused or sample:
+        kw = dict(fused=fused, sample=sample, temperature=temperature,
+                  seed=steve_render._fresh_seed() if seed is None else seed,
+                  sample_seed=steve_render._fresh_seed() if sample_seed is None else sample_seed)
+    elif seed is not None:
+        kw = dict(seed=seed)
     for a, b in render_chunks(F_, frames_per_call):
-        frames = model.render(flat[a:b], soft=soft)[key]
+        if fused or sample:
+            kw['first_frame'] = a
+        frames = model.render(flat[a:b], soft=soft, **kw)[key]
         if not to_host:
             if out is None:
                 out = torch.empty((F_, ) + tuple(frames.shape[1:]), dtype=torch.float32, device=frames.device)

@@ -1022,8 +1022,9 @@ def gumbel_softmax(logits, gumbels=None, tau=1., hard=False, seed=None):
     return y_hard - y_soft.detach() + y_soft
 
 
-def gumbel_noise(seed, numel):
-    """Host restatement of the in-kernel Gumbel noise (steve_decoder.hip: sf_gumbel) for tests: float32 [numel]."""
+def gumbel_noise(seed, numel, start=0):
+    """Host restatement of the in-kernel Gumbel noise (csrc/gumbel_noise.h: sf_gumbel) for tests: float32 [numel], the elements
+    [start, start + numel) of the stream of `seed` (indices are uint32)."""
     import numpy as np
 
     def mix(h):
@@ -1038,7 +1039,7 @@ def gumbel_noise(seed, numel):
     with np.errstate(over='ignore'):
         inner = mix(np.array([np.uint32((seed >> 32) & 0xffffffff) + np.uint32(0x9e3779b9)], dtype=np.uint32))
         sseed = mix(np.array([np.uint32(seed & 0xffffffff)], dtype=np.uint32) ^ inner)[0]
-        h = mix(np.arange(numel, dtype=np.uint32) ^ sseed)
+        h = mix(np.arange(int(start), int(start) + int(numel), dtype=np.uint64).astype(np.uint32) ^ sseed)
     u = ((h >> np.uint32(9)).astype(np.float32) + np.float32(0.5)) * np.float32(1.1920929e-7)
     return torch.from_numpy(-np.log(-np.log(u)))
 

@@ -66,11 +66,13 @@ class STEVESlotFormer(SlotFormer):
         hard = self.dvae.detokenize(self._token_map(one_hot))
         return soft, hard
 
-    def render(self, slots, soft=False, gumbel=None, seed=None, frames_per_wg=0):
+    def render(self, slots, soft=False, gumbel=None, seed=None, frames_per_wg=0, fused=False, first_frame=0, sample=False, temperature=1.0,
+               sample_seed=None):
         """`decode` that stays on the device (`steve_render.render_slots`): slots [F,N,D] -> {'tokens' [F,h,w], 'hard' [F,3,H,W]}
         (+ 'soft' with soft=True; its noise is `gumbel` [F,V,h,w] or generated in the kernel from `seed`)."""
         from ...steve_render import render_slots
-        return render_slots(self.decoder, self.dvae, slots, soft=soft, gumbel=gumbel, seed=seed, frames_per_wg=frames_per_wg)
+        return render_slots(self.decoder, self.dvae, slots, soft=soft, gumbel=gumbel, seed=seed, frames_per_wg=frames_per_wg, fused=fused,
+                            first_frame=first_frame, sample=sample, temperature=temperature, sample_seed=sample_seed)
 
     def rollout(self, past_slots, pred_len, decode=False, with_gt=True):
         """Slots only: this model never renders inside rollout (steve_slotformer.py:105-109)."""

@@ -12,7 +12,15 @@ At the Physion decoder shape (V 4096, d 192, 4 heads of 48, 4 blocks, 6 slots) a
 All forms run in the same process, alternating call by call after a warm-up of each, timed with device events around whole calls.  The tables replace the
 text between the two `bench_steve_render` marker lines of the --md file.  `--counter-run` does one fused generation (12 frames, one frame per
 workgroup) and nothing else: the command a counter pass (rocprofv3 --pmc FETCH_SIZE, in a run of its own: tools/pmc_cmd.sh) is made over.
-No GPU: the tool fails, it measures nothing."""
+No GPU: the tool fails, it measures nothing.
+
+`--soft` measures the head epilogues of the fused step instead (profiles/steve_render_soft.md), at 12 and 64 frames, every pair of forms in one
+process in alternating windows of `--window` seconds (1 s or more) of whole calls:
+  (a) microseconds per token step, greedy against greedy + soft rows (C ABI, no logits written); with `--other-lib PATH` also the greedy step of
+      another build of the library (the parent commit's) in the same alternation;
+  (b) milliseconds per soft frame, `render_slots(soft=True, fused=True)` against `render_slots(soft=True)`;
+  (c) `torch.cuda.max_memory_allocated` of one call of each;
+  (d) 64 sampled steps, `generate(sample=True, seed=...)` (the fused step) against `generate(sample=True)` (prefix re-run + torch.multinomial)."""
 import argparse
 import ctypes as C
 import json
@@ -130,6 +138,104 @@ def measure_render(dec, dvae, F_, reps):
     return row
 
 
+def windows(forms, window_s, rounds):
+    """forms: name -> callable.  `rounds` alternating windows per form, each of whole calls until window_s seconds have passed (at least two calls);
+    returns name -> list of per-window mean milliseconds per call"""
+    import time
+    out = {k: [] for k in forms}
+    for fn in forms.values():
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for k, fn in forms.items():
+            t0, n, ms = time.perf_counter(), 0, 0.
+            while n < 2 or time.perf_counter() - t0 < window_s:
+                ms += timed(fn)
+                n += 1
+            out[k].append(ms / n)
+    return out
+
+
+def summary(v, scale=1.0, nd=1):
+    return {'median': round(statistics.median(v) * scale, nd), 'min': round(min(v) * scale, nd), 'max': round(max(v) * scale, nd), 'windows': len(v)}
+
+
+def measure_soft(dec, dvae, B, window_s, rounds, other_lib):
+    from slotformer_amd import steve_render
+    from slotformer_amd._lib import SIGNATURES, check, sf_slate_step_opts
+    g = Generator(dec, B, STEPS)
+    dev = dec.head.weight.device
+    table = dvae.conv0_table()
+    rows = torch.empty(B, STEPS, 64, device=dev)
+    o = sf_slate_step_opts()
+    o.soft_rows, o.conv0_t, o.conv0_width, o.soft_scale, o.soft_seed = rows.data_ptr(), table.data_ptr(), 64, 10.0, 1
+    st = torch.cuda.current_stream().cuda_stream
+
+    def soft_step():
+        check(g.lib.sf_slate_generate_tok_opts_f32(C.byref(g.m), g.slots.data_ptr(), B, STEPS, g.tokens.data_ptr(), None, 1, g.ws.data_ptr(), g.nb,
+                                                   st, None, C.byref(o)))
+
+    forms = {'greedy': lambda: g.run(1), 'greedy_soft': soft_step}
+    if other_lib:
+        h = C.CDLL(other_lib)
+        fn = h.sf_slate_generate_tok_f32
+        fn.restype, fn.argtypes = SIGNATURES['sf_slate_generate_tok_f32']
+
+        def other():
+            assert fn(C.byref(g.m), g.slots.data_ptr(), B, STEPS, g.tokens.data_ptr(), None, 1, g.ws.data_ptr(), g.nb, st, None) == 0
+
+        forms['greedy_other_lib'] = other
+    row = {'frames': B, 'steps': STEPS, 'window_s': window_s}
+    for k, v in windows(forms, window_s, rounds).items():
+        row[k + '_us_per_step'] = summary(v, 1e3 / STEPS)
+    g.run(1)
+    greedy_tokens = g.tokens.clone()
+    soft_step()
+    row['tokens_equal_with_soft_rows'] = bool(torch.equal(g.tokens, greedy_tokens))
+    # (b), (c): whole soft frames
+    slots = g.slots
+    del g, rows
+    render = {'unfused': lambda: steve_render.render_slots(dec, dvae, slots, soft=True, seed=1),
+              'fused': lambda: steve_render.render_slots(dec, dvae, slots, soft=True, seed=1, fused=True)}
+    for k, v in windows(render, window_s, rounds).items():
+        row['render_soft_' + k + '_ms_per_frame'] = summary(v, 1.0 / B, 2)
+    for k, fn in render.items():
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        out = fn()
+        torch.cuda.synchronize()
+        row['render_soft_' + k + '_peak_MiB'] = round((torch.cuda.max_memory_allocated() - base) / 2**20, 1)
+        del out
+    a, b = render['unfused'](), render['fused']()
+    row['soft_image_fused_vs_unfused_rel_err'] = float((a['soft'] - b['soft']).abs().max() / a['soft'].abs().max())
+    del a, b
+    # (d) 64 sampled steps
+    sampled = {'fused_step': lambda: dec.generate(slots, 64, sample=True, temperature=1.0, seed=3),
+               'prefix_rerun': lambda: dec.generate(slots, 64, sample=True, temperature=1.0)}
+    for k, v in windows(sampled, window_s, rounds).items():
+        row['sample64_' + k + '_ms'] = summary(v, 1.0, 2)
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def soft_tables(rows, device_name, other):
+    cell = lambda d: f"{d['median']} ({d['min']} - {d['max']})"   # noqa: E731
+    out = [f'Measured by `tools/bench_steve_render.py --soft` on {device_name} (torch {torch.__version__}): every pair of forms in one process, in '
+           f"alternating windows of {rows[0]['window_s']} s of whole calls; medians over the windows (min - max of the window means), device events.", '',
+           '| frames | greedy us/step | greedy + soft rows us/step | ' + ('greedy, other build us/step | ' if other else '') +
+           'soft frame, unfused ms | soft frame, fused ms | peak MiB unfused | peak MiB fused | 64 sampled steps, fused step ms | prefix re-run ms |',
+           '|---|---|---|' + ('---|' if other else '') + '---|---|---|---|---|---|']
+    for r in rows:
+        out.append(f"| {r['frames']} | {cell(r['greedy_us_per_step'])} | {cell(r['greedy_soft_us_per_step'])} | " +
+                   (f"{cell(r['greedy_other_lib_us_per_step'])} | " if other else '') +
+                   f"{cell(r['render_soft_unfused_ms_per_frame'])} | {cell(r['render_soft_fused_ms_per_frame'])} | "
+                   f"{r['render_soft_unfused_peak_MiB']} | {r['render_soft_fused_peak_MiB']} | {cell(r['sample64_fused_step_ms'])} | "
+                   f"{cell(r['sample64_prefix_rerun_ms'])} |")
+    return '\n'.join(out)
+
+
 def tables(gen, ren, device_name):
     out = [f'Measured by `tools/bench_steve_render.py` on {device_name} (torch {torch.__version__}); medians of alternating whole calls '
            f'({STEPS} token steps each), device events.', '',
@@ -160,6 +266,10 @@ def main():
     ap.add_argument('--batches', default='1,12,64,192')
     ap.add_argument('--render-frames', default='12,64')
     ap.add_argument('--counter-run', action='store_true')
+    ap.add_argument('--soft', action='store_true')
+    ap.add_argument('--window', type=float, default=1.0)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--other-lib', default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_steve_render: no GPU; nothing is measured without one')
@@ -176,6 +286,17 @@ def main():
             print('counter run done: 12 frames, 1 frame per workgroup,', STEPS, 'steps')
             return
         dvae = dVAE(SHAPE[0]).eval().to(dev)
+        if a.soft:
+            if a.window < 1.0:
+                raise SystemExit('bench_steve_render --soft: windows of 1 s or more')
+            rows = [measure_soft(dec, dvae, int(f), a.window, a.rounds, a.other_lib) for f in a.render_frames.split(',') if f]
+            text = soft_tables(rows, torch.cuda.get_device_name(0), bool(a.other_lib))
+            print(text)
+            if a.json:
+                os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+                with open(a.json, 'w') as f:
+                    json.dump({'soft': rows, 'table': text}, f, indent=1)
+            return
         gen = [measure_generation(dec, int(b), a.reps) for b in a.batches.split(',') if b]
         ren = [measure_render(dec, dvae, int(f), max(2, a.reps - 1)) for f in a.render_frames.split(',') if f]
     text = tables(gen, ren, torch.cuda.get_device_name(0))
