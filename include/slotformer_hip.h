@@ -60,6 +60,11 @@ int sf_profile_read(int kernel_class, double* total_ms, long long* launches, dou
 int sf_linear_f32(const float* A, int lda, const float* W, const float* bias, const float* ln_gamma,
                   const float* ln_beta, float ln_eps, const float* residual, int ldr, float* C, int ldc,
                   int M, int N, int K, int relu, void* stream);
+/* Which tile configuration of csrc/gemm.hip (the ids of launch_by_id) sf_linear_f32 launches for a shape: the host rule and nothing else, no
+ * device work.  precision 0, 1 or 2 is taken as given (ids < 100: exact-f32 tiles, ids >= 100: split-bf16 tiles, which mode 2 shares); -1 = the
+ * calling thread's current precision (sf_get_precision).  The rule's id whatever SF_DBG=gemmcfg forces.  < 0: bad arguments (M < 0, N <= 0,
+ * K <= 0, K % 4 != 0, any other precision).  For tests and tools that have to know which kernel a shape runs. */
+int sf_linear_config(int M, int N, int K, int precision);
 
 /* nn.LayerNorm over the last dim (savi.py:41,50,66; predictor.py:57). */
 int sf_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int rows, int D,

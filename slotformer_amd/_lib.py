@@ -178,6 +178,7 @@ SIGNATURES = {
     'sf_get_ffn_rows64': (I, []),
     'sf_profile_read': (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     'sf_linear_f32': (I, [FP, I, FP, FP, FP, FP, F32, FP, I, FP, I, I, I, I, I, VP]),
+    'sf_linear_config': (I, [I, I, I, I]),
     'sf_layernorm_f32': (I, [FP, FP, FP, FP, I, I, F32, VP]),
     'sf_conv2d_nchw_in_f32': (I, [FP, LL, FP, FP, FP, FP, I, I, I, I, I, I, I, I, VP]),
     'sf_conv2d_nchw_in_grouped_f32': (I, [FP, LL, I, LL, FP, FP, FP, FP, I, I, I, I, I, I, I, I, VP]),

@@ -647,41 +647,46 @@ static int launch_by_id(int id, const SfGemmArgs& a, hipStream_t st) {
   return sf_set_err(-1, "unknown GEMM configuration id", __FILE__, __LINE__);
 }
 
+// The tile choice for plain A rows (sf_linear_f32 and the other linear entry points): (M, N, K, precision) -> id, from
+// tools/gemm_bench.py on MI355X (profiles/r01_gemm_configs.txt).  Pure: the forced id of SF_DBG=gemmcfg is not looked at here.
+static int linear_config(int M, int N, int K, int precision) {
+  auto tiles = [&](int bm, int bn) {
+    return (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+  };
+  const bool bf3 = precision >= 1;
+  // big problems (tools/gemm_bench.py [train], profiles/r01_gemm_configs.txt): the single-buffered tiles win everywhere --
+  // with 31 .. 74 KB of LDS two or more workgroups share a CU, which hides the fill of the first chunk and the C store
+  // that a double-buffered 128x128 workgroup (147 KB, alone on its CU) leaves exposed
+  if (N > 64 && tiles(128, 128) >= 384) {
+    if (!bf3) return 31;
+    return (N % 128 == 0 || N >= 512) ? 131 : 133;
+  }
+  if (tiles(128, 64) >= 384) return bf3 ? (K >= 2048 ? 132 : 133) : 1;
+  // small-M regime (rollout / slot-level GEMMs): latency-bound, favour many small workgroups
+  if (bf3) {
+    if (K >= 512) return M >= 512 ? 109 : 115;
+    const long long t64 = tiles(64, 64);
+    if (t64 > 300) return K <= 256 ? 122 : 107;
+    if (t64 >= 192) return 108;
+    return M >= 512 ? 109 : 106;
+  }
+  if (K >= 512) return 7;
+  if (tiles(32, 64) >= 256) return 4;
+  return 3;
+}
+
 template <int ALOAD, bool LN>
 static int dispatch_tiles(const SfGemmArgs& a, hipStream_t stream) {
-  auto tiles = [&](int bm, int bn) {
-    return (long long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
-  };
   if constexpr (ALOAD == ALOAD_CONV_NCHW) {
     return launch_cfg<128, 64, 4, 1, 1, 32, 1, 2, ALOAD, false, false>(a, stream);
   } else {
     const int f = forced_cfg();
     if (f >= 0) return launch_by_id<ALOAD, LN>(f, a, stream);
-    const bool bf3 = sf_get_precision() >= 1;
-    // choices below come from tools/gemm_bench.py on MI355X (profiles/r01_gemm_configs.txt)
     if constexpr (ALOAD == ALOAD_CONV_NHWC || ALOAD == ALOAD_DECONV_NHWC) {
       static const int conv_cfg = sf_dbg("convcfg") > 0 ? sf_dbg("convcfg") : 132;
-      return launch_by_id<ALOAD, LN>(bf3 ? conv_cfg : 28, a, stream);
+      return launch_by_id<ALOAD, LN>(sf_get_precision() >= 1 ? conv_cfg : 28, a, stream);
     } else {
-      // big problems (tools/gemm_bench.py [train], profiles/r01_gemm_configs.txt): the single-buffered tiles win everywhere --
-      // with 31 .. 74 KB of LDS two or more workgroups share a CU, which hides the fill of the first chunk and the C store
-      // that a double-buffered 128x128 workgroup (147 KB, alone on its CU) leaves exposed
-      if (a.N > 64 && tiles(128, 128) >= 384) {
-        if (!bf3) return launch_by_id<ALOAD, LN>(31, a, stream);
-        return launch_by_id<ALOAD, LN>((a.N % 128 == 0 || a.N >= 512) ? 131 : 133, a, stream);
-      }
-      if (tiles(128, 64) >= 384) return launch_by_id<ALOAD, LN>(bf3 ? (a.K >= 2048 ? 132 : 133) : 1, a, stream);
-      // small-M regime (rollout / slot-level GEMMs): latency-bound, favour many small workgroups
-      if (bf3) {
-        if (a.K >= 512) return launch_by_id<ALOAD, LN>(a.M >= 512 ? 109 : 115, a, stream);
-        const long long t64 = tiles(64, 64);
-        if (t64 > 300) return launch_by_id<ALOAD, LN>(a.K <= 256 ? 122 : 107, a, stream);
-        if (t64 >= 192) return launch_by_id<ALOAD, LN>(108, a, stream);
-        return launch_by_id<ALOAD, LN>(a.M >= 512 ? 109 : 106, a, stream);
-      }
-      if (a.K >= 512) return launch_by_id<ALOAD, LN>(7, a, stream);
-      if (tiles(32, 64) >= 256) return launch_by_id<ALOAD, LN>(4, a, stream);
-      return launch_by_id<ALOAD, LN>(3, a, stream);
+      return launch_by_id<ALOAD, LN>(linear_config(a.M, a.N, a.K, sf_get_precision()), a, stream);
     }
   }
 }
@@ -740,6 +745,13 @@ int sf_linear_masked_ex(const float* A, const float* W, const float* mask, float
 // C ABI
 // ---------------------------------------------------------------------------------------
 extern "C" {
+
+// which tile configuration (launch_by_id) sf_linear_f32 runs for a shape: the rule's id, whatever SF_DBG=gemmcfg forces
+int sf_linear_config(int M, int N, int K, int precision) {
+  SF_REQUIRE(M >= 0 && N > 0 && K > 0 && (K % 4) == 0, "K must be a positive multiple of 4");
+  SF_REQUIRE(precision >= -1 && precision <= 2, "precision must be 0, 1, 2 or -1 (the current one)");
+  return linear_config(M, N, K, precision < 0 ? sf_get_precision() : precision);
+}
 
 int sf_linear_f32(const float* A, int lda, const float* W, const float* bias, const float* ln_gamma,
                   const float* ln_beta, float ln_eps, const float* residual, int ldr, float* C, int ldc,
